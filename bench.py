@@ -173,6 +173,27 @@ def cpu_baseline_c1(rt):
                       "-O3 -ffast-math, 1 task/pixel dynamic", "mrays_per_s": round(rays / best / 1e6, 3), "seconds": round(best, 4)}
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(out_dir, arrays, limit_bytes=DUMP_LIMIT_BYTES):
+    """Write per-pixel arrays (name -> tensor or array with one row per pixel) as out_dir/<name>.npy in float32.  When all of them would take more
+    than `limit_bytes`, every array keeps the same fixed, seeded sample of pixels instead, and out_dir/pixel_index.npy (float64) names them."""
+    import numpy as np
+    host = {k: np.ascontiguousarray((v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)), dtype=np.float32) for k, v in arrays.items()}
+    n = len(next(iter(host.values())))
+    per_pixel = sum(v.size // n for v in host.values()) * 4
+    room = limit_bytes - 4096                                  # the .npy headers
+    os.makedirs(out_dir, exist_ok=True)
+    if n * per_pixel > room:
+        keep = room // (per_pixel + 8)
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        host = {k: v[idx] for k, v in host.items()}
+        np.save(os.path.join(out_dir, "pixel_index.npy"), idx.astype(np.float64))
+    for k, v in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+
+
 def post_passes(rt, ctx, lib, torch, dev, stream, sizes=((1920, 1080), (3840, 2160)), iters=20):
     """Achieved HBM GB/s of the post passes next to the sample kernel (JOBS/CombineJob.cs:29-71, JOBS/FinalizeTexturesJob.cs:23-55,
     JOBS/ReduceMetricsJob.cs:22-45, rtowAddAccumDevice), timed with HIP events on the stream they are launched on.  Bytes per pixel are the
@@ -259,7 +280,12 @@ def main():
                     "behind the C ABI (the reference stream's scalable split), tiles = rows only (north_star's), batches = hybrid with one tile")
     ap.add_argument("--group", type=int, default=None, help="N > 1, hybrid partition: sub-batches (steps) a rank renders per launch (rtowSampleBatchGroupDevice; 1 .. 16); default min(8, steps)")
     ap.add_argument("--tiles", type=int, default=None, help="T of the hybrid partition (must divide the number of GPUs); default: 1 unless spp < GPUs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                    "(float32, at most 64 MB: a fixed, seeded sample of pixels beyond that, DIR/pixel_index.npy): one GPU - the four accumulators and the batch's RayCount "
+                    "records; several - the colour frame rank 0 gathered")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     cfg = CONFIGS[args.config]
     overridden = [k for k in ("scene", "width", "height", "spp", "depth") if getattr(args, k) is not None]
     for k in ("scene", "width", "height", "spp", "depth"):
@@ -657,6 +683,10 @@ def main():
     main_partition = args.partition if world > 1 else "single"
     m = measure(args.partition, args.rng, args.chain, args.steps, args.warmup, prewarm_s=args.prewarm)
     hybrid = m["hybrid"]
+    if args.dump_outputs and rank == 0:
+        # the seeds are the step numbers, so the same arguments give the same inputs; with several ranks only the colour frame is whole on rank 0
+        names = ("color", "normal", "albedo", "sample_count_weight")
+        dump_outputs(args.dump_outputs, dict(zip(names, m["last"]), ray_count=m["diag"]) if world == 1 else {"color": m["last"][0]})
 
     def summary(mm):
         return {"value": round(float(n) * spp * args.steps / mm["elapsed"] / 1e6, 2), "ms_per_step": round(mm["elapsed"] / args.steps * 1e3, 3),

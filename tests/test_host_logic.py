@@ -107,3 +107,30 @@ def test_bench_configs_are_the_baseline_configs():
         assert cfg["depth"] == (int(b.group(1)) if b else 8), text             # configs 4 and 5 do not name a bounce count: the metric's 8
     assert "10k-sphere" in base["configs"][3] and bench.CONFIGS[4]["scene"] == "stress"
     assert "Moving spheres" in base["configs"][4] and bench.CONFIGS[5]["scene"] == "moving"
+
+
+def test_bench_dump_outputs_writes_whole_frames_and_a_fixed_sample_of_large_ones(tmp_path):
+    """bench.py --dump-outputs: a small frame goes out whole; a 1080p frame's five arrays are cut to the same seeded pixels, within 64 MB (10^6 bytes) in all."""
+    import importlib.util
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(1)
+    for n, whole in ((96 * 54, True), (1920 * 1080, False)):
+        arrays = {"color": rng.random((n, 4), np.float32), "normal": rng.random((n, 3), np.float32), "albedo": rng.random((n, 3), np.float32),
+                  "sample_count_weight": rng.random(n, np.float32), "ray_count": rng.random(n, np.float32)}
+        dirs = [tmp_path / ("%d_%d" % (n, k)) for k in range(2)]
+        for d in dirs:
+            bench.dump_outputs(str(d), arrays)
+        files = sorted(os.listdir(dirs[0]))
+        assert files == sorted([k + ".npy" for k in arrays] + ([] if whole else ["pixel_index.npy"]))
+        assert sum(os.path.getsize(dirs[0] / f) for f in files) <= 64 * 1000 * 1000
+        idx = np.arange(n) if whole else np.load(dirs[0] / "pixel_index.npy")
+        assert whole or (idx.dtype == np.float64 and len(idx) > n // 2 and np.all(np.diff(idx) > 0))
+        for k, v in arrays.items():
+            got = np.load(dirs[0] / (k + ".npy"))
+            assert got.dtype == np.float32 and np.array_equal(got, v[idx.astype(np.int64)])
+        for f in files:                                                    # the same sample every time
+            assert np.array_equal(np.load(dirs[0] / f), np.load(dirs[1] / f))

@@ -55,7 +55,7 @@ def _worker(rank, world, port, out_path):
     else:
         assert frame is None
     assert list(mg.owned_rows(rank, world, H)) == list(range(rank, H, world))
-    dist.barrier()
+    dist.monitored_barrier()                          # not dist.barrier(): that asks torch for the accelerator first, which opens the GPU in every rank
     dist.destroy_process_group()
     osc.close()
 
@@ -118,7 +118,7 @@ def _batch_worker(rank, world, port, out_path):
         np.save(out_path, res.numpy())
     else:
         assert res is None
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
     osc.close()
 
@@ -203,7 +203,7 @@ def _hybrid_worker(rank, world, port, tiles, out_path):
         np.save(out_path, frame.numpy())
     else:
         assert frame is None
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
     osc.close()
 
