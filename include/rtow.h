@@ -42,7 +42,7 @@ extern "C" {
 #define RTOW_API __attribute__((visibility("default")))
 #endif
 
-#define RTOW_API_VERSION 11
+#define RTOW_API_VERSION 12
 
 /* ---- result codes (0 == success, like CudaError/OptixResult in OptixApi.cs:24-78) ---- */
 typedef enum RtowResult {
@@ -415,6 +415,33 @@ RTOW_API int rtowSampleBatchDevice(RtowContext context, const RtowSampleParams* 
 RTOW_API int rtowSampleBatchChainDevice(RtowContext context, int32_t count, const RtowSampleParams* params /* [count] */,
                                         const RtowAccumBuffers* in, const RtowAccumBuffers* out,
                                         void* const* diagnostics /* [count] or NULL */, void* stream, const volatile uint8_t* cancel);
+
+/* The reference host's adaptive schedule fed from the device.  Each pixel picks its sample count from its accumulated weight against the frame's
+ * SampleCountWeightExtrema (JOBS/SampleBatchJob.cs:118-126), which the ReduceMetricsJob of an EARLIER batch produced (UNITY/Raytracer.cs:527-543,742-751:
+ * with two batches in flight batch i uses the extrema of batch i - 2).  Here those extrema stay on the device. */
+typedef struct RtowAdaptiveFeed {
+    const RtowFloat2* extremaIn;    /* device-readable, [lag] or NULL: the extrema batches 0 .. lag-1 of this call decide their counts from;
+                                       NULL = params[k].sampleCountWeightExtrema, as rtowSampleBatchChainDevice does */
+    RtowFloat2* extremaOut;         /* device-writable, [count]: ReduceMetricsJob's SampleCountWeightExtrema (JOBS/ReduceMetricsJob.cs:22-45) of the
+                                       whole W x H accumulators after batch k */
+    int32_t lag;                    /* >= 1: batch k >= lag decides from extremaOut[k - lag]; the reference host with two batches in flight: 2 */
+    int32_t reserved;               /* 0 */
+} RtowAdaptiveFeed;
+
+/* `count` successive batches of one frame whose sample-count extrema come from the device: exactly what
+ *     for k = 0 .. count-1:
+ *         e = k < lag ? (extremaIn ? extremaIn[k] : params[k].sampleCountWeightExtrema) : extremaOut[k - lag]
+ *         rtowSampleBatchDevice(params[k] with sampleCountWeightExtrema = e, k == 0 ? in : out, out, diagnostics[k])
+ *         extremaOut[k] = rtowReduceMetricsDevice(W * H, ..., out->color, out->sampleCountWeight).sampleCountWeightExtrema
+ * computes, bit for bit, all of it enqueued on `stream`: the host never waits for the device (unless `cancel` is non-NULL, as for
+ * rtowSampleBatchChainDevice).  params[k].sampleCountWeightExtrema is ignored for k >= lag.  A host continues the schedule across calls with
+ * extremaIn = previous extremaOut + (previous count - lag).  Errors, cancellation, hit-list growth and rtowGetLastSampleKernelMs behave as
+ * for rtowSampleBatchChainDevice.  RTOW_ERROR_INVALID_VALUE: feed NULL, lag < 1, extremaOut NULL,
+ * reserved != 0, or batches that differ in size, slice or diagnosticsStride - nothing is enqueued then. */
+RTOW_API int rtowSampleBatchChainAdaptiveDevice(RtowContext context, int32_t count, const RtowSampleParams* params /* [count] */,
+                                                const RtowAccumBuffers* in, const RtowAccumBuffers* out,
+                                                void* const* diagnostics /* [count] or NULL */, const RtowAdaptiveFeed* feed,
+                                                void* stream, const volatile uint8_t* cancel);
 
 /* `count` INDEPENDENT batches of one frame, enqueued together: exactly what
  *     rtowSampleBatchDevice(params[k], in, &outs[k], diagnostics[k])   for k = 0 .. count-1

@@ -6,7 +6,7 @@ library is compiled from the same header and exposes the sizes it saw).
 """
 import ctypes as C
 
-RTOW_API_VERSION = 11
+RTOW_API_VERSION = 12
 
 # RtowResult
 RTOW_SUCCESS = 0
@@ -131,6 +131,10 @@ class AccumBuffers(C.Structure):
                 ("sampleCountWeight", C.c_void_p)]
 
 
+class AdaptiveFeed(C.Structure):
+    _fields_ = [("extremaIn", C.c_void_p), ("extremaOut", C.c_void_p), ("lag", C.c_int32), ("reserved", C.c_int32)]
+
+
 LogCallback = C.CFUNCTYPE(None, C.c_int32, C.c_char_p, C.c_char_p, C.c_void_p)
 
 
@@ -172,5 +176,5 @@ EXPORTED_SYMBOLS = [
     "rtowDeviceCopy", "rtowDeviceMemset", "rtowSynchronize", "rtowGetBatchStatus", "rtowRegisterHostBuffer", "rtowUnregisterHostBuffer",
     "rtowSampleBatchChainDevice", "rtowSampleBatchChain", "rtowCommSetLibraryPath", "rtowCommGetUniqueId", "rtowCommInit", "rtowCommDestroy", "rtowGatherRowsDevice",
     "rtowHybridPlan", "rtowExchangeAccumDevice", "rtowSampleBatchGroupDevice",
-    "rtowCombineFinalizeDevice", "rtowReduceMetricsDeviceAsync", "rtowProbeNearestHit",
+    "rtowCombineFinalizeDevice", "rtowReduceMetricsDeviceAsync", "rtowProbeNearestHit", "rtowSampleBatchChainAdaptiveDevice",
 ]

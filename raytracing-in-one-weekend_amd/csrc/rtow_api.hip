@@ -156,6 +156,8 @@ struct RtowContext_t {
     size_t stagingPixels = 0, stagingDiagBytes = 0;
 
     MetricsPartial* dPartials = nullptr;
+    RtowFloat2* dExtremaPartials = nullptr;   // [kMetricsBlocks] rtowSampleBatchChainAdaptiveDevice: partials of the per-batch weight-extrema reduction
+    unsigned* dExtremaKeys = nullptr;         // [2 x kMaxChain] ... of a fused launch: every batch's (min, max) folded at store time
 
     // nearest-hit ties of the rank-rule sphere kernels (SampleKernelArgs.tieBits / tieRedo): the bitmap the fast kernel marks, the list the fix-up launch renders, a copy
     // of the inputs of launches that accumulate in place, and the fix-up launch's own (small) hit-list spill area
@@ -254,7 +256,8 @@ int ownedRows(const RtowSampleParams* p)
 // chain (optional): {count, seeds[count], diagnostics[count]} - `count` successive batches of the frame in this one launch (seeds[0] / diags[0] are
 // batch 0's; p->seed and diag are ignored then)
 // outs (optional): a batch group - batch b stores to outs[b] and every batch reads `in` (rtowSampleBatchGroupDevice); null: a chain, batch b reads what b - 1 stored to `out`
-struct ChainSpec { int count; const uint32_t* seeds; void* const* diags; const RtowAccumBuffers* outs; };
+// extrema / extremaKeys (optional, chains only): per batch where it reads SampleCountWeightExtrema (null = p's), and the [2 x count] keys its stores fold the batch's extrema into
+struct ChainSpec { int count; const uint32_t* seeds; void* const* diags; const RtowAccumBuffers* outs; const RtowFloat2* const* extrema = nullptr; unsigned* extremaKeys = nullptr; };
 
 // per-scene threshold measurement (launchSample): forget a measurement in flight (new scene, context going away)
 void dropThresholdTuning(RtowContext ctx)
@@ -315,8 +318,9 @@ uint64_t listCapacity(const RtowContext_t* ctx, bool volumes);    // (defined wi
 inline bool triangleKind(uint32_t kind) { return kind == SCENE_KIND_TRIANGLES || kind == SCENE_KIND_TRIANGLES_TEXTURED; }
 constexpr unsigned kTieWatchBusy = 4096;   // a watched launch of an all-triangle scene that lists more pixel-batches than this (8 workgroups render them) sends the scene to the exact-tie kernels
 
+// extremaIn (optional): device memory the kernel reads the SampleCountWeightExtrema from instead of p's (rtowSampleBatchChainAdaptiveDevice)
 int launchSample(RtowContext ctx, const RtowSampleParams* p, const RtowAccumBuffers* in, const RtowAccumBuffers* out, void* diag,
-                 hipStream_t stream, bool useCancelFlag, const ChainSpec* chain = nullptr)
+                 hipStream_t stream, bool useCancelFlag, const ChainSpec* chain = nullptr, const RtowFloat2* extremaIn = nullptr)
 {
     SampleKernelArgs a{};
     a.inColor = in->color; a.inNormal = in->normal; a.inAlbedo = in->albedo; a.inScw = in->sampleCountWeight;
@@ -356,6 +360,7 @@ int launchSample(RtowContext ctx, const RtowSampleParams* p, const RtowAccumBuff
     a.subPixelJitter = p->subPixelJitter;
     a.extremaX = p->sampleCountWeightExtrema.x;
     a.extremaY = p->sampleCountWeightExtrema.y;
+    a.extremaIn = extremaIn;
     a.refTree = (ctx->flags & RTOW_CONTEXT_REFERENCE_DIAGNOSTICS) ? ctx->dRefTree : nullptr;
     a.hitSpill = ctx->hitSpillEntries ? ctx->dHitSpill : nullptr;
     a.hitSpillEntries = ctx->hitSpillEntries;
@@ -721,7 +726,12 @@ int launchSample(RtowContext ctx, const RtowSampleParams* p, const RtowAccumBuff
         // (the previous chain's kernel may still be reading its own table: this copy is enqueued behind it)
         if (!ctx->dChainBatches) HIP_TRY(ctx, hipMalloc(&ctx->dChainBatches, sizeof(ChainBatch) * kMaxChain), RTOW_ERROR_MEMORY_ALLOCATION);
         ChainBatch table[kMaxChain] = {};
-        for (int b = 0; b < chain->count; b++) { table[b].seed = chain->seeds[b]; table[b].diagnostics = chain->diags ? (uint8_t*)chain->diags[b] : nullptr; }
+        for (int b = 0; b < chain->count; b++) {
+            table[b].seed = chain->seeds[b];
+            table[b].diagnostics = chain->diags ? (uint8_t*)chain->diags[b] : nullptr;
+            table[b].extrema = chain->extrema ? chain->extrema[b] : nullptr;
+        }
+        a.extremaKeys = chain->extremaKeys;
         HIP_TRY(ctx, hipMemcpyAsync(ctx->dChainBatches, table, sizeof(ChainBatch) * (size_t)chain->count, hipMemcpyHostToDevice, stream), RTOW_ERROR_LAUNCH_FAILURE);
         a.chainBatches = ctx->dChainBatches;
     }
@@ -1182,6 +1192,8 @@ RTOW_API int rtowDestroyContext(RtowContext ctx)
     if (ctx->dHitSpill) (void)hipFree(ctx->dHitSpill);
     if (ctx->dUnitRecords) (void)hipFree(ctx->dUnitRecords);
     if (ctx->dPartials) (void)hipFree(ctx->dPartials);
+    if (ctx->dExtremaPartials) (void)hipFree(ctx->dExtremaPartials);
+    if (ctx->dExtremaKeys) (void)hipFree(ctx->dExtremaKeys);
     if (ctx->dByteThresholds) (void)hipFree(ctx->dByteThresholds);
     dropThresholdTuning(ctx);
     if (ctx->dProbeSink) (void)hipFree(ctx->dProbeSink);
@@ -1462,6 +1474,89 @@ RTOW_API int rtowSampleBatchChainDevice(RtowContext ctx, int32_t count, const Rt
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     *ctx->hCancel = 0u;
     return enqueueChain(ctx, count, params, in, out, diagnostics, s, cancel);
+}
+
+// The adaptive schedule fed from the device (rtow.h).  Batches that differ in nothing but Seed and SampleCountWeightExtrema run as chained launches of at most `lag`
+// batches (kMaxChain), so every extrema value a batch of a launch reads was written by an EARLIER launch - after its tie fix-up - and no batch of a launch waits for
+// another batch of the same launch to end frame-wide.  A launch cannot reduce batch k's accumulators after it ends (batch k + 1 overwrote them in place): the kernel
+// folds every batch's weights at store time into extrema keys (SampleKernelArgs.extremaKeys; the fix-up launch folds the pixels it renders again, the kernel skips the
+// ones it marked), an init pass folds the rows of a sliced frame the launch never writes, and a decode pass writes extremaOut.  Per-sample policies, partial
+// diagnostics, contexts without chain fusion, frames of 2^27 pixels or more and lag 1 run batch by batch, each launch reading its extrema through SampleKernelArgs.extremaIn
+// and followed by the two-stage reduction of the frame into extremaOut[k].
+RTOW_API int rtowSampleBatchChainAdaptiveDevice(RtowContext ctx, int32_t count, const RtowSampleParams* params, const RtowAccumBuffers* in, const RtowAccumBuffers* out,
+                                                void* const* diagnostics, const RtowAdaptiveFeed* feed, void* stream, const volatile uint8_t* cancel)
+{
+    if (!ctx || !in || !out || !params || !feed || count < 1) return RTOW_ERROR_INVALID_VALUE;
+    if (feed->lag < 1 || !feed->extremaOut || feed->reserved != 0) return RTOW_ERROR_INVALID_VALUE;
+    for (int b = 0; b < count; b++) {
+        const int v = validateParams(&params[b]);
+        if (v != RTOW_SUCCESS) return v;
+        // one frame: the reduction behind every batch covers the same W x H pixels
+        if (memcmp(&params[b].size, &params[0].size, sizeof(RtowFloat2)) != 0 || params[b].sliceOffset != params[0].sliceOffset ||
+            params[b].sliceDivider != params[0].sliceDivider || params[b].diagnosticsStride != params[0].diagnosticsStride)
+            return RTOW_ERROR_INVALID_VALUE;
+    }
+    if (!in->color || !in->normal || !in->albedo || !in->sampleCountWeight || !out->color || !out->normal || !out->albedo || !out->sampleCountWeight)
+        return RTOW_ERROR_INVALID_VALUE;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
+    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    *ctx->hCancel = 0u;
+    if (!ctx->dExtremaPartials) HIP_TRY(ctx, hipMalloc(&ctx->dExtremaPartials, sizeof(RtowFloat2) * kMetricsBlocks), RTOW_ERROR_MEMORY_ALLOCATION);
+    const int pixels = (int)params[0].size.x * (int)params[0].size.y;
+    const int lag = feed->lag;
+    auto source = [&](int k) -> const RtowFloat2* { return k < lag ? (feed->extremaIn ? feed->extremaIn + k : nullptr) : feed->extremaOut + (k - lag); };
+    // what enqueueChain fuses, with the extrema free to differ; the variant follows the record format, so diagnostics on all batches or on none
+    bool fusable = lag > 1 && params[0].rngPolicy == RTOW_RNG_REFERENCE && ctx->chainFusion;
+    for (int b = 1; b < count && fusable; b++) {
+        RtowSampleParams q = params[b];
+        q.seed = params[0].seed;
+        q.sampleCountWeightExtrema = params[0].sampleCountWeightExtrema;
+        fusable = memcmp(&q, &params[0], sizeof(q)) == 0;
+    }
+    if (((uint64_t)ownedRows(&params[0]) * (uint64_t)(int)params[0].size.x + 63u) >= (1ull << 27) || (uint64_t)pixels >= (1ull << 27)) fusable = false;
+    if (diagnostics) {
+        int withDiag = 0;
+        for (int b = 0; b < count; b++) withDiag += diagnostics[b] != nullptr ? 1 : 0;
+        if (withDiag != 0 && withDiag != count) fusable = false;
+    }
+    if (fusable && !ctx->dExtremaKeys) HIP_TRY(ctx, hipMalloc(&ctx->dExtremaKeys, 2u * sizeof(unsigned) * kMaxChain), RTOW_ERROR_MEMORY_ALLOCATION);
+    for (int first = 0; first < count;) {
+        int n = fusable ? std::min(count - first, std::min(lag, (int)kMaxChain)) : 1;
+        // a batch without a device source reads the launch's kernarg extrema, i.e. batch `first`'s: the others must carry the same values
+        for (int b = 1; b < n; b++)
+            if (!source(first + b) && memcmp(&params[first + b].sampleCountWeightExtrema, &params[first].sampleCountWeightExtrema, sizeof(RtowFloat2)) != 0) n = 1;
+        const RtowAccumBuffers* src = first == 0 ? in : out;
+        int rc;
+        if (n == 1) {
+            rc = launchSample(ctx, &params[first], src, out, diagnostics ? diagnostics[first] : nullptr, s, cancel != nullptr, nullptr, source(first));
+            if (rc != RTOW_SUCCESS) return rc;
+            HIP_TRY(ctx, launchReduceWeightExtrema(pixels, out->color, out->sampleCountWeight, ctx->dExtremaPartials, feed->extremaOut + first, s), RTOW_ERROR_LAUNCH_FAILURE);
+        } else {
+            uint32_t seeds[kMaxChain];
+            const RtowFloat2* sources[kMaxChain];
+            for (int b = 0; b < n; b++) { seeds[b] = params[first + b].seed; sources[b] = source(first + b); }
+            // the keys are the context's: after the previous batch's decode, whatever stream that was
+            if (ctx->haveBatchDone) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->evBatchDone, 0), RTOW_ERROR_LAUNCH_FAILURE);
+            HIP_TRY(ctx, launchInitExtremaKeys(ctx->dExtremaKeys, (unsigned)n, (int)params[0].size.x, (int)params[0].size.y, params[0].sliceOffset, params[0].sliceDivider,
+                                               out->color, out->sampleCountWeight, s), RTOW_ERROR_LAUNCH_FAILURE);
+            ChainSpec chain{n, seeds, diagnostics ? diagnostics + first : nullptr, nullptr};
+            chain.extrema = sources;
+            chain.extremaKeys = ctx->dExtremaKeys;
+            rc = launchSample(ctx, &params[first], src, out, nullptr, s, cancel != nullptr, &chain);
+            if (rc != RTOW_SUCCESS) return rc;
+            HIP_TRY(ctx, launchDecodeExtremaKeys(ctx->dExtremaKeys, (unsigned)n, feed->extremaOut + first, s), RTOW_ERROR_LAUNCH_FAILURE);
+        }
+        // the batch ends with its extrema: the next batch of this context, on whatever stream, starts after them (it may read them; partials and keys are the context's)
+        HIP_TRY(ctx, hipEventRecord(ctx->evBatchDone, s), RTOW_ERROR_LAUNCH_FAILURE);
+        if (cancel) {
+            rc = waitWithCancel(ctx, cancel);
+            if (rc != RTOW_SUCCESS) return rc;
+        }
+        first += n;
+    }
+    return RTOW_SUCCESS;
 }
 
 RTOW_API int rtowSampleBatchGroupDevice(RtowContext ctx, int32_t count, const RtowSampleParams* params, const RtowAccumBuffers* in, const RtowAccumBuffers* outs,

@@ -116,7 +116,15 @@ struct ChainBatch {
     uint32_t seed;          // Seed (JOBS/SampleBatchJob.cs:28,91)
     uint32_t pad;
     float *outColor, *outNormal, *outAlbedo, *outScw;   // batch groups (rtowSampleBatchGroupDevice): this batch's own outputs; unused in a chain
+    const RtowFloat2* extrema;                          // rtowSampleBatchChainAdaptiveDevice: where this batch reads SampleCountWeightExtrema (written by an EARLIER launch); null = the kernarg values
 };
+
+// SampleCountWeightExtrema folded at store time (rtowSampleBatchChainAdaptiveDevice): a float as an unsigned whose unsigned order is the float order (-0 < +0; NaN is never folded),
+// so that atomicMin / atomicMax on it are um_min / um_max over any set of weights in any order.  The fold starts at (+inf, -inf).
+__host__ __device__ inline unsigned extrema_key(float f) { unsigned u; __builtin_memcpy(&u, &f, 4); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
+__host__ __device__ inline float extrema_value(unsigned k) { const unsigned u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k; float f; __builtin_memcpy(&f, &u, 4); return f; }
+constexpr unsigned kExtremaMinStart = 0xff800000u;   // extrema_key(+inf)
+constexpr unsigned kExtremaMaxStart = 0x007fffffu;   // extrema_key(-inf)
 
 // Everything the sample kernel needs, passed by value (kernarg segment).
 // Owned pixel number -> (column, owned row).  The 64 tickets of a chunk go to the 64 lanes of one wave: numbered row by row they are a 64 x 1 strip of
@@ -197,6 +205,9 @@ struct SampleKernelArgs {
     int32_t traceDepth;
     int32_t subPixelJitter;
     float extremaX, extremaY;
+    unsigned* extremaKeys;                // chained adaptive launches: [2 x chainCount] (min, max) extrema_key of every batch's weights, folded at each pixel store (also by the fix-up launch); null = none
+    const RtowFloat2* extremaIn;          // null = (extremaX, extremaY); else where this launch reads SampleCountWeightExtrema - device memory written in stream order before the launch
+                                          // (rtowSampleBatchChainAdaptiveDevice: an earlier batch's reduction).  Read at every pixel boundary, like the kernarg values
 
     // RTOW_RNG_PER_SAMPLE: work units are (owned pixel, group of kSampleGroup samples); totalWork counts units
     float* unitRecords;                   // [totalWork] x 16 floats, null = reference policy (units are pixels)
@@ -333,6 +344,13 @@ struct MetricsPartial {
 constexpr int kMetricsBlocks = 2048;   // 8 workgroups of 256 lanes per CU: 256 blocks (one per CU) left the reduction at 3.5 TB/s, latency bound (profiles/r03a_post_passes.json)
 hipError_t launchReduceMetrics(int pixelCount, const uint8_t* diagnostics, int stride, const float* color, const float* scw,
                                MetricsPartial* partials, hipStream_t stream);
+// ReduceMetricsJob's SampleCountWeightExtrema alone (min / max of scw / (int)color.w over `pixelCount` pixels) -> *out in stream order; partials: kMetricsBlocks float2
+// keys[2 b], keys[2 b + 1] = the fold's start for b < batches, then (sliceDivider > 1) the weights of the W x H frame's rows OTHER than row % sliceDivider == sliceOffset folded
+// into every batch's pair: rows a sliced launch never writes, which ReduceMetricsJob reduces all the same
+hipError_t launchInitExtremaKeys(unsigned* keys, unsigned batches, int width, int height, int sliceOffset, int sliceDivider, const float* color, const float* scw, hipStream_t stream);
+// out[b] = (extrema_value(keys[2 b]), extrema_value(keys[2 b + 1])) for b < batches
+hipError_t launchDecodeExtremaKeys(const unsigned* keys, unsigned batches, RtowFloat2* out, hipStream_t stream);
+hipError_t launchReduceWeightExtrema(int pixelCount, const float* color, const float* scw, RtowFloat2* partials, RtowFloat2* out, hipStream_t stream);
 // the partials of launchReduceMetrics -> one RtowMetrics record in device-visible memory (the asynchronous form of the reduction)
 hipError_t launchFoldMetrics(const MetricsPartial* partials, RtowMetrics* out, hipStream_t stream);
 

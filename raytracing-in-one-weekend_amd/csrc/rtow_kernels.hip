@@ -521,6 +521,88 @@ __global__ void __launch_bounds__(256) reduce_metrics_kernel(int n, const uint8_
     if (threadIdx.x == 0) partials[blockIdx.x] = sh[0];
 }
 
+// rtowSampleBatchChainAdaptiveDevice: the SampleCountWeightExtrema of reduce_metrics_kernel alone (same weight w, same um_min / um_max fold from (+inf, -inf), so a NaN
+// weight - 0 / 0 - is skipped and +inf counts), the partials folded by the last stage into one float2 in device memory that the next batches read.  Weights are sums of
+// non-negative counts divided by a count: -0 does not occur, so the order of the fold cannot tell +0 from -0 apart.
+__global__ void __launch_bounds__(256) reduce_weight_extrema_kernel(int n, const float4* __restrict__ color, const float* __restrict__ scw, RtowFloat2* __restrict__ partials)
+{
+    float minW = __builtin_inff(), maxW = -__builtin_inff();
+    for (int i = (int)(blockIdx.x * blockDim.x + threadIdx.x); i < n; i += (int)(gridDim.x * blockDim.x)) {
+        const int sc = (int)color[i].w;
+        const float w = scw[i] / (float)sc;
+        minW = um_min(minW, w); maxW = um_max(maxW, w);
+    }
+    __shared__ float2 sh[256];
+    sh[threadIdx.x] = make_float2(minW, maxW);
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) {
+            const float2 a = sh[threadIdx.x], b = sh[threadIdx.x + s];
+            sh[threadIdx.x] = make_float2(um_min(a.x, b.x), um_max(a.y, b.y));
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partials[blockIdx.x] = RtowFloat2{sh[0].x, sh[0].y};
+}
+
+__global__ void __launch_bounds__(256) fold_weight_extrema_kernel(const RtowFloat2* __restrict__ parts, int count, RtowFloat2* __restrict__ out)
+{
+    float minW = __builtin_inff(), maxW = -__builtin_inff();
+    for (int i = (int)threadIdx.x; i < count; i += (int)blockDim.x) { const RtowFloat2 p = parts[i]; minW = um_min(minW, p.x); maxW = um_max(maxW, p.y); }
+    __shared__ float2 sh[256];
+    sh[threadIdx.x] = make_float2(minW, maxW);
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) {
+            const float2 a = sh[threadIdx.x], b = sh[threadIdx.x + s];
+            sh[threadIdx.x] = make_float2(um_min(a.x, b.x), um_max(a.y, b.y));
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *out = RtowFloat2{sh[0].x, sh[0].y};
+}
+
+// rtowSampleBatchChainAdaptiveDevice, fused launches: the start of every batch's store-time fold, and the rows of the frame a sliced launch does not own
+__global__ void __launch_bounds__(256) init_extrema_keys_kernel(unsigned* __restrict__ keys, unsigned batches)
+{
+    const unsigned i = threadIdx.x;
+    if (i < 2u * batches) keys[i] = (i & 1u) ? kExtremaMaxStart : kExtremaMinStart;
+}
+
+__global__ void __launch_bounds__(256) fold_unowned_rows_kernel(unsigned* __restrict__ keys, unsigned batches, int width, int height, int sliceOffset, int sliceDivider,
+                                                                const float4* __restrict__ color, const float* __restrict__ scw)
+{
+    float minW = __builtin_inff(), maxW = -__builtin_inff();
+    const long long n = (long long)width * height;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        if ((int)(i / width) % sliceDivider == sliceOffset) continue;          // an owned row: the launch's stores fold it
+        const int sc = (int)color[i].w;
+        const float w = scw[i] / (float)sc;
+        minW = um_min(minW, w); maxW = um_max(maxW, w);
+    }
+    __shared__ float2 sh[256];
+    sh[threadIdx.x] = make_float2(minW, maxW);
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) {
+            const float2 a = sh[threadIdx.x], b = sh[threadIdx.x + s];
+            sh[threadIdx.x] = make_float2(um_min(a.x, b.x), um_max(a.y, b.y));
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < batches) {
+        // (a block whose weights were all NaN holds (+inf, -inf): the fold's start, which moves nothing)
+        atomicMin(keys + 2u * threadIdx.x, extrema_key(sh[0].x));
+        atomicMax(keys + 2u * threadIdx.x + 1u, extrema_key(sh[0].y));
+    }
+}
+
+__global__ void __launch_bounds__(64) decode_extrema_keys_kernel(const unsigned* __restrict__ keys, unsigned batches, RtowFloat2* __restrict__ out)
+{
+    const unsigned b = threadIdx.x;
+    if (b < batches) out[b] = RtowFloat2{extrema_value(keys[2u * b]), extrema_value(keys[2u * b + 1u])};
+}
+
 // CombineJob + FinalizeTexturesJob in one pass (the reference's default chain with denoiseMode 0, Assets/Prefabs/Raytracer.prefab:391: combine -> finalize back to
 // back, UNITY/Raytracer.cs:806-807): 40 B read and 12 B written per pixel instead of 80 + 48 through the float3 intermediates.  Same float program as the two
 // kernels one after the other (combine_pixel, to_bytes_table), so the bytes equal oracle.combine -> oracle.finalize.
@@ -785,6 +867,28 @@ hipError_t launchAddAccum(size_t pixels, float* const dst[4], const float* const
     }
     if (blocks == 0) return hipSuccess;
     hipLaunchKernelGGL(add_accum_kernel, dim3(blocks), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launchInitExtremaKeys(unsigned* keys, unsigned batches, int width, int height, int sliceOffset, int sliceDivider, const float* color, const float* scw, hipStream_t stream)
+{
+    hipLaunchKernelGGL(init_extrema_keys_kernel, dim3(1), dim3(256), 0, stream, keys, batches);
+    if (sliceDivider > 1)
+        hipLaunchKernelGGL(fold_unowned_rows_kernel, dim3(kMetricsBlocks), dim3(256), 0, stream, keys, batches, width, height, sliceOffset, sliceDivider,
+                           reinterpret_cast<const float4*>(color), scw);
+    return hipGetLastError();
+}
+
+hipError_t launchDecodeExtremaKeys(const unsigned* keys, unsigned batches, RtowFloat2* out, hipStream_t stream)
+{
+    hipLaunchKernelGGL(decode_extrema_keys_kernel, dim3(1), dim3(64), 0, stream, keys, batches, out);
+    return hipGetLastError();
+}
+
+hipError_t launchReduceWeightExtrema(int pixelCount, const float* color, const float* scw, RtowFloat2* partials, RtowFloat2* out, hipStream_t stream)
+{
+    hipLaunchKernelGGL(reduce_weight_extrema_kernel, dim3(kMetricsBlocks), dim3(256), 0, stream, pixelCount, reinterpret_cast<const float4*>(color), scw, partials);
+    hipLaunchKernelGGL(fold_weight_extrema_kernel, dim3(1), dim3(256), 0, stream, partials, kMetricsBlocks, out);
     return hipGetLastError();
 }
 

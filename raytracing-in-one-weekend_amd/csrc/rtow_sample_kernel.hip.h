@@ -1521,6 +1521,21 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
                             oa[3 * (size_t)pix + 0] = alb.x; oa[3 * (size_t)pix + 1] = alb.y; oa[3 * (size_t)pix + 2] = alb.z;
                         }
                         os[pix] = scwAcc;
+                        if (unsigned* const keys = C.extremaKeys) {
+                            // ReduceMetricsJob's weight of this pixel after this batch (JOBS/ReduceMetricsJob.cs:22-45: scw / (float)(int)color.w) folded into the batch's extrema: the
+                            // accumulators are overwritten by the next batch of this launch before any pass could reduce them.  A pixel the tie watch marked is stored again by the
+                            // fix-up launch, which folds the right value: it is left out here (its bit was set by this lane, before this store).  Most stores cannot move the extrema -
+                            // a coherent load filters them, so the atomics are few instead of one per pixel on one address
+                            const float wgt = scwAcc / (float)sampleCount;
+                            bool live = wgt == wgt;
+                            if (live && C.tieBits) live = !((__hip_atomic_load(C.tieBits + ((unsigned)pix >> 5), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> ((unsigned)pix & 31u)) & 1u);
+                            if (live) {
+                                const unsigned key = extrema_key(wgt);
+                                unsigned* const kb = keys + 2u * batch;
+                                if (key < __hip_atomic_load(kb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) __hip_atomic_fetch_min(kb, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                if (key > __hip_atomic_load(kb + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) __hip_atomic_fetch_max(kb + 1, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            }
+                        }
                         uint8_t* dg = C.chainBatches[batch].diagnostics;
                         if (dg) {
                             if (FULL_DIAG && C.diagnosticsStride >= 16)
@@ -1740,7 +1755,10 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
                     if (w == 0) {
                         nsamp = C.sampleCountMin;
                     } else {
-                        const float nw = um_saturate((w - C.extremaX) / (C.extremaY - C.extremaX));
+                        // the frame's SampleCountWeightExtrema: the parameter block's, or (rtowSampleBatchChainAdaptiveDevice) what an earlier batch's reduction left in device memory
+                        const RtowFloat2* const fed = chained ? C.chainBatches[newBatch].extrema : C.extremaIn;
+                        const float ex = fed ? fed->x : C.extremaX, ey = fed ? fed->y : C.extremaY;
+                        const float nw = um_saturate((w - ex) / (ey - ex));
                         const float lo = (float)C.sampleCountMin, hi = (float)C.sampleCountMax;
                         nsamp = (unsigned)__builtin_rintf(lo + nw * (hi - lo));
                     }

@@ -287,6 +287,22 @@ def sample_batch_chain_device(context, params_list, ins, outs, diags=None, strea
     return load().rtowSampleBatchChainDevice(context.handle, count, arr, C.byref(bi), C.byref(bo), dptr, stream, cancel)
 
 
+def sample_batch_chain_adaptive_device(context, params_list, ins, outs, extrema_out, lag=2, extrema_in=None, diags=None, stream=None, cancel=None):
+    """rtowSampleBatchChainAdaptiveDevice: the chain above, batch k >= lag deciding its sample counts from the SampleCountWeightExtrema the device reduced
+    after batch k - lag (extrema_out: a DeviceBuffer of len(params_list) float2, or a device address); batches k < lag from extrema_in (a DeviceBuffer or device
+    address of `lag` float2) or, if None, from their own params.  Continue a schedule with extrema_in = previous extrema_out address + 8 * (previous count - lag)."""
+    count = len(params_list)
+    arr = (abi.SampleParams * count)(*params_list)
+    bi = _buffers(*[b.ptr for b in ins])
+    bo = _buffers(*[b.ptr for b in outs])
+    dptr = None
+    if diags is not None:
+        dptr = (C.c_void_p * count)(*[d.ptr if d is not None else None for d in diags])
+    addr = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
+    feed = abi.AdaptiveFeed(addr(extrema_in), addr(extrema_out), int(lag), 0)
+    return load().rtowSampleBatchChainAdaptiveDevice(context.handle, count, arr, C.byref(bi), C.byref(bo), dptr, C.byref(feed), stream, cancel)
+
+
 def sample_batch_group_device(context, params_list, ins, outs_list, diags=None, stream=None, cancel=None):
     """rtowSampleBatchGroupDevice: `len(params_list)` INDEPENDENT batches of one frame in one launch; every batch reads `ins` (four DeviceBuffers) and stores
     to its own four DeviceBuffers outs_list[k]; diags: one DeviceBuffer (or None) per batch."""
