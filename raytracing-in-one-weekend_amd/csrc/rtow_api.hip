@@ -13,6 +13,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -72,6 +73,15 @@ constexpr int kTuneProbeSamples = 4, kTuneProbeRepeats = 3;
 constexpr uint64_t kTuneMinSamplesPerPixel = 64;    // ... and the scene must have been asked for this many samples per pixel since its upload before it is worth 40 - 76 of probes
 constexpr float kTuneMargin = 0.98f;      // a candidate replaces the kind's built-in family only if its best probe is more than 2 % faster: single probes (1 - 10 ms)
                                           // scatter by a few per cent, and a wrong pick costs more than a missed one (10 000 spheres: family 2 picked once in r03bw, -7 %)
+// The families above, by candidate number: candidate c of a measurement is family c % kFamilies, with the volume stage from half of the live lanes for c >= kFamilies
+// (the ninth value, the walk slice, is set by rtowUploadScene)
+constexpr int kFamilies = 3;
+constexpr int kThresholdFamilies[kFamilies][9] = {{RTOW_DEFAULT_TUNE}, {RTOW_GENERAL_TUNE}, {RTOW_GENERAL_TUNE_2}};
+static void candidateThresholds(int candidate, int* tune, int count)
+{
+    for (int k = 0; k < count; k++) tune[k] = kThresholdFamilies[candidate % kFamilies][k];
+    if (candidate >= kFamilies) tune[5] = 32;
+}
 
 using namespace rtow;
 
@@ -175,7 +185,13 @@ struct RtowContext_t {
     uint32_t ldsSceneBudget = 0;          // 0 = everything that fits
     int tune[9] = {RTOW_DEFAULT_TUNE};
     bool userTune = false;                // RtowContextOptions.schedulerTune was given: no per-scene adjustment
-    int regroupSide = RTOW_DEFAULT_REGROUP_SIDE;   // RtowContextOptions.schedulerTune[7] (see RTOW_DEFAULT_REGROUP_SIDE)
+    // RtowContextOptions.schedulerTune[7] (see RTOW_DEFAULT_REGROUP_SIDE), as given and decoded by rtowCreateContext
+    int schedulerKnob = RTOW_DEFAULT_REGROUP_SIDE;
+    unsigned ticketMapSide = 0;           // which pixel a ticket stands for: 0 = its place in its tile, 1 = a tile's tickets most expensive first, 2 / 4 / 8 = super-tiles of that many tiles
+    unsigned regroupMode = 0;             // development: what the ticket map sorts by (0 ray count, 1 sky / not sky, 2 / 3 classes of rays per sample)
+    bool orderByTotal = false;            // development: chunks ordered by their total ray count instead of by their most expensive pixel
+    unsigned slotBlockOverride = 0;       // batch groups' (chunk, batch) slots per pull (0 = by the launch: prepareChunkOrder)
+    int pixelGateOverride = 0;            // lanes that must want a pixel boundary (0 = by the samples a unit of work takes: setSchedulerValues)
     bool userSliceDefault = false;        // ... with a zero walk slice: the per-scene built-in value
     bool chainFusion = true;              // the same-XCD hand-over litmus passed on this device (rtowCreateContext): chains may run as one launch
     uint64_t tunedScene = ~0ull;          // sceneSerial whose thresholds were measured (tuneThresholds)
@@ -231,6 +247,28 @@ void logf(RtowContext ctx, int level, const char* tag, const char* fmt, ...)
         }                                                                                             \
     } while (0)
 
+#define RTOW_TRY(expr)                                                                                \
+    do {                                                                                              \
+        const int _rc = (expr);                                                                       \
+        if (_rc != RTOW_SUCCESS) return _rc;                                                          \
+    } while (0)
+
+// Grow-only device buffers of the context: when `need` exceeds `capacity` (in the caller's unit) each buffer is freed and allocated again at its own size - the
+// contents are not kept - and `capacity` becomes `need`.  Several buffers may share one capacity.  A failed allocation leaves the capacity 0, so the next call
+// allocates again.  Callers do around it what the old buffer needs first (a batch in flight may still read it) and what a new one invalidates.
+struct DeviceBuf { void** p; size_t bytes; };
+template <typename T> DeviceBuf devBuf(T*& p, size_t bytes) { return DeviceBuf{reinterpret_cast<void**>(&p), bytes}; }
+template <typename C>
+int growDevice(RtowContext ctx, C& capacity, uint64_t need, std::initializer_list<DeviceBuf> bufs)
+{
+    if (need <= (uint64_t)capacity) return RTOW_SUCCESS;
+    for (const DeviceBuf& b : bufs) { if (*b.p) (void)hipFree(*b.p); *b.p = nullptr; }
+    capacity = 0;
+    for (const DeviceBuf& b : bufs) HIP_TRY(ctx, hipMalloc(b.p, b.bytes), RTOW_ERROR_MEMORY_ALLOCATION);
+    capacity = (C)need;
+    return RTOW_SUCCESS;
+}
+
 int validateParams(const RtowSampleParams* p)
 {
     if (!p) return RTOW_ERROR_INVALID_VALUE;
@@ -281,8 +319,6 @@ bool finishThresholdTuning(RtowContext ctx, bool wait)
     if (!ctx->tunePending || ctx->tuneEvents.empty()) return false;
     const hipError_t q = wait ? hipEventSynchronize(ctx->tuneEvents.back()) : hipEventQuery(ctx->tuneEvents.back());
     if (q == hipErrorNotReady) { (void)hipGetLastError(); return false; }
-    constexpr int kFamilies = 3;
-    static const int kSets[kFamilies][9] = {{RTOW_DEFAULT_TUNE}, {RTOW_GENERAL_TUNE}, {RTOW_GENERAL_TUNE_2}};
     const int candidates = ctx->tuneCandidates, builtin = ctx->tuneBuiltin;
     bool ok = q == hipSuccess;
     float best = 0.0f, builtinMs = 0.0f;
@@ -299,8 +335,7 @@ bool finishThresholdTuning(RtowContext ctx, bool wait)
     }
     if (ok && winner >= 0) {
         if (winner != builtin && !(best < kTuneMargin * builtinMs)) { winner = builtin; best = builtinMs; }
-        for (int k = 0; k < 8; k++) ctx->tune[k] = kSets[winner % kFamilies][k];
-        if (winner >= kFamilies) ctx->tune[5] = 32;
+        candidateThresholds(winner, ctx->tune, 8);
         ctx->tunedCandidate = winner;
         ctx->tuneCache.push_back({ctx->sceneSignatureNow, winner});
         logf(ctx, 4, "tune", "stage thresholds measured on this scene: candidate %d of %d (%.3f ms per %d-sample probe)", winner, candidates, best, kTuneProbeSamples);
@@ -318,11 +353,12 @@ uint64_t listCapacity(const RtowContext_t* ctx, bool volumes);    // (defined wi
 inline bool triangleKind(uint32_t kind) { return kind == SCENE_KIND_TRIANGLES || kind == SCENE_KIND_TRIANGLES_TEXTURED; }
 constexpr unsigned kTieWatchBusy = 4096;   // a watched launch of an all-triangle scene that lists more pixel-batches than this (8 workgroups render them) sends the scene to the exact-tie kernels
 
-// extremaIn (optional): device memory the kernel reads the SampleCountWeightExtrema from instead of p's (rtowSampleBatchChainAdaptiveDevice)
-int launchSample(RtowContext ctx, const RtowSampleParams* p, const RtowAccumBuffers* in, const RtowAccumBuffers* out, void* diag,
-                 hipStream_t stream, bool useCancelFlag, const ChainSpec* chain = nullptr, const RtowFloat2* extremaIn = nullptr)
+// ---- launchSample, step by step ----
+
+// The kernel's arguments from the batch's params and buffers and the context's scene, noise textures and cubemap (RTOW_ERROR_INVALID_VALUE: the noise set is not uploaded)
+int buildArgs(RtowContext ctx, const RtowSampleParams* p, const RtowAccumBuffers* in, const RtowAccumBuffers* out, void* diag, bool useCancelFlag, const ChainSpec* chain,
+              const RtowFloat2* extremaIn, SampleKernelArgs& a)
 {
-    SampleKernelArgs a{};
     a.inColor = in->color; a.inNormal = in->normal; a.inAlbedo = in->albedo; a.inScw = in->sampleCountWeight;
     a.outColor = out->color; a.outNormal = out->normal; a.outAlbedo = out->albedo; a.outScw = out->sampleCountWeight;
     a.diagnostics = (uint8_t*)diag;
@@ -331,7 +367,7 @@ int launchSample(RtowContext ctx, const RtowSampleParams* p, const RtowAccumBuff
     a.layout = ctx->scene.layout;
     a.ldsSceneBytes = ctx->ldsSceneBytes;
     a.ldsNodeCount = ctx->ldsNodeCount;
-    a.ldsStackRows = ctx->ldsPlan.stackRows; a.ldsHistOffset = 0u; a.ldsFrontBytes = ctx->ldsPlan.frontBytes;      // (launches of the generic variants plan again below: their history rows)
+    a.ldsStackRows = ctx->ldsPlan.stackRows; a.ldsHistOffset = 0u; a.ldsFrontBytes = ctx->ldsPlan.frontBytes;      // (launches of the generic variants plan again: planHistory)
     a.workCounter = ctx->dWorkCounter;
     a.cancelFlag = useCancelFlag ? ctx->hCancel : nullptr;
     a.overflowFlag = const_cast<uint32_t*>(ctx->hCancel) + 1;      // [1]: a ray beyond the hit-list capacity (grows: takeOverflow); [2]: more tied pixel-batches than the fix-up list holds (final)
@@ -345,8 +381,8 @@ int launchSample(RtowContext ctx, const RtowSampleParams* p, const RtowAccumBuff
     a.seed = chain ? chain->seeds[0] : p->seed;
     a.chainCount = chain ? (uint32_t)chain->count : 1u;
     a.chainIndependent = (chain && chain->outs) ? 1 : 0;
-    // slot / chainCount = (slot * groupRecip) >> 32 for every slot of a launch (chunkCount * chainCount <= 2^25); a count of one has no 32-bit reciprocal (2^32 + 1 would truncate
-    // to 1): 2^32 - 1 is exact for slots below 2^32 - and groups of one batch are plain launches anyway (rtowSampleBatchGroupDevice)
+    // slot / chainCount = (slot * groupRecip) >> 32 for every slot of a launch (chunkCount * chainCount <= 2^25).  A count of one has no 32-bit reciprocal, and the value
+    // here is not one either (__umulhi(slot, 2^32 - 1) is slot - 1): the kernel reads groupRecip only in batch groups of more than one batch, never when chainCount <= 1
     a.groupRecip = a.chainCount <= 1u ? 0xffffffffu : (uint32_t)((1ull << 32) / a.chainCount + 1ull);
     if (chain) {
         if (diag == nullptr && chain->diags) diag = chain->diags[0];
@@ -388,36 +424,36 @@ int launchSample(RtowContext ctx, const RtowSampleParams* p, const RtowAccumBuff
     a.cubemapPixelStride = ctx->cubemap.pixelStride; a.cubemapRowStride = ctx->cubemap.pixelStride * ctx->cubemap.faceWidth;   // :167
     a.cubemapFaceStride = ctx->cubemap.pixelStride * ctx->cubemap.faceWidth * ctx->cubemap.faceHeight;         // :168
     a.cubemapChannelType = ctx->cubemap.channelType;
+    return RTOW_SUCCESS;
+}
 
-    {
-        // The variants for paths deeper than 16 (and the generic ones: 16-byte records, texture-driven noise, the per-sample policies beyond depth 8) keep the path-history codes
-        // beyond the first eight in LDS rows: this launch's LDS is planned with them, and the scene image takes what is left (a scene that no longer fits whole keeps the top of
-        // its tree there and reads the rest through L2, like any scene beyond LDS)
-        const bool fullDiag = a.diagnostics && a.diagnosticsStride >= 16;
-        const bool perSample = p->rngPolicy != RTOW_RNG_REFERENCE;
-        int hw = historyWords(a.noiseColor, perSample, ctx->wideCodes, ctx->scene.layout.exactTies != 0, fullDiag, a.traceDepth);
-        // (an all-triangle scene under the tie watch launches its rank-rule kernels first and its exact-tie kernels on the marked pixels, with the one plan: the wider of the two)
-        if (ctx->scene.layout.exactTies) hw = std::max(hw, historyWords(a.noiseColor, perSample, ctx->wideCodes, false, fullDiag, a.traceDepth));
-        if (hw == 32 && a.traceDepth > kHistoryInRegisters) {
-            const LdsPlan plan = planLds(ctx->wideCodes, ctx->scene.layout, (uint32_t)(a.traceDepth - kHistoryInRegisters), ctx->ldsSceneBudget);
-            a.ldsStackRows = plan.stackRows; a.ldsHistOffset = plan.histOffset; a.ldsFrontBytes = plan.frontBytes; a.ldsHistRows = plan.histRows;
-            a.ldsSceneBytes = plan.sceneBytes; a.ldsNodeCount = plan.nodeCount;
-            if (plan.histSpillRows) {
-                // the rows that do not fit LDS (32-bit stack rows of a deep tree next to a deep trace depth; a scene kept whole in LDS): 2 bytes per lane and row in HBM
-                const size_t stride = (size_t)ctx->cuCount * (size_t)kBlockThreads, need = (size_t)plan.histSpillRows * stride * sizeof(unsigned short);
-                if (need > ctx->histSpillBytes) {
-                    HIP_TRY(ctx, hipDeviceSynchronize(), RTOW_ERROR_LAUNCH_FAILURE);          // a batch in flight may still use the smaller area
-                    if (ctx->dHistSpill) (void)hipFree(ctx->dHistSpill);
-                    ctx->dHistSpill = nullptr;
-                    ctx->histSpillBytes = 0;
-                    HIP_TRY(ctx, hipMalloc(&ctx->dHistSpill, need), RTOW_ERROR_MEMORY_ALLOCATION);
-                    ctx->histSpillBytes = need;
-                }
-                a.histSpill = ctx->dHistSpill; a.histSpillRows = plan.histSpillRows; a.histSpillStride = (uint32_t)stride;
-            }
-        }
+// The variants for paths deeper than 16 (and the generic ones: 16-byte records, texture-driven noise, the per-sample policies beyond depth 8) keep the path-history codes
+// beyond the first eight in LDS rows: this launch's LDS is planned with them, and the scene image takes what is left (a scene that no longer fits whole keeps the top of
+// its tree there and reads the rest through L2, like any scene beyond LDS)
+int planHistory(RtowContext ctx, const RtowSampleParams* p, SampleKernelArgs& a)
+{
+    const bool fullDiag = a.diagnostics && a.diagnosticsStride >= 16;
+    const bool perSample = p->rngPolicy != RTOW_RNG_REFERENCE;
+    int hw = historyWords(a.noiseColor, perSample, ctx->wideCodes, ctx->scene.layout.exactTies != 0, fullDiag, a.traceDepth);
+    // (an all-triangle scene under the tie watch launches its rank-rule kernels first and its exact-tie kernels on the marked pixels, with the one plan: the wider of the two)
+    if (ctx->scene.layout.exactTies) hw = std::max(hw, historyWords(a.noiseColor, perSample, ctx->wideCodes, false, fullDiag, a.traceDepth));
+    if (hw != 32 || a.traceDepth <= kHistoryInRegisters) return RTOW_SUCCESS;
+    const LdsPlan plan = planLds(ctx->wideCodes, ctx->scene.layout, (uint32_t)(a.traceDepth - kHistoryInRegisters), ctx->ldsSceneBudget);
+    a.ldsStackRows = plan.stackRows; a.ldsHistOffset = plan.histOffset; a.ldsFrontBytes = plan.frontBytes; a.ldsHistRows = plan.histRows;
+    a.ldsSceneBytes = plan.sceneBytes; a.ldsNodeCount = plan.nodeCount;
+    if (plan.histSpillRows) {
+        // the rows that do not fit LDS (32-bit stack rows of a deep tree next to a deep trace depth; a scene kept whole in LDS): 2 bytes per lane and row in HBM
+        const size_t stride = (size_t)ctx->cuCount * (size_t)kBlockThreads, need = (size_t)plan.histSpillRows * stride * sizeof(unsigned short);
+        if (need > ctx->histSpillBytes) HIP_TRY(ctx, hipDeviceSynchronize(), RTOW_ERROR_LAUNCH_FAILURE);          // a batch in flight may still use the smaller area
+        RTOW_TRY(growDevice(ctx, ctx->histSpillBytes, need, {devBuf(ctx->dHistSpill, need)}));
+        a.histSpill = ctx->dHistSpill; a.histSpillRows = plan.histSpillRows; a.histSpillStride = (uint32_t)stride;
     }
-    // scheduler thresholds (lane population a stage needs before it runs) and box-walk slice (RtowContextOptions.schedulerTune overrides)
+    return RTOW_SUCCESS;
+}
+
+// Scheduler thresholds (lane population a stage needs before it runs) and box-walk slice (RtowContextOptions.schedulerTune overrides); tune[7] = pixel gate | hurry rate
+void setSchedulerValues(const RtowContext_t* ctx, const RtowSampleParams* p, SampleKernelArgs& a)
+{
     for (int i = 0; i < 8; i++) a.tune[i] = ctx->tune[i] < 1 ? 1 : ctx->tune[i];
     a.travSlice = ctx->tune[8] < 1 ? 1 : ctx->tune[8];
     // Lanes that wait for company at a pixel boundary (kernel: A.tune[7]; schedulerTune[7] bits 12 .. 15 override).  Measured (profiles/r06d_pixel_boundaries_in_company.json):
@@ -425,94 +461,370 @@ int launchSample(RtowContext ctx, const RtowSampleParams* p, const RtowAccumBuff
     // (the adaptive {1, 50} schedule +0.5 ... 1 %) and a loss of 1 - 3 % where a pixel takes hundreds of samples (the wait costs more than the shared instructions save):
     // so by the samples a unit of work takes at most
     const unsigned unitSamples = p->rngPolicy != RTOW_RNG_REFERENCE ? kSampleGroup : (a.sampleCountMax > a.sampleCountMin ? a.sampleCountMax : a.sampleCountMin);
-    const int pixelGate = (ctx->regroupSide >> 12) & 15 ? (ctx->regroupSide >> 12) & 15 : (unitSamples <= 64u ? 4 : RTOW_PIXEL_GATE);
-    a.tune[7] = pixelGate;
+    const int pixelGate = ctx->pixelGateOverride ? ctx->pixelGateOverride : (unitSamples <= 64u ? 4 : RTOW_PIXEL_GATE);
     // Lanes in a hurry (kernel: HURRY; twins of the static-sphere kind's generic reference-stream variants): a pixel that runs at more than this many rays per sample stops waiting for
     // company.  Batch groups run a pixel's batches side by side and keep every wave busy to the end: no bound, and the variants without the code.  Static spheres only: measured at
     // depth 32, same box (profiles/r06x_lanes_in_a_hurry.json) - cover scene +21 % (adaptive) / +33 % (chains), 10 000 spheres +24 %; in its first form (a bound on the batch's
     // rays) moving spheres with a lens -1.6 %, the 250 882-triangle mesh -8.6 % (a stage run for one lane costs the whole wave a memory round trip there).
-    {
-        // (exactly the launches launchByDiagGeo serves from a twin: every other variant reads tune[7] as the pixel gate alone)
-        const bool records16 = a.diagnostics && a.diagnosticsStride >= 16;
-        const bool twin = RTOW_URGENT_LANES && !a.chainIndependent && a.layout.sceneKind == SCENE_KIND_SPHERES && !a.layout.exactTies && !ctx->wideCodes && p->rngPolicy == RTOW_RNG_REFERENCE &&
-                          a.noiseColor == RTOW_NOISE_WHITE && !(records16 && a.refTree) && historyWords(a.noiseColor, false, false, false, records16, a.traceDepth) == 32;
-        const float urgentRays = !twin ? __builtin_inff() : (a.ldsSceneBytes == a.layout.totalBytes ? RTOW_URGENT_RAYS_PER_SAMPLE : RTOW_URGENT_RAYS_PER_SAMPLE_BEYOND_LDS);
-        uint32_t bits;
-        memcpy(&bits, &urgentRays, sizeof bits);
-        if (!(urgentRays < __builtin_inff())) bits = 0u;                                  // no bound: the variants without the code (they read tune[7] as the pixel gate alone)
-        a.tune[7] = (int32_t)((bits & 0xffffff00u) | (uint32_t)(pixelGate & 255));
-    }
-    const uint32_t ownedPixels = a.totalWork;
-    if (ownedPixels == 0) {
-        // a slice that owns no row (SliceOffset >= height): Execute returns for every index (JOBS/SampleBatchJob.cs:69-70) - nothing is
-        // written, nothing is launched (a zero-sized grid is not a valid launch); the events still bracket "this batch"
-        if (ctx->haveBatchDone) HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->evBatchDone, 0), RTOW_ERROR_LAUNCH_FAILURE);
-        HIP_TRY(ctx, hipEventRecord(ctx->evStart, stream), RTOW_ERROR_LAUNCH_FAILURE);
-        HIP_TRY(ctx, hipEventRecord(ctx->evStop, stream), RTOW_ERROR_LAUNCH_FAILURE);
-        HIP_TRY(ctx, hipEventRecord(ctx->evBatchDone, stream), RTOW_ERROR_LAUNCH_FAILURE);
-        ctx->haveBatchDone = true;
-        ctx->haveTiming = true;
-        return RTOW_SUCCESS;
-    }
+    // (hurryTwin: exactly the launches launchByDiagGeo serves from a twin; on top of it this host's policy - not for groups, the reference stream only)
+    const bool records16 = a.diagnostics && a.diagnosticsStride >= 16;
+    const bool twin = !a.chainIndependent && p->rngPolicy == RTOW_RNG_REFERENCE &&
+                      hurryTwin(a.layout.sceneKind, a.layout.exactTies != 0, ctx->wideCodes, a.noiseColor, false, records16, a.refTree != nullptr, a.traceDepth);
+    const float urgentRays = !twin ? __builtin_inff() : (a.ldsSceneBytes == a.layout.totalBytes ? RTOW_URGENT_RAYS_PER_SAMPLE : RTOW_URGENT_RAYS_PER_SAMPLE_BEYOND_LDS);
+    uint32_t bits;
+    memcpy(&bits, &urgentRays, sizeof bits);
+    if (!(urgentRays < __builtin_inff())) bits = 0u;                                  // no bound: the variants without the code (they read tune[7] as the pixel gate alone)
+    a.tune[7] = (int32_t)((bits & 0xffffff00u) | (uint32_t)(pixelGate & 255));
+}
+
+// A slice that owns no row (SliceOffset >= height): Execute returns for every index (JOBS/SampleBatchJob.cs:69-70) - nothing is
+// written, nothing is launched (a zero-sized grid is not a valid launch); the events still bracket "this batch"
+int recordEmptyBatch(RtowContext ctx, hipStream_t stream)
+{
+    if (ctx->haveBatchDone) HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->evBatchDone, 0), RTOW_ERROR_LAUNCH_FAILURE);
+    HIP_TRY(ctx, hipEventRecord(ctx->evStart, stream), RTOW_ERROR_LAUNCH_FAILURE);
+    HIP_TRY(ctx, hipEventRecord(ctx->evStop, stream), RTOW_ERROR_LAUNCH_FAILURE);
+    HIP_TRY(ctx, hipEventRecord(ctx->evBatchDone, stream), RTOW_ERROR_LAUNCH_FAILURE);
+    ctx->haveBatchDone = true;
+    ctx->haveTiming = true;
+    return RTOW_SUCCESS;
+}
+
+// Per-sample policies: work units are (owned pixel, group of kSampleGroup samples); each leaves a record that fold_unit_records_kernel adds up
+int planUnits(RtowContext ctx, const RtowSampleParams* p, SampleKernelArgs& a)
+{
     a.groupsPerPixel = 1;
     a.xoroshiro = p->rngPolicy == RTOW_RNG_PER_SAMPLE_XOROSHIRO ? 1 : 0;
-    if (p->rngPolicy != RTOW_RNG_REFERENCE) {
-        // work units are (owned pixel, group of kSampleGroup samples); each leaves a record that fold_unit_records_kernel adds up
-        uint32_t groups = (a.sampleCountMax > a.sampleCountMin ? a.sampleCountMax : a.sampleCountMin);
-        groups = (groups + kSampleGroup - 1) / kSampleGroup;
-        if (groups < 1) groups = 1;
-        if ((uint64_t)ownedPixels * groups > 0x7fffffffull) return RTOW_ERROR_CAPACITY;
-        a.groupsPerPixel = groups;
-        a.totalWork = ownedPixels * groups;
-        if ((size_t)a.totalWork > ctx->unitRecordCapacity) {
-            if (ctx->dUnitRecords) (void)hipFree(ctx->dUnitRecords);
-            ctx->dUnitRecords = nullptr;
-            ctx->unitRecordCapacity = 0;
-            HIP_TRY(ctx, hipMalloc(&ctx->dUnitRecords, (size_t)a.totalWork * 64u), RTOW_ERROR_MEMORY_ALLOCATION);
-            ctx->unitRecordCapacity = a.totalWork;
-        }
-        a.unitRecords = ctx->dUnitRecords;
-    }
-    // ---- nearest-hit ties under the rank rule: sphere kinds of more than 16 entities, reference stream - a pixel that meets two different spheres at
-    // bit-identical distance at a nearest hit is listed instead of stored, and the exact-tie kernel of the same kind renders the list in a second, tiny launch
-    // All-triangle scenes whose exact-tie kernels were chosen for their size alone (no triangle twice: SceneLayout.tieWatchOk) are watched too: the rank-rule kernels trace the
-    // frame, the exact-tie kernels the marked pixels - unless the scene has shown that it ties often (triWatchOff: the flag below, or a list that overflowed)
+    if (p->rngPolicy == RTOW_RNG_REFERENCE) return RTOW_SUCCESS;
+    const uint32_t ownedPixels = a.totalWork;
+    uint32_t groups = (a.sampleCountMax > a.sampleCountMin ? a.sampleCountMax : a.sampleCountMin);
+    groups = (groups + kSampleGroup - 1) / kSampleGroup;
+    if (groups < 1) groups = 1;
+    if ((uint64_t)ownedPixels * groups > 0x7fffffffull) return RTOW_ERROR_CAPACITY;
+    a.groupsPerPixel = groups;
+    a.totalWork = ownedPixels * groups;
+    RTOW_TRY(growDevice(ctx, ctx->unitRecordCapacity, a.totalWork, {devBuf(ctx->dUnitRecords, (size_t)a.totalWork * 64u)}));
+    a.unitRecords = ctx->dUnitRecords;
+    return RTOW_SUCCESS;
+}
+
+struct TieWatch {
+    bool on = false;         // this launch lists tied pixels for the fix-up launch
+    bool triangles = false;  // ... of an all-triangle scene (its exact-tie kernels render them)
+    bool inPlace = false;    // an output buffer is also the input buffer (a chain's later batches always read the outputs, but they read what THIS launch stored: only batch 0's inputs count)
+};
+
+// ---- nearest-hit ties under the rank rule: sphere kinds of more than 16 entities, reference stream - a pixel that meets two different spheres at
+// bit-identical distance at a nearest hit is listed instead of stored, and the exact-tie kernel of the same kind renders the list in a second, tiny launch
+// All-triangle scenes whose exact-tie kernels were chosen for their size alone (no triangle twice: SceneLayout.tieWatchOk) are watched too: the rank-rule kernels trace the
+// frame, the exact-tie kernels the marked pixels - unless the scene has shown that it ties often (triWatchOff: the flag below, or a list that overflowed)
+int prepareTieWatch(RtowContext ctx, const RtowSampleParams* p, const RtowAccumBuffers* in, const RtowAccumBuffers* out, SampleKernelArgs& a, TieWatch& tie)
+{
     if (ctx->hCancel[3] != 0u) { ctx->hCancel[3] = 0u; if (triangleKind(ctx->scene.layout.sceneKind)) { ctx->triWatchOff = true; logf(ctx, 3, "rtow", "this scene's nearest hits tie often: exact-tie kernels from now on"); } }
     const bool sphereWatch = ctx->scene.layout.sceneKind <= SCENE_KIND_SPHERES_MOTION && !ctx->scene.layout.exactTies && ctx->scene.entityCount > 16;
-    const bool triWatch = triangleKind(ctx->scene.layout.sceneKind) && ctx->scene.layout.exactTies && ctx->scene.layout.tieWatchOk && !ctx->triWatchOff &&
-                          !(ctx->flags & RTOW_CONTEXT_EXACT_TIES_ALWAYS);
-    const bool tieWatch = (sphereWatch || triWatch) && !(ctx->flags & RTOW_CONTEXT_EXACT_TIES_NEVER) && p->rngPolicy == RTOW_RNG_REFERENCE;
-    if (tieWatch && triWatch) a.layout.exactTies = 0u;               // this launch goes through the rank-rule kernels of the kind; the fix-up launch below sets the bit again
-    // in place: an output buffer that is also the input buffer (a chain's later batches always read the outputs, but they read what THIS launch stored: only batch 0's inputs count)
-    const bool inPlace = in->color == out->color || in->normal == out->normal || in->albedo == out->albedo || in->sampleCountWeight == out->sampleCountWeight;
-    if (tieWatch) {
-        if (!ctx->dTieRedo) HIP_TRY(ctx, hipMalloc(&ctx->dTieRedo, (4u + (size_t)kTieRedoCapacity) * sizeof(unsigned)), RTOW_ERROR_MEMORY_ALLOCATION);
-        const uint32_t most = (uint32_t)std::min<uint64_t>((uint64_t)ctx->scene.entityCount, listCapacity(ctx, false));
-        const uint32_t entries = most > (uint32_t)kLocalHitEntries ? most - (uint32_t)kLocalHitEntries : 0u;
-        if (entries > ctx->redoSpillEntries) {
-            if (ctx->dRedoSpill) (void)hipFree(ctx->dRedoSpill);
-            ctx->dRedoSpill = nullptr;
-            ctx->redoSpillEntries = 0;
-            HIP_TRY(ctx, hipMalloc(&ctx->dRedoSpill, (size_t)entries * kTieRedoBlocks * kBlockThreads * sizeof(uint4)), RTOW_ERROR_MEMORY_ALLOCATION);
-            ctx->redoSpillEntries = entries;
-        }
-        const size_t framePixels = (size_t)a.width * (size_t)a.height;
-        const size_t words = (framePixels + 31u) / 32u;
-        if (words > ctx->tieBitsWords) {
-            if (ctx->dTieBits) (void)hipFree(ctx->dTieBits);
-            ctx->dTieBits = nullptr;
-            ctx->tieBitsWords = 0;
-            HIP_TRY(ctx, hipMalloc(&ctx->dTieBits, words * sizeof(unsigned)), RTOW_ERROR_MEMORY_ALLOCATION);
-            ctx->tieBitsWords = words;
-        }
-        if (inPlace && framePixels > ctx->tieInputPixels) {
-            if (ctx->dTieInputs) (void)hipFree(ctx->dTieInputs);
-            ctx->dTieInputs = nullptr;
-            ctx->tieInputPixels = 0;
-            HIP_TRY(ctx, hipMalloc(&ctx->dTieInputs, framePixels * 11u * sizeof(float)), RTOW_ERROR_MEMORY_ALLOCATION);
-            ctx->tieInputPixels = framePixels;
+    tie.triangles = triangleKind(ctx->scene.layout.sceneKind) && ctx->scene.layout.exactTies && ctx->scene.layout.tieWatchOk && !ctx->triWatchOff &&
+                    !(ctx->flags & RTOW_CONTEXT_EXACT_TIES_ALWAYS);
+    tie.on = (sphereWatch || tie.triangles) && !(ctx->flags & RTOW_CONTEXT_EXACT_TIES_NEVER) && p->rngPolicy == RTOW_RNG_REFERENCE;
+    if (tie.on && tie.triangles) a.layout.exactTies = 0u;               // this launch goes through the rank-rule kernels of the kind; the fix-up launch sets the bit again
+    tie.inPlace = in->color == out->color || in->normal == out->normal || in->albedo == out->albedo || in->sampleCountWeight == out->sampleCountWeight;
+    if (!tie.on) return RTOW_SUCCESS;
+    if (!ctx->dTieRedo) HIP_TRY(ctx, hipMalloc(&ctx->dTieRedo, (4u + (size_t)kTieRedoCapacity) * sizeof(unsigned)), RTOW_ERROR_MEMORY_ALLOCATION);
+    const uint32_t most = (uint32_t)std::min<uint64_t>((uint64_t)ctx->scene.entityCount, listCapacity(ctx, false));
+    const uint32_t entries = most > (uint32_t)kLocalHitEntries ? most - (uint32_t)kLocalHitEntries : 0u;
+    RTOW_TRY(growDevice(ctx, ctx->redoSpillEntries, entries, {devBuf(ctx->dRedoSpill, (size_t)entries * kTieRedoBlocks * kBlockThreads * sizeof(uint4))}));
+    const size_t framePixels = (size_t)a.width * (size_t)a.height;
+    const size_t words = (framePixels + 31u) / 32u;
+    RTOW_TRY(growDevice(ctx, ctx->tieBitsWords, words, {devBuf(ctx->dTieBits, words * sizeof(unsigned))}));
+    if (tie.inPlace) RTOW_TRY(growDevice(ctx, ctx->tieInputPixels, framePixels, {devBuf(ctx->dTieInputs, framePixels * 11u * sizeof(float))}));
+    return RTOW_SUCCESS;
+}
+
+// ---- camera-ray candidate lists: one conservative beam walk per pixel, reused by all its samples (and by later batches of the same view) ----
+int refreshCameraRays(RtowContext ctx, SampleKernelArgs& a, uint32_t ownedPixels, hipStream_t stream)
+{
+    if (ctx->flags & RTOW_CONTEXT_NO_CAMERA_RAY_LISTS) return RTOW_SUCCESS;
+    const size_t pixels = (size_t)a.width * (size_t)a.height;
+    const size_t listBytes = pixels * sizeof(uint4);      // 8 x 16-bit node codes per pixel; 4 x 32-bit with wide codes
+    if (listBytes > ctx->pixCandCapacity) ctx->pixCandValid = false;
+    RTOW_TRY(growDevice(ctx, ctx->pixCandCapacity, listBytes, {devBuf(ctx->dPixCand, listBytes)}));
+    const bool same = ctx->pixCandValid && ctx->pixCandScene == ctx->sceneSerial && memcmp(&ctx->pixCandView, &a.view, sizeof(RtowView)) == 0 &&
+                      ctx->pixCandW == a.width && ctx->pixCandH == a.height && ctx->pixCandOff == a.sliceOffset && ctx->pixCandDiv == a.sliceDivider &&
+                      ctx->pixCandJitter == (a.subPixelJitter ? 1 : 0);
+    if (!same) {
+        SampleKernelArgs perPixel = a;                       // the lists are per pixel whatever the work units are
+        perPixel.totalWork = ownedPixels;
+        HIP_TRY(ctx, launchPrimaryCandidates(perPixel, ctx->dPixCand, stream), RTOW_ERROR_LAUNCH_FAILURE);
+        ctx->pixCandValid = true;
+        ctx->pixCandScene = ctx->sceneSerial;
+        ctx->pixCandView = a.view;
+        ctx->pixCandW = a.width; ctx->pixCandH = a.height; ctx->pixCandOff = a.sliceOffset; ctx->pixCandDiv = a.sliceDivider;
+        ctx->pixCandJitter = a.subPixelJitter ? 1 : 0;
+    }
+    a.pixelCandidates = ctx->dPixCand;
+    return RTOW_SUCCESS;
+}
+
+struct OrderPlan {
+    bool want = false;     // the launch runs its chunks in an order, and leaves the order for the next batch
+    bool mapped = false;   // ... and a ticket map (which pixels share a chunk), re-sorted behind the launch too
+    bool have = false;     // an order is on hand for this launch (else it runs in natural order and records the first one)
+};
+
+// Ticket-map classes (regroup_tickets_kernel) for costs of at least floorCost rays per pixel
+void regroupClasses(const RtowContext_t* ctx, unsigned floorCost, unsigned out[3])
+{
+    const unsigned mode = ctx->regroupMode;
+    if (ctx->ticketMapSide == 1u) { out[0] = mode == 0u ? 0u : (2u << mode); out[1] = out[2] = 0u; return; }      // tile order: levels of the tile's cost range (mode 1 / 2 / 3: 4 / 8 / 16), 0 = by the ray count itself
+    out[0] = mode == 0u ? 0u : floorCost; out[1] = mode >= 2u ? (floorCost * 11u) / 4u : 0xffffffffu; out[2] = mode >= 2u ? floorCost * 4u : 0xffffffffu;
+}
+
+int regroupTickets(RtowContext ctx, const SampleKernelArgs& a, unsigned floorCost, hipStream_t stream)
+{
+    unsigned cls[3];
+    regroupClasses(ctx, floorCost, cls);
+    const unsigned tileRows = a.tilesPerRow ? a.tiledPixels / (64u * a.tilesPerRow) : 0u;
+    HIP_TRY(ctx, launchRegroupTickets(ctx->dPixelCost, ctx->dTicketMap, a.tilesPerRow, tileRows, ctx->ticketMapSide, cls, stream), RTOW_ERROR_LAUNCH_FAILURE);
+    return RTOW_SUCCESS;
+}
+
+// ---- chunk order: most expensive 64-pixel chunks first, from the ray counts of the previous launch (or of a probe) ----
+// ---- and which pixels share a chunk (a wave): the pixels of a super-tile of ticketMapSide x ticketMapSide tiles sorted by the ray counts of the previous launch and dealt out
+// 64 at a time (regroup_tickets_kernel), re-sorted behind every launch like the order.  Reference stream only (per-sample units are alike by construction).
+int prepareChunkOrder(RtowContext ctx, SampleKernelArgs& a, int blocks, hipStream_t stream, OrderPlan& order)
+{
+    a.chunkCount = (a.totalWork + 63u) / 64u;
+    order.want = a.chunkCount >= (uint32_t)(4 * ctx->cuCount) && !(ctx->flags & RTOW_CONTEXT_NO_CHUNK_ORDER);   // tiny frames: not worth it
+    // batch groups: (chunk, batch) slots a wave reserves at a time (schedulerTune[7] bits 8 .. 11 override the default for A/B runs)
+    a.slotBlock = ctx->slotBlockOverride ? ctx->slotBlockOverride : kGroupSlotBlock;
+    if (!ctx->slotBlockOverride) {
+        // Reserving several (chunk, batch) slots per pull pays where a wave has dozens of them to work through (a whole frame's group: 79 slots per wave, +1.8 %); a launch that
+        // owns a few slots per wave - the sub-batches of an 8-way row slice: 7.9 - must balance with single slots (profiles/r06j_partitions_c2.json: 10.9 ms per step against the
+        // 7.9 of round 5's single slots)
+        const uint64_t slotsPerWave = (uint64_t)a.chunkCount * a.chainCount / ((uint64_t)blocks * (uint64_t)(kBlockThreads / 64));
+        if (slotsPerWave < 32u) a.slotBlock = 1u;
+        else if (slotsPerWave < 64u && a.slotBlock > 2u) a.slotBlock = 2u;
+    }
+    order.mapped = order.want && ctx->ticketMapSide >= 1u && a.tiledPixels != 0u && !a.unitRecords;
+    if (!order.want) return RTOW_SUCCESS;
+    if (a.chunkCount > ctx->chunkCapacity) ctx->orderValid = false;
+    RTOW_TRY(growDevice(ctx, ctx->chunkCapacity, a.chunkCount,
+                        {devBuf(ctx->dChunkCost, (2 * (size_t)a.chunkCount + kChunkOrderScratchWords) * sizeof(unsigned)), devBuf(ctx->dChunkOrder, a.chunkCount * sizeof(unsigned)),
+                         devBuf(ctx->dPixelCost, (size_t)a.chunkCount * 64 * sizeof(unsigned short)), devBuf(ctx->dTicketMap, (size_t)a.chunkCount * 64 * sizeof(unsigned))}));
+    if (ctx->orderW != a.width || ctx->orderH != a.height || ctx->orderOff != a.sliceOffset || ctx->orderDiv != a.sliceDivider || ctx->orderGroups != a.groupsPerPixel ||
+        ctx->orderMapped != order.mapped) ctx->orderValid = false;
+    a.pixelCost = ctx->dPixelCost;
+    a.ticketMap = order.mapped ? ctx->dTicketMap : nullptr;
+    order.have = true;
+    if (!ctx->orderValid && a.unitRecords) {
+        // per-sample units are small and alike: the first batch simply runs in natural order and records the map for the next
+        HIP_TRY(ctx, hipMemsetAsync(ctx->dPixelCost, 0, (size_t)a.chunkCount * 64 * sizeof(unsigned short), stream), RTOW_ERROR_LAUNCH_FAILURE);
+        order.have = false;
+        ctx->orderValid = true;
+        ctx->orderW = a.width; ctx->orderH = a.height; ctx->orderOff = a.sliceOffset; ctx->orderDiv = a.sliceDivider; ctx->orderGroups = a.groupsPerPixel;
+        ctx->orderMapped = false;
+    }
+    if (!ctx->orderValid) {
+        // no cost map yet for this frame configuration: a 1-sample-per-pixel probe of the same kernel (stores nothing else)
+        SampleKernelArgs probe = a;
+        probe.probeOnly = 1;
+        probe.chunkOrder = nullptr;
+        probe.ticketMap = nullptr;                           // the probe runs over the tiles themselves; the map starts from them
+        if (order.mapped) HIP_TRY(ctx, launchInitTicketMap(ctx->dTicketMap, a.tiledPixels, stream), RTOW_ERROR_LAUNCH_FAILURE);
+        probe.cancelFlag = nullptr;
+        probe.chainCount = 1;                                // one pass over the pixels, whatever the launch it prepares
+        HIP_TRY(ctx, hipMemsetAsync(ctx->dWorkCounter, 0, sizeof(unsigned int), stream), RTOW_ERROR_LAUNCH_FAILURE);
+        HIP_TRY(ctx, hipMemsetAsync(ctx->dPixelCost, 0, (size_t)a.chunkCount * 64 * sizeof(unsigned short), stream), RTOW_ERROR_LAUNCH_FAILURE);   // the last chunk's tail
+        HIP_TRY(ctx, launchSampleBatch(probe, blocks, stream), RTOW_ERROR_LAUNCH_FAILURE);
+        if (order.mapped) RTOW_TRY(regroupTickets(ctx, a, 1u, stream));
+        HIP_TRY(ctx, launchBuildChunkOrder(ctx->dPixelCost, ctx->dChunkCost, a.chunkCount, ctx->dChunkOrder, 0, stream), RTOW_ERROR_LAUNCH_FAILURE);
+        ctx->orderValid = true;
+        ctx->orderW = a.width; ctx->orderH = a.height; ctx->orderOff = a.sliceOffset; ctx->orderDiv = a.sliceDivider; ctx->orderGroups = a.groupsPerPixel;
+        ctx->orderMapped = order.mapped;
+    }
+    a.chunkOrder = order.have ? ctx->dChunkOrder : nullptr;
+    return RTOW_SUCCESS;
+}
+
+// ---- stage thresholds: measured once per scene on this batch's own kernel, frame and view (see kTuneProbeSamples) ----
+// Never waited for: the probes are enqueued in front of a batch, timed with events, and a LATER call that finds the last event complete reads them
+// and switches the thresholds (scheduling only: no result depends on when that happens).  Until then the kernel kind's built-in values run.
+void measureThresholds(RtowContext ctx, SampleKernelArgs& a, int blocks, bool haveOrder, hipStream_t stream)
+{
+    for (int k = 0; k < 7; k++) a.tune[k] = ctx->tune[k] < 1 ? 1 : ctx->tune[k];
+    if (ctx->tunePending && ctx->tunePendingScene == ctx->sceneSerial && finishThresholdTuning(ctx, /*wait*/ false))
+        for (int k = 0; k < 7; k++) a.tune[k] = ctx->tune[k] < 1 ? 1 : ctx->tune[k];
+    ctx->sppSinceUpload += (uint64_t)a.chainCount * (a.sampleCountMax > a.sampleCountMin ? a.sampleCountMax : a.sampleCountMin);
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;                   // a stream that is being captured into a graph cannot carry the event pairs: no measurement then
+    if (hipStreamIsCapturing(stream, &capturing) != hipSuccess) { (void)hipGetLastError(); capturing = hipStreamCaptureStatusNone; }
+    // worth it only where the scene is rendered for longer than the probes take (3 or 6 candidates x 3 repeats x 4 samples per pixel: 40 - 76 samples per
+    // pixel): a one-shot render of a few samples per pixel (BASELINE.json configs[0]: 8) must not pay several times its own work first
+    const bool worthIt = ctx->sppSinceUpload >= kTuneMinSamplesPerPixel;
+    if (ctx->userTune || (ctx->flags & RTOW_CONTEXT_NO_THRESHOLD_TUNING) || ctx->tunedScene == ctx->sceneSerial || ctx->tunePending || a.unitRecords || !haveOrder ||
+        !worthIt || capturing != hipStreamCaptureStatusNone)
+        return;
+    const bool volumes = a.layout.sceneKind == SCENE_KIND_VOLUMES || a.layout.sceneKind == SCENE_KIND_VOLUMES_TEXTURED;
+    const int candidates = volumes ? 2 * kFamilies : kFamilies;                      // volume kinds: each family also with the volume stage from half of the live lanes
+    const int launches = candidates * kTuneProbeRepeats;
+    ctx->tuneEvents.assign((size_t)launches + 1, nullptr);
+    bool ok = true;
+    for (auto& e : ctx->tuneEvents) ok = ok && hipEventCreate(&e) == hipSuccess;
+    if (!ctx->dProbeSink) ok = ok && hipMalloc(&ctx->dProbeSink, 64) == hipSuccess;
+    SampleKernelArgs probe = a;
+    probe.probeOnly = kTuneProbeSamples;
+    probe.pixelCost = nullptr;                           // the cost map stays the cost probe's (or the previous batch's)
+    probe.cancelFlag = nullptr;
+    probe.overflowFlag = ctx->dProbeSink;                // a probe's ray beyond the hit-list capacity is not the batch's (which may trace fewer samples than a probe)
+    probe.chainCount = 1;
+    probe.chainIndependent = 0;
+    // one untimed probe first: clocks, L2 and the instruction cache are warm before the first timed one
+    candidateThresholds(0, probe.tune, 7);
+    if (ok) ok = hipMemsetAsync(ctx->dWorkCounter, 0, sizeof(unsigned int), stream) == hipSuccess && launchSampleBatch(probe, blocks, stream) == hipSuccess;
+    if (ok) ok = hipEventRecord(ctx->tuneEvents[0], stream) == hipSuccess;
+    for (int l = 0; ok && l < launches; l++) {
+        candidateThresholds(l % candidates, probe.tune, 7);
+        ok = hipMemsetAsync(ctx->dWorkCounter, 0, sizeof(unsigned int), stream) == hipSuccess && launchSampleBatch(probe, blocks, stream) == hipSuccess &&
+             hipEventRecord(ctx->tuneEvents[(size_t)l + 1], stream) == hipSuccess;
+    }
+    if (ok) {
+        ctx->tunePending = true;
+        ctx->tunePendingScene = ctx->sceneSerial;
+        ctx->tuneCandidates = candidates;
+        ctx->tuneBuiltin = a.layout.sceneKind <= SCENE_KIND_SPHERES_MOTION ? 0 : 1;       // what rtowUploadScene set for this kernel kind
+    } else {
+        (void)hipGetLastError();
+        dropThresholdTuning(ctx);
+        ctx->tunedCandidate = -1;
+        ctx->tunedScene = ctx->sceneSerial;             // not measurable: do not try again for this scene
+        logf(ctx, 2, "tune", "threshold probes failed; the per-kind values stay");
+    }
+}
+
+// Plain or chained launches with paths deeper than 16 segments are bound by their slowest pixels (see "lanes in a hurry" above), not by lane occupancy: a static-sphere scene
+// that is whole in LDS runs them with REGEN from a quarter of the live lanes, HIT from 3/8, and the walk's hand-over at 4 candidates (profiles/r06u_deep_plain_launch_thresholds.json:
+// +7 ... +10 %; the same values cost batch groups 2.8 %, launches at depth <= 16 1.3 ... 3 %, moving spheres 2 %, and 10 000 spheres - next to the lanes in a hurry - 2 %)
+void applyDeepPlainThresholds(const RtowContext_t* ctx, const RtowSampleParams* p, SampleKernelArgs& a)
+{
+    const int* builtin = kThresholdFamilies[0];
+    if (!ctx->userTune && !a.chainIndependent && a.traceDepth > 16 && p->rngPolicy == RTOW_RNG_REFERENCE && a.layout.sceneKind == SCENE_KIND_SPHERES && a.ldsSceneBytes == a.layout.totalBytes &&
+        a.tune[0] == builtin[0] && a.tune[3] == builtin[3] && a.tune[6] == builtin[6]) {
+        a.tune[0] = 16; a.tune[3] = 24; a.tune[6] = 4;
+    }
+}
+
+// The per-batch table of a chained launch or a batch group - seed and diagnostics; a group's outputs, a chain's extrema source (a zeroed entry is null for the rest) - in device
+// memory, written in stream order (the previous launch's kernel may still be reading its own table: this copy is enqueued behind it).  A chain also zeroes its hand-over state.
+int writeBatchTable(RtowContext ctx, const ChainSpec* chain, SampleKernelArgs& a, hipStream_t stream)
+{
+    if (a.chainCount <= 1u) return RTOW_SUCCESS;
+    if (!a.chainIndependent) {
+        // per-chunk hand-off counters of the chain: pixels stored so far (all batches); batch b of a chunk waits for b x its pixels
+        RTOW_TRY(growDevice(ctx, ctx->chunkDoneCapacity, a.chunkCount,
+                            {devBuf(ctx->dChunkDone, (size_t)a.chunkCount * sizeof(unsigned)), devBuf(ctx->dXcdState, sizeof(XcdState) + (size_t)kMaxXcds * a.chunkCount * sizeof(unsigned))}));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->dChunkDone, 0, (size_t)a.chunkCount * sizeof(unsigned), stream), RTOW_ERROR_LAUNCH_FAILURE);
+        a.chunkDone = ctx->dChunkDone;
+        // chunk ownership per XCD: counters zero, list entries "not written yet" (the kernel indexes the lists with THIS launch's chunkCount)
+        HIP_TRY(ctx, hipMemsetAsync(ctx->dXcdState, 0, sizeof(XcdState), stream), RTOW_ERROR_LAUNCH_FAILURE);
+        HIP_TRY(ctx, hipMemsetAsync(ctx->dXcdState + sizeof(XcdState), 0xff, (size_t)kMaxXcds * a.chunkCount * sizeof(unsigned), stream), RTOW_ERROR_LAUNCH_FAILURE);
+        a.xcdState = reinterpret_cast<XcdState*>(ctx->dXcdState);
+        a.extremaKeys = chain->extremaKeys;
+    }
+    if (!ctx->dChainBatches) HIP_TRY(ctx, hipMalloc(&ctx->dChainBatches, sizeof(ChainBatch) * kMaxChain), RTOW_ERROR_MEMORY_ALLOCATION);
+    ChainBatch table[kMaxChain] = {};
+    for (int b = 0; b < chain->count; b++) {
+        table[b].seed = chain->seeds[b];
+        table[b].diagnostics = chain->diags ? (uint8_t*)chain->diags[b] : nullptr;
+        if (chain->outs) { table[b].outColor = chain->outs[b].color; table[b].outNormal = chain->outs[b].normal; table[b].outAlbedo = chain->outs[b].albedo; table[b].outScw = chain->outs[b].sampleCountWeight; }
+        if (chain->extrema) table[b].extrema = chain->extrema[b];
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->dChainBatches, table, sizeof(ChainBatch) * (size_t)chain->count, hipMemcpyHostToDevice, stream), RTOW_ERROR_LAUNCH_FAILURE);
+    a.chainBatches = ctx->dChainBatches;
+    return RTOW_SUCCESS;
+}
+
+// The tie watch's state for this launch: an empty list and bitmap, and - the fix-up launch renders a marked pixel again from the launch's inputs, which an in-place
+// launch overwrites - a copy of those inputs (44 B per pixel through HBM, ~0.05 ms at 1920 x 1080 against a batch's tens of milliseconds); redoIn: where the fix-up reads them
+int prepareTieInputs(RtowContext ctx, const RtowSampleParams* p, SampleKernelArgs& a, const TieWatch& tie, const float* redoIn[4], hipStream_t stream)
+{
+    const size_t framePixels = (size_t)a.width * (size_t)a.height;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->dTieRedo, 0, 4u * sizeof(unsigned), stream), RTOW_ERROR_LAUNCH_FAILURE);
+    HIP_TRY(ctx, hipMemsetAsync(ctx->dTieBits, 0, ((framePixels + 31u) / 32u) * sizeof(unsigned), stream), RTOW_ERROR_LAUNCH_FAILURE);
+    if (tie.inPlace) {
+        static const size_t comps[4] = {4, 3, 3, 1};
+        float* at = ctx->dTieInputs;
+        const size_t rows = (size_t)ownedRows(p);                // the rows this launch writes (row % SliceDivider == SliceOffset), at their places in the frame
+        for (int k = 0; k < 4; k++) {
+            const size_t rowBytes = (size_t)a.width * comps[k] * sizeof(float), first = (size_t)a.sliceOffset * rowBytes, pitch = (size_t)a.sliceDivider * rowBytes;
+            HIP_TRY(ctx, hipMemcpy2DAsync((uint8_t*)at + first, pitch, (const uint8_t*)redoIn[k] + first, pitch, rowBytes, rows, hipMemcpyDeviceToDevice, stream), RTOW_ERROR_LAUNCH_FAILURE);
+            redoIn[k] = at;
+            at += framePixels * comps[k];
         }
     }
+    a.tieBits = ctx->dTieBits;
+    return RTOW_SUCCESS;
+}
+
+// the fix-up: marked pixels -> list -> the exact-tie kernel of the same kind over the list (almost always empty: that kernel then leaves before it stages the scene).
+// A chain's pixel is listed once and carried through all its batches; a group's once per batch.
+int launchTieFixup(RtowContext ctx, const SampleKernelArgs& a, const TieWatch& tie, const float* const redoIn[4], hipStream_t stream)
+{
+    const size_t framePixels = (size_t)a.width * (size_t)a.height;
+    HIP_TRY(ctx, launchCollectTiedPixels(ctx->dTieBits, (unsigned)((framePixels + 31u) / 32u), ctx->dTieRedo, kTieRedoCapacity, a.chainIndependent ? a.chainCount : 1u, a.overflowFlag + 1,
+                                         tie.triangles ? kTieWatchBusy : 0xffffffffu, stream),
+            RTOW_ERROR_LAUNCH_FAILURE);
+    SampleKernelArgs r = a;
+    r.layout.exactTies = 1u;
+    r.redoMode = 1;
+    r.tune[7] &= 255;                      // (the exact-tie kernels have no lanes in a hurry: the pixel gate alone)
+    r.tieBits = nullptr;
+    r.tieRedo = ctx->dTieRedo;
+    r.tieRedoCapacity = kTieRedoCapacity;
+    r.inColor = redoIn[0]; r.inNormal = redoIn[1]; r.inAlbedo = redoIn[2]; r.inScw = redoIn[3];
+    r.pixelCost = nullptr;
+    r.chunkOrder = nullptr;
+    r.pixelCandidates = a.pixelCandidates;
+    r.hitSpill = ctx->redoSpillEntries ? ctx->dRedoSpill : nullptr;
+    r.hitSpillEntries = ctx->redoSpillEntries;
+    r.hitSpillStride = (uint32_t)kTieRedoBlocks * (uint32_t)kBlockThreads;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->dWorkCounter, 0, sizeof(unsigned int), stream), RTOW_ERROR_LAUNCH_FAILURE);
+    HIP_TRY(ctx, launchSampleBatch(r, kTieRedoBlocks < ctx->cuCount ? kTieRedoBlocks : ctx->cuCount, stream), RTOW_ERROR_LAUNCH_FAILURE);
+    return RTOW_SUCCESS;
+}
+
+// The batch itself: the launch (timed, with its tie fix-up and the fold of per-sample records), then the order for the next batch from what this one measured
+int enqueueLaunch(RtowContext ctx, const RtowSampleParams* p, SampleKernelArgs& a, int blocks, const TieWatch& tie, const OrderPlan& order, hipStream_t stream)
+{
+    const float* redoIn[4] = {a.inColor, a.inNormal, a.inAlbedo, a.inScw};
+    if (tie.on) RTOW_TRY(prepareTieInputs(ctx, p, a, tie, redoIn, stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->dWorkCounter, 0, sizeof(unsigned int), stream), RTOW_ERROR_LAUNCH_FAILURE);
+    HIP_TRY(ctx, hipEventRecord(ctx->evStart, stream), RTOW_ERROR_LAUNCH_FAILURE);
+    HIP_TRY(ctx, launchSampleBatch(a, blocks, stream), RTOW_ERROR_LAUNCH_FAILURE);
+    if (tie.on) RTOW_TRY(launchTieFixup(ctx, a, tie, redoIn, stream));
+    if (a.unitRecords) HIP_TRY(ctx, launchFoldUnitRecords(a, stream), RTOW_ERROR_LAUNCH_FAILURE);   // inside the timed region: part of the batch
+    HIP_TRY(ctx, hipEventRecord(ctx->evStop, stream), RTOW_ERROR_LAUNCH_FAILURE);
+    // refresh the order for the next batch from what this one measured (same stream, after the timed kernel)
+    if (order.mapped) RTOW_TRY(regroupTickets(ctx, a, std::max(1u, a.sampleCountMin), stream));
+    // (development: schedulerTune[7] + 64 orders the chunks by their TOTAL ray count instead of by their most expensive pixel)
+    if (order.want) HIP_TRY(ctx, launchBuildChunkOrder(ctx->dPixelCost, ctx->dChunkCost, a.chunkCount, ctx->dChunkOrder, ctx->orderByTotal ? 0 : 1, stream), RTOW_ERROR_LAUNCH_FAILURE);
+    HIP_TRY(ctx, hipEventRecord(ctx->evBatchDone, stream), RTOW_ERROR_LAUNCH_FAILURE);
+    ctx->haveBatchDone = true;
+    ctx->haveTiming = true;
+    return RTOW_SUCCESS;
+}
+
+// One launch of one batch, a chain or a group (chain), enqueued on `stream` behind everything the context's previous batch enqueued.
+// extremaIn (optional): device memory the kernel reads the SampleCountWeightExtrema from instead of p's (rtowSampleBatchChainAdaptiveDevice)
+int launchSample(RtowContext ctx, const RtowSampleParams* p, const RtowAccumBuffers* in, const RtowAccumBuffers* out, void* diag,
+                 hipStream_t stream, bool useCancelFlag, const ChainSpec* chain = nullptr, const RtowFloat2* extremaIn = nullptr)
+{
+    SampleKernelArgs a{};
+    RTOW_TRY(buildArgs(ctx, p, in, out, diag, useCancelFlag, chain, extremaIn, a));
+    RTOW_TRY(planHistory(ctx, p, a));
+    setSchedulerValues(ctx, p, a);                       // (the hurry rate reads a.layout.exactTies before the triangle tie watch clears it)
+    const uint32_t ownedPixels = a.totalWork;
+    if (ownedPixels == 0) return recordEmptyBatch(ctx, stream);
+    RTOW_TRY(planUnits(ctx, p, a));
+    TieWatch tie;
+    RTOW_TRY(prepareTieWatch(ctx, p, in, out, a, tie));
 
     // ---- launch geometry: one persistent 1024-lane workgroup per CU (four waves per SIMD).  Smaller workgroups for launches that own about one pixel
     // per resident lane were built, measured and removed: results never depended on it.
@@ -525,273 +837,13 @@ int launchSample(RtowContext ctx, const RtowSampleParams* p, const RtowAccumBuff
     // Batches of one context share its ticket counter, cost map, chunk order and candidate lists, and each one consumes what the
     // previous one produced: whatever stream this batch was given, it starts after everything the previous batch enqueued.
     if (ctx->haveBatchDone) HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->evBatchDone, 0), RTOW_ERROR_LAUNCH_FAILURE);
-
-    // ---- camera-ray candidate lists: one conservative beam walk per pixel, reused by all its samples (and by later batches of the same view) ----
-    if (!(ctx->flags & RTOW_CONTEXT_NO_CAMERA_RAY_LISTS)) {
-        const size_t pixels = (size_t)a.width * (size_t)a.height;
-        const size_t listBytes = pixels * sizeof(uint4);      // 8 x 16-bit node codes per pixel; 4 x 32-bit with wide codes
-        if (listBytes > ctx->pixCandCapacity) {
-            if (ctx->dPixCand) (void)hipFree(ctx->dPixCand);
-            ctx->dPixCand = nullptr;
-            ctx->pixCandCapacity = 0;
-            HIP_TRY(ctx, hipMalloc(&ctx->dPixCand, listBytes), RTOW_ERROR_MEMORY_ALLOCATION);
-            ctx->pixCandCapacity = listBytes;
-            ctx->pixCandValid = false;
-        }
-        const bool same = ctx->pixCandValid && ctx->pixCandScene == ctx->sceneSerial && memcmp(&ctx->pixCandView, &a.view, sizeof(RtowView)) == 0 &&
-                          ctx->pixCandW == a.width && ctx->pixCandH == a.height && ctx->pixCandOff == a.sliceOffset && ctx->pixCandDiv == a.sliceDivider &&
-                          ctx->pixCandJitter == (a.subPixelJitter ? 1 : 0);
-        if (!same) {
-            SampleKernelArgs perPixel = a;                       // the lists are per pixel whatever the work units are
-            perPixel.totalWork = ownedPixels;
-            HIP_TRY(ctx, launchPrimaryCandidates(perPixel, ctx->dPixCand, stream), RTOW_ERROR_LAUNCH_FAILURE);
-            ctx->pixCandValid = true;
-            ctx->pixCandScene = ctx->sceneSerial;
-            ctx->pixCandView = a.view;
-            ctx->pixCandW = a.width; ctx->pixCandH = a.height; ctx->pixCandOff = a.sliceOffset; ctx->pixCandDiv = a.sliceDivider;
-            ctx->pixCandJitter = a.subPixelJitter ? 1 : 0;
-        }
-        a.pixelCandidates = ctx->dPixCand;
-    }
-
-    // ---- chunk order: most expensive 64-pixel chunks first, from the ray counts of the previous launch (or of a probe) ----
-    a.chunkCount = (a.totalWork + 63u) / 64u;
-    const bool wantOrder = a.chunkCount >= (uint32_t)(4 * ctx->cuCount) && !(ctx->flags & RTOW_CONTEXT_NO_CHUNK_ORDER);   // tiny frames: not worth it
-    // ---- and which pixels share a chunk (a wave): the pixels of a super-tile of regroupSide x regroupSide tiles sorted by the ray counts of the previous launch and dealt out
-    // 64 at a time (regroup_tickets_kernel), re-sorted behind every launch like the order.  Reference stream only (per-sample units are alike by construction).
-    // schedulerTune[7]: 1 = no map; 3 = the tiles as they are, each tile's tickets most expensive first (regroupSide 1 below); 2 / 4 / 8 (+ 16 x mode) = super-tiles of that many tiles
-    const unsigned knob = (unsigned)(ctx->regroupSide & 15);
-    const unsigned regroupSide = knob == 3u ? 1u : (knob == 2u || knob == 4u || knob == 8u) ? knob : 0u;
-    // (development: schedulerTune[7] = side + 16 * mode; mode 0 sorts by the ray count itself, 1 by sky / not sky, 2 by four classes of rays per sample - pixels of a class in tile order)
-    const unsigned regroupMode = ((unsigned)ctx->regroupSide >> 4) & 3u;
-    // batch groups: (chunk, batch) slots a wave reserves at a time (schedulerTune[7] bits 8 .. 11 override the default for A/B runs)
-    a.slotBlock = (((unsigned)ctx->regroupSide >> 8) & 15u) ? (((unsigned)ctx->regroupSide >> 8) & 15u) : kGroupSlotBlock;
-    if ((((unsigned)ctx->regroupSide >> 8) & 15u) == 0u) {
-        // Reserving several (chunk, batch) slots per pull pays where a wave has dozens of them to work through (a whole frame's group: 79 slots per wave, +1.8 %); a launch that
-        // owns a few slots per wave - the sub-batches of an 8-way row slice: 7.9 - must balance with single slots (profiles/r06j_partitions_c2.json: 10.9 ms per step against the
-        // 7.9 of round 5's single slots)
-        const uint64_t slotsPerWave = (uint64_t)a.chunkCount * a.chainCount / ((uint64_t)blocks * (uint64_t)(kBlockThreads / 64));
-        if (slotsPerWave < 32u) a.slotBlock = 1u;
-        else if (slotsPerWave < 64u && a.slotBlock > 2u) a.slotBlock = 2u;
-    }
-    auto regroupClasses = [&](unsigned floorCost, unsigned out[3]) {
-        if (regroupSide == 1u) { out[0] = regroupMode == 0u ? 0u : (2u << regroupMode); out[1] = out[2] = 0u; return; }      // tile order: levels of the tile's cost range (mode 1 / 2 / 3: 4 / 8 / 16), 0 = by the ray count itself
-        out[0] = regroupMode == 0u ? 0u : floorCost; out[1] = regroupMode >= 2u ? (floorCost * 11u) / 4u : 0xffffffffu; out[2] = regroupMode >= 2u ? floorCost * 4u : 0xffffffffu;
-    };
-    const bool wantMap = wantOrder && regroupSide >= 1u && a.tiledPixels != 0u && !a.unitRecords;
-    const unsigned tileRows = a.tilesPerRow ? a.tiledPixels / (64u * a.tilesPerRow) : 0u;
-    if (wantOrder) {
-        if (a.chunkCount > ctx->chunkCapacity) {
-            if (ctx->dChunkCost) { (void)hipFree(ctx->dChunkCost); (void)hipFree(ctx->dChunkOrder); (void)hipFree(ctx->dPixelCost); (void)hipFree(ctx->dTicketMap); }
-            ctx->dChunkCost = ctx->dChunkOrder = nullptr;
-            ctx->dPixelCost = nullptr;
-            ctx->dTicketMap = nullptr;
-            ctx->chunkCapacity = 0;
-            HIP_TRY(ctx, hipMalloc(&ctx->dChunkCost, (2 * (size_t)a.chunkCount + kChunkOrderScratchWords) * sizeof(unsigned)), RTOW_ERROR_MEMORY_ALLOCATION);
-            HIP_TRY(ctx, hipMalloc(&ctx->dChunkOrder, a.chunkCount * sizeof(unsigned)), RTOW_ERROR_MEMORY_ALLOCATION);
-            HIP_TRY(ctx, hipMalloc(&ctx->dPixelCost, (size_t)a.chunkCount * 64 * sizeof(unsigned short)), RTOW_ERROR_MEMORY_ALLOCATION);
-            HIP_TRY(ctx, hipMalloc(&ctx->dTicketMap, (size_t)a.chunkCount * 64 * sizeof(unsigned)), RTOW_ERROR_MEMORY_ALLOCATION);
-            ctx->chunkCapacity = a.chunkCount;
-            ctx->orderValid = false;
-        }
-        if (ctx->orderW != a.width || ctx->orderH != a.height || ctx->orderOff != a.sliceOffset || ctx->orderDiv != a.sliceDivider || ctx->orderGroups != a.groupsPerPixel ||
-            ctx->orderMapped != wantMap) ctx->orderValid = false;
-        a.pixelCost = ctx->dPixelCost;
-        a.ticketMap = wantMap ? ctx->dTicketMap : nullptr;
-        bool haveOrder = true;
-        if (!ctx->orderValid && a.unitRecords) {
-            // per-sample units are small and alike: the first batch simply runs in natural order and records the map for the next
-            HIP_TRY(ctx, hipMemsetAsync(ctx->dPixelCost, 0, (size_t)a.chunkCount * 64 * sizeof(unsigned short), stream), RTOW_ERROR_LAUNCH_FAILURE);
-            haveOrder = false;
-            ctx->orderValid = true;
-            ctx->orderW = a.width; ctx->orderH = a.height; ctx->orderOff = a.sliceOffset; ctx->orderDiv = a.sliceDivider; ctx->orderGroups = a.groupsPerPixel;
-            ctx->orderMapped = false;
-        }
-        if (!ctx->orderValid) {
-            // no cost map yet for this frame configuration: a 1-sample-per-pixel probe of the same kernel (stores nothing else)
-            SampleKernelArgs probe = a;
-            probe.probeOnly = 1;
-            probe.chunkOrder = nullptr;
-            probe.ticketMap = nullptr;                           // the probe runs over the tiles themselves; the map starts from them
-            if (wantMap) HIP_TRY(ctx, launchInitTicketMap(ctx->dTicketMap, a.tiledPixels, stream), RTOW_ERROR_LAUNCH_FAILURE);
-            probe.cancelFlag = nullptr;
-            probe.chainCount = 1;                                // one pass over the pixels, whatever the launch it prepares
-            HIP_TRY(ctx, hipMemsetAsync(ctx->dWorkCounter, 0, sizeof(unsigned int), stream), RTOW_ERROR_LAUNCH_FAILURE);
-            HIP_TRY(ctx, hipMemsetAsync(ctx->dPixelCost, 0, (size_t)a.chunkCount * 64 * sizeof(unsigned short), stream), RTOW_ERROR_LAUNCH_FAILURE);   // the last chunk's tail
-            HIP_TRY(ctx, launchSampleBatch(probe, blocks, stream), RTOW_ERROR_LAUNCH_FAILURE);
-            if (wantMap) { unsigned cls[3]; regroupClasses(1u, cls); HIP_TRY(ctx, launchRegroupTickets(ctx->dPixelCost, ctx->dTicketMap, a.tilesPerRow, tileRows, regroupSide, cls, stream), RTOW_ERROR_LAUNCH_FAILURE); }
-            HIP_TRY(ctx, launchBuildChunkOrder(ctx->dPixelCost, ctx->dChunkCost, a.chunkCount, ctx->dChunkOrder, 0, stream), RTOW_ERROR_LAUNCH_FAILURE);
-            ctx->orderValid = true;
-            ctx->orderW = a.width; ctx->orderH = a.height; ctx->orderOff = a.sliceOffset; ctx->orderDiv = a.sliceDivider; ctx->orderGroups = a.groupsPerPixel;
-            ctx->orderMapped = wantMap;
-        }
-        a.chunkOrder = haveOrder ? ctx->dChunkOrder : nullptr;
-
-        // ---- stage thresholds: measured once per scene on this batch's own kernel, frame and view (see kTuneProbeSamples) ----
-        // Never waited for: the probes are enqueued in front of a batch, timed with events, and a LATER call that finds the last event complete reads them
-        // and switches the thresholds (scheduling only: no result depends on when that happens).  Until then the kernel kind's built-in values run.
-        for (int k = 0; k < 7; k++) a.tune[k] = ctx->tune[k] < 1 ? 1 : ctx->tune[k];
-        if (ctx->tunePending && ctx->tunePendingScene == ctx->sceneSerial && finishThresholdTuning(ctx, /*wait*/ false))
-            for (int k = 0; k < 7; k++) a.tune[k] = ctx->tune[k] < 1 ? 1 : ctx->tune[k];
-        ctx->sppSinceUpload += (uint64_t)a.chainCount * (a.sampleCountMax > a.sampleCountMin ? a.sampleCountMax : a.sampleCountMin);
-        hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;                   // a stream that is being captured into a graph cannot carry the event pairs: no measurement then
-        if (hipStreamIsCapturing(stream, &capturing) != hipSuccess) { (void)hipGetLastError(); capturing = hipStreamCaptureStatusNone; }
-        // worth it only where the scene is rendered for longer than the probes take (3 or 6 candidates x 3 repeats x 4 samples per pixel: 40 - 76 samples per
-        // pixel): a one-shot render of a few samples per pixel (BASELINE.json configs[0]: 8) must not pay several times its own work first
-        const bool worthIt = ctx->sppSinceUpload >= kTuneMinSamplesPerPixel;
-        if (!ctx->userTune && !(ctx->flags & RTOW_CONTEXT_NO_THRESHOLD_TUNING) && ctx->tunedScene != ctx->sceneSerial && !ctx->tunePending && !a.unitRecords && haveOrder &&
-            worthIt && capturing == hipStreamCaptureStatusNone) {
-            constexpr int kFamilies = 3;
-            static const int kSets[kFamilies][9] = {{RTOW_DEFAULT_TUNE}, {RTOW_GENERAL_TUNE}, {RTOW_GENERAL_TUNE_2}};     // (the ninth value, the walk slice, is set by rtowUploadScene)
-            const bool volumes = a.layout.sceneKind == SCENE_KIND_VOLUMES || a.layout.sceneKind == SCENE_KIND_VOLUMES_TEXTURED;
-            const int candidates = volumes ? 2 * kFamilies : kFamilies;                      // volume kinds: each family also with the volume stage from half of the live lanes
-            const int launches = candidates * kTuneProbeRepeats;
-            ctx->tuneEvents.assign((size_t)launches + 1, nullptr);
-            bool ok = true;
-            for (auto& e : ctx->tuneEvents) ok = ok && hipEventCreate(&e) == hipSuccess;
-            if (!ctx->dProbeSink) ok = ok && hipMalloc(&ctx->dProbeSink, 64) == hipSuccess;
-            SampleKernelArgs probe = a;
-            probe.probeOnly = kTuneProbeSamples;
-            probe.pixelCost = nullptr;                           // the cost map stays the cost probe's (or the previous batch's)
-            probe.cancelFlag = nullptr;
-            probe.overflowFlag = ctx->dProbeSink;                // a probe's ray beyond the hit-list capacity is not the batch's (which may trace fewer samples than a probe)
-            probe.chainCount = 1;
-            probe.chainIndependent = 0;
-            // one untimed probe first: clocks, L2 and the instruction cache are warm before the first timed one
-            for (int k = 0; k < 7; k++) probe.tune[k] = kSets[0][k];
-            if (ok) ok = hipMemsetAsync(ctx->dWorkCounter, 0, sizeof(unsigned int), stream) == hipSuccess && launchSampleBatch(probe, blocks, stream) == hipSuccess;
-            if (ok) ok = hipEventRecord(ctx->tuneEvents[0], stream) == hipSuccess;
-            for (int l = 0; ok && l < launches; l++) {
-                const int c = l % candidates;
-                for (int k = 0; k < 7; k++) probe.tune[k] = kSets[c % kFamilies][k];
-                if (c >= kFamilies) probe.tune[5] = 32;
-                ok = hipMemsetAsync(ctx->dWorkCounter, 0, sizeof(unsigned int), stream) == hipSuccess && launchSampleBatch(probe, blocks, stream) == hipSuccess &&
-                     hipEventRecord(ctx->tuneEvents[(size_t)l + 1], stream) == hipSuccess;
-            }
-            if (ok) {
-                ctx->tunePending = true;
-                ctx->tunePendingScene = ctx->sceneSerial;
-                ctx->tuneCandidates = candidates;
-                ctx->tuneBuiltin = a.layout.sceneKind <= SCENE_KIND_SPHERES_MOTION ? 0 : 1;       // what rtowUploadScene set for this kernel kind
-            } else {
-                (void)hipGetLastError();
-                dropThresholdTuning(ctx);
-                ctx->tunedCandidate = -1;
-                ctx->tunedScene = ctx->sceneSerial;             // not measurable: do not try again for this scene
-                logf(ctx, 2, "tune", "threshold probes failed; the per-kind values stay");
-            }
-        }
-    }
-
-    {
-        // Plain or chained launches with paths deeper than 16 segments are bound by their slowest pixels (see "lanes in a hurry" above), not by lane occupancy: a static-sphere scene
-        // that is whole in LDS runs them with REGEN from a quarter of the live lanes, HIT from 3/8, and the walk's hand-over at 4 candidates (profiles/r06u_deep_plain_launch_thresholds.json:
-        // +7 ... +10 %; the same values cost batch groups 2.8 %, launches at depth <= 16 1.3 ... 3 %, moving spheres 2 %, and 10 000 spheres - next to the lanes in a hurry - 2 %)
-        static const int kDefault[9] = {RTOW_DEFAULT_TUNE};
-        if (!ctx->userTune && !a.chainIndependent && a.traceDepth > 16 && p->rngPolicy == RTOW_RNG_REFERENCE && a.layout.sceneKind == SCENE_KIND_SPHERES && a.ldsSceneBytes == a.layout.totalBytes &&
-            a.tune[0] == kDefault[0] && a.tune[3] == kDefault[3] && a.tune[6] == kDefault[6]) {
-            a.tune[0] = 16; a.tune[3] = 24; a.tune[6] = 4;
-        }
-    }
-    if (a.chainCount > 1u && a.chainIndependent) {
-        // a batch group: nothing is handed over between its batches; only the per-batch table (seed, diagnostics, outputs)
-        if (!ctx->dChainBatches) HIP_TRY(ctx, hipMalloc(&ctx->dChainBatches, sizeof(ChainBatch) * kMaxChain), RTOW_ERROR_MEMORY_ALLOCATION);
-        ChainBatch table[kMaxChain] = {};
-        for (int b = 0; b < chain->count; b++) {
-            table[b].seed = chain->seeds[b];
-            table[b].diagnostics = chain->diags ? (uint8_t*)chain->diags[b] : nullptr;
-            table[b].outColor = chain->outs[b].color; table[b].outNormal = chain->outs[b].normal; table[b].outAlbedo = chain->outs[b].albedo; table[b].outScw = chain->outs[b].sampleCountWeight;
-        }
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->dChainBatches, table, sizeof(ChainBatch) * (size_t)chain->count, hipMemcpyHostToDevice, stream), RTOW_ERROR_LAUNCH_FAILURE);
-        a.chainBatches = ctx->dChainBatches;
-    } else if (a.chainCount > 1u) {
-        // per-chunk hand-off counters of the chain: pixels stored so far (all batches); batch b of a chunk waits for b x its pixels
-        if (a.chunkCount > ctx->chunkDoneCapacity) {
-            if (ctx->dChunkDone) (void)hipFree(ctx->dChunkDone);
-            if (ctx->dXcdState) (void)hipFree(ctx->dXcdState);
-            ctx->dChunkDone = nullptr;
-            ctx->dXcdState = nullptr;
-            ctx->chunkDoneCapacity = 0;
-            HIP_TRY(ctx, hipMalloc(&ctx->dChunkDone, (size_t)a.chunkCount * sizeof(unsigned)), RTOW_ERROR_MEMORY_ALLOCATION);
-            HIP_TRY(ctx, hipMalloc(&ctx->dXcdState, sizeof(XcdState) + (size_t)kMaxXcds * a.chunkCount * sizeof(unsigned)), RTOW_ERROR_MEMORY_ALLOCATION);
-            ctx->chunkDoneCapacity = a.chunkCount;
-        }
-        HIP_TRY(ctx, hipMemsetAsync(ctx->dChunkDone, 0, (size_t)a.chunkCount * sizeof(unsigned), stream), RTOW_ERROR_LAUNCH_FAILURE);
-        a.chunkDone = ctx->dChunkDone;
-        // chunk ownership per XCD: counters zero, list entries "not written yet" (the kernel indexes the lists with THIS launch's chunkCount)
-        HIP_TRY(ctx, hipMemsetAsync(ctx->dXcdState, 0, sizeof(XcdState), stream), RTOW_ERROR_LAUNCH_FAILURE);
-        HIP_TRY(ctx, hipMemsetAsync(ctx->dXcdState + sizeof(XcdState), 0xff, (size_t)kMaxXcds * a.chunkCount * sizeof(unsigned), stream), RTOW_ERROR_LAUNCH_FAILURE);
-        a.xcdState = reinterpret_cast<XcdState*>(ctx->dXcdState);
-        // what differs between the chain's batches, indexed per lane by the kernel: a small table in device memory, written in stream order
-        // (the previous chain's kernel may still be reading its own table: this copy is enqueued behind it)
-        if (!ctx->dChainBatches) HIP_TRY(ctx, hipMalloc(&ctx->dChainBatches, sizeof(ChainBatch) * kMaxChain), RTOW_ERROR_MEMORY_ALLOCATION);
-        ChainBatch table[kMaxChain] = {};
-        for (int b = 0; b < chain->count; b++) {
-            table[b].seed = chain->seeds[b];
-            table[b].diagnostics = chain->diags ? (uint8_t*)chain->diags[b] : nullptr;
-            table[b].extrema = chain->extrema ? chain->extrema[b] : nullptr;
-        }
-        a.extremaKeys = chain->extremaKeys;
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->dChainBatches, table, sizeof(ChainBatch) * (size_t)chain->count, hipMemcpyHostToDevice, stream), RTOW_ERROR_LAUNCH_FAILURE);
-        a.chainBatches = ctx->dChainBatches;
-    }
-    const float* redoIn[4] = {a.inColor, a.inNormal, a.inAlbedo, a.inScw};
-    if (tieWatch) {
-        const size_t framePixels = (size_t)a.width * (size_t)a.height;
-        HIP_TRY(ctx, hipMemsetAsync(ctx->dTieRedo, 0, 4u * sizeof(unsigned), stream), RTOW_ERROR_LAUNCH_FAILURE);
-        HIP_TRY(ctx, hipMemsetAsync(ctx->dTieBits, 0, ((framePixels + 31u) / 32u) * sizeof(unsigned), stream), RTOW_ERROR_LAUNCH_FAILURE);
-        if (inPlace) {
-            // the fix-up launch renders a marked pixel again from the launch's inputs, which an in-place launch overwrites: they are copied first (44 B per pixel through HBM,
-            // ~0.05 ms at 1920 x 1080 against a batch's tens of milliseconds)
-            static const size_t comps[4] = {4, 3, 3, 1};
-            float* at = ctx->dTieInputs;
-            const size_t rows = (size_t)ownedRows(p);                // the rows this launch writes (row % SliceDivider == SliceOffset), at their places in the frame
-            for (int k = 0; k < 4; k++) {
-                const size_t rowBytes = (size_t)a.width * comps[k] * sizeof(float), first = (size_t)a.sliceOffset * rowBytes, pitch = (size_t)a.sliceDivider * rowBytes;
-                HIP_TRY(ctx, hipMemcpy2DAsync((uint8_t*)at + first, pitch, (const uint8_t*)redoIn[k] + first, pitch, rowBytes, rows, hipMemcpyDeviceToDevice, stream), RTOW_ERROR_LAUNCH_FAILURE);
-                redoIn[k] = at;
-                at += framePixels * comps[k];
-            }
-        }
-        a.tieBits = ctx->dTieBits;
-    }
-    HIP_TRY(ctx, hipMemsetAsync(ctx->dWorkCounter, 0, sizeof(unsigned int), stream), RTOW_ERROR_LAUNCH_FAILURE);
-    HIP_TRY(ctx, hipEventRecord(ctx->evStart, stream), RTOW_ERROR_LAUNCH_FAILURE);
-    HIP_TRY(ctx, launchSampleBatch(a, blocks, stream), RTOW_ERROR_LAUNCH_FAILURE);
-    if (tieWatch) {
-        // the fix-up: marked pixels -> list -> the exact-tie kernel of the same kind over the list (almost always empty: that kernel then leaves before it stages the scene).
-        // A chain's pixel is listed once and carried through all its batches; a group's once per batch.
-        const size_t framePixels = (size_t)a.width * (size_t)a.height;
-        HIP_TRY(ctx, launchCollectTiedPixels(ctx->dTieBits, (unsigned)((framePixels + 31u) / 32u), ctx->dTieRedo, kTieRedoCapacity, a.chainIndependent ? a.chainCount : 1u, a.overflowFlag + 1,
-                                             triWatch ? kTieWatchBusy : 0xffffffffu, stream),
-                RTOW_ERROR_LAUNCH_FAILURE);
-        SampleKernelArgs r = a;
-        r.layout.exactTies = 1u;
-        r.redoMode = 1;
-        r.tune[7] &= 255;                      // (the exact-tie kernels have no lanes in a hurry: the pixel gate alone)
-        r.tieBits = nullptr;
-        r.tieRedo = ctx->dTieRedo;
-        r.tieRedoCapacity = kTieRedoCapacity;
-        r.inColor = redoIn[0]; r.inNormal = redoIn[1]; r.inAlbedo = redoIn[2]; r.inScw = redoIn[3];
-        r.pixelCost = nullptr;
-        r.chunkOrder = nullptr;
-        r.pixelCandidates = a.pixelCandidates;
-        r.hitSpill = ctx->redoSpillEntries ? ctx->dRedoSpill : nullptr;
-        r.hitSpillEntries = ctx->redoSpillEntries;
-        r.hitSpillStride = (uint32_t)kTieRedoBlocks * (uint32_t)kBlockThreads;
-        HIP_TRY(ctx, hipMemsetAsync(ctx->dWorkCounter, 0, sizeof(unsigned int), stream), RTOW_ERROR_LAUNCH_FAILURE);
-        HIP_TRY(ctx, launchSampleBatch(r, kTieRedoBlocks < ctx->cuCount ? kTieRedoBlocks : ctx->cuCount, stream), RTOW_ERROR_LAUNCH_FAILURE);
-    }
-    if (a.unitRecords) HIP_TRY(ctx, launchFoldUnitRecords(a, stream), RTOW_ERROR_LAUNCH_FAILURE);   // inside the timed region: part of the batch
-    HIP_TRY(ctx, hipEventRecord(ctx->evStop, stream), RTOW_ERROR_LAUNCH_FAILURE);
-    // refresh the order for the next batch from what this one measured (same stream, after the timed kernel)
-    if (wantMap) { unsigned cls[3]; regroupClasses(std::max(1u, a.sampleCountMin), cls); HIP_TRY(ctx, launchRegroupTickets(ctx->dPixelCost, ctx->dTicketMap, a.tilesPerRow, tileRows, regroupSide, cls, stream), RTOW_ERROR_LAUNCH_FAILURE); }
-    // (development: schedulerTune[7] + 64 orders the chunks by their TOTAL ray count instead of by their most expensive pixel)
-    if (wantOrder) HIP_TRY(ctx, launchBuildChunkOrder(ctx->dPixelCost, ctx->dChunkCost, a.chunkCount, ctx->dChunkOrder, (ctx->regroupSide & 64) ? 0 : 1, stream), RTOW_ERROR_LAUNCH_FAILURE);
-    HIP_TRY(ctx, hipEventRecord(ctx->evBatchDone, stream), RTOW_ERROR_LAUNCH_FAILURE);
-    ctx->haveBatchDone = true;
-    ctx->haveTiming = true;
-    return RTOW_SUCCESS;
+    RTOW_TRY(refreshCameraRays(ctx, a, ownedPixels, stream));
+    OrderPlan order;
+    RTOW_TRY(prepareChunkOrder(ctx, a, blocks, stream, order));
+    if (order.want) measureThresholds(ctx, a, blocks, order.have, stream);
+    applyDeepPlainThresholds(ctx, p, a);                 // (after a finished measurement may have replaced a.tune[0 .. 6])
+    RTOW_TRY(writeBatchTable(ctx, chain, a, stream));
+    return enqueueLaunch(ctx, p, a, blocks, tie, order, stream);
 }
 
 // Most surfaces one ray may meet where whole hit lists are kept: the caller's bound if it gave one, else a default that GROWS (growHitList) - the
@@ -811,14 +863,8 @@ int sizeHitSpill(RtowContext ctx, uint32_t sceneKind, bool exactTies, int entity
     const uint64_t cap = listCapacity(ctx, volumes);
     if (most > cap) most = cap;
     const uint32_t entries = most > (uint64_t)kLocalHitEntries ? (uint32_t)(most - kLocalHitEntries) : 0u;
-    if (entries > ctx->hitSpillCapacity) {
-        if (ctx->dHitSpill) (void)hipFree(ctx->dHitSpill);
-        ctx->dHitSpill = nullptr;
-        ctx->hitSpillCapacity = 0;
-        ctx->hitSpillEntries = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->dHitSpill, (size_t)entries * (size_t)ctx->cuCount * kBlockThreads * sizeof(uint4)), RTOW_ERROR_MEMORY_ALLOCATION);
-        ctx->hitSpillCapacity = entries;
-    }
+    if (entries > ctx->hitSpillCapacity) ctx->hitSpillEntries = 0;
+    RTOW_TRY(growDevice(ctx, ctx->hitSpillCapacity, entries, {devBuf(ctx->dHitSpill, (size_t)entries * (size_t)ctx->cuCount * kBlockThreads * sizeof(uint4))}));
     ctx->hitSpillEntries = entries;
     return RTOW_SUCCESS;
 }
@@ -923,25 +969,14 @@ uint8_t* mappedHost(RtowContext ctx, const void* p, size_t bytes)
     return nullptr;
 }
 
-int ensureStaging(RtowContext ctx, size_t pixels, size_t diagBytes)
+// The host-buffer calls' grow-only staging: the frame's four accumulators, and one diagnostics frame per batch - devDiag[b], null for a batch without a buffer
+int prepareStaging(RtowContext ctx, int count, const RtowSampleParams* p, void* const* diagnostics, std::vector<void*>& devDiag)
 {
-    if (pixels > ctx->stagingPixels) {
-        if (ctx->dColor) { (void)hipFree(ctx->dColor); (void)hipFree(ctx->dNormal); (void)hipFree(ctx->dAlbedo); (void)hipFree(ctx->dScw); }
-        ctx->dColor = ctx->dNormal = ctx->dAlbedo = ctx->dScw = nullptr;
-        ctx->stagingPixels = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->dColor, pixels * 16), RTOW_ERROR_MEMORY_ALLOCATION);
-        HIP_TRY(ctx, hipMalloc(&ctx->dNormal, pixels * 12), RTOW_ERROR_MEMORY_ALLOCATION);
-        HIP_TRY(ctx, hipMalloc(&ctx->dAlbedo, pixels * 12), RTOW_ERROR_MEMORY_ALLOCATION);
-        HIP_TRY(ctx, hipMalloc(&ctx->dScw, pixels * 4), RTOW_ERROR_MEMORY_ALLOCATION);
-        ctx->stagingPixels = pixels;
-    }
-    if (diagBytes > ctx->stagingDiagBytes) {
-        if (ctx->dDiag) (void)hipFree(ctx->dDiag);
-        ctx->dDiag = nullptr;
-        ctx->stagingDiagBytes = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->dDiag, diagBytes), RTOW_ERROR_MEMORY_ALLOCATION);
-        ctx->stagingDiagBytes = diagBytes;
-    }
+    const size_t pixels = (size_t)(int)p->size.x * (size_t)(int)p->size.y, diagBytes = pixels * (size_t)p->diagnosticsStride;
+    RTOW_TRY(growDevice(ctx, ctx->stagingPixels, pixels, {devBuf(ctx->dColor, pixels * 16), devBuf(ctx->dNormal, pixels * 12), devBuf(ctx->dAlbedo, pixels * 12), devBuf(ctx->dScw, pixels * 4)}));
+    RTOW_TRY(growDevice(ctx, ctx->stagingDiagBytes, diagnostics ? diagBytes * (size_t)count : 0, {devBuf(ctx->dDiag, diagBytes * (size_t)count)}));
+    devDiag.assign((size_t)count, nullptr);
+    if (diagnostics) for (int b = 0; b < count; b++) devDiag[(size_t)b] = diagnostics[b] ? ctx->dDiag + (size_t)b * diagBytes : nullptr;
     return RTOW_SUCCESS;
 }
 
@@ -1013,47 +1048,124 @@ RcclApi* rccl()
 // rows of the frame owned by `rank` under the reference's interlacing (row % divider == rank, JOBS/SampleBatchJob.cs:69-70)
 unsigned rowsOwnedBy(int rank, int divider, int height) { return rank >= height ? 0u : (unsigned)((height - rank + divider - 1) / divider); }
 
-// `count` successive batches (batch 0 reads `in`, every later one what its predecessor wrote to `out`), enqueued on `stream`: as ONE launch per
-// group of up to kMaxChain batches when they differ in nothing but Seed, else one after the other (what the chain is defined to equal).
-// The caller holds ctx->mu and has validated params / buffers.
-int enqueueChain(RtowContext ctx, int count, const RtowSampleParams* params, const RtowAccumBuffers* in, const RtowAccumBuffers* out, void* const* diagnostics,
-                 hipStream_t s, const volatile uint8_t* cancel)
+// Whether the `count` batches of one call may share launches: they differ in nothing but Seed (the reference's successive batches of a frame: UNITY/Raytracer.cs:656-661) -
+// and SampleCountWeightExtrema where `extremaFree` (the adaptive call: each batch reads its own from device memory) - under the reference RNG policy (per-sample units
+// fold through records), in a frame of fewer than 2^27 padded owned pixels.  Batches of a chain hand accumulators over inside the launch (handOver): only where this
+// device passed the same-XCD litmus (ctx->chainFusion); the batches of a group hand nothing over.
+bool canFuse(const RtowContext_t* ctx, int count, const RtowSampleParams* params, void* const* diagnostics, bool handOver, bool extremaFree)
 {
-    // One launch needs batches that differ in nothing but Seed (the reference's successive batches of a frame: UNITY/Raytracer.cs:656-661),
-    // the reference RNG policy (per-sample units fold through records) and a frame of fewer than 2^27 padded pixels.
-    bool fusable = params[0].rngPolicy == RTOW_RNG_REFERENCE && ctx->chainFusion;
-    for (int b = 1; b < count && fusable; b++) {
+    if (params[0].rngPolicy != RTOW_RNG_REFERENCE || (handOver && !ctx->chainFusion)) return false;
+    for (int b = 1; b < count; b++) {
         RtowSampleParams q = params[b];
         q.seed = params[0].seed;
-        fusable = memcmp(&q, &params[0], sizeof(q)) == 0;
+        if (extremaFree) q.sampleCountWeightExtrema = params[0].sampleCountWeightExtrema;
+        if (memcmp(&q, &params[0], sizeof(q)) != 0) return false;
     }
-    const uint64_t paddedPixels = ((uint64_t)ownedRows(&params[0]) * (uint64_t)(int)params[0].size.x + 63u) & ~63ull;
-    if (paddedPixels >= (1ull << 27)) fusable = false;
+    if ((uint64_t)ownedRows(&params[0]) * (uint64_t)(int)params[0].size.x + 63u >= (1ull << 27)) return false;     // (padded to chunks of 64: 2^27 is a multiple of 64)
     // (the tie fix-up list names FRAME pixels beside the batch number, batch << 27 | pixel: a sliced launch of a frame of 2^27 pixels or more runs batch by batch)
-    if ((uint64_t)(int)params[0].size.x * (uint64_t)(int)params[0].size.y >= (1ull << 27)) fusable = false;
+    if ((uint64_t)(int)params[0].size.x * (uint64_t)(int)params[0].size.y >= (1ull << 27)) return false;
     // one launch is one kernel variant, and the variant follows the record format (launchByDiag: 16-byte FULL_DIAGNOSTICS records need the
-    // counters compiled in): a chain in which only SOME batches carry a diagnostics buffer runs batch by batch, each with its own variant
+    // counters compiled in): a call in which only SOME batches carry a diagnostics buffer runs batch by batch, each with its own variant
     if (diagnostics) {
         int withDiag = 0;
         for (int b = 0; b < count; b++) withDiag += diagnostics[b] != nullptr ? 1 : 0;
-        if (withDiag != 0 && withDiag != count) fusable = false;
+        if (withDiag != 0 && withDiag != count) return false;
     }
+    return true;
+}
+
+// `count` batches enqueued on `s`: one launch per kMaxChain of them when `fuse`, else one per batch.  A chain: batch 0 reads `in`, every later one what its
+// predecessor stored to `out` (what the chain is defined to equal).  A group: every batch reads `in` and stores to out[b].  With `cancel` every launch is waited for.
+// The caller holds ctx->mu and has validated params / buffers.
+int enqueueBatches(RtowContext ctx, int count, const RtowSampleParams* params, const RtowAccumBuffers* in, const RtowAccumBuffers* out, void* const* diagnostics,
+                   bool group, bool fuse, hipStream_t s, const volatile uint8_t* cancel)
+{
     int rc = RTOW_SUCCESS;
     for (int first = 0; first < count && rc == RTOW_SUCCESS;) {
-        const int n = fusable ? std::min(count - first, (int)kMaxChain) : 1;
-        const RtowAccumBuffers* src = first == 0 ? in : out;
+        const int n = fuse ? std::min(count - first, (int)kMaxChain) : 1;
+        const RtowAccumBuffers* src = (group || first == 0) ? in : out;
+        const RtowAccumBuffers* dst = group ? &out[first] : out;
         if (n == 1) {
-            rc = launchSample(ctx, &params[first], src, out, diagnostics ? diagnostics[first] : nullptr, s, cancel != nullptr);
+            rc = launchSample(ctx, &params[first], src, dst, diagnostics ? diagnostics[first] : nullptr, s, cancel != nullptr);
         } else {
             uint32_t seeds[kMaxChain];
             for (int b = 0; b < n; b++) seeds[b] = params[first + b].seed;
-            const ChainSpec chain{n, seeds, diagnostics ? diagnostics + first : nullptr, nullptr};
-            rc = launchSample(ctx, &params[first], src, out, nullptr, s, cancel != nullptr, &chain);
+            const ChainSpec spec{n, seeds, diagnostics ? diagnostics + first : nullptr, group ? out + first : nullptr};
+            rc = launchSample(ctx, &params[first], src, dst, nullptr, s, cancel != nullptr, &spec);
         }
         if (rc == RTOW_SUCCESS && cancel) rc = waitWithCancel(ctx, cancel);
         first += n;
     }
     return rc;
+}
+
+// The sample entry points' common start, in this order (the same bad input gets the same code): every batch's params - validateParams, where a trace depth beyond 64
+// is RTOW_ERROR_CAPACITY - each followed by the call's own per-batch check; the four input buffers and, unless `out` is null (groups check theirs per batch), the four
+// output buffers; then the lock, the scene, the device (calls come from a different worker thread each time), the stream (null: the context's) and a clear cancel word.
+template <typename BatchCheck>
+int beginSample(RtowContext ctx, std::unique_lock<std::mutex>& lock, int count, const RtowSampleParams* params, const RtowAccumBuffers* in, const RtowAccumBuffers* out,
+                BatchCheck check, void* stream, hipStream_t* s)
+{
+    if (!ctx || !in || !params || count < 1) return RTOW_ERROR_INVALID_VALUE;
+    for (int b = 0; b < count; b++) {
+        int v = validateParams(&params[b]);
+        if (v == RTOW_SUCCESS) v = check(b);
+        if (v != RTOW_SUCCESS) return v;
+    }
+    if (!in->color || !in->normal || !in->albedo || !in->sampleCountWeight) return RTOW_ERROR_INVALID_VALUE;
+    if (out && (!out->color || !out->normal || !out->albedo || !out->sampleCountWeight)) return RTOW_ERROR_INVALID_VALUE;
+    lock = std::unique_lock<std::mutex>(ctx->mu);
+    if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
+    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
+    *s = stream ? (hipStream_t)stream : ctx->stream;
+    *ctx->hCancel = 0u;
+    return RTOW_SUCCESS;
+}
+int noBatchCheck(int) { return RTOW_SUCCESS; }
+
+// The host-buffer calls: the caller's inputs -> staging (one DMA per buffer: pinned when the caller registered its pools, pageable otherwise), the batches into `out`
+// (null: in place in the staging - each lane reads its pixel before writing it), and a wait.  The reference's hit list grows without bound (UTIL/HybridCollections.cs:65-71).
+// Here a ray that outgrew the lists made the batches invalid and the lists twice as long (hitListCapacity 0: growHitList): the batches run again from the caller's
+// inputs - if nothing has overwritten them (inputsSurvive) - until they fit or the scene's own bound / the memory is reached.
+int sampleFromHost(RtowContext ctx, int count, const RtowSampleParams* params, const RtowAccumBuffers* in, const RtowAccumBuffers* out, void* const* diagnostics, bool fuse,
+                   bool inputsSurvive, const volatile uint8_t* cancel)
+{
+    const size_t n = (size_t)(int)params[0].size.x * (size_t)(int)params[0].size.y;
+    const RtowAccumBuffers dev{ctx->dColor, ctx->dNormal, ctx->dAlbedo, ctx->dScw};
+    hipStream_t s = ctx->stream;
+    for (;;) {
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->dColor, in->color, n * 16, hipMemcpyHostToDevice, s), RTOW_ERROR_LAUNCH_FAILURE);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->dNormal, in->normal, n * 12, hipMemcpyHostToDevice, s), RTOW_ERROR_LAUNCH_FAILURE);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->dAlbedo, in->albedo, n * 12, hipMemcpyHostToDevice, s), RTOW_ERROR_LAUNCH_FAILURE);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->dScw, in->sampleCountWeight, n * 4, hipMemcpyHostToDevice, s), RTOW_ERROR_LAUNCH_FAILURE);
+        *ctx->hCancel = 0u;
+        ctx->overflowGrew = false;
+        int rc = enqueueBatches(ctx, count, params, &dev, out ? out : &dev, diagnostics, false, fuse, s, cancel);
+        if (rc == RTOW_SUCCESS && !cancel) rc = waitWithCancel(ctx, nullptr);
+        if (rc == RTOW_ERROR_CAPACITY && ctx->overflowGrew && inputsSurvive) continue;
+        return rc;
+    }
+}
+
+// copy back ONLY the rows this slice owns from the staging - skipped pixels write nothing (JOBS/SampleBatchJob.cs:69-70) - and each batch's diagnostics (devDiag[b])
+int copyOwnedRows(RtowContext ctx, const RtowSampleParams* p, const RtowAccumBuffers* out, int count, void* const* diagnostics, void* const* devDiag)
+{
+    const int rows = ownedRows(p);
+    if (rows <= 0) return RTOW_SUCCESS;
+    const size_t w = (size_t)(int)p->size.x, D = (size_t)p->sliceDivider, O = (size_t)p->sliceOffset;
+    auto copyRows = [&](void* dst, const void* src, size_t bytesPerPixel) -> hipError_t {
+        const size_t rowBytes = w * bytesPerPixel;
+        return hipMemcpy2DAsync((uint8_t*)dst + O * rowBytes, D * rowBytes, (const uint8_t*)src + O * rowBytes, D * rowBytes, rowBytes, (size_t)rows,
+                                hipMemcpyDeviceToHost, ctx->stream);
+    };
+    HIP_TRY(ctx, copyRows(out->color, ctx->dColor, 16), RTOW_ERROR_LAUNCH_FAILURE);
+    HIP_TRY(ctx, copyRows(out->normal, ctx->dNormal, 12), RTOW_ERROR_LAUNCH_FAILURE);
+    HIP_TRY(ctx, copyRows(out->albedo, ctx->dAlbedo, 12), RTOW_ERROR_LAUNCH_FAILURE);
+    HIP_TRY(ctx, copyRows(out->sampleCountWeight, ctx->dScw, 4), RTOW_ERROR_LAUNCH_FAILURE);
+    if (diagnostics)
+        for (int b = 0; b < count; b++)
+            if (diagnostics[b]) HIP_TRY(ctx, copyRows(diagnostics[b], devDiag[b], (size_t)p->diagnosticsStride), RTOW_ERROR_LAUNCH_FAILURE);
+    return RTOW_SUCCESS;
 }
 
 } // namespace
@@ -1117,7 +1229,7 @@ RTOW_API int rtowCreateContext(const RtowContextOptions* options, RtowContext* o
                 delete ctx;
                 return RTOW_ERROR_INVALID_VALUE;
             }
-            ctx->regroupSide = v;
+            ctx->schedulerKnob = v;
         }
         if (anyTune) {
             // stage thresholds below 1 mean "any lane" (1); a zero hand-over count or walk slice means "the built-in value" (3; per scene at upload), as in API v6
@@ -1126,6 +1238,14 @@ RTOW_API int rtowCreateContext(const RtowContextOptions* options, RtowContext* o
             ctx->userSliceDefault = options->schedulerTune[8] < 1;
         }
         ctx->userTune = anyTune;
+    }
+    {
+        const int v = ctx->schedulerKnob, side = v & 15;
+        ctx->ticketMapSide = side == 3 ? 1u : (side == 2 || side == 4 || side == 8) ? (unsigned)side : 0u;     // (1: no map)
+        ctx->regroupMode = ((unsigned)v >> 4) & 3u;
+        ctx->orderByTotal = (v & 64) != 0;
+        ctx->slotBlockOverride = ((unsigned)v >> 8) & 15u;
+        ctx->pixelGateOverride = (v >> 12) & 15;
     }
     bool ok = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) == hipSuccess;
     ok = ok && hipEventCreate(&ctx->evStart) == hipSuccess && hipEventCreate(&ctx->evStop) == hipSuccess;
@@ -1235,22 +1355,10 @@ RTOW_API int rtowUploadScene(RtowContext ctx, const RtowSceneDesc* scene)
         return rc;
     }
     HIP_TRY(ctx, hipDeviceSynchronize(), RTOW_ERROR_LAUNCH_FAILURE);   // no batch (on whatever stream it was given) may still be reading the old scene
-    if (compiled.blob.size() > ctx->dSceneCapacity) {
-        if (ctx->dScene) (void)hipFree(ctx->dScene);
-        ctx->dScene = nullptr;
-        ctx->dSceneCapacity = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->dScene, compiled.blob.size()), RTOW_ERROR_MEMORY_ALLOCATION);
-        ctx->dSceneCapacity = compiled.blob.size();
-    }
+    RTOW_TRY(growDevice(ctx, ctx->dSceneCapacity, compiled.blob.size(), {devBuf(ctx->dScene, compiled.blob.size())}));
     HIP_TRY(ctx, hipMemcpy(ctx->dScene, compiled.blob.data(), compiled.blob.size(), hipMemcpyHostToDevice), RTOW_ERROR_LAUNCH_FAILURE);
     if (!compiled.texBlob.empty()) {
-        if (compiled.texBlob.size() > ctx->texBlobCapacity) {
-            if (ctx->dTexBlob) (void)hipFree(ctx->dTexBlob);
-            ctx->dTexBlob = nullptr;
-            ctx->texBlobCapacity = 0;
-            HIP_TRY(ctx, hipMalloc(&ctx->dTexBlob, compiled.texBlob.size()), RTOW_ERROR_MEMORY_ALLOCATION);
-            ctx->texBlobCapacity = compiled.texBlob.size();
-        }
+        RTOW_TRY(growDevice(ctx, ctx->texBlobCapacity, compiled.texBlob.size(), {devBuf(ctx->dTexBlob, compiled.texBlob.size())}));
         HIP_TRY(ctx, hipMemcpy(ctx->dTexBlob, compiled.texBlob.data(), compiled.texBlob.size(), hipMemcpyHostToDevice), RTOW_ERROR_LAUNCH_FAILURE);
         compiled.texBlob.clear();
         compiled.texBlob.shrink_to_fit();                                     // the host copy is not needed again
@@ -1258,13 +1366,7 @@ RTOW_API int rtowUploadScene(RtowContext ctx, const RtowSceneDesc* scene)
     if (ctx->flags & RTOW_CONTEXT_REFERENCE_DIAGNOSTICS) {
         // the counters' walk keeps one stack entry per level of the reference tree (+1): 64 entries of scratch
         if (compiled.refTreeDepth > 62) { logf(ctx, 2, "scene", "RTOW_CONTEXT_REFERENCE_DIAGNOSTICS supports MaxBvhDepth <= 62"); return RTOW_ERROR_CAPACITY; }
-        if (compiled.refTree.size() > ctx->refTreeCapacity) {
-            if (ctx->dRefTree) (void)hipFree(ctx->dRefTree);
-            ctx->dRefTree = nullptr;
-            ctx->refTreeCapacity = 0;
-            HIP_TRY(ctx, hipMalloc(&ctx->dRefTree, compiled.refTree.size()), RTOW_ERROR_MEMORY_ALLOCATION);
-            ctx->refTreeCapacity = compiled.refTree.size();
-        }
+        RTOW_TRY(growDevice(ctx, ctx->refTreeCapacity, compiled.refTree.size(), {devBuf(ctx->dRefTree, compiled.refTree.size())}));
         HIP_TRY(ctx, hipMemcpy(ctx->dRefTree, compiled.refTree.data(), compiled.refTree.size(), hipMemcpyHostToDevice), RTOW_ERROR_LAUNCH_FAILURE);
     }
     compiled.refTree.clear();
@@ -1294,8 +1396,7 @@ RTOW_API int rtowUploadScene(RtowContext ctx, const RtowSceneDesc* scene)
         // thousands of nodes is read from HBM at several times the latency per visit, and a ray visits twice as many nodes: longer slices amortise the
         // trip around them (250 882-triangle mesh, 24 / 32 / 40 visits: 2.04 / 1.97 / 1.86 Gsamples/s; gpurun_out/r03bc.  With walks that ran until the
         // candidate list was full the optima were 16 / 20 / 32: r03h, r03ap).
-        static const int kDefault[9] = {RTOW_DEFAULT_TUNE}, kGeneral[9] = {RTOW_GENERAL_TUNE};
-        const int* base = compiled.layout.sceneKind <= SCENE_KIND_SPHERES_MOTION ? kDefault : kGeneral;      // measured per family: see RTOW_DEFAULT_TUNE
+        const int* base = kThresholdFamilies[compiled.layout.sceneKind <= SCENE_KIND_SPHERES_MOTION ? 0 : 1];      // measured per family: see RTOW_DEFAULT_TUNE
         for (int k = 0; k < 9; k++) ctx->tune[k] = base[k];
         // (round 6: on the rank-rule triangle kernel that traces meshes now, 12 / 16 / 20 / 24 / 32 visits run 2 374 / 2 361 / 2 326 / 2 343 / 2 231 Msamples/s: the 24 of
         // round 3's exact-tie kernel is no better than the 16 everything else uses, profiles/r06n_mesh_scheduler_sweep.json)
@@ -1320,9 +1421,7 @@ RTOW_API int rtowUploadScene(RtowContext ctx, const RtowSceneDesc* scene)
         for (const RtowContext_t::TuneCacheEntry& e : ctx->tuneCache)
             if (e.signature == ctx->sceneSignatureNow) {
                 // a scene like one this context has measured before (same kernel kind, entity / node / material counts): its thresholds, no new probes
-                static const int kSets[3][9] = {{RTOW_DEFAULT_TUNE}, {RTOW_GENERAL_TUNE}, {RTOW_GENERAL_TUNE_2}};
-                for (int k = 0; k < 8; k++) ctx->tune[k] = kSets[e.winner % 3][k];
-                if (e.winner >= 3) ctx->tune[5] = 32;
+                candidateThresholds(e.winner, ctx->tune, 8);
                 ctx->tunedCandidate = e.winner;
                 ctx->tunedScene = ctx->sceneSerial;
             }
@@ -1353,14 +1452,8 @@ RTOW_API int rtowUploadSkyCubemap(RtowContext ctx, const RtowCubemapDesc* cubema
     const size_t bytes = (size_t)6 * (size_t)cubemap->faceWidth * (size_t)cubemap->faceHeight * (size_t)cubemap->pixelStride;
     if (bytes > 0x7fffffffull) return RTOW_ERROR_CAPACITY;                                      // Cubemap.Sample's strides are int32 here as in the reference (RT/Texture.cs:146-148)
     HIP_TRY(ctx, hipDeviceSynchronize(), RTOW_ERROR_LAUNCH_FAILURE);                            // no batch may still be reading the old faces
-    if (bytes > ctx->cubemapCapacity) {
-        if (ctx->dCubemap) (void)hipFree(ctx->dCubemap);
-        ctx->dCubemap = nullptr;
-        ctx->cubemapCapacity = 0;
-        ctx->cubemap = RtowCubemapDesc{};
-        HIP_TRY(ctx, hipMalloc(&ctx->dCubemap, bytes), RTOW_ERROR_MEMORY_ALLOCATION);
-        ctx->cubemapCapacity = bytes;
-    }
+    if (bytes > ctx->cubemapCapacity) ctx->cubemap = RtowCubemapDesc{};
+    RTOW_TRY(growDevice(ctx, ctx->cubemapCapacity, bytes, {devBuf(ctx->dCubemap, bytes)}));
     HIP_TRY(ctx, hipMemcpy(ctx->dCubemap, cubemap->faces, bytes, hipMemcpyHostToDevice), RTOW_ERROR_LAUNCH_FAILURE);
     ctx->cubemap = *cubemap;
     ctx->cubemap.faces = nullptr;
@@ -1435,45 +1528,28 @@ RTOW_API int rtowGetSceneInfo(RtowContext ctx, RtowSceneInfo* info)
     info->wideCodes = ctx->wideCodes ? 1 : 0;
     info->thresholdSet = ctx->tunedScene == ctx->sceneSerial ? ctx->tunedCandidate : -1;
     for (int k = 0; k < 9; k++) info->schedulerTune[k] = ctx->tune[k];
-    info->schedulerTune[7] = ctx->regroupSide;
+    info->schedulerTune[7] = ctx->schedulerKnob;
     return RTOW_SUCCESS;
 }
 
 RTOW_API int rtowSampleBatchDevice(RtowContext ctx, const RtowSampleParams* params, const RtowAccumBuffers* in, const RtowAccumBuffers* out,
                                    void* diagnostics, void* stream, const volatile uint8_t* cancel)
 {
-    if (!ctx || !in || !out) return RTOW_ERROR_INVALID_VALUE;
-    const int v = validateParams(params);
-    if (v != RTOW_SUCCESS) return v;
-    if (!in->color || !in->normal || !in->albedo || !in->sampleCountWeight || !out->color || !out->normal || !out->albedo || !out->sampleCountWeight)
-        return RTOW_ERROR_INVALID_VALUE;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
-    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE); // called from a different worker thread each time
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    *ctx->hCancel = 0u;
-    const int rc = launchSample(ctx, params, in, out, diagnostics, s, cancel != nullptr);
-    if (rc != RTOW_SUCCESS) return rc;
-    if (cancel) return waitWithCancel(ctx, cancel);
-    return RTOW_SUCCESS;
+    if (!out) return RTOW_ERROR_INVALID_VALUE;
+    std::unique_lock<std::mutex> lock;
+    hipStream_t s;
+    RTOW_TRY(beginSample(ctx, lock, 1, params, in, out, noBatchCheck, stream, &s));
+    return enqueueBatches(ctx, 1, params, in, out, &diagnostics, false, false, s, cancel);
 }
 
 RTOW_API int rtowSampleBatchChainDevice(RtowContext ctx, int32_t count, const RtowSampleParams* params, const RtowAccumBuffers* in, const RtowAccumBuffers* out,
                                         void* const* diagnostics, void* stream, const volatile uint8_t* cancel)
 {
-    if (!ctx || !in || !out || !params || count < 1) return RTOW_ERROR_INVALID_VALUE;
-    for (int b = 0; b < count; b++) {
-        const int v = validateParams(&params[b]);
-        if (v != RTOW_SUCCESS) return v;
-    }
-    if (!in->color || !in->normal || !in->albedo || !in->sampleCountWeight || !out->color || !out->normal || !out->albedo || !out->sampleCountWeight)
-        return RTOW_ERROR_INVALID_VALUE;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
-    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    *ctx->hCancel = 0u;
-    return enqueueChain(ctx, count, params, in, out, diagnostics, s, cancel);
+    if (!out) return RTOW_ERROR_INVALID_VALUE;
+    std::unique_lock<std::mutex> lock;
+    hipStream_t s;
+    RTOW_TRY(beginSample(ctx, lock, count, params, in, out, noBatchCheck, stream, &s));
+    return enqueueBatches(ctx, count, params, in, out, diagnostics, false, canFuse(ctx, count, params, diagnostics, /*handOver*/ true, false), s, cancel);
 }
 
 // The adaptive schedule fed from the device (rtow.h).  Batches that differ in nothing but Seed and SampleCountWeightExtrema run as chained launches of at most `lag`
@@ -1486,41 +1562,21 @@ RTOW_API int rtowSampleBatchChainDevice(RtowContext ctx, int32_t count, const Rt
 RTOW_API int rtowSampleBatchChainAdaptiveDevice(RtowContext ctx, int32_t count, const RtowSampleParams* params, const RtowAccumBuffers* in, const RtowAccumBuffers* out,
                                                 void* const* diagnostics, const RtowAdaptiveFeed* feed, void* stream, const volatile uint8_t* cancel)
 {
-    if (!ctx || !in || !out || !params || !feed || count < 1) return RTOW_ERROR_INVALID_VALUE;
-    if (feed->lag < 1 || !feed->extremaOut || feed->reserved != 0) return RTOW_ERROR_INVALID_VALUE;
-    for (int b = 0; b < count; b++) {
-        const int v = validateParams(&params[b]);
-        if (v != RTOW_SUCCESS) return v;
-        // one frame: the reduction behind every batch covers the same W x H pixels
-        if (memcmp(&params[b].size, &params[0].size, sizeof(RtowFloat2)) != 0 || params[b].sliceOffset != params[0].sliceOffset ||
-            params[b].sliceDivider != params[0].sliceDivider || params[b].diagnosticsStride != params[0].diagnosticsStride)
-            return RTOW_ERROR_INVALID_VALUE;
-    }
-    if (!in->color || !in->normal || !in->albedo || !in->sampleCountWeight || !out->color || !out->normal || !out->albedo || !out->sampleCountWeight)
-        return RTOW_ERROR_INVALID_VALUE;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
-    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    *ctx->hCancel = 0u;
+    if (!out || !feed || feed->lag < 1 || !feed->extremaOut || feed->reserved != 0) return RTOW_ERROR_INVALID_VALUE;
+    auto oneFrame = [&](int b) -> int {         // the reduction behind every batch covers the same W x H pixels
+        return memcmp(&params[b].size, &params[0].size, sizeof(RtowFloat2)) != 0 || params[b].sliceOffset != params[0].sliceOffset ||
+                       params[b].sliceDivider != params[0].sliceDivider || params[b].diagnosticsStride != params[0].diagnosticsStride
+                   ? RTOW_ERROR_INVALID_VALUE : RTOW_SUCCESS;
+    };
+    std::unique_lock<std::mutex> lock;
+    hipStream_t s;
+    RTOW_TRY(beginSample(ctx, lock, count, params, in, out, oneFrame, stream, &s));
     if (!ctx->dExtremaPartials) HIP_TRY(ctx, hipMalloc(&ctx->dExtremaPartials, sizeof(RtowFloat2) * kMetricsBlocks), RTOW_ERROR_MEMORY_ALLOCATION);
     const int pixels = (int)params[0].size.x * (int)params[0].size.y;
     const int lag = feed->lag;
     auto source = [&](int k) -> const RtowFloat2* { return k < lag ? (feed->extremaIn ? feed->extremaIn + k : nullptr) : feed->extremaOut + (k - lag); };
-    // what enqueueChain fuses, with the extrema free to differ; the variant follows the record format, so diagnostics on all batches or on none
-    bool fusable = lag > 1 && params[0].rngPolicy == RTOW_RNG_REFERENCE && ctx->chainFusion;
-    for (int b = 1; b < count && fusable; b++) {
-        RtowSampleParams q = params[b];
-        q.seed = params[0].seed;
-        q.sampleCountWeightExtrema = params[0].sampleCountWeightExtrema;
-        fusable = memcmp(&q, &params[0], sizeof(q)) == 0;
-    }
-    if (((uint64_t)ownedRows(&params[0]) * (uint64_t)(int)params[0].size.x + 63u) >= (1ull << 27) || (uint64_t)pixels >= (1ull << 27)) fusable = false;
-    if (diagnostics) {
-        int withDiag = 0;
-        for (int b = 0; b < count; b++) withDiag += diagnostics[b] != nullptr ? 1 : 0;
-        if (withDiag != 0 && withDiag != count) fusable = false;
-    }
+    // what a chain fuses, with the extrema free to differ - and a launch of at most `lag` batches, so lag 1 runs batch by batch
+    const bool fusable = lag > 1 && canFuse(ctx, count, params, diagnostics, /*handOver*/ true, /*extremaFree*/ true);
     if (fusable && !ctx->dExtremaKeys) HIP_TRY(ctx, hipMalloc(&ctx->dExtremaKeys, 2u * sizeof(unsigned) * kMaxChain), RTOW_ERROR_MEMORY_ALLOCATION);
     for (int first = 0; first < count;) {
         int n = fusable ? std::min(count - first, std::min(lag, (int)kMaxChain)) : 1;
@@ -1562,111 +1618,39 @@ RTOW_API int rtowSampleBatchChainAdaptiveDevice(RtowContext ctx, int32_t count, 
 RTOW_API int rtowSampleBatchGroupDevice(RtowContext ctx, int32_t count, const RtowSampleParams* params, const RtowAccumBuffers* in, const RtowAccumBuffers* outs,
                                         void* const* diagnostics, void* stream, const volatile uint8_t* cancel)
 {
-    if (!ctx || !in || !outs || !params || count < 1) return RTOW_ERROR_INVALID_VALUE;
-    for (int b = 0; b < count; b++) {
-        const int v = validateParams(&params[b]);
-        if (v != RTOW_SUCCESS) return v;
+    if (!outs) return RTOW_ERROR_INVALID_VALUE;
+    auto ownOutputs = [&](int b) -> int {
         if (!outs[b].color || !outs[b].normal || !outs[b].albedo || !outs[b].sampleCountWeight) return RTOW_ERROR_INVALID_VALUE;
         for (int c = 0; c < b; c++)                                                 // every batch its own outputs (a batch may store over the shared inputs only if it is alone)
             if (outs[b].color == outs[c].color || outs[b].normal == outs[c].normal || outs[b].albedo == outs[c].albedo || outs[b].sampleCountWeight == outs[c].sampleCountWeight) return RTOW_ERROR_INVALID_VALUE;
         if (count > 1 && (outs[b].color == in->color || outs[b].normal == in->normal || outs[b].albedo == in->albedo || outs[b].sampleCountWeight == in->sampleCountWeight)) return RTOW_ERROR_INVALID_VALUE;
-    }
-    if (!in->color || !in->normal || !in->albedo || !in->sampleCountWeight) return RTOW_ERROR_INVALID_VALUE;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
-    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    *ctx->hCancel = 0u;
-    // one launch needs batches that differ in nothing but Seed, the reference RNG policy, fewer than 2^27 padded pixels, and diagnostics for all batches or for none
-    bool fusable = params[0].rngPolicy == RTOW_RNG_REFERENCE;
-    for (int b = 1; b < count && fusable; b++) {
-        RtowSampleParams q = params[b];
-        q.seed = params[0].seed;
-        fusable = memcmp(&q, &params[0], sizeof(q)) == 0;
-    }
-    const uint64_t paddedPixels = ((uint64_t)ownedRows(&params[0]) * (uint64_t)(int)params[0].size.x + 63u) & ~63ull;
-    if (paddedPixels >= (1ull << 27)) fusable = false;
-    if ((uint64_t)(int)params[0].size.x * (uint64_t)(int)params[0].size.y >= (1ull << 27)) fusable = false;      // tie fix-up entries: batch << 27 | FRAME pixel (enqueueChain)
-    if (diagnostics) {
-        int withDiag = 0;
-        for (int b = 0; b < count; b++) withDiag += diagnostics[b] != nullptr ? 1 : 0;
-        if (withDiag != 0 && withDiag != count) fusable = false;
-    }
-    int rc = RTOW_SUCCESS;
-    for (int first = 0; first < count && rc == RTOW_SUCCESS;) {
-        const int n = fusable ? std::min(count - first, (int)kMaxChain) : 1;
-        if (n == 1) {
-            rc = launchSample(ctx, &params[first], in, &outs[first], diagnostics ? diagnostics[first] : nullptr, s, cancel != nullptr);
-        } else {
-            uint32_t seeds[kMaxChain];
-            for (int b = 0; b < n; b++) seeds[b] = params[first + b].seed;
-            const ChainSpec group{n, seeds, diagnostics ? diagnostics + first : nullptr, outs + first};
-            rc = launchSample(ctx, &params[first], in, &outs[first], nullptr, s, cancel != nullptr, &group);
-        }
-        if (rc == RTOW_SUCCESS && cancel) rc = waitWithCancel(ctx, cancel);
-        first += n;
-    }
-    return rc;
+        return RTOW_SUCCESS;
+    };
+    std::unique_lock<std::mutex> lock;
+    hipStream_t s;
+    RTOW_TRY(beginSample(ctx, lock, count, params, in, nullptr, ownOutputs, stream, &s));
+    return enqueueBatches(ctx, count, params, in, outs, diagnostics, /*group*/ true, canFuse(ctx, count, params, diagnostics, /*handOver*/ false, false), s, cancel);
 }
 
 RTOW_API int rtowSampleBatchChain(RtowContext ctx, int32_t count, const RtowSampleParams* params, const RtowAccumBuffers* in, const RtowAccumBuffers* out,
                                   void* const* diagnostics, const volatile uint8_t* cancel)
 {
-    if (!ctx || !in || !out || !params || count < 1) return RTOW_ERROR_INVALID_VALUE;
-    for (int b = 0; b < count; b++) {
-        const int v = validateParams(&params[b]);
-        if (v != RTOW_SUCCESS) return v;
-        // one staging set serves the whole chain: the batches share the frame and the record format
-        if ((int)params[b].size.x != (int)params[0].size.x || (int)params[b].size.y != (int)params[0].size.y || params[b].diagnosticsStride != params[0].diagnosticsStride ||
-            params[b].sliceOffset != params[0].sliceOffset || params[b].sliceDivider != params[0].sliceDivider)
-            return RTOW_ERROR_INVALID_VALUE;
-    }
-    if (!in->color || !in->normal || !in->albedo || !in->sampleCountWeight || !out->color || !out->normal || !out->albedo || !out->sampleCountWeight)
-        return RTOW_ERROR_INVALID_VALUE;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
-    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
-    const int w = (int)params[0].size.x, h = (int)params[0].size.y;
-    const size_t n = (size_t)w * (size_t)h;
-    const size_t diagBytes = n * (size_t)params[0].diagnosticsStride;
-    int rc = ensureStaging(ctx, n, diagnostics ? diagBytes * (size_t)count : 0);
-    if (rc != RTOW_SUCCESS) return rc;
-    hipStream_t s = ctx->stream;
+    if (!out) return RTOW_ERROR_INVALID_VALUE;
+    auto oneStaging = [&](int b) -> int {       // one staging set serves the whole chain: the batches share the frame and the record format
+        return (int)params[b].size.x != (int)params[0].size.x || (int)params[b].size.y != (int)params[0].size.y || params[b].diagnosticsStride != params[0].diagnosticsStride ||
+                       params[b].sliceOffset != params[0].sliceOffset || params[b].sliceDivider != params[0].sliceDivider
+                   ? RTOW_ERROR_INVALID_VALUE : RTOW_SUCCESS;
+    };
+    std::unique_lock<std::mutex> lock;
+    hipStream_t s;
+    RTOW_TRY(beginSample(ctx, lock, count, params, in, out, oneStaging, nullptr, &s));
+    std::vector<void*> devDiag;
+    RTOW_TRY(prepareStaging(ctx, count, params, diagnostics, devDiag));
     // the chain accumulates in place in the staging buffers (its batches read what their predecessors wrote there); only the final
-    // accumulators and each batch's diagnostics travel back
-    RtowAccumBuffers dev{ctx->dColor, ctx->dNormal, ctx->dAlbedo, ctx->dScw};
-    std::vector<void*> devDiag((size_t)count, nullptr);
-    if (diagnostics) for (int b = 0; b < count; b++) devDiag[(size_t)b] = diagnostics[b] ? ctx->dDiag + (size_t)b * diagBytes : nullptr;
-    for (;;) {
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->dColor, in->color, n * 16, hipMemcpyHostToDevice, s), RTOW_ERROR_LAUNCH_FAILURE);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->dNormal, in->normal, n * 12, hipMemcpyHostToDevice, s), RTOW_ERROR_LAUNCH_FAILURE);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->dAlbedo, in->albedo, n * 12, hipMemcpyHostToDevice, s), RTOW_ERROR_LAUNCH_FAILURE);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->dScw, in->sampleCountWeight, n * 4, hipMemcpyHostToDevice, s), RTOW_ERROR_LAUNCH_FAILURE);
-        *ctx->hCancel = 0u;
-        ctx->overflowGrew = false;
-        rc = enqueueChain(ctx, count, params, &dev, &dev, diagnostics ? devDiag.data() : nullptr, s, cancel);
-        if (rc == RTOW_SUCCESS && !cancel) rc = waitWithCancel(ctx, nullptr);
-        // a ray outgrew the hit lists and they have grown since (hitListCapacity 0): the caller's inputs are untouched - nothing has been copied back - so the chain runs again
-        if (rc == RTOW_ERROR_CAPACITY && ctx->overflowGrew) continue;
-        if (rc != RTOW_SUCCESS) return rc;
-        break;
-    }
-    const int rows = ownedRows(&params[0]);
-    if (rows > 0) {
-        const size_t D = (size_t)params[0].sliceDivider, O = (size_t)params[0].sliceOffset;
-        auto copyRows = [&](void* dst, const void* src, size_t bytesPerPixel) -> hipError_t {
-            const size_t rowBytes = (size_t)w * bytesPerPixel;
-            return hipMemcpy2DAsync((uint8_t*)dst + O * rowBytes, D * rowBytes, (const uint8_t*)src + O * rowBytes, D * rowBytes, rowBytes, (size_t)rows,
-                                    hipMemcpyDeviceToHost, s);
-        };
-        HIP_TRY(ctx, copyRows(out->color, ctx->dColor, 16), RTOW_ERROR_LAUNCH_FAILURE);
-        HIP_TRY(ctx, copyRows(out->normal, ctx->dNormal, 12), RTOW_ERROR_LAUNCH_FAILURE);
-        HIP_TRY(ctx, copyRows(out->albedo, ctx->dAlbedo, 12), RTOW_ERROR_LAUNCH_FAILURE);
-        HIP_TRY(ctx, copyRows(out->sampleCountWeight, ctx->dScw, 4), RTOW_ERROR_LAUNCH_FAILURE);
-        if (diagnostics)
-            for (int b = 0; b < count; b++)
-                if (diagnostics[b]) HIP_TRY(ctx, copyRows(diagnostics[b], devDiag[(size_t)b], (size_t)params[0].diagnosticsStride), RTOW_ERROR_LAUNCH_FAILURE);
-    }
+    // accumulators and each batch's diagnostics travel back - so the caller's inputs are untouched, and a chain whose lists have grown runs again
+    const bool fuse = canFuse(ctx, count, params, diagnostics, /*handOver*/ true, false);
+    RTOW_TRY(sampleFromHost(ctx, count, params, in, nullptr, diagnostics ? devDiag.data() : nullptr, fuse, /*inputsSurvive*/ true, cancel));
+    RTOW_TRY(copyOwnedRows(ctx, &params[0], out, count, diagnostics, devDiag.data()));
     HIP_TRY(ctx, hipStreamSynchronize(s), RTOW_ERROR_LAUNCH_FAILURE);
     return RTOW_SUCCESS;
 }
@@ -1674,64 +1658,26 @@ RTOW_API int rtowSampleBatchChain(RtowContext ctx, int32_t count, const RtowSamp
 RTOW_API int rtowSampleBatch(RtowContext ctx, const RtowSampleParams* params, const RtowAccumBuffers* in, const RtowAccumBuffers* out,
                              void* diagnostics, const volatile uint8_t* cancel)
 {
-    if (!ctx || !in || !out) return RTOW_ERROR_INVALID_VALUE;
-    const int v = validateParams(params);
-    if (v != RTOW_SUCCESS) return v;
-    if (!in->color || !in->normal || !in->albedo || !in->sampleCountWeight || !out->color || !out->normal || !out->albedo || !out->sampleCountWeight)
-        return RTOW_ERROR_INVALID_VALUE;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
-    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
-    const int w = (int)params->size.x, h = (int)params->size.y;
-    const size_t n = (size_t)w * (size_t)h;
-    const size_t diagBytes = diagnostics ? n * (size_t)params->diagnosticsStride : 0;
-    int rc = ensureStaging(ctx, n, diagBytes);
-    if (rc != RTOW_SUCCESS) return rc;
-    hipStream_t s = ctx->stream;
-
+    if (!out) return RTOW_ERROR_INVALID_VALUE;
+    std::unique_lock<std::mutex> lock;
+    hipStream_t s;
+    RTOW_TRY(beginSample(ctx, lock, 1, params, in, out, noBatchCheck, nullptr, &s));
+    void* const* diagList = diagnostics ? &diagnostics : nullptr;
+    std::vector<void*> devDiag;
+    RTOW_TRY(prepareStaging(ctx, 1, params, diagList, devDiag));
     // outputs: when every output buffer (and the diagnostics) lies in registered host memory the kernel stores straight into it - each
     // pixel's 48 + stride bytes leave over PCIe when that pixel finishes, spread over the whole batch, and there is no copy-back at all.
     // Pixels skipped by the slice test are not touched either way (JOBS/SampleBatchJob.cs:69-70).
-    RtowAccumBuffers dev{ctx->dColor, ctx->dNormal, ctx->dAlbedo, ctx->dScw}; // staging is read and (copy-back path) written in place: each lane reads its pixel before writing it
+    const size_t n = (size_t)(int)params->size.x * (size_t)(int)params->size.y;
     RtowAccumBuffers direct{(float*)mappedHost(ctx, out->color, n * 16), (float*)mappedHost(ctx, out->normal, n * 12), (float*)mappedHost(ctx, out->albedo, n * 12),
                             (float*)mappedHost(ctx, out->sampleCountWeight, n * 4)};
-    uint8_t* directDiag = diagnostics ? mappedHost(ctx, diagnostics, diagBytes) : nullptr;
+    uint8_t* directDiag = diagnostics ? mappedHost(ctx, diagnostics, n * (size_t)params->diagnosticsStride) : nullptr;
     const bool zeroCopyOut = direct.color && direct.normal && direct.albedo && direct.sampleCountWeight && (!diagnostics || directDiag);
     // (stores that go straight into the caller's OUTPUT arrays leave its input arrays alone unless they are the same arrays: only then a batch cannot be run twice)
     const bool inputsSurvive = !zeroCopyOut || (in->color != out->color && in->normal != out->normal && in->albedo != out->albedo && in->sampleCountWeight != out->sampleCountWeight);
-    for (;;) {
-        // inputs: one DMA per buffer into the grow-only staging (pinned when the caller registered its pools, pageable otherwise)
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->dColor, in->color, n * 16, hipMemcpyHostToDevice, s), RTOW_ERROR_LAUNCH_FAILURE);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->dNormal, in->normal, n * 12, hipMemcpyHostToDevice, s), RTOW_ERROR_LAUNCH_FAILURE);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->dAlbedo, in->albedo, n * 12, hipMemcpyHostToDevice, s), RTOW_ERROR_LAUNCH_FAILURE);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->dScw, in->sampleCountWeight, n * 4, hipMemcpyHostToDevice, s), RTOW_ERROR_LAUNCH_FAILURE);
-        *ctx->hCancel = 0u;
-        ctx->overflowGrew = false;
-        rc = launchSample(ctx, params, &dev, zeroCopyOut ? &direct : &dev, diagnostics ? (zeroCopyOut ? (void*)directDiag : (void*)ctx->dDiag) : nullptr, s, cancel != nullptr);
-        if (rc != RTOW_SUCCESS) return rc;
-        rc = waitWithCancel(ctx, cancel);
-        // The reference's hit list grows without bound (UTIL/HybridCollections.cs:65-71).  Here a ray that outgrew the lists made the batch invalid and the lists twice
-        // as long (hitListCapacity 0: growHitList): the batch runs again from the caller's inputs, until it fits or the scene's own bound / the memory is reached.
-        if (rc == RTOW_ERROR_CAPACITY && ctx->overflowGrew && inputsSurvive) continue;
-        if (rc != RTOW_SUCCESS) return rc;
-        break;
-    }
-
-    // copy back ONLY the rows this slice owns: skipped pixels write nothing (JOBS/SampleBatchJob.cs:69-70)
-    const int rows = ownedRows(params);
-    if (rows > 0 && !zeroCopyOut) {
-        const size_t D = (size_t)params->sliceDivider, O = (size_t)params->sliceOffset;
-        auto copyRows = [&](void* dst, const void* src, size_t bytesPerPixel) -> hipError_t {
-            const size_t rowBytes = (size_t)w * bytesPerPixel;
-            return hipMemcpy2DAsync((uint8_t*)dst + O * rowBytes, D * rowBytes, (const uint8_t*)src + O * rowBytes, D * rowBytes, rowBytes, (size_t)rows,
-                                    hipMemcpyDeviceToHost, s);
-        };
-        HIP_TRY(ctx, copyRows(out->color, ctx->dColor, 16), RTOW_ERROR_LAUNCH_FAILURE);
-        HIP_TRY(ctx, copyRows(out->normal, ctx->dNormal, 12), RTOW_ERROR_LAUNCH_FAILURE);
-        HIP_TRY(ctx, copyRows(out->albedo, ctx->dAlbedo, 12), RTOW_ERROR_LAUNCH_FAILURE);
-        HIP_TRY(ctx, copyRows(out->sampleCountWeight, ctx->dScw, 4), RTOW_ERROR_LAUNCH_FAILURE);
-        if (diagnostics) HIP_TRY(ctx, copyRows(diagnostics, ctx->dDiag, (size_t)params->diagnosticsStride), RTOW_ERROR_LAUNCH_FAILURE);
-    }
+    void* diag = diagnostics ? (zeroCopyOut ? (void*)directDiag : devDiag[0]) : nullptr;
+    RTOW_TRY(sampleFromHost(ctx, 1, params, in, zeroCopyOut ? &direct : nullptr, &diag, false, inputsSurvive, cancel));
+    if (!zeroCopyOut) RTOW_TRY(copyOwnedRows(ctx, params, out, 1, diagList, devDiag.data()));
     HIP_TRY(ctx, hipStreamSynchronize(s), RTOW_ERROR_LAUNCH_FAILURE);
     if (ctx->haveBatchDone) HIP_TRY(ctx, hipEventSynchronize(ctx->evBatchDone), RTOW_ERROR_LAUNCH_FAILURE);
     return RTOW_SUCCESS;
@@ -1981,16 +1927,9 @@ RTOW_API int rtowGatherRowsDevice(RtowContext ctx, int32_t width, int32_t height
         if (!api) return RTOW_ERROR_UNSUPPORTED;
         if (ctx->haveGatherDone) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->evGatherDone, 0), RTOW_ERROR_LAUNCH_FAILURE);
         const size_t need = packedFloats(0);
-        if (need > ctx->gatherSendFloats || need > ctx->gatherRecvFloats) {
-            HIP_TRY(ctx, hipStreamSynchronize(s), RTOW_ERROR_LAUNCH_FAILURE);
-            if (ctx->dGatherSend) (void)hipFree(ctx->dGatherSend);
-            if (ctx->dGatherRecv) (void)hipFree(ctx->dGatherRecv);
-            ctx->dGatherSend = ctx->dGatherRecv = nullptr; ctx->gatherSendFloats = ctx->gatherRecvFloats = 0;
-            HIP_TRY(ctx, hipMalloc(&ctx->dGatherSend, need * 4u), RTOW_ERROR_MEMORY_ALLOCATION);
-            ctx->gatherSendFloats = need;
-            HIP_TRY(ctx, hipMalloc(&ctx->dGatherRecv, need * 4u), RTOW_ERROR_MEMORY_ALLOCATION);
-            ctx->gatherRecvFloats = need;
-        }
+        if (need > ctx->gatherSendFloats || need > ctx->gatherRecvFloats) HIP_TRY(ctx, hipStreamSynchronize(s), RTOW_ERROR_LAUNCH_FAILURE);
+        RTOW_TRY(growDevice(ctx, ctx->gatherSendFloats, need, {devBuf(ctx->dGatherSend, need * 4u)}));
+        RTOW_TRY(growDevice(ctx, ctx->gatherRecvFloats, need, {devBuf(ctx->dGatherRecv, need * 4u)}));
         size_t at = 0;
         for (int b = 0; b < 4; b++)
             if (what & (1 << b)) {
@@ -2040,13 +1979,8 @@ RTOW_API int rtowGatherRowsDevice(RtowContext ctx, int32_t width, int32_t height
     if (rank != root) {
         // pack this rank's rows of the selected buffers back to back, one send to the root over this GPU's own xGMI link to it
         const size_t need = packedFloats(rank);
-        if (need > ctx->gatherSendFloats) {
-            HIP_TRY(ctx, hipStreamSynchronize(s), RTOW_ERROR_LAUNCH_FAILURE);          // the old block may still be travelling
-            if (ctx->dGatherSend) (void)hipFree(ctx->dGatherSend);
-            ctx->dGatherSend = nullptr; ctx->gatherSendFloats = 0;
-            HIP_TRY(ctx, hipMalloc(&ctx->dGatherSend, need * 4u), RTOW_ERROR_MEMORY_ALLOCATION);
-            ctx->gatherSendFloats = need;
-        }
+        if (need > ctx->gatherSendFloats) HIP_TRY(ctx, hipStreamSynchronize(s), RTOW_ERROR_LAUNCH_FAILURE);          // the old block may still be travelling
+        RTOW_TRY(growDevice(ctx, ctx->gatherSendFloats, need, {devBuf(ctx->dGatherSend, need * 4u)}));
         size_t at = 0;
         const unsigned rows = rowsOwnedBy(rank, world, height);
         for (int b = 0; b < 4; b++)
@@ -2062,13 +1996,8 @@ RTOW_API int rtowGatherRowsDevice(RtowContext ctx, int32_t width, int32_t height
     size_t total = 0;
     std::vector<size_t> offset((size_t)world, 0);
     for (int r = 0; r < world; r++) { offset[(size_t)r] = total; if (r != root) total += packedFloats(r); }
-    if (total > ctx->gatherRecvFloats) {
-        HIP_TRY(ctx, hipStreamSynchronize(s), RTOW_ERROR_LAUNCH_FAILURE);
-        if (ctx->dGatherRecv) (void)hipFree(ctx->dGatherRecv);
-        ctx->dGatherRecv = nullptr; ctx->gatherRecvFloats = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->dGatherRecv, total * 4u), RTOW_ERROR_MEMORY_ALLOCATION);
-        ctx->gatherRecvFloats = total;
-    }
+    if (total > ctx->gatherRecvFloats) HIP_TRY(ctx, hipStreamSynchronize(s), RTOW_ERROR_LAUNCH_FAILURE);
+    RTOW_TRY(growDevice(ctx, ctx->gatherRecvFloats, total, {devBuf(ctx->dGatherRecv, total * 4u)}));
     RCCL_TRY(ctx, api, api->GroupStart());
     int posted = 0;                                       // a failed ncclRecv must not leave the communicator's group open: it is closed on every path
     for (int r = 0; r < world && posted == 0; r++)
@@ -2147,22 +2076,12 @@ RTOW_API int rtowExchangeAccumDevice(RtowContext ctx, int32_t width, int32_t hei
         std::vector<size_t> sendOffset((size_t)groups, 0);
         for (int g = 0; g < groups; g++) { sendOffset[(size_t)g] = sendTotal; if (g != own) sendTotal += packedFloats(tile + tileCount * g); }
         const size_t recvTotal = regionFloats * (size_t)groups;
-        if (sendTotal > ctx->gatherSendFloats) {
-            HIP_TRY(ctx, hipStreamSynchronize(s), RTOW_ERROR_LAUNCH_FAILURE);          // the old block may still be travelling
+        if (sendTotal > ctx->gatherSendFloats || recvTotal > ctx->gatherRecvFloats) {
+            HIP_TRY(ctx, hipStreamSynchronize(s), RTOW_ERROR_LAUNCH_FAILURE);          // the old blocks may still be travelling
             if (ctx->haveGatherDone) HIP_TRY(ctx, hipEventSynchronize(ctx->evGatherDone), RTOW_ERROR_LAUNCH_FAILURE);
-            if (ctx->dGatherSend) (void)hipFree(ctx->dGatherSend);
-            ctx->dGatherSend = nullptr; ctx->gatherSendFloats = 0;
-            HIP_TRY(ctx, hipMalloc(&ctx->dGatherSend, sendTotal * 4u), RTOW_ERROR_MEMORY_ALLOCATION);
-            ctx->gatherSendFloats = sendTotal;
         }
-        if (recvTotal > ctx->gatherRecvFloats) {
-            HIP_TRY(ctx, hipStreamSynchronize(s), RTOW_ERROR_LAUNCH_FAILURE);
-            if (ctx->haveGatherDone) HIP_TRY(ctx, hipEventSynchronize(ctx->evGatherDone), RTOW_ERROR_LAUNCH_FAILURE);
-            if (ctx->dGatherRecv) (void)hipFree(ctx->dGatherRecv);
-            ctx->dGatherRecv = nullptr; ctx->gatherRecvFloats = 0;
-            HIP_TRY(ctx, hipMalloc(&ctx->dGatherRecv, recvTotal * 4u), RTOW_ERROR_MEMORY_ALLOCATION);
-            ctx->gatherRecvFloats = recvTotal;
-        }
+        RTOW_TRY(growDevice(ctx, ctx->gatherSendFloats, sendTotal, {devBuf(ctx->dGatherSend, sendTotal * 4u)}));
+        RTOW_TRY(growDevice(ctx, ctx->gatherRecvFloats, recvTotal, {devBuf(ctx->dGatherRecv, recvTotal * 4u)}));
         for (int g = 0; g < groups; g++) {
             if (g == own) continue;
             const int peer = tile + tileCount * g;

@@ -87,6 +87,14 @@ constexpr unsigned kNoPrimaryList = 0x0000ffffu;   // pixelCandidates[pix].x: fi
 #ifndef RTOW_URGENT_LANES
 #define RTOW_URGENT_LANES 1   // 0: A/B build without the lanes in a hurry (rtow_sample_kernel.hip.h HURRY; rtow_api.hip then sets no rate)
 #endif
+// Launches a "lanes in a hurry" twin can serve (kGeoHurry, rtow_sample_kernel.hip.h): static spheres without the exact-tie resolver or wide codes, white noise, the reference
+// stream, the generic 32-word history, and not the reference's own counters (16-byte records next to a reference tree).  The one rule for both sides: the host gives a rate in
+// tune[7] to no other launch (rtow_api.hip), and launchByDiagGeo refuses a launch with a rate that fails it
+inline bool hurryTwin(uint32_t sceneKind, bool ties, bool wide, int noiseColor, bool perSample, bool records16, bool refTree, int traceDepth)
+{
+    return RTOW_URGENT_LANES && sceneKind == SCENE_KIND_SPHERES && !ties && !wide && noiseColor == RTOW_NOISE_WHITE && !perSample && !(records16 && refTree) &&
+           historyWords(noiseColor, perSample, wide, ties, records16, traceDepth) == 32;
+}
 #ifndef RTOW_SAMPLE_GROUP
 #define RTOW_SAMPLE_GROUP 16     // (other values: timing builds only - the oracle's restatement of the policy sums groups of 16)
 #endif

@@ -2548,10 +2548,10 @@ hipError_t launchByDiagGeo(const SampleKernelArgs& args, int numBlocks, hipStrea
     const int hw = historyWords(args.noiseColor, args.unitRecords != nullptr, WIDE, TIES, fullDiag, args.traceDepth);
     // lanes in a hurry (kGeoHurry): the launch carries a rate in tune[7], above the pixel gate's eight bits (plain and chained launches of static-sphere scenes: rtow_api.hip) - the
     // twins of that kind's generic variants serve it.  Every other variant reads tune[7] as the pixel gate alone and would wait for millions of lanes at every pixel boundary:
-    // a launch with a rate that no twin serves is refused, loudly, instead of running slowly
-    constexpr bool HAS_HURRY_TWIN = RTOW_URGENT_LANES && !WIDE && !TIES && (KIND & 7) == SCENE_KIND_SPHERES;
+    // a launch with a rate that no twin serves (hurryTwin, rtow_kernels.h) is refused, loudly, instead of running slowly
+    constexpr bool HAS_HURRY_TWIN = RTOW_URGENT_LANES && !WIDE && !TIES && (KIND & 7) == SCENE_KIND_SPHERES;     // (which kinds instantiate the twins at all)
     const bool hurry = ((uint32_t)args.tune[7] >> 8) != 0u;
-    if (hurry && !(HAS_HURRY_TWIN && args.noiseColor == RTOW_NOISE_WHITE && !args.unitRecords && hw == 32 && !(fullDiag && args.refTree))) return hipErrorInvalidValue;
+    if (hurry && !hurryTwin(KIND & 7, TIES, WIDE, args.noiseColor, args.unitRecords != nullptr, fullDiag, args.refTree != nullptr, args.traceDepth)) return hipErrorInvalidValue;
     if (args.noiseColor == RTOW_NOISE_BLUE) return launchVariant<ALL_LDS, KIND, 32, 2, RTOW_NOISE_BLUE, false, GEO>(args, numBlocks, stream);
     if (args.noiseColor == RTOW_NOISE_SPATIOTEMPORAL_BLUE) return launchVariant<ALL_LDS, KIND, 32, 2, RTOW_NOISE_SPATIOTEMPORAL_BLUE, false, GEO>(args, numBlocks, stream);
     if (args.unitRecords) {      // RTOW_RNG_PER_SAMPLE
