@@ -8,12 +8,13 @@ ping-pong buffers with a fresh seed, exactly like the reference's successive bat
 (Assets/Scripts/Unity/Raytracer.cs:656-661,798-802).
 
   python bench.py --gpus 1 --steps 8 --warmup 1
+  python bench.py --gpus 1 --steps 8 --warmup 1 --full        # and every secondary measurement, CPU baseline and post-pass figure after it
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
 N = 1: the K timed steps are enqueued as equally long chains of at most 16 successive batches (`--chain`) (rtowSampleBatchChainDevice; the reference itself keeps
 two batches in flight, Raytracer.cs:586-593): one launch per chain, in which a pixel chunk's next batch starts as soon as its previous
-batch is stored.  The same K steps as plain one-launch-per-batch calls and the host-buffer form (rtowSampleBatch on pinned host arrays)
+batch is stored.  Under `--full`, the same K steps as plain one-launch-per-batch calls and the host-buffer form (rtowSampleBatch on pinned host arrays)
 are measured after the timed region and reported next to `value` (`plain_batches`, `host_buffer_ms_per_step`).
 
 N > 1: one process per GPU, no data-path collective inside a batch; the batch's results are combined over RCCL afterwards.  The total work is fixed
@@ -25,16 +26,18 @@ N > 1: one process per GPU, no data-path collective inside a batch; the batch's 
            ncclSend / ncclRecv exchange folds every row on the rank that owns it (row % G) in group order, ONE gather of colour rows per batch brings
            the frame to rank 0.  T = 1 (samples only) unless spp < G (`--tiles`); bit-identical to the sub-batches folded in group order on one GPU,
            within 1e-4 of the mean of the sequential accumulation (tests/);
-and the line also carries, measured in the same run (`partitions`):
+and under `--full` the line also carries, measured in the same run (`partitions`), each partition's self-check (`self_check`, before anything is timed):
   tiles    north_star's partition: the frame row-interleaved over the GPUs (SliceDivider = N), one gather of colour rows per batch
            (rtowCommInit / rtowGatherRowsDevice); bit-identical to the single-GPU frame; limited by lane-per-pixel granularity under
            the reference RNG stream (a GPU with one pixel per lane finishes when its slowest pixel's sequential samples do: DESIGN.md 6);
   tiles under --rng per-sample (RTOW_RNG_PER_SAMPLE, NOT the reference's random stream: a pixel's samples become independent units).
 
-Rank 0 prints ONE JSON line (see the task contract) that also carries `roofline`, `cpu_baseline` (the C2 sample), `cpu_baseline_c1`
-(BASELINE.json configs[0] in full: 400x225, 8 spp), `plain_batches` (one launch per batch), `chain2` (two batches per launch: the queue depth of
-the unmodified reference host, UNITY/Raytracer.cs:586-593) and `post_passes` (CombineJob / FinalizeTexturesJob / ReduceMetricsJob / accumulator
-add on the device: achieved GB/s against the HBM roofline, the kernels of this repository that ARE bandwidth bound).
+Rank 0 prints ONE JSON line: the headline (`metric`, `value`, `unit`, `ms_per_step`, ...) and `roofline`, both from the timed steps (no run of their own; roofline.traffic from the committed PMC profile).  A plain run
+does nothing else: it sets up, warms up, times the steps, writes `--dump-outputs` and prints.  `--full` adds, after the timed steps, `cpu_baseline`
+(the C2 sample), `cpu_baseline_c1` (BASELINE.json configs[0] in full: 400x225, 8 spp), `plain_batches` (one launch per batch), `chain2` (two batches
+per launch: the queue depth of the unmodified reference host, UNITY/Raytracer.cs:586-593), the other secondary legs and `post_passes` (CombineJob /
+FinalizeTexturesJob / ReduceMetricsJob / accumulator add on the device: achieved GB/s against the HBM roofline, the kernels of this repository that
+ARE bandwidth bound).
 
 RTOW_BENCH_DEBUG_SHARED_GPU=1 (development, one-GPU box): every rank uses cuda:0, torch.distributed runs over gloo and the C-ABI communicator
 over the tests' stand-in transport (tests/native/fake_rccl.cpp) - the N > 1 code path end to end, never a measurement (the line says so).
@@ -267,8 +270,11 @@ def main():
     ap.add_argument("--rng", choices=["reference", "per-sample", "per-sample-xoroshiro"], default="reference",
                     help="reference: the reference's per-pixel generator (same seed, same image: the headline); per-sample: RTOW_RNG_PER_SAMPLE, a different stream")
     ap.add_argument("--depth", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements (plain batches, host-buffer form, other partitions)")
+    ap.add_argument("--full", action="store_true", help="after the headline, run everything else the line can carry: one GPU - the secondary measurements (plain batches, "
+                    "chain2, other RNG policies, batch groups, the reference host's defaults, host-buffer form), post_passes and the CPU baselines; several - both "
+                    "partitions' self-checks before anything is timed and the other partitions.  Off: set up, warm up, time the steps, dump, print")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary measurements (plain batches, host-buffer form, other partitions) and post_passes")
     ap.add_argument("--chain", type=int, default=None, help="batches per launch (rtowSampleBatchChainDevice); default: on one GPU the steps split into equal chains of at most 16, on several 1 (one gather per batch)")
     ap.add_argument("--prewarm", type=float, default=2.0, help="seconds of untimed launches of the timed kind in front of the W warmup steps of the main measurement (clocks / power state of a fresh box; 0 = none)")
     ap.add_argument("--tune", default=None, help="development: RtowContextOptions.schedulerTune as 9 comma-separated integers")
@@ -659,9 +665,9 @@ def main():
             W, H, n, spp = keep
             ctx.synchronize()
 
-    # N > 1: both partitions check themselves before anything is timed - the one `value` is quoted for, and the other, reported beside it as a first-class block
+    # N > 1, --full: both partitions check themselves before anything is timed - the one `value` is quoted for, and the other, reported beside it as a first-class block
     self_checks = {}
-    if world > 1:
+    if world > 1 and args.full:
         for part in ("tiles", "hybrid") if args.partition != "batches" else ("tiles", "batches"):
             self_checks[part] = partition_self_check(part)
     self_check = self_checks.get(args.partition)
@@ -694,7 +700,7 @@ def main():
 
     extras = {}
     host_ms = None
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         if world == 1:
             if args.chain > 1:
                 extras["plain_batches"] = dict(summary(measure("tiles", args.rng, 1, args.steps, 1)), batches_per_launch=1, note="the same steps as one launch per batch (rtowSampleBatchDevice): like for like with round 1's `value`")
@@ -880,9 +886,9 @@ def main():
             out["host_buffer_ms_per_step"] = host_ms
             out["host_buffer_note"] = ("rtowSampleBatch on pinned host arrays registered with rtowRegisterHostBuffer: inputs by one DMA, outputs stored by the kernel straight into "
                                        "host memory (best of 3 after 1 warm-up); host_buffer_chain_ms_per_step: rtowSampleBatchChain on the same arrays, batches_per_launch batches per call")
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             out["post_passes"] = post_passes(rt, ctx, lib, torch, dev, stream)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(rt, scene, W, H, depth, scene_name=args.scene, full_spp=spp)
             out["cpu_baseline_c1"] = cpu_baseline_c1(rt)
         print(json.dumps(out), flush=True)

@@ -6,8 +6,8 @@ mkdir -p "$OUT"
 for rep in $(seq 1 $REPS); do
   for cfg in $CONFIGS; do
     for side in $SIDES; do
-      extras="--no-extras"; [ "$cfg" = "2" ] && extras=""
-      python bench.py --config $cfg --steps 20 --warmup 5 --no-cpu-baseline $extras --tune 0,0,0,0,0,0,0,$side,0 > "$OUT/c${cfg}_side${side}_rep${rep}.json" 2> "$OUT/c${cfg}_side${side}_rep${rep}.err"
+      extras=""; [ "$cfg" = "2" ] && extras="--full --no-cpu-baseline"
+      python bench.py --config $cfg --steps 20 --warmup 5 $extras --tune 0,0,0,0,0,0,0,$side,0 > "$OUT/c${cfg}_side${side}_rep${rep}.json" 2> "$OUT/c${cfg}_side${side}_rep${rep}.err"
       python - "$OUT/c${cfg}_side${side}_rep${rep}.json" $cfg $side $rep <<'PY'
 import json, sys
 try:

@@ -201,7 +201,7 @@ def test_gather_closes_the_rccl_group_on_a_failed_receive(rt, gpu_context):
 
 
 def test_bench_with_two_ranks_runs_end_to_end_through_the_c_abi_gather(rt):
-    """bench.py --gpus 2 as the driver launches it (torch.distributed.run, one process per rank), on this one-GPU box in its debug mode: both ranks on
+    """bench.py --gpus 2 --full as the driver launches it (torch.distributed.run, one process per rank), on this one-GPU box in its debug mode: both ranks on
     cuda:0, torch.distributed over gloo, the tile partition's gather through rtowCommInit / rtowGatherRowsDevice on the stand-in transport.  The
     N > 1 JSON line - `value` from the tiles x batches partition (rtowExchangeAccumDevice + rtowGatherRowsDevice on the stand-in transport), the tile
     partition beside it in `partitions`, `config.gather` naming the C-ABI path - prints and is consistent."""
@@ -214,7 +214,7 @@ def test_bench_with_two_ranks_runs_end_to_end_through_the_c_abi_gather(rt):
     s.close()
     env = dict(os.environ, RTOW_BENCH_DEBUG_SHARED_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--width", "320", "--height", "181", "--spp", "8"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--width", "320", "--height", "181", "--spp", "8", "--full"]
     proc = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=560, cwd=ROOT)
     assert proc.returncode == 0, proc.stdout[-2000:] + proc.stderr[-4000:]
     lines = [l for l in proc.stdout.splitlines() if l.startswith("{")]
