@@ -533,6 +533,47 @@ RTOW_API int rtowCombineFinalizeDevice(RtowContext context, const RtowCombinePar
                                        const float* inColor /*float4*/, const float* inNormal, const float* inAlbedo,
                                        uint8_t* outColor /*RGBA32*/, uint8_t* outNormal, uint8_t* outAlbedo, void* stream);
 
+/* replaces: OpenImageDenoiseJob / OptixDenoiseJob (JOBS/DenoiseJobs.cs:10-38, :44-119) in the reference's
+ * ScheduleDenoise (UNITY/Raytracer.cs:874-949): float3 colour / normal / albedo from rtowCombineDevice in,
+ * float3 colour out for rtowFinalizeDevice.  Not a neural denoiser: an edge-avoiding a-trous wavelet filter
+ * (Dammertz et al., HPG 2010) guided by combine's normal and albedo, specified exactly below.
+ * Added after API version 12 without changing it: a host detects the call by its entry point (C#: EntryPointNotFoundException). */
+typedef enum RtowDenoiseFlags { RTOW_DENOISE_DEMODULATE_ALBEDO = 1 } RtowDenoiseFlags;
+typedef struct RtowDenoiseParams {
+    int32_t width, height;
+    int32_t iterations;        /* a-trous levels 1..8; level k uses step 2^k                          recommended: 5 */
+    int32_t normalSharpness;   /* 0..8: normal weight max(0, n.n')^(2^normalSharpness)               recommended: 4 */
+    float   colorSigma;        /* >= 0, finite; 0 switches the colour term off                       recommended: 0.5 */
+    float   albedoSigma;       /* >= 0, finite; 0 switches the albedo term off                       recommended: 0.5 */
+    int32_t flags;             /* RtowDenoiseFlags                              recommended: RTOW_DENOISE_DEMODULATE_ALBEDO */
+    int32_t reserved;          /* must be 0 */
+} RtowDenoiseParams;           /* 32 bytes.  The recommended values minimise the squared error of a 4-spp cover-scene frame against 1024 spp
+                                  (tests/test_gpu_denoise.py): 0.43 of the noisy frame's; normalSharpness 7 leaves 0.53 there (noisy 4-spp normals) */
+/* the ping-pong colour buffer of the levels (float3 per pixel); `scratch` may be NULL when iterations == 1 */
+#define RTOW_DENOISE_SCRATCH_BYTES(w, h) ((size_t)(w) * (size_t)(h) * (size_t)12)
+/* Numeric specification (float32, in this order; no contraction, correctly rounded `/`; no exp, no pow):
+ *   demodulate (flag only): per channel c' = a >= 2^-10 ? c / a : c; at the end r' = a >= 2^-10 ? r * a : r with the pixel's own albedo.
+ *   level k = 0 .. iterations-1, step s = 1 << k, reads level k-1's colour (level 0: the demodulated input); the guides are always the inputs.
+ *   The levels ping-pong between scratch and outColor so that the last one lands in outColor.
+ *   A pixel p whose own colour is non-finite passes through unchanged at that level.  Otherwise taps q = p + s * (i, j), j = -2..2 (outer),
+ *   i = -2..2 (inner); taps outside the image are skipped (not clamped).  h(-2..2) = {1/16, 1/4, 3/8, 1/4, 1/16}.
+ *     centre tap: w = h(0) * h(0) = 9/64, no guide consulted;
+ *     other taps: skipped if the colour c_q has a non-finite channel; else w = ((h(i) * h(j)) * wc) * wn * wa with
+ *       wc = 1 / (1 + dc * invC_k), dc = (dx*dx + dy*dy) + dz*dz of c_p - c_q, invC_k = (float)(1 << 2k) / (colorSigma * colorSigma) (host);
+ *            wc = 1 when colorSigma == 0;
+ *       wn = 1 if n_p and n_q are both exactly (0, 0, 0), 0 if exactly one is; else d = (nx*nx' + ny*ny') + nz*nz', d = d > 0 ? d : 0,
+ *            then d = d * d, normalSharpness times;
+ *       wa = 1 / (1 + da * (1 / (albedoSigma * albedoSigma))), da the squared albedo distance as dc; wa = 1 when albedoSigma == 0;
+ *     a tap whose w is not > 0 (NaN included) is skipped.  Skipped taps add nothing.
+ *   acc and wsum start at +0 and add w * c_q and w in tap order; the result is acc / wsum per channel.
+ * Validation (RTOW_ERROR_INVALID_VALUE, nothing enqueued): a NULL pointer other than scratch with iterations == 1; width or height <= 0 or
+ * width * height > INT32_MAX; a parameter out of range, a negative or non-finite sigma, unknown flag bits, reserved != 0; outColor or scratch
+ * overlapping an input, or each other.  Enqueued on `stream` (NULL = the context's own stream), one launch per level; no allocation, no wait,
+ * so the call may be captured in a graph. */
+RTOW_API int rtowDenoiseDevice(RtowContext context, const RtowDenoiseParams* params,
+                               const float* inColor, const float* inNormal, const float* inAlbedo,
+                               void* scratch, float* outColor, void* stream);
+
 /* dst += src for the four accumulation buffers (device pointers, `pixelCount` elements each).  The reference accumulates
  * successive batches by feeding a batch's outputs to the next one as inputs (UNITY/Raytracer.cs:798-802); when batches run
  * CONCURRENTLY on several GPUs (each from zeroed accumulators, its own Seed) their partial sums are folded with this, in

@@ -168,6 +168,26 @@ class CombineParams(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("debugMode", C.c_int32), ("ldrAlbedo", C.c_int32)]
 
 
+# RtowDenoiseFlags
+RTOW_DENOISE_DEMODULATE_ALBEDO = 1
+# recommended settings of rtowDenoiseDevice (include/rtow.h; the sigmas are tuned on tests/test_gpu_denoise.py's quality test)
+DENOISE_DEFAULT_ITERATIONS = 5
+DENOISE_DEFAULT_NORMAL_SHARPNESS = 4
+DENOISE_DEFAULT_COLOR_SIGMA = 0.5
+DENOISE_DEFAULT_ALBEDO_SIGMA = 0.5
+DENOISE_DEFAULT_FLAGS = RTOW_DENOISE_DEMODULATE_ALBEDO
+
+
+class DenoiseParams(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("iterations", C.c_int32), ("normalSharpness", C.c_int32),
+                ("colorSigma", C.c_float), ("albedoSigma", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+def denoise_scratch_bytes(width, height):
+    """RTOW_DENOISE_SCRATCH_BYTES(w, h): the ping-pong float3 colour buffer of the levels"""
+    return int(width) * int(height) * 12
+
+
 # every symbol include/rtow.h declares (tests/test_abi.py checks the library exports all of them)
 EXPORTED_SYMBOLS = [
     "rtowGetApiVersion", "rtowErrorString", "rtowCreateContext", "rtowDestroyContext", "rtowUploadScene",
@@ -177,4 +197,5 @@ EXPORTED_SYMBOLS = [
     "rtowSampleBatchChainDevice", "rtowSampleBatchChain", "rtowCommSetLibraryPath", "rtowCommGetUniqueId", "rtowCommInit", "rtowCommDestroy", "rtowGatherRowsDevice",
     "rtowHybridPlan", "rtowExchangeAccumDevice", "rtowSampleBatchGroupDevice",
     "rtowCombineFinalizeDevice", "rtowReduceMetricsDeviceAsync", "rtowProbeNearestHit", "rtowSampleBatchChainAdaptiveDevice",
+    "rtowDenoiseDevice",
 ]

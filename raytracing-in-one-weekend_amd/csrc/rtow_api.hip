@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cfloat>
 #include <chrono>
 #include <cstdarg>
 #include <cstdio>
@@ -1782,6 +1783,31 @@ RTOW_API int rtowFinalizeDevice(RtowContext ctx, int32_t pixelCount, const float
     HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     HIP_TRY(ctx, launchFinalize(pixelCount, inColor, inNormal, inAlbedo, outColor, outNormal, outAlbedo, ctx->dByteThresholds, s), RTOW_ERROR_LAUNCH_FAILURE);
+    return RTOW_SUCCESS;
+}
+
+RTOW_API int rtowDenoiseDevice(RtowContext ctx, const RtowDenoiseParams* params, const float* inColor, const float* inNormal, const float* inAlbedo,
+                               void* scratch, float* outColor, void* stream)
+{
+    if (!ctx || !params || !inColor || !inNormal || !inAlbedo || !outColor) return RTOW_ERROR_INVALID_VALUE;
+    const RtowDenoiseParams& p = *params;
+    if (p.width <= 0 || p.height <= 0 || (int64_t)p.width * p.height > INT32_MAX) return RTOW_ERROR_INVALID_VALUE;
+    if (p.iterations < 1 || p.iterations > 8 || p.normalSharpness < 0 || p.normalSharpness > 8) return RTOW_ERROR_INVALID_VALUE;
+    if (!(p.colorSigma >= 0.0f && p.colorSigma <= FLT_MAX) || !(p.albedoSigma >= 0.0f && p.albedoSigma <= FLT_MAX)) return RTOW_ERROR_INVALID_VALUE;   // NaN fails both
+    if ((p.flags & ~(int32_t)RTOW_DENOISE_DEMODULATE_ALBEDO) != 0 || p.reserved != 0) return RTOW_ERROR_INVALID_VALUE;
+    if (!scratch && p.iterations > 1) return RTOW_ERROR_INVALID_VALUE;
+    // the levels write outColor and scratch while they read the inputs and each other: no byte of a written buffer may be another buffer's
+    const size_t bytes = RTOW_DENOISE_SCRATCH_BYTES(p.width, p.height);
+    const auto overlap = [bytes](const void* a, const void* b) {
+        return a && b && (uintptr_t)a < (uintptr_t)b + bytes && (uintptr_t)b < (uintptr_t)a + bytes;
+    };
+    for (const void* in : {(const void*)inColor, (const void*)inNormal, (const void*)inAlbedo})
+        if (overlap(outColor, in) || overlap(scratch, in)) return RTOW_ERROR_INVALID_VALUE;
+    if (overlap(outColor, scratch)) return RTOW_ERROR_INVALID_VALUE;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    HIP_TRY(ctx, launchDenoise(p, inColor, inNormal, inAlbedo, (float*)scratch, outColor, s), RTOW_ERROR_LAUNCH_FAILURE);
     return RTOW_SUCCESS;
 }
 

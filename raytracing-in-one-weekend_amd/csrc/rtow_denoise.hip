@@ -1,0 +1,147 @@
+// rtow_denoise.hip - rtowDenoiseDevice's kernel: one level of the edge-avoiding a-trous wavelet filter (Dammertz et al., HPG 2010), guided by the
+// normal and albedo that CombineJob writes.  The numeric specification is in include/rtow.h next to RtowDenoiseParams (and DESIGN.md 5);
+// tests/denoise_reference.py restates it in numpy and the GPU tests compare the two bit for bit.
+#include "rtow_kernels.h"
+
+namespace rtow {
+
+namespace {
+
+// float3 at a 4-byte aligned address (the buffers are tightly packed float3; a caller may pass views that start 4 bytes into an allocation)
+struct __attribute__((packed, aligned(4))) P3 { float x, y, z; };
+__device__ __forceinline__ P3 ld3(const float* p, size_t index) { return reinterpret_cast<const P3*>(p)[index]; }
+
+constexpr float kDemodMin = 0.0009765625f;      // 2^-10
+
+struct DenoiseLevel {
+    int width, height;
+    int step;                   // 1 << k
+    int normalSharpness;
+    float invC;                 // (float)(1 << 2k) / (colorSigma * colorSigma), used when useColor
+    float invA;                 // 1 / (albedoSigma * albedoSigma), used when useAlbedo
+    int useColor, useAlbedo;    // sigma != 0
+    int demodIn, remodOut;      // level 0 / last level with RTOW_DENOISE_DEMODULATE_ALBEDO
+    unsigned tilesX, tiles;     // 64 x 4 pixel tiles per row / in all
+};
+
+__device__ __forceinline__ bool finite3(P3 c) { return __builtin_isfinite(c.x) && __builtin_isfinite(c.y) && __builtin_isfinite(c.z); }
+__device__ __forceinline__ bool zero3(P3 n) { return n.x == 0.0f && n.y == 0.0f && n.z == 0.0f; }
+__device__ __forceinline__ float dist2(P3 a, P3 b)
+{
+    const float dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;
+    return (dx * dx + dy * dy) + dz * dz;
+}
+__device__ __forceinline__ P3 demod(P3 c, P3 a)
+{
+    return P3{a.x >= kDemodMin ? c.x / a.x : c.x, a.y >= kDemodMin ? c.y / a.y : c.y, a.z >= kDemodMin ? c.z / a.z : c.z};
+}
+__device__ __forceinline__ P3 remod(P3 r, P3 a)
+{
+    return P3{a.x >= kDemodMin ? r.x * a.x : r.x, a.y >= kDemodMin ? r.y * a.y : r.y, a.z >= kDemodMin ? r.z * a.z : r.z};
+}
+// B3 spline tap h(i), i = -2..2: exact binary fractions, so h(i) * h(j) is exact
+__device__ __forceinline__ float b3(int i) { return i == 0 ? 0.375f : (i == 1 || i == -1) ? 0.25f : 0.0625f; }
+
+// One lane per output pixel; a workgroup is a 64 x 4 tile, so every tap load of a wave reads one contiguous row segment (768 bytes of float3).
+// The guides are read from the inputs at every level.  The 25 taps stay a loop: unrolled, the compiler hoists the loads of several taps and the
+// kernel leaves the 64-VGPR budget of 8 waves per SIMD (tests/test_denoise_isa.py).
+__global__ void __launch_bounds__(256, 8) denoise_level_kernel(DenoiseLevel L, const float* __restrict__ inColor, const float* __restrict__ normal,
+                                                               const float* __restrict__ albedo, float* __restrict__ outColor)
+{
+    for (unsigned t = blockIdx.x; t < L.tiles; t += gridDim.x) {
+        const int x = (int)(t % L.tilesX) * 64 + (int)(threadIdx.x & 63u);
+        const int y = (int)(t / L.tilesX) * 4 + (int)(threadIdx.x >> 6);
+        if (x >= L.width || y >= L.height) continue;
+        const size_t p = (size_t)y * (size_t)L.width + (size_t)x;
+        const bool needAlbedo = L.demodIn || L.useAlbedo;
+        const P3 ap = (needAlbedo || L.remodOut) ? ld3(albedo, p) : P3{0.0f, 0.0f, 0.0f};
+        P3 cp = ld3(inColor, p);
+        if (L.demodIn) cp = demod(cp, ap);
+        P3 r = cp;
+        if (finite3(cp)) {
+            const P3 np = ld3(normal, p);
+            const bool npZero = zero3(np);
+            float ax = 0.0f, ay = 0.0f, az = 0.0f, ws = 0.0f;
+#pragma unroll 1
+            for (int j = -2; j <= 2; ++j) {
+                const int dy = j * L.step;
+                if (dy < -y || dy > L.height - 1 - y) continue;           // outside the image: skipped (no overflow near INT32_MAX)
+                const int qy = y + dy;
+                const float hj = b3(j);
+#pragma unroll 1
+                for (int i = -2; i <= 2; ++i) {
+                    const int dx = i * L.step;
+                    if (dx < -x || dx > L.width - 1 - x) continue;
+                    const int qx = x + dx;
+                    const float hij = b3(i) * hj;
+                    if (i == 0 && j == 0) {                              // the centre: 9/64, no guide consulted
+                        ax = ax + hij * cp.x; ay = ay + hij * cp.y; az = az + hij * cp.z;
+                        ws = ws + hij;
+                        continue;
+                    }
+                    const size_t q = (size_t)qy * (size_t)L.width + (size_t)qx;
+                    P3 cq = ld3(inColor, q);
+                    const P3 aq = needAlbedo ? ld3(albedo, q) : P3{0.0f, 0.0f, 0.0f};
+                    if (L.demodIn) cq = demod(cq, aq);
+                    if (!finite3(cq)) continue;
+                    const float wc = L.useColor ? 1.0f / (1.0f + dist2(cp, cq) * L.invC) : 1.0f;
+                    const P3 nq = ld3(normal, q);
+                    const bool nqZero = zero3(nq);
+                    float wn;
+                    if (npZero || nqZero) wn = (npZero && nqZero) ? 1.0f : 0.0f;
+                    else {
+                        float d = (np.x * nq.x + np.y * nq.y) + np.z * nq.z;
+                        d = d > 0.0f ? d : 0.0f;
+                        for (int e = 0; e < L.normalSharpness; ++e) d = d * d;
+                        wn = d;
+                    }
+                    const float wa = L.useAlbedo ? 1.0f / (1.0f + dist2(ap, aq) * L.invA) : 1.0f;
+                    const float w = ((hij * wc) * wn) * wa;
+                    if (!(w > 0.0f)) continue;
+                    ax = ax + w * cq.x; ay = ay + w * cq.y; az = az + w * cq.z;
+                    ws = ws + w;
+                }
+            }
+            r = P3{ax / ws, ay / ws, az / ws};
+        }
+        if (L.remodOut) r = remod(r, ap);
+        reinterpret_cast<P3*>(outColor)[p] = r;
+    }
+}
+
+constexpr unsigned kDenoiseMaxBlocks = 1u << 20;     // tiles beyond this (frames of more than 2^28 pixels) are walked by a grid-stride loop
+
+}  // namespace
+
+hipError_t launchDenoise(const RtowDenoiseParams& p, const float* inColor, const float* inNormal, const float* inAlbedo, float* scratch, float* outColor,
+                         hipStream_t stream)
+{
+    DenoiseLevel L;
+    L.width = p.width;
+    L.height = p.height;
+    L.normalSharpness = p.normalSharpness;
+    L.useColor = p.colorSigma != 0.0f;
+    L.useAlbedo = p.albedoSigma != 0.0f;
+    L.invA = L.useAlbedo ? 1.0f / (p.albedoSigma * p.albedoSigma) : 0.0f;
+    L.tilesX = ((unsigned)p.width + 63u) / 64u;
+    const uint64_t tiles = (uint64_t)L.tilesX * (((uint64_t)p.height + 3u) / 4u);   // (w / 64 + 1) (h / 4 + 1) < 2^30 for w h < 2^31
+    L.tiles = (unsigned)tiles;
+    const unsigned blocks = L.tiles < kDenoiseMaxBlocks ? L.tiles : kDenoiseMaxBlocks;
+    const bool demod = (p.flags & RTOW_DENOISE_DEMODULATE_ALBEDO) != 0;
+    const float sigma2 = p.colorSigma * p.colorSigma;
+    const float* src = inColor;
+    for (int k = 0; k < p.iterations; ++k) {
+        float* dst = ((p.iterations - 1 - k) & 1) ? scratch : outColor;      // the last level lands in outColor
+        L.step = 1 << k;
+        L.invC = L.useColor ? (float)(1 << (2 * k)) / sigma2 : 0.0f;
+        L.demodIn = demod && k == 0;
+        L.remodOut = demod && k == p.iterations - 1;
+        hipLaunchKernelGGL(denoise_level_kernel, dim3(blocks), dim3(256), 0, stream, L, src, inNormal, inAlbedo, dst);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        src = dst;
+    }
+    return hipSuccess;
+}
+
+}  // namespace rtow

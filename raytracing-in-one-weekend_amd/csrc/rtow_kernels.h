@@ -328,6 +328,10 @@ hipError_t launchFinalize(int pixelCount, const float* inColor, const float* inN
 // CombineJob -> FinalizeTexturesJob in one pass (the bytes of the two kernels one after the other)
 hipError_t launchCombineFinalize(const RtowCombineParams& p, const float* inColor, const float* inNormal, const float* inAlbedo,
                                  uint8_t* outColor, uint8_t* outNormal, uint8_t* outAlbedo, const float* thresholds, hipStream_t stream);
+
+// rtowDenoiseDevice (rtow_denoise.hip): one launch per a-trous level on `stream`, ping-pong between scratch and outColor (params validated by the caller)
+hipError_t launchDenoise(const RtowDenoiseParams& p, const float* inColor, const float* inNormal, const float* inAlbedo, float* scratch, float* outColor,
+                         hipStream_t stream);
 // dst[k] += src[k] for the four accumulators (float4 / float3 / float3 / float per pixel) in one launch
 hipError_t launchAddAccum(size_t pixels, float* const dst[4], const float* const src[4], hipStream_t stream);
 // rows first, first + step, ... (`rows` of them, `rowFloats` floats each) of a full-frame buffer -> / <- one contiguous block

@@ -386,6 +386,34 @@ class FinalizeTexturesJob:
         return JobHandle(rc)
 
 
+def _device_ptr(buf):
+    """a DeviceBuffer, or a raw device address (int) such as a view into one"""
+    return buf.ptr if isinstance(buf, DeviceBuffer) else buf
+
+
+class DenoiseJob:
+    """The reference's denoise step (OpenImageDenoiseJob / OptixDenoiseJob, JOBS/DenoiseJobs.cs:10-119) as rtowDenoiseDevice: the edge-avoiding
+    a-trous filter of include/rtow.h on combine's float3 colour, normal and albedo.  Device buffers (or raw device addresses); `Scratch` holds
+    abi.denoise_scratch_bytes(Width, Height) bytes and may stay None with Iterations == 1."""
+
+    def __init__(self, context, Width, Height, Iterations=abi.DENOISE_DEFAULT_ITERATIONS, NormalSharpness=abi.DENOISE_DEFAULT_NORMAL_SHARPNESS,
+                 ColorSigma=abi.DENOISE_DEFAULT_COLOR_SIGMA, AlbedoSigma=abi.DENOISE_DEFAULT_ALBEDO_SIGMA, Flags=abi.DENOISE_DEFAULT_FLAGS, Reserved=0):
+        self.context, self.Width, self.Height = context, Width, Height
+        self.Iterations, self.NormalSharpness, self.ColorSigma, self.AlbedoSigma, self.Flags, self.Reserved = \
+            Iterations, NormalSharpness, ColorSigma, AlbedoSigma, Flags, Reserved
+        self.InputColor = self.InputNormal = self.InputAlbedo = self.OutputColor = self.Scratch = None
+
+    def params(self):
+        return abi.DenoiseParams(int(self.Width), int(self.Height), int(self.Iterations), int(self.NormalSharpness), float(self.ColorSigma),
+                                 float(self.AlbedoSigma), int(self.Flags), int(self.Reserved))
+
+    def Schedule(self, stream=None):
+        p = self.params()
+        rc = load().rtowDenoiseDevice(self.context.handle, C.byref(p), _device_ptr(self.InputColor), _device_ptr(self.InputNormal),
+                                      _device_ptr(self.InputAlbedo), _device_ptr(self.Scratch), _device_ptr(self.OutputColor), stream)
+        return JobHandle(rc)
+
+
 class ReduceMetricsJob:
     """Mirror of `struct ReduceMetricsJob` (JOBS/ReduceMetricsJob.cs:10-20); device buffers in, scalars out."""
 

@@ -63,6 +63,7 @@ def load():
     lib.rtowCombineDevice.argtypes = [vp, C.POINTER(abi.CombineParams), vp, vp, vp, vp, vp, vp, vp]
     lib.rtowFinalizeDevice.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
     lib.rtowCombineFinalizeDevice.argtypes = [vp, C.POINTER(abi.CombineParams), vp, vp, vp, vp, vp, vp, vp]
+    lib.rtowDenoiseDevice.argtypes = [vp, C.POINTER(abi.DenoiseParams), vp, vp, vp, vp, vp, vp]
     lib.rtowReduceMetricsDeviceAsync.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp]
     lib.rtowAddAccumDevice.argtypes = [vp, C.c_int32, AB, AB, vp]
     lib.rtowDeviceAlloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
