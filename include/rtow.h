@@ -486,6 +486,52 @@ RTOW_API int rtowUnregisterHostBuffer(RtowContext context, void* pointer);
  * launch could only start when that batch ends.  RTOW_ERROR_NO_SCENE before rtowUploadScene. */
 RTOW_API int rtowProbeNearestHit(RtowContext context, const RtowFloat3* origin, const RtowFloat3* direction, float time, float* distance, int32_t* entityIndex);
 
+/* ---- batched nearest-hit queries on the device: the many-ray form of rtowProbeNearestHit ----
+ * replaces: what a host used its own BvhRoot->Hit for beyond the one focus ray (UNITY/Raytracer.cs:1353): a depth map and an entity-ID map of the current view
+ * (picking, selection outlines, compositing with rasterised gizmos, a noise-free edge guide for rtowDenoiseDevice), auto-focus over a region, line-of-sight queries.
+ * One ray has the semantics of rtowProbeNearestHit exactly - the same walk, compiled for the device (csrc/rtow_walk.hip.h): the nearest Entity.Hit with tMin 0,
+ * tMax +inf at the ray's time; `distance` bit for bit what rtowProbeNearestHit returns for that ray; of several entities at the bit-identical nearest distance the one
+ * first in the reference tree's leaf order; volume entities are hit as their hull, as HitWorld does.
+ * Added after API version 12 without changing it: a host detects the calls by their entry points (C#: EntryPointNotFoundException). */
+typedef struct RtowRay {            /* 32 bytes */
+    RtowFloat3 origin;  float time; /* Ray.Origin, Ray.Time */
+    RtowFloat3 direction; float pad;/* Ray.Direction as given: NOT normalised by the library; pad is ignored */
+} RtowRay;
+
+typedef struct RtowHitBuffers {     /* device pointers, `count` elements each, tightly packed; any may be NULL (not written), not all three */
+    float*   distance;              /* hitRec.Distance, +INFINITY on a miss                                  */
+    int32_t* entityIndex;           /* index into RtowSceneDesc.entities, -1 on a miss                       */
+    float*   normal;                /* float3: hitRec.Normal (world space, as Entity.Hit returns it); (0,0,0) on a miss */
+} RtowHitBuffers;
+
+/* `count` rays (device memory, 4-byte aligned) against the resident scene; hits->X[i] belongs to rays[i].  `count` is 32 bits wide like every other element count of
+ * this interface (pixelCount): 2^31 rays are 64 GB of RtowRay, and a C# `int` binds it.
+ * Enqueued on `stream` (NULL = the context's own stream): one launch, one lane per ray; no allocation, no wait.  Reads only the resident scene; ordered against
+ * rtowUploadScene like a sample batch (an upload waits for the device).  A launch QUEUES BEHIND a sample batch that is running - the sample kernel owns every CU until it
+ * ends, which is why the one-ray rtowProbeNearestHit is a host walk - so these calls are for callers that want stream order (a depth map after the frame's batches), not
+ * for a question whose answer the host needs while a batch is tracing.
+ * Validation (RTOW_ERROR_INVALID_VALUE, nothing enqueued): NULL context / rays / hits, all three hit pointers NULL, count < 0.  count == 0 succeeds and launches
+ * nothing.  RTOW_ERROR_NO_SCENE before rtowUploadScene. */
+RTOW_API int rtowTraceRaysDevice(RtowContext context, int32_t count, const RtowRay* rays /* device */,
+                                 const RtowHitBuffers* hits, void* stream);
+
+typedef struct RtowTraceViewParams {
+    int32_t width, height;
+    RtowView view;                  /* lensRadius is ignored: rays leave view.origin (a pinhole)             */
+    float time;                     /* Ray.Time of every ray                                                */
+    int32_t reserved;               /* 0 */
+} RtowTraceViewParams;
+
+/* The ray of every pixel centre of `view`: the sample path's camera ray with SubPixelJitter off and LensRadius 0 (JOBS/SampleBatchJob.cs:134, RT/View.cs:38-47):
+ * origin = view.origin, direction = normalize(lowerLeftCorner + u * horizontal + v * vertical), (u, v) = (col + 0.5, row + 0.5) / (width, height) - so a pixel's hit is
+ * the first hit of that pixel's unjittered camera ray, and hits->normal is what such a one-sample batch accumulates at trace depth 0.  A wave traces an 8 x 8 pixel tile.
+ * outRays (device, width * height, or NULL) receives the rays (pad = 0); fed to rtowTraceRaysDevice they return the same hits.
+ * Stream order, allocation and queueing as rtowTraceRaysDevice.  Validation (RTOW_ERROR_INVALID_VALUE, nothing enqueued): NULL context / params / hits, all three hit
+ * pointers NULL, width or height <= 0 or width * height > INT32_MAX, reserved != 0.  RTOW_ERROR_NO_SCENE before rtowUploadScene. */
+RTOW_API int rtowTraceViewDevice(RtowContext context, const RtowTraceViewParams* params,
+                                 const RtowHitBuffers* hits /* width*height, pixel = row*width+col, row 0 at the bottom */,
+                                 RtowRay* outRays /* device, width*height, or NULL */, void* stream);
+
 /* Device time (ms) of the most recent sample kernel of this context, measured with HIP events recorded on the
  * stream the kernel was launched on (the RecordTimeJob 0/1 bracket, JOBS/UtilJobs.cs:77-86). Synchronises on the end event. */
 RTOW_API int rtowGetLastSampleKernelMs(RtowContext context, float* outMs);

@@ -183,6 +183,24 @@ class DenoiseParams(C.Structure):
                 ("colorSigma", C.c_float), ("albedoSigma", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
+class Ray(C.Structure):
+    """RtowRay (32 bytes): Ray.Origin, Ray.Time, Ray.Direction (not normalised by the library), pad."""
+    _fields_ = [("origin", Float3), ("time", C.c_float), ("direction", Float3), ("pad", C.c_float)]
+
+
+# numpy view of an RtowRay array: rays["origin"], rays["time"], rays["direction"]
+RAY_DTYPE = [("origin", "<f4", (3,)), ("time", "<f4"), ("direction", "<f4", (3,)), ("pad", "<f4")]
+
+
+class HitBuffers(C.Structure):
+    """RtowHitBuffers: device pointers, any may be NULL (not written), not all three."""
+    _fields_ = [("distance", C.c_void_p), ("entityIndex", C.c_void_p), ("normal", C.c_void_p)]
+
+
+class TraceViewParams(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("view", View), ("time", C.c_float), ("reserved", C.c_int32)]
+
+
 def denoise_scratch_bytes(width, height):
     """RTOW_DENOISE_SCRATCH_BYTES(w, h): the ping-pong float3 colour buffer of the levels"""
     return int(width) * int(height) * 12
@@ -197,5 +215,5 @@ EXPORTED_SYMBOLS = [
     "rtowSampleBatchChainDevice", "rtowSampleBatchChain", "rtowCommSetLibraryPath", "rtowCommGetUniqueId", "rtowCommInit", "rtowCommDestroy", "rtowGatherRowsDevice",
     "rtowHybridPlan", "rtowExchangeAccumDevice", "rtowSampleBatchGroupDevice",
     "rtowCombineFinalizeDevice", "rtowReduceMetricsDeviceAsync", "rtowProbeNearestHit", "rtowSampleBatchChainAdaptiveDevice",
-    "rtowDenoiseDevice",
+    "rtowDenoiseDevice", "rtowTraceRaysDevice", "rtowTraceViewDevice",
 ]

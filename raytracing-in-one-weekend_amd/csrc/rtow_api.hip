@@ -104,6 +104,8 @@ struct RtowContext_t {
     CompiledScene scene;
     uint8_t* dScene = nullptr;
     size_t dSceneCapacity = 0;
+    int32_t* dEntityOfPrim = nullptr;     // device copy of scene.entityOfPrim for rtowTraceRaysDevice / rtowTraceViewDevice (read only while scene.entityOfPrim is not empty)
+    size_t entityOfPrimCapacity = 0;      // in entries
     uint32_t ldsSceneBytes = 0, ldsNodeCount = 0;
     unsigned short* dHistSpill = nullptr; // path-history rows that do not fit LDS (LdsPlan.histSpillRows), [row][workgroup x 1024 + lane]
     size_t histSpillBytes = 0;
@@ -1299,6 +1301,7 @@ RTOW_API int rtowDestroyContext(RtowContext ctx)
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->dScene) (void)hipFree(ctx->dScene);
+    if (ctx->dEntityOfPrim) (void)hipFree(ctx->dEntityOfPrim);
     if (ctx->dWorkCounter) (void)hipFree(ctx->dWorkCounter);
     if (ctx->dChunkCost) { (void)hipFree(ctx->dChunkCost); (void)hipFree(ctx->dChunkOrder); (void)hipFree(ctx->dPixelCost); (void)hipFree(ctx->dTicketMap); }
     if (ctx->dChunkDone) (void)hipFree(ctx->dChunkDone);
@@ -1358,6 +1361,11 @@ RTOW_API int rtowUploadScene(RtowContext ctx, const RtowSceneDesc* scene)
     HIP_TRY(ctx, hipDeviceSynchronize(), RTOW_ERROR_LAUNCH_FAILURE);   // no batch (on whatever stream it was given) may still be reading the old scene
     RTOW_TRY(growDevice(ctx, ctx->dSceneCapacity, compiled.blob.size(), {devBuf(ctx->dScene, compiled.blob.size())}));
     HIP_TRY(ctx, hipMemcpy(ctx->dScene, compiled.blob.data(), compiled.blob.size(), hipMemcpyHostToDevice), RTOW_ERROR_LAUNCH_FAILURE);
+    if (!compiled.entityOfPrim.empty()) {      // all-triangle scenes: the device queries report the host's entity index, as rtowProbeNearestHit does
+        const size_t n = compiled.entityOfPrim.size();
+        RTOW_TRY(growDevice(ctx, ctx->entityOfPrimCapacity, n, {devBuf(ctx->dEntityOfPrim, n * sizeof(int32_t))}));
+        HIP_TRY(ctx, hipMemcpy(ctx->dEntityOfPrim, compiled.entityOfPrim.data(), n * sizeof(int32_t), hipMemcpyHostToDevice), RTOW_ERROR_LAUNCH_FAILURE);
+    }
     if (!compiled.texBlob.empty()) {
         RTOW_TRY(growDevice(ctx, ctx->texBlobCapacity, compiled.texBlob.size(), {devBuf(ctx->dTexBlob, compiled.texBlob.size())}));
         HIP_TRY(ctx, hipMemcpy(ctx->dTexBlob, compiled.texBlob.data(), compiled.texBlob.size(), hipMemcpyHostToDevice), RTOW_ERROR_LAUNCH_FAILURE);
@@ -1730,6 +1738,32 @@ RTOW_API int rtowProbeNearestHit(RtowContext ctx, const RtowFloat3* origin, cons
     (void)probeNearestHitHost(ctx->scene.blob.data(), ctx->scene.layout, ctx->scene.entityOfPrim.empty() ? nullptr : ctx->scene.entityOfPrim.data(), o, d, time, &t, &prim);      // no device work: batches in flight are neither waited for nor disturbed
     if (distance) *distance = t;
     if (entityIndex) *entityIndex = prim;
+    return RTOW_SUCCESS;
+}
+
+RTOW_API int rtowTraceRaysDevice(RtowContext ctx, int32_t count, const RtowRay* rays, const RtowHitBuffers* hits, void* stream)
+{
+    if (!ctx || !rays || !hits || count < 0) return RTOW_ERROR_INVALID_VALUE;
+    if (!hits->distance && !hits->entityIndex && !hits->normal) return RTOW_ERROR_INVALID_VALUE;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
+    if (count == 0) return RTOW_SUCCESS;
+    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    HIP_TRY(ctx, launchTraceRays(ctx->dScene, ctx->scene.layout, ctx->scene.entityOfPrim.empty() ? nullptr : ctx->dEntityOfPrim, count, rays, *hits, s), RTOW_ERROR_LAUNCH_FAILURE);
+    return RTOW_SUCCESS;
+}
+
+RTOW_API int rtowTraceViewDevice(RtowContext ctx, const RtowTraceViewParams* params, const RtowHitBuffers* hits, RtowRay* outRays, void* stream)
+{
+    if (!ctx || !params || !hits) return RTOW_ERROR_INVALID_VALUE;
+    if (!hits->distance && !hits->entityIndex && !hits->normal) return RTOW_ERROR_INVALID_VALUE;
+    if (params->width <= 0 || params->height <= 0 || (int64_t)params->width * params->height > INT32_MAX || params->reserved != 0) return RTOW_ERROR_INVALID_VALUE;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
+    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    HIP_TRY(ctx, launchTraceView(ctx->dScene, ctx->scene.layout, ctx->scene.entityOfPrim.empty() ? nullptr : ctx->dEntityOfPrim, *params, *hits, outRays, s), RTOW_ERROR_LAUNCH_FAILURE);
     return RTOW_SUCCESS;
 }
 

@@ -345,6 +345,13 @@ hipError_t launchFoldRows(float* accum, const float* ownPartial, const float* re
 // rtowProbeNearestHit (rtow_probe.hip): one ray walked on the host through the scene's host image (derived entity transforms included); false = miss
 bool probeNearestHitHost(const uint8_t* blob, const SceneLayout& L, const int32_t* entityOfPrim, const float origin[3], const float direction[3], float time, float* distance, int* entity);
 
+// rtowTraceRaysDevice / rtowTraceViewDevice (rtow_trace.hip): one launch on `stream`, one lane per ray, through the DEVICE image of the scene (arguments validated by the caller);
+// entityOfPrim: the device copy of CompiledScene.entityOfPrim, or null
+hipError_t launchTraceRays(const uint8_t* blob, const SceneLayout& layout, const int32_t* entityOfPrim, int64_t count, const RtowRay* rays, const RtowHitBuffers& hits,
+                           hipStream_t stream);
+hipError_t launchTraceView(const uint8_t* blob, const SceneLayout& layout, const int32_t* entityOfPrim, const RtowTraceViewParams& p, const RtowHitBuffers& hits,
+                           RtowRay* outRays, hipStream_t stream);
+
 // same-XCD hand-over litmus of the chained launches (rtow_kernels.hip): pairs of workgroups that ran on one XCD, stale dwords seen, waits that timed out
 hipError_t runXcdCoherenceLitmus(int cuCount, hipStream_t stream, unsigned* outPairs, unsigned* outStale, unsigned* outTimeouts);
 

@@ -1,0 +1,193 @@
+// rtow_trace.hip - rtowTraceRaysDevice / rtowTraceViewDevice: batched nearest-hit queries against the resident scene, on the device.
+//
+// The many-ray form of rtowProbeNearestHit: the same walk (rtow_walk.hip.h, the text the host probe compiles) with the same hit tests, one lane per ray, on the device image
+// of the scene.  Per ray: HitRecord.Distance, the host's entity index and the world-space HitRecord.Normal of the nearest Entity.Hit (tMin 0, tMax +inf).
+//
+// Launch shape:
+//  * a plain grid of 256-lane workgroups, one lane per ray, no workgroup barrier - a lane that has no ray leaves at once;
+//  * tree and primitives come from HBM / L2 (load_node<false>, general_hit<false>): the rays of a query are arbitrary and the kernel is short, staging the scene into LDS
+//    per workgroup would cost more than it saves;
+//  * the traversal stack (at most one pending far child per inner level of the tree: RTOW_STACK_CAPACITY, + 2 as the host probe reserves) is an LDS array [entry][lane]:
+//    a lane's entries are 1 KB apart, the 64 lanes of a wave read 64 consecutive dwords - no bank conflict, no scratch; 26 x 256 x 4 B = 26 KB per workgroup, so LDS admits
+//    six workgroups (24 waves) per CU; the kernels' register counts admit that too, but for the general ray form (90 VGPRs: five waves per SIMD;
+//    tests/test_trace_rays_isa.py prints the counts);
+//  * the view form maps a wave's 64 lanes to an 8 x 8 pixel tile, so that the rays of a wave stay together in the tree; its rays are the sample kernel's REGEN expressions with
+//    SubPixelJitter off and LensRadius 0.
+#include "rtow_walk.hip.h"
+
+#include "rtow_bvh.h"
+
+namespace rtow {
+
+namespace {
+
+constexpr int kTraceBlock = 256;
+constexpr int kTraceStackEntries = RTOW_STACK_CAPACITY + 2;
+
+// a lane's column of the workgroup's [entry][lane] LDS array
+struct LdsStack {
+    int* col;
+    int sp;
+    __device__ __forceinline__ bool push(int x)
+    {
+        if (sp >= kTraceStackEntries) return false;
+        col[sp * kTraceBlock] = x;
+        sp++;
+        return true;
+    }
+    __device__ __forceinline__ int pop() { sp--; return col[sp * kTraceBlock]; }
+    __device__ __forceinline__ bool empty() const { return sp == 0; }
+};
+
+// a ray at a 4-byte aligned address (a caller may pass a view that starts anywhere in an allocation)
+struct __attribute__((packed, aligned(4))) Ray8 { float ox, oy, oz, time, dx, dy, dz, pad; };
+static_assert(sizeof(Ray8) == sizeof(RtowRay), "RtowRay is eight floats");
+
+struct TraceArgs {
+    const uint8_t* blob;            // device image of the scene
+    const int32_t* entityOfPrim;    // primitive -> the host's entity index, or null (the same number)
+    SceneLayout layout;
+    RtowHitBuffers hits;
+    // ray form
+    const RtowRay* rays;
+    long long count;
+    // view form
+    RtowRay* outRays;
+    RtowView view;
+    float time, sizeX, sizeY;
+    int width, height;
+    unsigned tilesX;
+    unsigned long long tiles;
+};
+
+// The camera ray of pixel (cx, cy): REGEN of the sample kernel (JOBS/SampleBatchJob.cs:134, RT/View.cs:38-47) with the jitter at the pixel centre and no lens offset
+__device__ __forceinline__ V3 view_direction(const RtowView& VW, int cx, int cy, float frameX, float frameY)
+{
+    const V3 viewLLC = v3(VW.lowerLeftCorner), viewH = v3(VW.horizontal), viewV = v3(VW.vertical);
+    const float jx = 0.5f, jy = 0.5f;
+    const float u = ((float)cx + jx) / frameX;
+    const float v = ((float)cy + jy) / frameY;
+    return normalize(v3(viewLLC.x + u * viewH.x + v * viewV.x,
+                        viewLLC.y + u * viewH.y + v * viewV.y,
+                        viewLLC.z + u * viewH.z + v * viewV.z));
+}
+
+// HitRecord.Normal of primitive `prim` hit at distance t: what the sample kernel's HIT stage derives (RT/Entity.cs:62-66) - the winner's test once more for its entity-space
+// normal, rotated out and normalised; spheres of the sphere kinds: r.GetPoint(t) / radius, normalised
+template <int BASE>
+__device__ __forceinline__ V3 hit_normal(const SceneRefs& sc, const SceneLayout& L, int prim, V3 ro, V3 rd, float rtime, float t)
+{
+    if (BASE >= SCENE_KIND_GENERAL) {
+        const unsigned mi = *reinterpret_cast<const unsigned*>(section<false>(sc, L.matIndexOffset) + (uint32_t)prim * 4u);
+        float t2; V3 nLocal; float4 rq;
+        (void)general_hit<false>(sc, L, prim, mi >> kPrimTypeShift, ro, rd, rtime, 0.0f, t2, nLocal, rq);
+        return normalize(rotate(rq, nLocal));
+    }
+    V3 c; float radius;
+    sphere_at<false, BASE == SCENE_KIND_SPHERES_MOTION>(sc, L, prim, rtime, c, radius);
+    const V3 oc = sub(ro, c);
+    const V3 nLocal = div3(v3(oc.x + t * rd.x, oc.y + t * rd.y, oc.z + t * rd.z), radius);
+    return normalize(nLocal);
+}
+
+template <int BASE, bool VIEW>
+__global__ void __launch_bounds__(kTraceBlock) trace_kernel(TraceArgs A)
+{
+    __shared__ int stackRows[kTraceStackEntries * kTraceBlock];
+    size_t index;
+    V3 ro, rd;
+    float time;
+    if (VIEW) {
+        // wave = 8 x 8 pixel tile, lane = (lane & 7, lane >> 3) inside it
+        const unsigned long long tile = (unsigned long long)blockIdx.x * (kTraceBlock / 64) + (threadIdx.x >> 6);
+        if (tile >= A.tiles) return;
+        const int cx = (int)(tile % A.tilesX) * 8 + (int)(threadIdx.x & 7u);
+        const int cy = (int)(tile / A.tilesX) * 8 + (int)((threadIdx.x >> 3) & 7u);
+        if (cx >= A.width || cy >= A.height) return;
+        index = (size_t)cy * (size_t)A.width + (size_t)cx;
+        ro = v3(A.view.origin);
+        rd = view_direction(A.view, cx, cy, A.sizeX, A.sizeY);
+        time = A.time;
+        if (A.outRays) {
+            reinterpret_cast<Ray8*>(A.outRays)[index] = Ray8{ro.x, ro.y, ro.z, time, rd.x, rd.y, rd.z, 0.0f};
+        }
+    } else {
+        const long long i = (long long)blockIdx.x * kTraceBlock + threadIdx.x;
+        if (i >= A.count) return;
+        index = (size_t)i;
+        const Ray8 r = reinterpret_cast<const Ray8*>(A.rays)[index];
+        ro = v3(r.ox, r.oy, r.oz);
+        time = r.time;
+        rd = v3(r.dx, r.dy, r.dz);
+    }
+    LdsStack stack;
+    stack.col = stackRows + threadIdx.x;
+    stack.sp = 0;
+    float t, rtime;
+    int prim;
+    (void)walk_nearest<BASE>(A.blob, A.layout, ro, rd, time, stack, t, prim, rtime);      // (the launcher refuses a tree deeper than the stack: push cannot fail)
+    if (A.hits.distance) A.hits.distance[index] = t;
+    if (A.hits.entityIndex) A.hits.entityIndex[index] = prim >= 0 && A.entityOfPrim ? A.entityOfPrim[prim] : prim;
+    if (A.hits.normal) {
+        V3 n = v3(0, 0, 0);
+        if (prim >= 0) {
+            SceneRefs sc;
+            sc.lds = nullptr;
+            sc.glob = A.blob;
+            sc.ldsNodeCount = 0;
+            n = hit_normal<BASE>(sc, A.layout, prim, ro, rd, rtime, t);
+        }
+        float* o = A.hits.normal + index * 3u;
+        o[0] = n.x; o[1] = n.y; o[2] = n.z;
+    }
+}
+
+template <bool VIEW>
+hipError_t launch(const TraceArgs& A, unsigned long long blocks, hipStream_t stream)
+{
+    if (A.layout.bvhDepth + 2u > (unsigned)kTraceStackEntries) return hipErrorInvalidValue;      // compileScene builds to RTOW_STACK_CAPACITY: not reachable
+    if (blocks == 0ull) return hipSuccess;
+    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)blocks), block(kTraceBlock);
+    if (A.layout.sceneKind == SCENE_KIND_SPHERES) hipLaunchKernelGGL((trace_kernel<SCENE_KIND_SPHERES, VIEW>), grid, block, 0, stream, A);
+    else if (A.layout.sceneKind == SCENE_KIND_SPHERES_MOTION) hipLaunchKernelGGL((trace_kernel<SCENE_KIND_SPHERES_MOTION, VIEW>), grid, block, 0, stream, A);
+    else hipLaunchKernelGGL((trace_kernel<SCENE_KIND_GENERAL, VIEW>), grid, block, 0, stream, A);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launchTraceRays(const uint8_t* blob, const SceneLayout& layout, const int32_t* entityOfPrim, int64_t count, const RtowRay* rays, const RtowHitBuffers& hits,
+                           hipStream_t stream)
+{
+    TraceArgs A{};
+    A.blob = blob;
+    A.entityOfPrim = entityOfPrim;
+    A.layout = layout;
+    A.hits = hits;
+    A.rays = rays;
+    A.count = count;
+    return launch<false>(A, ((unsigned long long)count + kTraceBlock - 1) / kTraceBlock, stream);
+}
+
+hipError_t launchTraceView(const uint8_t* blob, const SceneLayout& layout, const int32_t* entityOfPrim, const RtowTraceViewParams& p, const RtowHitBuffers& hits,
+                           RtowRay* outRays, hipStream_t stream)
+{
+    TraceArgs A{};
+    A.blob = blob;
+    A.entityOfPrim = entityOfPrim;
+    A.layout = layout;
+    A.hits = hits;
+    A.outRays = outRays;
+    A.view = p.view;
+    A.time = p.time;
+    A.sizeX = (float)p.width;       // SampleBatchJob.Size is a float2 (JOBS/SampleBatchJob.cs:24)
+    A.sizeY = (float)p.height;
+    A.width = p.width;
+    A.height = p.height;
+    A.tilesX = ((unsigned)p.width + 7u) / 8u;
+    A.tiles = (unsigned long long)A.tilesX * (((unsigned long long)p.height + 7u) / 8u);
+    return launch<true>(A, (A.tiles + kTraceBlock / 64 - 1) / (kTraceBlock / 64), stream);
+}
+
+}  // namespace rtow

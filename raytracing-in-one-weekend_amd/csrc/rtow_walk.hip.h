@@ -1,0 +1,118 @@
+// rtow_walk.hip.h - the nearest-hit walk of one ray through the scene image, shared by the host probe (rtow_probe.hip: rtowProbeNearestHit) and the device
+// queries (rtow_trace.hip: rtowTraceRaysDevice / rtowTraceViewDevice).  One text, compiled for the host and for gfx950, so the two cannot drift apart.
+//
+// What the reference's recursion (HitTests.Hit(BvhNode), RT/HitTests.cs:152-196) computes: the smallest Entity.Hit distance (tMin 0, tMax +inf) over the entities of the
+// leaves it reaches, and it reaches a leaf iff the ray passes the box of every node above it under AxisAlignedBoundingBox.Hit (RT/HitTests.cs:9-21).  A box that encloses
+// another passes whenever the inner one does (subtraction, multiplication, min and max are monotone in binary32), so that set is "the entities whose own box the ray passes" -
+// what the leaf children of this library's tree carry (the reference's own entity boxes under the reference's own slab test; the leaf's box where the host forced a leaf at
+// MaxBvhDepth).  The walk visits them with the sample kernel's own hit tests (sphere_at / sphere_hit / general_hit of rtow_sample_kernel.hip.h: the same expressions in the
+// same order, IEEE division and square root, no contraction), pruning inner boxes by the best distance so far with the kernel's 2^-12 of slack.
+// Hits at bit-identical distance: the entity that comes first in the reference tree's leaf order (what the sample path shades).
+//
+// Stack: where the pending far children live.  `bool push(int)` (false: no room - the walk then reports overflow instead of dropping a subtree silently), `int pop()`,
+// `bool empty()`.  The host keeps a growing array; the device a column of an LDS array (rtow_trace.hip).
+#pragma once
+#include "rtow_sample_kernel.hip.h"
+
+namespace rtow {
+
+namespace {
+
+// v_min_f32 / v_max_f32 in IEEE mode as the kernels' slab tests use them: a NaN operand yields the other operand.  On the device that is the instruction itself (minnum /
+// maxnum); the host spells it out.  (The two may differ in the sign of a zero result, which no comparison below can see.)
+__host__ __device__ __forceinline__ float hmin(float a, float b)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_fminf(a, b);
+#else
+    return a != a ? b : (b != b ? a : (a < b ? a : b));
+#endif
+}
+__host__ __device__ __forceinline__ float hmax(float a, float b)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_fmaxf(a, b);
+#else
+    return a != a ? b : (b != b ? a : (a > b ? a : b));
+#endif
+}
+
+// BASE: SCENE_KIND_SPHERES, SCENE_KIND_SPHERES_MOTION, or SCENE_KIND_GENERAL for every kind that keeps GpuPrim records.  blob: the scene image with the derived entity
+// transforms in place (the device's own copy, or the host image rtowUploadScene copied them back into).  bestPrim: the PRIMITIVE number (CompiledScene.entityOfPrim takes it
+// to the host's entity index), -1 on a miss; bestT then stays +inf.  rtimeOut: the ray time as sphere_at expects it (for the caller that derives the winner's normal).
+// Returns false if the stack refused a push (the result is then not to be used).
+template <int BASE, typename Stack>
+__host__ __device__ __forceinline__ bool walk_nearest(const uint8_t* blob, const SceneLayout& L, V3 ro, V3 rd, float time, Stack& stack, float& bestT, int& bestPrim, float& rtimeOut)
+{
+    constexpr bool GENERAL = BASE >= SCENE_KIND_GENERAL;
+    constexpr bool HAS_MOTION = BASE == SCENE_KIND_SPHERES_MOTION;
+    SceneRefs sc;
+    sc.lds = nullptr;
+    sc.glob = blob;
+    sc.ldsNodeCount = 0;
+    float rtime = time;
+    if (HAS_MOTION) { if (L.commonTimeRange) rtime = um_max(0.0f, um_min(1.0f, (rtime - L.commonT0) / (L.commonT1 - L.commonT0))); }     // what sphere_at expects (the kernel's REGEN does the same)
+    const V3 inv = v3(exact_rcp_nan_to_inf(rd.x), exact_rcp_nan_to_inf(rd.y), exact_rcp_nan_to_inf(rd.z));
+    const float a = dot(rd, rd);
+    const unsigned* rank = reinterpret_cast<const unsigned*>(blob + L.rankOffset);
+    const bool twoChildren = L.sphereCount > 1u;
+    float best = __builtin_inff();
+    int prim = -1;
+    bool ok = true;
+    int cur = 0;
+    while (cur >= 0) {
+        float4 q0, q1, q2;
+        int c0, c1;
+        load_node<false>(sc, L, cur, q0, q1, q2, c0, c1);
+        const float bestPrune = best * 1.000244140625f;
+        int next[2];
+        float entry[2];
+        int inner = 0;
+        for (int side = 0; side < 2; side++) {
+            if (side == 1 && !twoChildren) break;
+            const int child = side ? c1 : c0;
+            const float lox = side ? q0.y : q0.x, loy = side ? q0.w : q0.z, loz = side ? q1.y : q1.x;
+            const float hix = side ? q1.w : q1.z, hiy = side ? q2.y : q2.x, hiz = side ? q2.w : q2.z;
+            const float tlx = (lox - ro.x) * inv.x, thx = (hix - ro.x) * inv.x;
+            const float tly = (loy - ro.y) * inv.y, thy = (hiy - ro.y) * inv.y;
+            const float tlz = (loz - ro.z) * inv.z, thz = (hiz - ro.z) * inv.z;
+            const float tmin = hmax(hmax(hmin(tlx, thx), hmin(tly, thy)), hmax(hmin(tlz, thz), 0.0f));
+            const float tfar = hmin(hmin(hmax(tlx, thx), hmax(tly, thy)), hmax(tlz, thz));
+            if (child >= 0) {
+                if (tmin <= hmin(tfar, bestPrune)) { next[inner] = child; entry[inner] = tmin; inner++; }      // padded inner box: conservative, pruned by the nearest hit so far
+                continue;
+            }
+            if (!(tmin < tfar)) continue;                                      // AxisAlignedBoundingBox.Hit on the entity's own box (RT/HitTests.cs:15-20)
+            const int i = ~child;
+            float t;
+            bool hit;
+            if (GENERAL) {
+                const unsigned type = *reinterpret_cast<const unsigned*>(blob + L.matIndexOffset + (uint32_t)i * 4u) >> kPrimTypeShift;
+                V3 nl; float4 rq;
+                hit = general_hit<false>(sc, L, i, type, ro, rd, rtime, 0.0f, t, nl, rq);
+            } else {
+                V3 c; float r;
+                sphere_at<false, HAS_MOTION>(sc, L, i, rtime, c, r);
+                hit = sphere_hit(sub(ro, c), rd, a, r, t);
+            }
+            if (hit && (t < best || (t == best && prim >= 0 && rank[i] < rank[prim]))) { best = t; prim = i; }
+        }
+        if (inner == 2) {
+            const int far = entry[1] < entry[0] ? 0 : 1;                       // near child first
+            if (!stack.push(next[far])) ok = false;                            // (cannot happen for a tree within its own depth bound; never drop a subtree silently)
+            cur = next[1 - far];
+        } else if (inner == 1) {
+            cur = next[0];
+        } else {
+            cur = stack.empty() ? -1 : stack.pop();
+        }
+    }
+    bestT = best;
+    bestPrim = prim;
+    rtimeOut = rtime;
+    return ok;
+}
+
+} // namespace
+
+} // namespace rtow

@@ -181,6 +181,45 @@ class Context:
         check(load().rtowProbeNearestHit(self.handle, C.byref(o3), C.byref(d3), float(time), C.byref(d), C.byref(e)), "rtowProbeNearestHit")
         return e.value >= 0, d.value, e.value
 
+    def _trace(self, count, launch, want, want_rays=False):
+        """The buffers of one query: allocate those named in `want`, run `launch(hits, rays_ptr)`, wait, download."""
+        kinds = {"distance": (np.float32, (count,)), "entityIndex": (np.int32, (count,)), "normal": (np.float32, (count, 3))}
+        bufs = {k: DeviceBuffer(self, max(1, count) * 4 * (3 if k == "normal" else 1)) for k in kinds if k in want}
+        rays = DeviceBuffer(self, max(1, count) * C.sizeof(abi.Ray)) if want_rays else None
+        try:
+            hits = abi.HitBuffers(*[bufs[k].handle.value if k in bufs else None for k in ("distance", "entityIndex", "normal")])
+            launch(hits, rays.handle if rays else None)
+            self.synchronize()
+            out = {k: bufs[k].download(*kinds[k]) for k in bufs}
+            if rays:
+                out["rays"] = rays.download(np.dtype(abi.RAY_DTYPE), (count,))
+            return out
+        finally:
+            for b in list(bufs.values()) + ([rays] if rays else []):
+                b.free()
+
+    def trace_rays(self, rays, want=("distance", "entityIndex", "normal"), stream=None):
+        """rtowTraceRaysDevice on host data: `rays` is an array of abi.RAY_DTYPE (or (n, 8) float32: origin, time, direction, pad).
+        Returns {"distance": (n,) float32, "entityIndex": (n,) int32, "normal": (n, 3) float32} for the names in `want`."""
+        a = np.ascontiguousarray(rays)
+        if a.dtype != np.dtype(abi.RAY_DTYPE):
+            a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 8)
+        count = int(a.shape[0])
+        dev = DeviceBuffer(self, max(1, count) * C.sizeof(abi.Ray))
+        try:
+            if count:
+                dev.upload(a)
+            return self._trace(count, lambda hits, _: check(load().rtowTraceRaysDevice(self.handle, count, dev.handle, C.byref(hits), stream), "rtowTraceRaysDevice"), want)
+        finally:
+            dev.free()
+
+    def trace_view(self, view, width, height, time=0.0, want_rays=False, want=("distance", "entityIndex", "normal"), stream=None):
+        """rtowTraceViewDevice: the first hit of every pixel centre's camera ray (pixel = row * width + col, row 0 at the bottom).
+        Returns the arrays of trace_rays, plus "rays" (abi.RAY_DTYPE) with want_rays."""
+        p = abi.TraceViewParams(int(width), int(height), view, float(time), 0)
+        return self._trace(int(width) * int(height),
+                           lambda hits, rays: check(load().rtowTraceViewDevice(self.handle, C.byref(p), C.byref(hits), rays, stream), "rtowTraceViewDevice"), want, want_rays)
+
     def synchronize(self):
         check(load().rtowSynchronize(self.handle), "rtowSynchronize")
 

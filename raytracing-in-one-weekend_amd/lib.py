@@ -64,6 +64,8 @@ def load():
     lib.rtowFinalizeDevice.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
     lib.rtowCombineFinalizeDevice.argtypes = [vp, C.POINTER(abi.CombineParams), vp, vp, vp, vp, vp, vp, vp]
     lib.rtowDenoiseDevice.argtypes = [vp, C.POINTER(abi.DenoiseParams), vp, vp, vp, vp, vp, vp]
+    lib.rtowTraceRaysDevice.argtypes = [vp, C.c_int32, vp, C.POINTER(abi.HitBuffers), vp]
+    lib.rtowTraceViewDevice.argtypes = [vp, C.POINTER(abi.TraceViewParams), C.POINTER(abi.HitBuffers), vp, vp]
     lib.rtowReduceMetricsDeviceAsync.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp]
     lib.rtowAddAccumDevice.argtypes = [vp, C.c_int32, AB, AB, vp]
     lib.rtowDeviceAlloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
