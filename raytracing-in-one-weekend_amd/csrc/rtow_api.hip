@@ -3,26 +3,23 @@
 // Host-side runtime of the path: context / device selection, scene compilation + upload, grow-only device staging
 // for the host-buffer entry point, kernel launch on a HIP stream with HIP-event timing, cooperative cancellation,
 // and the post passes.  There is no CPU implementation behind any entry point: without a usable HIP device
-// rtowCreateContext fails with RTOW_ERROR_NO_DEVICE and nothing else can be called.
+// rtowCreateContext fails with RTOW_ERROR_NO_DEVICE and nothing else can be called.  The multi-GPU entry points (rtowComm*, rtowGatherRowsDevice,
+// rtowHybridPlan, rtowExchangeAccumDevice) are in rtow_comm.hip; the context itself is rtow_context.h.
 #include <hip/hip_runtime.h>
-#include <dlfcn.h>
 
 #include <algorithm>
 #include <atomic>
 #include <cfloat>
 #include <chrono>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/rtow.h"
-#include "rtow_bvh.h"
-#include "rtow_kernels.h"
+#include "rtow_context.h"
 
 // minimum lane population per stage, in 64ths of the wave's live lanes: REGEN TRAV TEST HIT SKY VOL | candidates that end a walk (hand-over to TEST) | unused | box-walk slice (node visits per trip).
 // Sphere kinds: REGEN from 3/8, the walk and HIT from 1/2, SKY from 7/16, TEST at once.  Since a chunk's 64 tickets are an 8 x 8 tile of the image
@@ -35,12 +32,6 @@
 #define RTOW_GROUP_SLOT_BLOCK 4     // (chunk, batch) slots a wave reserves at a time in a batch group (SampleKernelArgs.slotBlock): groups + fold 9 978 -> 10 160 Msamples/s at 4, 10 118 at 2
 #endif
 static constexpr unsigned kGroupSlotBlock = RTOW_GROUP_SLOT_BLOCK;
-#ifndef RTOW_DEFAULT_REGROUP_SIDE
-// RtowContextOptions.schedulerTune[7], which pixel a ticket stands for: 1 = its place in its 8 x 8 tile; 3 = the tiles as they are, each tile's tickets most expensive pixel first
-// (order_tile_tickets_kernel: +0.7 % on the headline, +0.9 % as plain launches, +1.3 % as groups, same box, three alternating runs - profiles/r05a_pixel_regrouping.json);
-// 2 / 4 / 8 (+ 16 x mode): pixels regrouped by cost or class inside super-tiles of that many tiles (0 ... -5 %: measured, not used)
-#define RTOW_DEFAULT_REGROUP_SIDE 3
-#endif
 #ifndef RTOW_PIXEL_GATE
 #define RTOW_PIXEL_GATE 1     // lanes of a wave that must want a pixel boundary before the boundary block runs (1 = at once; the kernel's A.tune[7]); measured: see HISTORY.md round 6
 #endif
@@ -50,9 +41,6 @@ static constexpr unsigned kGroupSlotBlock = RTOW_GROUP_SLOT_BLOCK;
 // 14 -> 5 370, 18 -> 4 895, 24 -> 4 180.  (Float bits with the low eight zero: they share tune[7] with the pixel gate.)
 #define RTOW_URGENT_RAYS_PER_SAMPLE 18.0f
 #define RTOW_URGENT_RAYS_PER_SAMPLE_BEYOND_LDS 14.0f
-#endif
-#ifndef RTOW_DEFAULT_TUNE
-#define RTOW_DEFAULT_TUNE 24, 32, 1, 32, 28, 1, 3, 1, 16
 #endif
 #ifndef RTOW_GENERAL_TUNE
 #define RTOW_GENERAL_TUNE 16, 48, 1, 1, 1, 1, 3, 1, 16
@@ -86,191 +74,8 @@ static void candidateThresholds(int candidate, int* tune, int count)
 
 using namespace rtow;
 
-struct RtowContext_t {
-    int device = 0;
-    int cuCount = 0;
-    RtowLogCallback logCb = nullptr;
-    void* logData = nullptr;
-    int logLevel = 0;
-
-    hipStream_t stream = nullptr;
-    hipEvent_t evStart = nullptr, evStop = nullptr;
-    hipEvent_t evBatchDone = nullptr;   // end of everything the last sample batch enqueued (kernel + chunk-order refresh)
-    bool haveBatchDone = false;
-    bool haveTiming = false;
-
-    // scene
-    bool haveScene = false;
-    CompiledScene scene;
-    uint8_t* dScene = nullptr;
-    size_t dSceneCapacity = 0;
-    int32_t* dEntityOfPrim = nullptr;     // device copy of scene.entityOfPrim for rtowTraceRaysDevice / rtowTraceViewDevice (read only while scene.entityOfPrim is not empty)
-    size_t entityOfPrimCapacity = 0;      // in entries
-    uint32_t ldsSceneBytes = 0, ldsNodeCount = 0;
-    unsigned short* dHistSpill = nullptr; // path-history rows that do not fit LDS (LdsPlan.histSpillRows), [row][workgroup x 1024 + lane]
-    size_t histSpillBytes = 0;
-    LdsPlan ldsPlan{};                    // of launches whose variant keeps its whole path history in registers (trace depth <= 16); the others plan per launch (launchSample)
-
-    // work distribution / cancellation
-    unsigned int* dWorkCounter = nullptr;
-    // chunk cost map -> launch order (longest chunks first); valid for one (width, height, slice, scene) configuration
-    unsigned int* dChunkDone = nullptr;   // chained batches: pixels stored per chunk
-    uint8_t* dXcdState = nullptr;         // chained batches: XcdState + kMaxXcds lists of chunkDoneCapacity entries (which XCD owns which chunk)
-    ChainBatch* dChainBatches = nullptr;  // chained batches: per-batch seed / diagnostics table of the launch being enqueued
-    uint32_t chunkDoneCapacity = 0;
-    unsigned int *dChunkCost = nullptr, *dChunkOrder = nullptr;
-    unsigned short* dPixelCost = nullptr;
-    unsigned int* dTicketMap = nullptr;   // ticket -> owned pixel (SampleKernelArgs.ticketMap), chunkCapacity * 64 entries; re-sorted from every launch's cost map
-    bool orderMapped = false;             // the cost map / order on hand were recorded under dTicketMap (else under the tiles themselves)
-    uint32_t chunkCapacity = 0;
-    bool orderValid = false;
-    int orderW = 0, orderH = 0, orderOff = 0, orderDiv = 0;
-    volatile uint32_t* hCancel = nullptr; // pinned, device-visible: [0] cancel, [1] hit-list overflow, [2] tie-list overflow; the metrics record of rtowReduceMetricsDevice at byte 64
-    volatile RtowMetrics* hMetricsRecord = nullptr;
-    RtowMetrics* dMetricsRecord = nullptr;
-    // RTOW_RNG_PER_SAMPLE: one 64-byte record per (owned pixel, sample group) unit
-    float* dUnitRecords = nullptr;
-    size_t unitRecordCapacity = 0;
-    uint32_t orderGroups = 1;     // groups per pixel the chunk cost map was recorded with
-    // RTOW_CONTEXT_REFERENCE_DIAGNOSTICS: the reference's own tree of the current scene (CompiledScene.refTree), HBM only
-    uint8_t* dRefTree = nullptr;
-    size_t refTreeCapacity = 0;
-    // hit lists beyond the 24 entries a lane holds itself (volume scenes, exact-tie kernels): [entry][lane] columns, grow-only
-    uint4* dHitSpill = nullptr;
-    uint32_t hitSpillEntries = 0;         // of the current scene (<= hitSpillCapacity)
-    uint32_t hitSpillCapacity = 0;        // entries per lane the allocation holds
-    uint32_t hitListCapacity = 0;         // RtowContextOptions.hitListCapacity (0 = default)
-    uint32_t grownListCapacity = 0;       // hitListCapacity == 0 only: what the capacity has grown to after batches that met longer lists (growHitList); kept across scenes
-    bool triWatchOff = false;             // this all-triangle scene ties too often for the tie watch (a watched launch marked thousands of pixels, or more than the list holds): exact-tie kernels from now on
-    bool overflowGrew = false;            // the last reported overflow enlarged the capacity: the same batch, issued again, has room
-    // Image-texture blob of the current scene (CompiledScene.texBlob), HBM only
-    uint8_t* dTexBlob = nullptr;
-    size_t texBlobCapacity = 0;
-    // noise texture sets (rtowUploadBlueNoise / rtowUploadStbNoise): device copies, `textureCount` textures back to back
-    uint8_t* dBlueNoise = nullptr;
-    uint32_t blueRowStride = 0, blueTextureCount = 0;
-    uint8_t* dStbNoise = nullptr;        // scalar | vector2 | cosineUnitVector3 | unitVector2 | unitVector3 sets, in this order
-    uint32_t stbRowStride = 0, stbTextureCount = 0;
-    // sky cubemap (rtowUploadSkyCubemap)
-    uint8_t* dCubemap = nullptr;
-    size_t cubemapCapacity = 0;
-    RtowCubemapDesc cubemap{};   // .faces is not kept (host pointer): dCubemap holds the copy, null when none
-    // camera-ray candidate lists (primary_candidates_kernel): valid for one (scene upload, view, size, slice, jitter) configuration
-    uint2* dPixCand = nullptr;
-    size_t pixCandCapacity = 0;           // bytes
-    bool pixCandValid = false;
-    uint64_t sceneSerial = 0, pixCandScene = 0;
-    RtowView pixCandView{};
-    int pixCandW = 0, pixCandH = 0, pixCandOff = 0, pixCandDiv = 0, pixCandJitter = 0;
-
-    // grow-only staging for rtowSampleBatch (host buffers) - like CudaBuffer.EnsureCapacity (OptixApi.cs:240-251)
-    float *dColor = nullptr, *dNormal = nullptr, *dAlbedo = nullptr, *dScw = nullptr;
-    uint8_t* dDiag = nullptr;
-    size_t stagingPixels = 0, stagingDiagBytes = 0;
-
-    MetricsPartial* dPartials = nullptr;
-    RtowFloat2* dExtremaPartials = nullptr;   // [kMetricsBlocks] rtowSampleBatchChainAdaptiveDevice: partials of the per-batch weight-extrema reduction
-    unsigned* dExtremaKeys = nullptr;         // [2 x kMaxChain] ... of a fused launch: every batch's (min, max) folded at store time
-
-    // nearest-hit ties of the rank-rule sphere kernels (SampleKernelArgs.tieBits / tieRedo): the bitmap the fast kernel marks, the list the fix-up launch renders, a copy
-    // of the inputs of launches that accumulate in place, and the fix-up launch's own (small) hit-list spill area
-    unsigned* dTieRedo = nullptr;
-    unsigned* dTieBits = nullptr;
-    size_t tieBitsWords = 0;
-    float* dTieInputs = nullptr;          // colour | normal | albedo | weight of `tieInputPixels` pixels
-    size_t tieInputPixels = 0;
-    uint4* dRedoSpill = nullptr;
-    uint32_t redoSpillEntries = 0;
-
-    // RtowContextOptions: behaviour switches and development knobs (nothing is read from the environment)
-    bool wideCodes = false;               // current scene: more than 65 535 entities or tree nodes (32-bit candidate / stack codes, tree read from HBM)
-    uint32_t flags = 0;
-    uint32_t ldsSceneBudget = 0;          // 0 = everything that fits
-    int tune[9] = {RTOW_DEFAULT_TUNE};
-    bool userTune = false;                // RtowContextOptions.schedulerTune was given: no per-scene adjustment
-    // RtowContextOptions.schedulerTune[7] (see RTOW_DEFAULT_REGROUP_SIDE), as given and decoded by rtowCreateContext
-    int schedulerKnob = RTOW_DEFAULT_REGROUP_SIDE;
-    unsigned ticketMapSide = 0;           // which pixel a ticket stands for: 0 = its place in its tile, 1 = a tile's tickets most expensive first, 2 / 4 / 8 = super-tiles of that many tiles
-    unsigned regroupMode = 0;             // development: what the ticket map sorts by (0 ray count, 1 sky / not sky, 2 / 3 classes of rays per sample)
-    bool orderByTotal = false;            // development: chunks ordered by their total ray count instead of by their most expensive pixel
-    unsigned slotBlockOverride = 0;       // batch groups' (chunk, batch) slots per pull (0 = by the launch: prepareChunkOrder)
-    int pixelGateOverride = 0;            // lanes that must want a pixel boundary (0 = by the samples a unit of work takes: setSchedulerValues)
-    bool userSliceDefault = false;        // ... with a zero walk slice: the per-scene built-in value
-    bool chainFusion = true;              // the same-XCD hand-over litmus passed on this device (rtowCreateContext): chains may run as one launch
-    uint64_t tunedScene = ~0ull;          // sceneSerial whose thresholds were measured (tuneThresholds)
-    int tunedCandidate = -1;              // which candidate won (rtowGetSceneInfo-independent; logged)
-    bool tunePending = false;             // probes of scene tunePendingScene are enqueued; their events are read by a later call, never waited for
-    uint64_t tunePendingScene = 0;
-    int tuneCandidates = 0, tuneBuiltin = 0;
-    std::vector<hipEvent_t> tuneEvents;
-    uint32_t* dProbeSink = nullptr;       // where probes report rays beyond the hit-list capacity (not the batch's flag)
-    uint64_t sppSinceUpload = 0;          // samples per pixel this scene has been asked for since its upload: a measurement must be worth its probes
-    uint64_t sceneSignatureNow = 0;       // of the current scene
-    struct TuneCacheEntry { uint64_t signature; int winner; };
-    std::vector<TuneCacheEntry> tuneCache;   // winners by scene signature: a re-upload of a like scene does not measure again
-
-    // rtowRegisterHostBuffer: pinned + device-mapped ranges of caller memory
-    struct HostRange { uint8_t* base; size_t size; uint8_t* device; };
-    std::vector<HostRange> hostRanges;
-
-    // rtowComm*: RCCL communicator of this rank (one process per GPU) and the packed-row staging of rtowGatherRowsDevice
-    void* comm = nullptr;                 // ncclComm_t
-    int commRank = 0, commWorld = 1;
-    float *dGatherSend = nullptr, *dGatherRecv = nullptr;
-    size_t gatherSendFloats = 0, gatherRecvFloats = 0;
-    float* dByteThresholds = nullptr;     // FinalizeTexturesJob's float -> byte step table (rtow_finalize.hip.h), built when the context is created
-    hipEvent_t evGatherDone = nullptr;    // end of the last gather: the staging blocks are per context, gathers may come on different streams
-    bool haveGatherDone = false;
-    hipEvent_t evMetricsDone = nullptr;   // end of the last metrics reduction (the per-block partials are per context)
-    bool haveMetricsDone = false;
-
-    std::mutex mu;
-    std::mutex sceneMu;      // guards the HOST image of the scene (scene.blob / layout / entityOfPrim, haveScene) between rtowUploadScene and rtowProbeNearestHit; taken after mu, never the other way round
-};
 
 namespace {
-
-void logf(RtowContext ctx, int level, const char* tag, const char* fmt, ...)
-{
-    if (!ctx || !ctx->logCb || level > ctx->logLevel) return;
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    ctx->logCb(level, tag, buf, ctx->logData);
-}
-
-#define HIP_TRY(ctx, expr, result)                                                                    \
-    do {                                                                                              \
-        hipError_t _e = (expr);                                                                       \
-        if (_e != hipSuccess) {                                                                       \
-            logf(ctx, 2, "hip", "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-            return (result);                                                                          \
-        }                                                                                             \
-    } while (0)
-
-#define RTOW_TRY(expr)                                                                                \
-    do {                                                                                              \
-        const int _rc = (expr);                                                                       \
-        if (_rc != RTOW_SUCCESS) return _rc;                                                          \
-    } while (0)
-
-// Grow-only device buffers of the context: when `need` exceeds `capacity` (in the caller's unit) each buffer is freed and allocated again at its own size - the
-// contents are not kept - and `capacity` becomes `need`.  Several buffers may share one capacity.  A failed allocation leaves the capacity 0, so the next call
-// allocates again.  Callers do around it what the old buffer needs first (a batch in flight may still read it) and what a new one invalidates.
-struct DeviceBuf { void** p; size_t bytes; };
-template <typename T> DeviceBuf devBuf(T*& p, size_t bytes) { return DeviceBuf{reinterpret_cast<void**>(&p), bytes}; }
-template <typename C>
-int growDevice(RtowContext ctx, C& capacity, uint64_t need, std::initializer_list<DeviceBuf> bufs)
-{
-    if (need <= (uint64_t)capacity) return RTOW_SUCCESS;
-    for (const DeviceBuf& b : bufs) { if (*b.p) (void)hipFree(*b.p); *b.p = nullptr; }
-    capacity = 0;
-    for (const DeviceBuf& b : bufs) HIP_TRY(ctx, hipMalloc(b.p, b.bytes), RTOW_ERROR_MEMORY_ALLOCATION);
-    capacity = (C)need;
-    return RTOW_SUCCESS;
-}
 
 int validateParams(const RtowSampleParams* p)
 {
@@ -983,74 +788,6 @@ int prepareStaging(RtowContext ctx, int count, const RtowSampleParams* p, void* 
     return RTOW_SUCCESS;
 }
 
-// ---- RCCL, loaded on first use: hosts that drive one GPU never map it, and a process that already holds a copy (PyTorch ships its own
-// librccl.so.1) shares that copy.  Only the point-to-point calls the row gather needs; types restated from <rccl/rccl.h> (ROCm 7.2:
-// NCCL_UNIQUE_ID_BYTES 128, ncclFloat32 = 7, ncclSuccess = 0) so that the library has no link-time dependency on RCCL. ----
-struct RcclUniqueId { char internal[128]; };
-static_assert(sizeof(RcclUniqueId) == sizeof(RtowCommId), "RtowCommId carries an ncclUniqueId");
-struct RcclApi {
-    void* handle = nullptr;
-    int (*GetUniqueId)(RcclUniqueId*) = nullptr;
-    int (*CommInitRank)(void**, int, RcclUniqueId, int) = nullptr;
-    int (*CommDestroy)(void*) = nullptr;
-    int (*GroupStart)() = nullptr;
-    int (*GroupEnd)() = nullptr;
-    int (*Send)(const void*, size_t, int, int, void*, hipStream_t) = nullptr;
-    int (*Recv)(void*, size_t, int, int, void*, hipStream_t) = nullptr;
-    const char* (*GetErrorString)(int) = nullptr;
-    bool ok() const { return handle && GetUniqueId && CommInitRank && CommDestroy && GroupStart && GroupEnd && Send && Recv && GetErrorString; }
-};
-constexpr int kRcclFloat32 = 7;
-
-std::mutex gRcclMu;
-std::string gRcclPath;        // rtowCommSetLibraryPath: the file to load instead of the default search
-std::string gRcclLoadError;   // why the last load attempt failed (dlerror() is per thread and may be null by the time it is logged)
-bool gRcclLoaded = false;
-
-RcclApi* rccl()
-{
-    static RcclApi api;
-    std::lock_guard<std::mutex> lock(gRcclMu);
-    if (api.ok()) return &api;
-    static const char* names[] = {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
-    void* h = nullptr;
-    if (!gRcclPath.empty()) {
-        h = dlopen(gRcclPath.c_str(), RTLD_NOW | RTLD_LOCAL);
-    } else {
-        for (const char* n : names) if ((h = dlopen(n, RTLD_NOW | RTLD_NOLOAD | RTLD_GLOBAL))) break;     // a copy this process already holds
-        if (!h) for (const char* n : names) if ((h = dlopen(n, RTLD_NOW | RTLD_GLOBAL))) break;
-    }
-    if (!h) {
-        const char* e = dlerror();
-        gRcclLoadError = e ? e : "dlopen failed";
-        return nullptr;
-    }
-    api.handle = h;
-    api.GetUniqueId = (int (*)(RcclUniqueId*))dlsym(h, "ncclGetUniqueId");
-    api.CommInitRank = (int (*)(void**, int, RcclUniqueId, int))dlsym(h, "ncclCommInitRank");
-    api.CommDestroy = (int (*)(void*))dlsym(h, "ncclCommDestroy");
-    api.GroupStart = (int (*)())dlsym(h, "ncclGroupStart");
-    api.GroupEnd = (int (*)())dlsym(h, "ncclGroupEnd");
-    api.Send = (int (*)(const void*, size_t, int, int, void*, hipStream_t))dlsym(h, "ncclSend");
-    api.Recv = (int (*)(void*, size_t, int, int, void*, hipStream_t))dlsym(h, "ncclRecv");
-    api.GetErrorString = (const char* (*)(int))dlsym(h, "ncclGetErrorString");
-    if (!api.ok()) { gRcclLoadError = "the library does not export the nccl* entry points the row gather needs"; return nullptr; }
-    gRcclLoaded = true;
-    return &api;
-}
-
-#define RCCL_TRY(ctx, api, expr)                                                                       \
-    do {                                                                                               \
-        const int _r = (expr);                                                                         \
-        if (_r != 0) {                                                                                 \
-            logf(ctx, 2, "rccl", "%s failed: %s (%s:%d)", #expr, (api)->GetErrorString(_r), __FILE__, __LINE__); \
-            return RTOW_ERROR_LAUNCH_FAILURE;                                                          \
-        }                                                                                              \
-    } while (0)
-
-// rows of the frame owned by `rank` under the reference's interlacing (row % divider == rank, JOBS/SampleBatchJob.cs:69-70)
-unsigned rowsOwnedBy(int rank, int divider, int height) { return rank >= height ? 0u : (unsigned)((height - rank + divider - 1) / divider); }
-
 // Whether the `count` batches of one call may share launches: they differ in nothing but Seed (the reference's successive batches of a frame: UNITY/Raytracer.cs:656-661) -
 // and SampleCountWeightExtrema where `extremaFree` (the adaptive call: each batch reads its own from device memory) - under the reference RNG policy (per-sample units
 // fold through records), in a frame of fewer than 2^27 padded owned pixels.  Batches of a chain hand accumulators over inside the launch (handOver): only where this
@@ -1329,15 +1066,12 @@ RTOW_API int rtowDestroyContext(RtowContext ctx)
     if (ctx->hCancel) (void)hipHostFree((void*)ctx->hCancel);
     if (ctx->dColor) { (void)hipFree(ctx->dColor); (void)hipFree(ctx->dNormal); (void)hipFree(ctx->dAlbedo); (void)hipFree(ctx->dScw); }
     if (ctx->dDiag) (void)hipFree(ctx->dDiag);
-    if (ctx->comm) { if (RcclApi* api = rccl()) (void)api->CommDestroy(ctx->comm); ctx->comm = nullptr; }
-    if (ctx->dGatherSend) (void)hipFree(ctx->dGatherSend);
-    if (ctx->dGatherRecv) (void)hipFree(ctx->dGatherRecv);
+    releaseComm(ctx);
     for (const RtowContext_t::HostRange& r : ctx->hostRanges) (void)hipHostUnregister(r.base);
     ctx->hostRanges.clear();
     if (ctx->evStart) (void)hipEventDestroy(ctx->evStart);
     if (ctx->evStop) (void)hipEventDestroy(ctx->evStop);
     if (ctx->evBatchDone) (void)hipEventDestroy(ctx->evBatchDone);
-    if (ctx->evGatherDone) (void)hipEventDestroy(ctx->evGatherDone);
     if (ctx->evMetricsDone) (void)hipEventDestroy(ctx->evMetricsDone);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -1893,293 +1627,6 @@ RTOW_API int rtowReduceMetricsDeviceAsync(RtowContext ctx, int32_t pixelCount, c
     HIP_TRY(ctx, launchFoldMetrics(ctx->dPartials, target, s), RTOW_ERROR_LAUNCH_FAILURE);
     HIP_TRY(ctx, hipEventRecord(ctx->evMetricsDone, s), RTOW_ERROR_LAUNCH_FAILURE);
     ctx->haveMetricsDone = true;
-    return RTOW_SUCCESS;
-}
-
-RTOW_API int rtowCommSetLibraryPath(const char* path)
-{
-    std::lock_guard<std::mutex> lock(gRcclMu);
-    if (gRcclLoaded) return RTOW_ERROR_INVALID_VALUE;              // loaded once per process: the choice comes before the first rtowComm* call
-    gRcclPath = path ? path : "";
-    return RTOW_SUCCESS;
-}
-
-RTOW_API int rtowCommGetUniqueId(RtowCommId* outId)
-{
-    if (!outId) return RTOW_ERROR_INVALID_VALUE;
-    RcclApi* api = rccl();
-    if (!api) return RTOW_ERROR_UNSUPPORTED;                       // no librccl.so in this process or on the loader path
-    RcclUniqueId id;
-    if (api->GetUniqueId(&id) != 0) return RTOW_ERROR_LAUNCH_FAILURE;
-    memcpy(outId->bytes, id.internal, sizeof(id.internal));
-    return RTOW_SUCCESS;
-}
-
-RTOW_API int rtowCommInit(RtowContext ctx, const RtowCommId* id, int32_t rank, int32_t worldSize)
-{
-    if (!ctx || !id || worldSize < 1 || rank < 0 || rank >= worldSize) return RTOW_ERROR_INVALID_VALUE;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    if (ctx->comm) return RTOW_ERROR_INVALID_VALUE;                // one communicator per context; rtowCommDestroy first
-    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
-    RcclApi* api = rccl();
-    if (!api) {
-        std::lock_guard<std::mutex> l2(gRcclMu);
-        logf(ctx, 2, "rccl", "the RCCL library could not be loaded: %s", gRcclLoadError.c_str());
-        return RTOW_ERROR_UNSUPPORTED;
-    }
-    RcclUniqueId uid;
-    memcpy(uid.internal, id->bytes, sizeof(uid.internal));
-    void* comm = nullptr;
-    RCCL_TRY(ctx, api, api->CommInitRank(&comm, worldSize, uid, rank));
-    ctx->comm = comm;
-    ctx->commRank = rank;
-    ctx->commWorld = worldSize;
-    logf(ctx, 4, "rccl", "rank %d of %d joined", rank, worldSize);
-    return RTOW_SUCCESS;
-}
-
-RTOW_API int rtowCommDestroy(RtowContext ctx)
-{
-    if (!ctx) return RTOW_ERROR_INVALID_VALUE;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    if (!ctx->comm) return RTOW_SUCCESS;
-    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
-    (void)hipDeviceSynchronize();
-    RcclApi* api = rccl();
-    if (api) (void)api->CommDestroy(ctx->comm);
-    ctx->comm = nullptr;
-    ctx->commRank = 0;
-    ctx->commWorld = 1;
-    return RTOW_SUCCESS;
-}
-
-RTOW_API int rtowGatherRowsDevice(RtowContext ctx, int32_t width, int32_t height, int32_t sliceDivider, const RtowAccumBuffers* mine,
-                                  const RtowAccumBuffers* frame, int32_t what, int32_t root, void* stream)
-{
-    if (!ctx || !mine || width <= 0 || height <= 0 || sliceDivider < 1 || (what & ~(RTOW_GATHER_ALL | RTOW_GATHER_NO_BATCH_WAIT | RTOW_GATHER_LOOPBACK)) || !(what & RTOW_GATHER_ALL)) return RTOW_ERROR_INVALID_VALUE;
-    const bool waitForBatch = !(what & RTOW_GATHER_NO_BATCH_WAIT);
-    const bool wantLoopback = (what & RTOW_GATHER_LOOPBACK) != 0;
-    what &= RTOW_GATHER_ALL;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    const int world = ctx->comm ? ctx->commWorld : 1, rank = ctx->comm ? ctx->commRank : 0;
-    const bool loopback = wantLoopback && ctx->comm && world == 1;      // one rank sending its rows to itself through the transport (RTOW_GATHER_LOOPBACK)
-    if (sliceDivider != world || root < 0 || root >= world) return RTOW_ERROR_INVALID_VALUE;   // rank g owns the rows of slice g: one slice per rank
-    if (rank == root && !frame) return RTOW_ERROR_INVALID_VALUE;
-    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    // the rows being gathered were written by the last sample batch, whatever stream that was enqueued on (RTOW_GATHER_NO_BATCH_WAIT: they were not)
-    if (waitForBatch && ctx->haveBatchDone) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->evBatchDone, 0), RTOW_ERROR_LAUNCH_FAILURE);
-
-    static const int kComponents[4] = {4, 3, 3, 1};
-    float* const mineBuf[4] = {mine->color, mine->normal, mine->albedo, mine->sampleCountWeight};
-    float* const frameBuf[4] = {frame ? frame->color : nullptr, frame ? frame->normal : nullptr, frame ? frame->albedo : nullptr, frame ? frame->sampleCountWeight : nullptr};
-    unsigned floatsPerPixel = 0;
-    for (int b = 0; b < 4; b++)
-        if (what & (1 << b)) {
-            if (!mineBuf[b] || (rank == root && !frameBuf[b])) return RTOW_ERROR_INVALID_VALUE;
-            floatsPerPixel += (unsigned)kComponents[b];
-        }
-    auto packedFloats = [&](int r) { return (size_t)rowsOwnedBy(r, world, height) * (size_t)width * floatsPerPixel; };
-
-    if (loopback) {
-        // the whole transport path of a peer AND of the root, against itself: pack -> {ncclSend, ncclRecv} to / from rank 0 in one group -> scatter
-        RcclApi* api = rccl();
-        if (!api) return RTOW_ERROR_UNSUPPORTED;
-        if (ctx->haveGatherDone) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->evGatherDone, 0), RTOW_ERROR_LAUNCH_FAILURE);
-        const size_t need = packedFloats(0);
-        if (need > ctx->gatherSendFloats || need > ctx->gatherRecvFloats) HIP_TRY(ctx, hipStreamSynchronize(s), RTOW_ERROR_LAUNCH_FAILURE);
-        RTOW_TRY(growDevice(ctx, ctx->gatherSendFloats, need, {devBuf(ctx->dGatherSend, need * 4u)}));
-        RTOW_TRY(growDevice(ctx, ctx->gatherRecvFloats, need, {devBuf(ctx->dGatherRecv, need * 4u)}));
-        size_t at = 0;
-        for (int b = 0; b < 4; b++)
-            if (what & (1 << b)) {
-                HIP_TRY(ctx, launchCopyRows(mineBuf[b], ctx->dGatherSend + at, (unsigned)(width * kComponents[b]), (unsigned)height, 0u, 1u, false, s), RTOW_ERROR_LAUNCH_FAILURE);
-                at += (size_t)height * width * kComponents[b];
-            }
-        RCCL_TRY(ctx, api, api->GroupStart());
-        int posted = api->Send(ctx->dGatherSend, need, kRcclFloat32, 0, ctx->comm, s);
-        if (posted == 0) posted = api->Recv(ctx->dGatherRecv, need, kRcclFloat32, 0, ctx->comm, s);
-        const int closed = api->GroupEnd();
-        if (posted != 0 || closed != 0) {
-            logf(ctx, 2, "rccl", "loop-back gather failed: ncclSend / ncclRecv %s, ncclGroupEnd %s", api->GetErrorString(posted), api->GetErrorString(closed));
-            return RTOW_ERROR_LAUNCH_FAILURE;
-        }
-        at = 0;
-        for (int b = 0; b < 4; b++)
-            if (what & (1 << b)) {
-                HIP_TRY(ctx, launchCopyRows(frameBuf[b], ctx->dGatherRecv + at, (unsigned)(width * kComponents[b]), (unsigned)height, 0u, 1u, true, s), RTOW_ERROR_LAUNCH_FAILURE);
-                at += (size_t)height * width * kComponents[b];
-            }
-        HIP_TRY(ctx, hipEventRecord(ctx->evGatherDone, s), RTOW_ERROR_LAUNCH_FAILURE);
-        ctx->haveGatherDone = true;
-        return RTOW_SUCCESS;
-    }
-    if (world == 1 || rank == root) {
-        // the root's own rows: already in place when frame == mine, else copied row by row on the device
-        const unsigned rows = rowsOwnedBy(rank, world, height);
-        for (int b = 0; b < 4; b++)
-            if ((what & (1 << b)) && frameBuf[b] != mineBuf[b]) {
-                const size_t rowBytes = (size_t)width * kComponents[b] * 4u;
-                HIP_TRY(ctx, hipMemcpy2DAsync((uint8_t*)frameBuf[b] + (size_t)rank * rowBytes, (size_t)world * rowBytes, (const uint8_t*)mineBuf[b] + (size_t)rank * rowBytes,
-                                              (size_t)world * rowBytes, rowBytes, rows, hipMemcpyDeviceToDevice, s), RTOW_ERROR_LAUNCH_FAILURE);
-            }
-        if (world == 1) return RTOW_SUCCESS;
-    }
-    RcclApi* api = rccl();
-    if (!api) return RTOW_ERROR_UNSUPPORTED;
-    // the packed-row staging is one block per context: a gather repacks it only after the previous gather's send / scatter is over,
-    // whatever stream that one was given
-    if (ctx->haveGatherDone) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->evGatherDone, 0), RTOW_ERROR_LAUNCH_FAILURE);
-    auto gatherEnds = [&]() -> int {
-        HIP_TRY(ctx, hipEventRecord(ctx->evGatherDone, s), RTOW_ERROR_LAUNCH_FAILURE);
-        ctx->haveGatherDone = true;
-        return RTOW_SUCCESS;
-    };
-
-    if (rank != root) {
-        // pack this rank's rows of the selected buffers back to back, one send to the root over this GPU's own xGMI link to it
-        const size_t need = packedFloats(rank);
-        if (need > ctx->gatherSendFloats) HIP_TRY(ctx, hipStreamSynchronize(s), RTOW_ERROR_LAUNCH_FAILURE);          // the old block may still be travelling
-        RTOW_TRY(growDevice(ctx, ctx->gatherSendFloats, need, {devBuf(ctx->dGatherSend, need * 4u)}));
-        size_t at = 0;
-        const unsigned rows = rowsOwnedBy(rank, world, height);
-        for (int b = 0; b < 4; b++)
-            if (what & (1 << b)) {
-                HIP_TRY(ctx, launchCopyRows(mineBuf[b], ctx->dGatherSend + at, (unsigned)(width * kComponents[b]), rows, (unsigned)rank, (unsigned)world, false, s), RTOW_ERROR_LAUNCH_FAILURE);
-                at += (size_t)rows * width * kComponents[b];
-            }
-        if (need) RCCL_TRY(ctx, api, api->Send(ctx->dGatherSend, need, kRcclFloat32, root, ctx->comm, s));
-        return gatherEnds();
-    }
-
-    // root: one receive per peer into its own region of the staging block (posted as one group: all seven links run at once), then scatter
-    size_t total = 0;
-    std::vector<size_t> offset((size_t)world, 0);
-    for (int r = 0; r < world; r++) { offset[(size_t)r] = total; if (r != root) total += packedFloats(r); }
-    if (total > ctx->gatherRecvFloats) HIP_TRY(ctx, hipStreamSynchronize(s), RTOW_ERROR_LAUNCH_FAILURE);
-    RTOW_TRY(growDevice(ctx, ctx->gatherRecvFloats, total, {devBuf(ctx->dGatherRecv, total * 4u)}));
-    RCCL_TRY(ctx, api, api->GroupStart());
-    int posted = 0;                                       // a failed ncclRecv must not leave the communicator's group open: it is closed on every path
-    for (int r = 0; r < world && posted == 0; r++)
-        if (r != root && packedFloats(r)) posted = api->Recv(ctx->dGatherRecv + offset[(size_t)r], packedFloats(r), kRcclFloat32, r, ctx->comm, s);
-    const int closed = api->GroupEnd();
-    if (posted != 0 || closed != 0) {
-        logf(ctx, 2, "rccl", "gather on the root failed: ncclRecv %s, ncclGroupEnd %s", api->GetErrorString(posted), api->GetErrorString(closed));
-        return RTOW_ERROR_LAUNCH_FAILURE;
-    }
-    for (int r = 0; r < world; r++) {
-        if (r == root) continue;
-        size_t at = offset[(size_t)r];
-        const unsigned rows = rowsOwnedBy(r, world, height);
-        for (int b = 0; b < 4; b++)
-            if (what & (1 << b)) {
-                HIP_TRY(ctx, launchCopyRows(frameBuf[b], ctx->dGatherRecv + at, (unsigned)(width * kComponents[b]), rows, (unsigned)r, (unsigned)world, true, s), RTOW_ERROR_LAUNCH_FAILURE);
-                at += (size_t)rows * width * kComponents[b];
-            }
-    }
-    return gatherEnds();
-}
-
-RTOW_API int rtowHybridPlan(int32_t worldSize, int32_t rank, int32_t tileCount, uint32_t samplesPerBatch, uint32_t step, RtowHybridPlan* out)
-{
-    if (!out || worldSize < 1 || rank < 0 || rank >= worldSize || tileCount < 1 || worldSize % tileCount != 0 || step < 1u) return RTOW_ERROR_INVALID_VALUE;
-    const int32_t groups = worldSize / tileCount;
-    RtowHybridPlan p{};
-    p.tileCount = tileCount;
-    p.groupCount = groups;
-    p.tile = rank % tileCount;
-    p.group = rank / tileCount;
-    p.sliceOffset = p.tile;
-    p.sliceDivider = tileCount;
-    p.samples = samplesPerBatch / (uint32_t)groups + ((uint32_t)p.group < samplesPerBatch % (uint32_t)groups ? 1u : 0u);
-    p.seed = (step - 1u) * (uint32_t)groups + (uint32_t)p.group + 1u;
-    *out = p;
-    return RTOW_SUCCESS;
-}
-
-RTOW_API int rtowExchangeAccumDevice(RtowContext ctx, int32_t width, int32_t height, int32_t tileCount, const RtowAccumBuffers* partial, const RtowAccumBuffers* accum,
-                                     int32_t what, void* stream)
-{
-    if (!ctx || !partial || !accum || width <= 0 || height <= 0 || tileCount < 1 || (what & ~(RTOW_GATHER_ALL | RTOW_GATHER_NO_BATCH_WAIT)) || !(what & RTOW_GATHER_ALL))
-        return RTOW_ERROR_INVALID_VALUE;
-    const bool waitForBatch = !(what & RTOW_GATHER_NO_BATCH_WAIT);
-    what &= RTOW_GATHER_ALL;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    const int world = ctx->comm ? ctx->commWorld : 1, rank = ctx->comm ? ctx->commRank : 0;
-    if (world % tileCount != 0) return RTOW_ERROR_INVALID_VALUE;                      // G = T x B
-    const int groups = world / tileCount, tile = rank % tileCount, own = rank / tileCount;
-    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    // the partial sums were written by the last sample batch, whatever stream that was enqueued on (RTOW_GATHER_NO_BATCH_WAIT: the caller ordered it)
-    if (waitForBatch && ctx->haveBatchDone) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->evBatchDone, 0), RTOW_ERROR_LAUNCH_FAILURE);
-
-    static const int kComponents[4] = {4, 3, 3, 1};
-    float* const partBuf[4] = {partial->color, partial->normal, partial->albedo, partial->sampleCountWeight};
-    float* const accBuf[4] = {accum->color, accum->normal, accum->albedo, accum->sampleCountWeight};
-    unsigned floatsPerPixel = 0;
-    for (int b = 0; b < 4; b++)
-        if (what & (1 << b)) {
-            if (!partBuf[b] || !accBuf[b] || partBuf[b] == accBuf[b]) return RTOW_ERROR_INVALID_VALUE;      // the fold reads partial rows while it writes accum rows
-            floatsPerPixel += (unsigned)kComponents[b];
-        }
-    // rank p folds the rows with row % G == p; they all lie in the tile p % T, i.e. in what every rank of that tile rendered
-    auto packedFloats = [&](int r) { return (size_t)rowsOwnedBy(r, world, height) * (size_t)width * floatsPerPixel; };
-    const unsigned myRows = rowsOwnedBy(rank, world, height);
-    const size_t regionFloats = packedFloats(rank);                                     // what every peer of the tile sends here: this rank's rows of ITS partial
-
-    if (groups > 1) {
-        RcclApi* api = rccl();
-        if (!api) return RTOW_ERROR_UNSUPPORTED;
-        // staging (shared with rtowGatherRowsDevice, ordered by the same event): packed rows for every peer | one region per group for what arrives
-        if (ctx->haveGatherDone) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->evGatherDone, 0), RTOW_ERROR_LAUNCH_FAILURE);
-        size_t sendTotal = 0;
-        std::vector<size_t> sendOffset((size_t)groups, 0);
-        for (int g = 0; g < groups; g++) { sendOffset[(size_t)g] = sendTotal; if (g != own) sendTotal += packedFloats(tile + tileCount * g); }
-        const size_t recvTotal = regionFloats * (size_t)groups;
-        if (sendTotal > ctx->gatherSendFloats || recvTotal > ctx->gatherRecvFloats) {
-            HIP_TRY(ctx, hipStreamSynchronize(s), RTOW_ERROR_LAUNCH_FAILURE);          // the old blocks may still be travelling
-            if (ctx->haveGatherDone) HIP_TRY(ctx, hipEventSynchronize(ctx->evGatherDone), RTOW_ERROR_LAUNCH_FAILURE);
-        }
-        RTOW_TRY(growDevice(ctx, ctx->gatherSendFloats, sendTotal, {devBuf(ctx->dGatherSend, sendTotal * 4u)}));
-        RTOW_TRY(growDevice(ctx, ctx->gatherRecvFloats, recvTotal, {devBuf(ctx->dGatherRecv, recvTotal * 4u)}));
-        for (int g = 0; g < groups; g++) {
-            if (g == own) continue;
-            const int peer = tile + tileCount * g;
-            const unsigned rows = rowsOwnedBy(peer, world, height);
-            size_t at = sendOffset[(size_t)g];
-            for (int b = 0; b < 4; b++)
-                if (what & (1 << b)) {
-                    HIP_TRY(ctx, launchCopyRows(partBuf[b], ctx->dGatherSend + at, (unsigned)(width * kComponents[b]), rows, (unsigned)peer, (unsigned)world, false, s), RTOW_ERROR_LAUNCH_FAILURE);
-                    at += (size_t)rows * width * kComponents[b];
-                }
-        }
-        // one group: a send and a receive per peer of the tile, each pair on its own xGMI link.  The group is closed on every path.
-        RCCL_TRY(ctx, api, api->GroupStart());
-        int posted = 0;
-        for (int g = 0; g < groups && posted == 0; g++) {
-            if (g == own) continue;
-            const int peer = tile + tileCount * g;
-            if (packedFloats(peer)) posted = api->Send(ctx->dGatherSend + sendOffset[(size_t)g], packedFloats(peer), kRcclFloat32, peer, ctx->comm, s);
-            if (posted == 0 && regionFloats) posted = api->Recv(ctx->dGatherRecv + (size_t)g * regionFloats, regionFloats, kRcclFloat32, peer, ctx->comm, s);
-        }
-        const int closed = api->GroupEnd();
-        if (posted != 0 || closed != 0) {
-            logf(ctx, 2, "rccl", "exchange of partial sums failed: ncclSend / ncclRecv %s, ncclGroupEnd %s", api->GetErrorString(posted), api->GetErrorString(closed));
-            return RTOW_ERROR_LAUNCH_FAILURE;
-        }
-    }
-    // the fold: this rank's rows, group order, own partial in place
-    size_t at = 0;
-    for (int b = 0; b < 4; b++)
-        if (what & (1 << b)) {
-            HIP_TRY(ctx, launchFoldRows(accBuf[b], partBuf[b], groups > 1 ? ctx->dGatherRecv + at : partBuf[b], regionFloats, (unsigned)(width * kComponents[b]), myRows, (unsigned)rank,
-                                        (unsigned)world, (unsigned)groups, (unsigned)own, s), RTOW_ERROR_LAUNCH_FAILURE);
-            at += (size_t)myRows * width * kComponents[b];
-        }
-    if (groups > 1) {
-        HIP_TRY(ctx, hipEventRecord(ctx->evGatherDone, s), RTOW_ERROR_LAUNCH_FAILURE);
-        ctx->haveGatherDone = true;
-    }
     return RTOW_SUCCESS;
 }
 

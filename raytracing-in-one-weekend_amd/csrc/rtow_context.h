@@ -1,0 +1,216 @@
+// rtow_context.h - the context behind RtowContext and the helpers every translation unit of the C-ABI layer shares (rtow_api.hip, rtow_comm.hip):
+// logging, the error-return macros and the grow-only device buffers.  Internal: nothing here is part of include/rtow.h.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdarg>
+#include <cstdio>
+#include <initializer_list>
+#include <mutex>
+#include <vector>
+
+#include "../../include/rtow.h"
+#include "rtow_bvh.h"
+#include "rtow_kernels.h"
+
+// The two tuning defaults the context's member initialisers need; the other tuning macros, and what the nine thresholds mean, are at the top of rtow_api.hip.
+#ifndef RTOW_DEFAULT_REGROUP_SIDE
+// RtowContextOptions.schedulerTune[7], which pixel a ticket stands for: 1 = its place in its 8 x 8 tile; 3 = the tiles as they are, each tile's tickets most expensive pixel first
+// (order_tile_tickets_kernel: +0.7 % on the headline, +0.9 % as plain launches, +1.3 % as groups, same box, three alternating runs - profiles/r05a_pixel_regrouping.json);
+// 2 / 4 / 8 (+ 16 x mode): pixels regrouped by cost or class inside super-tiles of that many tiles (0 ... -5 %: measured, not used)
+#define RTOW_DEFAULT_REGROUP_SIDE 3
+#endif
+#ifndef RTOW_DEFAULT_TUNE
+#define RTOW_DEFAULT_TUNE 24, 32, 1, 32, 28, 1, 3, 1, 16
+#endif
+
+struct RtowContext_t {
+    int device = 0;
+    int cuCount = 0;
+    RtowLogCallback logCb = nullptr;
+    void* logData = nullptr;
+    int logLevel = 0;
+
+    hipStream_t stream = nullptr;
+    hipEvent_t evStart = nullptr, evStop = nullptr;
+    hipEvent_t evBatchDone = nullptr;   // end of everything the last sample batch enqueued (kernel + chunk-order refresh)
+    bool haveBatchDone = false;
+    bool haveTiming = false;
+
+    // scene
+    bool haveScene = false;
+    rtow::CompiledScene scene;
+    uint8_t* dScene = nullptr;
+    size_t dSceneCapacity = 0;
+    int32_t* dEntityOfPrim = nullptr;     // device copy of scene.entityOfPrim for rtowTraceRaysDevice / rtowTraceViewDevice (read only while scene.entityOfPrim is not empty)
+    size_t entityOfPrimCapacity = 0;      // in entries
+    uint32_t ldsSceneBytes = 0, ldsNodeCount = 0;
+    unsigned short* dHistSpill = nullptr; // path-history rows that do not fit LDS (LdsPlan.histSpillRows), [row][workgroup x 1024 + lane]
+    size_t histSpillBytes = 0;
+    rtow::LdsPlan ldsPlan{};              // of launches whose variant keeps its whole path history in registers (trace depth <= 16); the others plan per launch (launchSample)
+
+    // work distribution / cancellation
+    unsigned int* dWorkCounter = nullptr;
+    // chunk cost map -> launch order (longest chunks first); valid for one (width, height, slice, scene) configuration
+    unsigned int* dChunkDone = nullptr;   // chained batches: pixels stored per chunk
+    uint8_t* dXcdState = nullptr;         // chained batches: XcdState + kMaxXcds lists of chunkDoneCapacity entries (which XCD owns which chunk)
+    rtow::ChainBatch* dChainBatches = nullptr;   // chained batches: per-batch seed / diagnostics table of the launch being enqueued
+    uint32_t chunkDoneCapacity = 0;
+    unsigned int *dChunkCost = nullptr, *dChunkOrder = nullptr;
+    unsigned short* dPixelCost = nullptr;
+    unsigned int* dTicketMap = nullptr;   // ticket -> owned pixel (SampleKernelArgs.ticketMap), chunkCapacity * 64 entries; re-sorted from every launch's cost map
+    bool orderMapped = false;             // the cost map / order on hand were recorded under dTicketMap (else under the tiles themselves)
+    uint32_t chunkCapacity = 0;
+    bool orderValid = false;
+    int orderW = 0, orderH = 0, orderOff = 0, orderDiv = 0;
+    volatile uint32_t* hCancel = nullptr; // pinned, device-visible: [0] cancel, [1] hit-list overflow, [2] tie-list overflow; the metrics record of rtowReduceMetricsDevice at byte 64
+    volatile RtowMetrics* hMetricsRecord = nullptr;
+    RtowMetrics* dMetricsRecord = nullptr;
+    // RTOW_RNG_PER_SAMPLE: one 64-byte record per (owned pixel, sample group) unit
+    float* dUnitRecords = nullptr;
+    size_t unitRecordCapacity = 0;
+    uint32_t orderGroups = 1;     // groups per pixel the chunk cost map was recorded with
+    // RTOW_CONTEXT_REFERENCE_DIAGNOSTICS: the reference's own tree of the current scene (CompiledScene.refTree), HBM only
+    uint8_t* dRefTree = nullptr;
+    size_t refTreeCapacity = 0;
+    // hit lists beyond the 24 entries a lane holds itself (volume scenes, exact-tie kernels): [entry][lane] columns, grow-only
+    uint4* dHitSpill = nullptr;
+    uint32_t hitSpillEntries = 0;         // of the current scene (<= hitSpillCapacity)
+    uint32_t hitSpillCapacity = 0;        // entries per lane the allocation holds
+    uint32_t hitListCapacity = 0;         // RtowContextOptions.hitListCapacity (0 = default)
+    uint32_t grownListCapacity = 0;       // hitListCapacity == 0 only: what the capacity has grown to after batches that met longer lists (growHitList); kept across scenes
+    bool triWatchOff = false;             // this all-triangle scene ties too often for the tie watch (a watched launch marked thousands of pixels, or more than the list holds): exact-tie kernels from now on
+    bool overflowGrew = false;            // the last reported overflow enlarged the capacity: the same batch, issued again, has room
+    // Image-texture blob of the current scene (CompiledScene.texBlob), HBM only
+    uint8_t* dTexBlob = nullptr;
+    size_t texBlobCapacity = 0;
+    // noise texture sets (rtowUploadBlueNoise / rtowUploadStbNoise): device copies, `textureCount` textures back to back
+    uint8_t* dBlueNoise = nullptr;
+    uint32_t blueRowStride = 0, blueTextureCount = 0;
+    uint8_t* dStbNoise = nullptr;        // scalar | vector2 | cosineUnitVector3 | unitVector2 | unitVector3 sets, in this order
+    uint32_t stbRowStride = 0, stbTextureCount = 0;
+    // sky cubemap (rtowUploadSkyCubemap)
+    uint8_t* dCubemap = nullptr;
+    size_t cubemapCapacity = 0;
+    RtowCubemapDesc cubemap{};   // .faces is not kept (host pointer): dCubemap holds the copy, null when none
+    // camera-ray candidate lists (primary_candidates_kernel): valid for one (scene upload, view, size, slice, jitter) configuration
+    uint2* dPixCand = nullptr;
+    size_t pixCandCapacity = 0;           // bytes
+    bool pixCandValid = false;
+    uint64_t sceneSerial = 0, pixCandScene = 0;
+    RtowView pixCandView{};
+    int pixCandW = 0, pixCandH = 0, pixCandOff = 0, pixCandDiv = 0, pixCandJitter = 0;
+
+    // grow-only staging for rtowSampleBatch (host buffers) - like CudaBuffer.EnsureCapacity (OptixApi.cs:240-251)
+    float *dColor = nullptr, *dNormal = nullptr, *dAlbedo = nullptr, *dScw = nullptr;
+    uint8_t* dDiag = nullptr;
+    size_t stagingPixels = 0, stagingDiagBytes = 0;
+
+    rtow::MetricsPartial* dPartials = nullptr;
+    RtowFloat2* dExtremaPartials = nullptr;   // [kMetricsBlocks] rtowSampleBatchChainAdaptiveDevice: partials of the per-batch weight-extrema reduction
+    unsigned* dExtremaKeys = nullptr;         // [2 x kMaxChain] ... of a fused launch: every batch's (min, max) folded at store time
+
+    // nearest-hit ties of the rank-rule sphere kernels (SampleKernelArgs.tieBits / tieRedo): the bitmap the fast kernel marks, the list the fix-up launch renders, a copy
+    // of the inputs of launches that accumulate in place, and the fix-up launch's own (small) hit-list spill area
+    unsigned* dTieRedo = nullptr;
+    unsigned* dTieBits = nullptr;
+    size_t tieBitsWords = 0;
+    float* dTieInputs = nullptr;          // colour | normal | albedo | weight of `tieInputPixels` pixels
+    size_t tieInputPixels = 0;
+    uint4* dRedoSpill = nullptr;
+    uint32_t redoSpillEntries = 0;
+
+    // RtowContextOptions: behaviour switches and development knobs (nothing is read from the environment)
+    bool wideCodes = false;               // current scene: more than 65 535 entities or tree nodes (32-bit candidate / stack codes, tree read from HBM)
+    uint32_t flags = 0;
+    uint32_t ldsSceneBudget = 0;          // 0 = everything that fits
+    int tune[9] = {RTOW_DEFAULT_TUNE};
+    bool userTune = false;                // RtowContextOptions.schedulerTune was given: no per-scene adjustment
+    // RtowContextOptions.schedulerTune[7] (see RTOW_DEFAULT_REGROUP_SIDE), as given and decoded by rtowCreateContext
+    int schedulerKnob = RTOW_DEFAULT_REGROUP_SIDE;
+    unsigned ticketMapSide = 0;           // which pixel a ticket stands for: 0 = its place in its tile, 1 = a tile's tickets most expensive first, 2 / 4 / 8 = super-tiles of that many tiles
+    unsigned regroupMode = 0;             // development: what the ticket map sorts by (0 ray count, 1 sky / not sky, 2 / 3 classes of rays per sample)
+    bool orderByTotal = false;            // development: chunks ordered by their total ray count instead of by their most expensive pixel
+    unsigned slotBlockOverride = 0;       // batch groups' (chunk, batch) slots per pull (0 = by the launch: prepareChunkOrder)
+    int pixelGateOverride = 0;            // lanes that must want a pixel boundary (0 = by the samples a unit of work takes: setSchedulerValues)
+    bool userSliceDefault = false;        // ... with a zero walk slice: the per-scene built-in value
+    bool chainFusion = true;              // the same-XCD hand-over litmus passed on this device (rtowCreateContext): chains may run as one launch
+    uint64_t tunedScene = ~0ull;          // sceneSerial whose thresholds were measured (tuneThresholds)
+    int tunedCandidate = -1;              // which candidate won (rtowGetSceneInfo-independent; logged)
+    bool tunePending = false;             // probes of scene tunePendingScene are enqueued; their events are read by a later call, never waited for
+    uint64_t tunePendingScene = 0;
+    int tuneCandidates = 0, tuneBuiltin = 0;
+    std::vector<hipEvent_t> tuneEvents;
+    uint32_t* dProbeSink = nullptr;       // where probes report rays beyond the hit-list capacity (not the batch's flag)
+    uint64_t sppSinceUpload = 0;          // samples per pixel this scene has been asked for since its upload: a measurement must be worth its probes
+    uint64_t sceneSignatureNow = 0;       // of the current scene
+    struct TuneCacheEntry { uint64_t signature; int winner; };
+    std::vector<TuneCacheEntry> tuneCache;   // winners by scene signature: a re-upload of a like scene does not measure again
+
+    // rtowRegisterHostBuffer: pinned + device-mapped ranges of caller memory
+    struct HostRange { uint8_t* base; size_t size; uint8_t* device; };
+    std::vector<HostRange> hostRanges;
+
+    // rtowComm*: RCCL communicator of this rank (one process per GPU) and the packed-row staging of rtowGatherRowsDevice
+    void* comm = nullptr;                 // ncclComm_t
+    int commRank = 0, commWorld = 1;
+    float *dGatherSend = nullptr, *dGatherRecv = nullptr;
+    size_t gatherSendFloats = 0, gatherRecvFloats = 0;
+    float* dByteThresholds = nullptr;     // FinalizeTexturesJob's float -> byte step table (rtow_finalize.hip.h), built when the context is created
+    hipEvent_t evGatherDone = nullptr;    // end of the last gather: the staging blocks are per context, gathers may come on different streams
+    bool haveGatherDone = false;
+    hipEvent_t evMetricsDone = nullptr;   // end of the last metrics reduction (the per-block partials are per context)
+    bool haveMetricsDone = false;
+
+    std::mutex mu;
+    std::mutex sceneMu;      // guards the HOST image of the scene (scene.blob / layout / entityOfPrim, haveScene) between rtowUploadScene and rtowProbeNearestHit; taken after mu, never the other way round
+};
+
+namespace rtow {
+
+inline void logf(RtowContext ctx, int level, const char* tag, const char* fmt, ...)
+{
+    if (!ctx || !ctx->logCb || level > ctx->logLevel) return;
+    char buf[1024];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    ctx->logCb(level, tag, buf, ctx->logData);
+}
+
+#define HIP_TRY(ctx, expr, result)                                                                    \
+    do {                                                                                              \
+        hipError_t _e = (expr);                                                                       \
+        if (_e != hipSuccess) {                                                                       \
+            logf(ctx, 2, "hip", "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
+            return (result);                                                                          \
+        }                                                                                             \
+    } while (0)
+
+#define RTOW_TRY(expr)                                                                                \
+    do {                                                                                              \
+        const int _rc = (expr);                                                                       \
+        if (_rc != RTOW_SUCCESS) return _rc;                                                          \
+    } while (0)
+
+// Grow-only device buffers of the context: when `need` exceeds `capacity` (in the caller's unit) each buffer is freed and allocated again at its own size - the
+// contents are not kept - and `capacity` becomes `need`.  Several buffers may share one capacity.  A failed allocation leaves the capacity 0, so the next call
+// allocates again.  Callers do around it what the old buffer needs first (a batch in flight may still read it) and what a new one invalidates.
+struct DeviceBuf { void** p; size_t bytes; };
+template <typename T> DeviceBuf devBuf(T*& p, size_t bytes) { return DeviceBuf{reinterpret_cast<void**>(&p), bytes}; }
+template <typename C>
+int growDevice(RtowContext ctx, C& capacity, uint64_t need, std::initializer_list<DeviceBuf> bufs)
+{
+    if (need <= (uint64_t)capacity) return RTOW_SUCCESS;
+    for (const DeviceBuf& b : bufs) { if (*b.p) (void)hipFree(*b.p); *b.p = nullptr; }
+    capacity = 0;
+    for (const DeviceBuf& b : bufs) HIP_TRY(ctx, hipMalloc(b.p, b.bytes), RTOW_ERROR_MEMORY_ALLOCATION);
+    capacity = (C)need;
+    return RTOW_SUCCESS;
+}
+
+// rtow_comm.hip, for rtowDestroyContext: destroys the communicator, frees the packed-row staging blocks and evGatherDone
+void releaseComm(RtowContext ctx);
+
+} // namespace rtow

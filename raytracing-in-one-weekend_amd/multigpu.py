@@ -161,7 +161,7 @@ def render_batches(render_full, acc_slice, n, rank, world, add_flat, group=None,
 # tiles x batches (rtowHybridPlan / rtowExchangeAccumDevice, include/rtow.h): G ranks = T row slices x B seed groups
 # ---------------------------------------------------------------------------------------------------
 def hybrid_plan(world, rank, tiles, samples_per_batch, step):
-    """The arithmetic of rtowHybridPlan (csrc/rtow_api.hip), for the hosts that run without the library (CPU tests): rank = tile + T * group renders
+    """The arithmetic of rtowHybridPlan (csrc/rtow_comm.hip), for the hosts that run without the library (CPU tests): rank = tile + T * group renders
     slice `tile` of T with its share of the batch's samples and the Seed of sub-batch `group` of step `step` (1-based)."""
     if world < 1 or not 0 <= rank < world or tiles < 1 or world % tiles or step < 1:
         raise ValueError("hybrid_plan: world = tiles x groups, 0 <= rank < world, step >= 1")
