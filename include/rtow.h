@@ -58,7 +58,9 @@ typedef enum RtowResult {
                                        * next rtowGetBatchStatus / rtowSynchronize - by a ray that met more surfaces than the hit lists hold.  The reference's
                                        * list grows without bound; with RtowContextOptions.hitListCapacity == 0 so do these: by the time the error is reported
                                        * the lists are twice as long, the host-buffer calls (rtowSampleBatch, rtowSampleBatchChain) have run the batch again
-                                       * themselves and do not report it at all, and a device-resident caller issues the batch again (see hitListCapacity) */
+                                       * themselves and do not report it at all, and a device-resident caller issues the batch again (see hitListCapacity).
+                                       * Also: a launch that marked more pixel-batches for the nearest-hit tie fix-up pass than its list of 2^20 holds - transient
+                                       * for all-triangle scenes, final for sphere scenes (RtowSceneInfo.hitListCapacity); the same rule serves both causes */
     RTOW_ERROR_INTERNAL = 99
 } RtowResult;
 
@@ -186,9 +188,13 @@ typedef struct RtowSceneInfo {
                                        ProbabilisticVolume materials, exact-tie kernels): 16 B x 1024 lanes x CUs x (list capacity - 24) entries,
                                        0 where no ray can need it.  Grow-only per context; RtowContextOptions.hitListCapacity sizes it */
     int32_t hitListCapacity;        /* most surfaces one ray may meet in this scene before the batch reports RTOW_ERROR_CAPACITY (0: only the nearest hit is kept; for sphere scenes
-                                       whose rare nearest-hit ties are settled by the fix-up pass: the capacity of that pass's lists).  A launch also reports RTOW_ERROR_CAPACITY - final,
-                                       this value unchanged - when it marks more than 2^20 pixel-batches for the fix-up pass: a scene of coinciding spheres that should run with
-                                       RTOW_CONTEXT_EXACT_TIES_ALWAYS */
+                                       whose rare nearest-hit ties are settled by the fix-up pass: the capacity of that pass's lists).  A launch also reports RTOW_ERROR_CAPACITY -
+                                       this value unchanged - when it marks more than 2^20 pixel-batches (a chain's pixel counts once, a group's once per batch) for the fix-up
+                                       pass.  In an all-triangle scene that happens once at most per rtowUploadScene, on its first heavy frame (coplanar, overlapping triangles
+                                       tie over whole regions): the scene has moved to its exact-tie kernels by the time the error is reported, and the same call, issued again,
+                                       succeeds.  In a sphere scene - spheres that coincide but are not duplicates to rtowUploadScene, such as a static sphere and a "moving" one
+                                       with a zero offset - the same call fails again: the scene should run with RTOW_CONTEXT_EXACT_TIES_ALWAYS.  The caller's rule for both,
+                                       and for the hit lists: see RtowContextOptions.hitListCapacity */
     int32_t wideCodes;              /* 1: more than 65 535 entities or tree nodes - the kernels that keep 32-bit candidate / stack codes run (tree read from HBM) */
     int32_t thresholdSet;           /* stage thresholds in use for this scene: -1 the built-in ones of its kernel kind (nothing measured yet - the probes of a measurement may be in
                                        flight -, too few samples asked for so far, tuning off, or RtowContextOptions.schedulerTune given); 0 / 1 / 2 the sphere family / the general family /
@@ -327,8 +333,10 @@ typedef struct RtowContextOptions {
     int32_t deviceOrdinal;          /* HIP device ordinal */
     RtowLogCallback logCallback;    /* may be NULL */
     void* logCallbackData;
-    int32_t logCallbackLevel;
-    uint32_t flags;                 /* RtowContextFlags, 0 = defaults */
+    int32_t logCallbackLevel;       /* most verbose level delivered: 2 errors, 3 notices (a scene that moved to its exact-tie kernels, lists that grew), 4 also one "launch"
+                                     * line per sample launch and per tie fix-up launch, naming the kernel family (sample_triangles, sample_triangles_ties ...).  The callback
+                                     * runs on the calling thread, inside the call */
+    uint32_t flags;                /* RtowContextFlags, 0 = defaults */
     int32_t ldsSceneBudgetBytes;    /* development: cap on the bytes of scene image staged into LDS (0 = all that fits); smaller scenes then run
                                      * through the kernels that read the tree from HBM */
     int32_t schedulerTune[9];       /* development: stage thresholds in 64ths of the live lanes (REGEN TRAV TEST HIT SKY VOL; values below 1 mean 1 = any lane), the number of
@@ -352,8 +360,14 @@ typedef struct RtowContextOptions {
                                      * that meets a longer ray doubles them (up to what the scene can produce, and to a quarter of the free device memory) when its
                                      * status is read.  rtowSampleBatch / rtowSampleBatchChain read it themselves and run the batch again from the caller's inputs
                                      * (unless outputs registered with rtowRegisterHostBuffer ARE the inputs); the device-resident forms report RTOW_ERROR_CAPACITY
-                                     * once through rtowGetBatchStatus / rtowSynchronize and the same call, issued again from inputs it did not overwrite, has room (if
-                                     * rtowGetSceneInfo.hitListCapacity did not change across the error the lists could not grow - device memory - and the error is final).
+                                     * once through rtowGetBatchStatus / rtowSynchronize (a cancellable call: itself).  The outputs of every batch enqueued since the
+                                     * last report are invalid then - accumulators that a call updates in place included: bring them back from a copy - and the inputs
+                                     * a call did not overwrite are untouched.  The caller's rule, whatever the cause: issue the same call again, once, from such inputs.
+                                     * If that reports RTOW_ERROR_CAPACITY again, compare rtowGetSceneInfo.hitListCapacity across this second error: changed - the lists
+                                     * have doubled again, go on; unchanged - the error is final (the lists cannot grow: device memory; or a sphere scene marks more
+                                     * pixel-batches than the tie fix-up pass lists: RtowSceneInfo.hitListCapacity).  The first error says nothing either way: an
+                                     * all-triangle scene whose first heavy frame marks more than 2^20 pixel-batches reports it with hitListCapacity unchanged, has moved
+                                     * to its exact-tie kernels by then, and succeeds when the call is issued again.
                                      * The capacity a context has grown to stays across rtowUploadScene (rtowGetSceneInfo.hitListCapacity shows it) */
     int32_t sliceBlockThreads;      /* reserved: 0 (or 1024).  Rounds 2 - 3 could run 512 / 256 lanes per workgroup for launches that own about one pixel per
                                      * resident lane; measured slower at every slice count and removed.  Other values: RTOW_ERROR_INVALID_VALUE */

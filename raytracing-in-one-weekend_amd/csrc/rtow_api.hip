@@ -161,6 +161,22 @@ uint64_t listCapacity(const RtowContext_t* ctx, bool volumes);    // (defined wi
 inline bool triangleKind(uint32_t kind) { return kind == SCENE_KIND_TRIANGLES || kind == SCENE_KIND_TRIANGLES_TEXTURED; }
 constexpr unsigned kTieWatchBusy = 4096;   // a watched launch of an all-triangle scene that lists more pixel-batches than this (8 workgroups render them) sends the scene to the exact-tie kernels
 
+// The kernel family launchSampleBatch picks for these arguments (rtow_kernels.hip; the names of the translation units): what the level-4 log says of every launch
+const char* sampleKernelName(const SceneLayout& L)
+{
+    const bool ties = L.exactTies != 0;
+    switch (L.sceneKind) {
+        case SCENE_KIND_SPHERES: return ties ? "sample_spheres_ties" : "sample_spheres";
+        case SCENE_KIND_SPHERES_MOTION: return ties ? "sample_spheres_motion_ties" : "sample_spheres_motion";
+        case SCENE_KIND_VOLUMES: return "sample_volumes";
+        case SCENE_KIND_TEXTURED: return ties ? "sample_textured_ties" : "sample_textured";
+        case SCENE_KIND_VOLUMES_TEXTURED: return "sample_volumes_textured";
+        case SCENE_KIND_TRIANGLES_TEXTURED: return ties ? "sample_triangles_textured_ties" : "sample_triangles_textured";
+        case SCENE_KIND_TRIANGLES: return ties ? "sample_triangles_ties" : "sample_triangles";
+        default: return ties ? "sample_general_ties" : "sample_general";
+    }
+}
+
 // ---- launchSample, step by step ----
 
 // The kernel's arguments from the batch's params and buffers and the context's scene, noise textures and cubemap (RTOW_ERROR_INVALID_VALUE: the noise set is not uploaded)
@@ -178,7 +194,7 @@ int buildArgs(RtowContext ctx, const RtowSampleParams* p, const RtowAccumBuffers
     a.ldsStackRows = ctx->ldsPlan.stackRows; a.ldsHistOffset = 0u; a.ldsFrontBytes = ctx->ldsPlan.frontBytes;      // (launches of the generic variants plan again: planHistory)
     a.workCounter = ctx->dWorkCounter;
     a.cancelFlag = useCancelFlag ? ctx->hCancel : nullptr;
-    a.overflowFlag = const_cast<uint32_t*>(ctx->hCancel) + 1;      // [1]: a ray beyond the hit-list capacity (grows: takeOverflow); [2]: more tied pixel-batches than the fix-up list holds (final)
+    a.overflowFlag = const_cast<uint32_t*>(ctx->hCancel) + 1;      // [1]: a ray beyond the hit-list capacity (grows: takeOverflow); [2]: more tied pixel-batches than the fix-up list holds (final for sphere scenes; an all-triangle scene moves to its exact-tie kernels); [3]: kTieWatchBusy
     a.width = (int)p->size.x;
     a.height = (int)p->size.y;
     a.totalWork = (uint32_t)ownedRows(p) * (uint32_t)a.width;
@@ -595,6 +611,7 @@ int launchTieFixup(RtowContext ctx, const SampleKernelArgs& a, const TieWatch& t
     r.hitSpillStride = (uint32_t)kTieRedoBlocks * (uint32_t)kBlockThreads;
     HIP_TRY(ctx, hipMemsetAsync(ctx->dWorkCounter, 0, sizeof(unsigned int), stream), RTOW_ERROR_LAUNCH_FAILURE);
     HIP_TRY(ctx, launchSampleBatch(r, kTieRedoBlocks < ctx->cuCount ? kTieRedoBlocks : ctx->cuCount, stream), RTOW_ERROR_LAUNCH_FAILURE);
+    logf(ctx, 4, "launch", "%s: tie fix-up over the pixels the watch listed", sampleKernelName(r.layout));
     return RTOW_SUCCESS;
 }
 
@@ -606,6 +623,7 @@ int enqueueLaunch(RtowContext ctx, const RtowSampleParams* p, SampleKernelArgs& 
     HIP_TRY(ctx, hipMemsetAsync(ctx->dWorkCounter, 0, sizeof(unsigned int), stream), RTOW_ERROR_LAUNCH_FAILURE);
     HIP_TRY(ctx, hipEventRecord(ctx->evStart, stream), RTOW_ERROR_LAUNCH_FAILURE);
     HIP_TRY(ctx, launchSampleBatch(a, blocks, stream), RTOW_ERROR_LAUNCH_FAILURE);
+    logf(ctx, 4, "launch", "%s: %u batch%s%s", sampleKernelName(a.layout), a.chainCount, a.chainCount > 1u ? (a.chainIndependent ? "es, a group" : "es, a chain") : "", tie.on ? ", tie watch" : "");
     if (tie.on) RTOW_TRY(launchTieFixup(ctx, a, tie, redoIn, stream));
     if (a.unitRecords) HIP_TRY(ctx, launchFoldUnitRecords(a, stream), RTOW_ERROR_LAUNCH_FAILURE);   // inside the timed region: part of the batch
     HIP_TRY(ctx, hipEventRecord(ctx->evStop, stream), RTOW_ERROR_LAUNCH_FAILURE);
@@ -715,7 +733,8 @@ int takeOverflow(RtowContext ctx)
 {
     if (ctx->hCancel[2] != 0u) {
         // not a hit list: a launch marked more pixel-batches for the tie fix-up pass than its list holds (kTieRedoCapacity = 2^20; a scene of coinciding spheres that
-        // did not go to the exact-tie kernels).  Growing the hit lists would not help and running the batch again would overflow again: the error is final
+        // did not go to the exact-tie kernels: e.g. one of the two "moving" by a zero offset).  Growing the hit lists would not help, and for a sphere scene running
+        // the batch again would overflow again: the error is final there (tests/test_gpu_tie_overflow.py)
         ctx->hCancel[2] = 0u;
         ctx->hCancel[1] = 0u;
         if (ctx->haveScene && triangleKind(ctx->scene.layout.sceneKind) && !ctx->triWatchOff) {

@@ -610,6 +610,28 @@ def triangle_layers_scene(layers=20, duplicate=False):
     return s
 
 
+def triangle_tie_field_scene(layers=15, tied=True):
+    """triangle_layers_scene's tie over (almost) the whole view, for the tests of the tie watch's lists: four pairs of DIFFERENT triangles in the plane z = 0, one pair per
+    quadrant about their common vertex (0, 0, 0) - small = {0, 8 a, 8 b}, large = {0, 16 a, 16 b} for consecutive axis directions a, b: the same exact factor of four in
+    determinant and numerator, so every ray through a small triangle (the view sees nothing else: |x| + |y| < 8 there) meets its pair at bit-identical distance.  A pair
+    lies inside its own quadrant, no triangle appears twice (SceneLayout.tieWatchOk stays 1), and `layers` walls behind bring a ray to layers + 2 hits.
+    `tied=False`: the control - the small triangles alone; what ties is left to the rays through an edge that two of them share."""
+    s = Scene("triangle_tie_field" if tied else "triangle_tie_field_quiet")
+    mats = [lambertian((0.8, 0.25, 0.2)), metal((0.9, 0.9, 0.9), 0.0), dielectric(1.5), standard((0.05, 0.05, 0.05), 0.0, 0.0, emission=(2.0, 1.6, 1.1)),
+            lambertian((0.15, 0.65, 0.25)), metal((0.8, 0.6, 0.2), 0.3), dielectric(1.33), lambertian((0.2, 0.3, 0.85))]
+    order = [int(k) for k in np.random.default_rng(31).permutation(layers)]               # not in depth order
+    for k in order:
+        z = -0.25 * (k + 1)
+        _quad(s, (-6, -4, z), (6, -4, z), (6, 4, z), (-6, 4, z), mats[(2 + k * 3) % len(mats)])
+    axes = [(1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0)]
+    for q in range(4):
+        (ax, ay), (bx, by) = axes[q], axes[(q + 1) % 4]
+        s.add_triangle((0.0, 0.0, 0.0), (8.0 * ax, 8.0 * ay, 0.0), (8.0 * bx, 8.0 * by, 0.0), mats[q])
+        if tied: s.add_triangle((0.0, 0.0, 0.0), (16.0 * ax, 16.0 * ay, 0.0), (16.0 * bx, 16.0 * by, 0.0), mats[4 + q])
+    s.camera = {"position": [0.3, 0.2, 7.0], "target": [0.0, 0.0, 0.0], "up": [0.0, 1.0, 0.0], "vfov": 40.0, "aperture": 0.0}
+    return s
+
+
 def textured_scene(triangles_only=False):
     """Triangle meshes with Image textures on every texture slot (albedo, emission, glossiness, metallic; Standard and Dielectric),
     a constant-scalar texture, a null image pointer, and image-textured spheres / rects (whose texture coordinates are always 0).
