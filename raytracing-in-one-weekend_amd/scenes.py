@@ -964,7 +964,15 @@ class NoiseTextures:
     """Stand-ins for the host's noise textures (the reference's blue-noise assets are not in the mount; any texel values exercise the
     samplers): a set of `count` square half4 textures for BlueNoise, and the five byte-texture sets of SpatioTemporalBlueNoise."""
 
-    def __init__(self, row_stride=16, count=2, seed=11):
+    # the ends of BlueNoise's domain [0, 1] and of the half format's subnormal range, as half bits: +0, 1, the smallest and the largest
+    # subnormal, the smallest normal, the half just below 1
+    PLANTED_BLUE = (0x0000, 0x3c00, 0x0001, 0x03ff, 0x0400, 0x3bff)
+
+    def __init__(self, row_stride=16, count=2, seed=11, planted=False):
+        """planted: overwrite texels with the values a texture made from 8-bit data holds and random draws do not (after every draw of
+        `rng`, so the other texels keep their values): texel j (counted through all textures) gets PLANTED_BLUE[j % 8] in blue .x and
+        PLANTED_BLUE[(3 * j + 1) % 8] in .y (slots 6 and 7 stay random), and channel c of its five STBN texels gets 0 / 255 where
+        ((2 * c + 1) * j + c) % 8 is 0 / 1 - so every planted value is in 1/8 of the texels of a texture of 8 texels or more."""
         rng = np.random.default_rng(seed)
         n = count * row_stride * row_stride
         self.row_stride, self.count = row_stride, count
@@ -979,6 +987,17 @@ class NoiseTextures:
         x, y, z = r * np.cos(th), np.sqrt(1 - u), r * np.sin(th)
         enc = lambda a: np.clip(np.floor((a + 1) / 2 * 256), 0, 255).astype(np.uint8)
         self.cosine_unit_vector3 = np.stack([enc(x), enc(z), enc(y), np.full(n, 255, np.uint8)], axis=1)
+        if planted:
+            j = np.arange(n)
+            bits = self.blue.view(np.uint16)
+            for channel, slot in ((0, j % 8), (1, (3 * j + 1) % 8)):
+                for k, value in enumerate(self.PLANTED_BLUE):
+                    bits[slot == k, channel] = value
+            for tex in (self.scalar.reshape(n, 1), self.vector2, self.cosine_unit_vector3, self.unit_vector2, self.unit_vector3):   # reshape: a view
+                for c in range(tex.shape[1]):
+                    slot = ((2 * c + 1) * j + c) % 8
+                    tex[slot == 0, c] = 0
+                    tex[slot == 1, c] = 255
 
     def blue_desc(self):
         return abi.BlueNoiseDesc(self.row_stride, self.count, self.blue.ctypes.data)
@@ -999,6 +1018,21 @@ class SkyCubemap:
     def desc(self):
         _, h, w, c = self.faces.shape
         return abi.CubemapDesc(w, h, self.channel_type, c * self.faces.itemsize, self.faces.ctypes.data)
+
+    @staticmethod
+    def from_values(width, height, channels, half=True, seed=5):
+        """Faces of any shape and pixel stride (channels * 2 bytes for halves, channels bytes otherwise) with unrelated random texels:
+        r, g, b in [0, 4) as halves or in 0..199 as bytes; every further channel holds what no r, g or b does - halves in
+        [1024, 2048), bytes in 200..255 - so a lookup that reads one of them shows."""
+        rng = np.random.default_rng(seed)
+        shape = (6, height, width, channels)
+        if half:
+            faces = (rng.random(shape, dtype=np.float32) * 4).astype(np.float16)
+            faces[..., 3:] = (1024 + 1024 * rng.random(shape, dtype=np.float32)[..., 3:]).astype(np.float16)
+            return SkyCubemap(faces, abi.CUBEMAP_SIGNED_HALF)
+        faces = rng.integers(0, 200, shape, dtype=np.uint8)
+        faces[..., 3:] = rng.integers(200, 256, shape, dtype=np.uint8)[..., 3:]
+        return SkyCubemap(faces, abi.CUBEMAP_UNSIGNED_BYTE)
 
 
 def synthetic_sky(size=64, half=True, seed=3):

@@ -43,7 +43,8 @@ def test_r2_sequence_and_texel_walk():
         ex, ey = r2(n)
         assert (f32(out[0]), f32(out[1])) == (ex, ey), n
         assert 0 <= out[0] < 1 and 0 <= out[1] < 1
-    for seed, x, y, stride in ((1, 0, 0, 16), (7, 5, 3, 16), (123456, 1919, 1079, 64), (3, 17, 40, 7), (1, 9, 9, 1)):
+    for seed, x, y, stride in ((1, 0, 0, 16), (7, 5, 3, 16), (123456, 1919, 1079, 64), (3, 17, 40, 7), (1, 9, 9, 1),
+                                  (1, 0, 0, 5), (11, 39, 35, 5), (2, 4, 4, 12), (4321, 39, 35, 12), ((1 << 24) + 5, 6, 7, 12)):
         got = (C.c_uint32 * 40)()
         lib.oracle_kat_per_pixel_noise(seed, x, y, stride, 40, got)
         assert list(got) == walk(seed, x, y, stride, 40), (seed, x, y, stride)
@@ -54,18 +55,14 @@ def test_r2_sequence_and_texel_walk():
     assert all((bi % 32) == ((ai % 32) + 1) % 32 and bi // 32 == ai // 32 for ai, bi in zip(a, b))
 
 
-@pytest.mark.parametrize("noise_color", [abi.NOISE_BLUE, abi.NOISE_SPATIOTEMPORAL_BLUE])
-def test_camera_rays_consume_the_textures_in_reference_order(noise_color):
-    """Depth-1 render of a scene with nothing in view: every sample is jitter (NextFloat2) + time (NextFloat) and the colour is the sky
-    gradient of the jittered direction - re-derived here from the texels, which pins draw order, texel addressing and decode."""
-    noise = S.NoiseTextures(row_stride=8, count=3)
+def _camera_rays_consume(noise, noise_color, tex):
     sc = S.Scene("empty")
     sc.add_sphere((0, 0, 50), 1.0, S.lambertian((0.5, 0.5, 0.5)))            # behind the camera
     sc.camera = {"position": [0, 0, 0], "target": [0, 0, -1], "up": [0, 1, 0], "vfov": 60.0, "aperture": 0.0}
     osc = ob.OracleScene(sc.desc())
     osc.set_blue_noise(noise.blue_desc())
     osc.set_stb_noise(noise.stb_desc())
-    w, h, spp, tex, seed = 6, 4, 3, 1, 9
+    w, h, spp, seed = 6, 4, 3, 9
     p = S.make_params(sc, w, h, spp=spp, trace_depth=2, seed=seed, noise_color=noise_color, noise_texture_index=tex)
     r = osc.sample_batch(p)
     stride = noise.row_stride
@@ -92,6 +89,30 @@ def test_camera_rays_consume_the_textures_in_reference_order(noise_color):
             assert got[3] == spp
             assert np.allclose(got[:3], total, rtol=2e-6, atol=0), (x, y)
     osc.close()
+
+
+@pytest.mark.parametrize("noise_color", [abi.NOISE_BLUE, abi.NOISE_SPATIOTEMPORAL_BLUE])
+def test_camera_rays_consume_the_textures_in_reference_order(noise_color):
+    """Depth-1 render of a scene with nothing in view: every sample is jitter (NextFloat2) + time (NextFloat) and the colour is the sky
+    gradient of the jittered direction - re-derived here from the texels, which pins draw order, texel addressing and decode."""
+    _camera_rays_consume(S.NoiseTextures(row_stride=8, count=3), noise_color, tex=1)
+
+
+@pytest.mark.parametrize("noise_color", [abi.NOISE_BLUE, abi.NOISE_SPATIOTEMPORAL_BLUE])
+@pytest.mark.parametrize("row_stride", [5, 12])
+def test_camera_rays_at_row_strides_that_are_no_power_of_two(row_stride, noise_color):
+    """The same re-derivation where `% rowStride` is not a mask, from the last texture of the set, and with the texels a texture made
+    from 8-bit data holds planted among the random ones: blue 0, 1 and the subnormal halves, STBN bytes 0 and 255."""
+    noise = S.NoiseTextures(row_stride=row_stride, count=3, planted=True)
+    n = 3 * row_stride * row_stride
+    bits = noise.blue.view(np.uint16)
+    for value in S.NoiseTextures.PLANTED_BLUE:
+        assert min((bits[:, 0] == value).sum(), (bits[:, 1] == value).sum()) * 16 >= n
+    for tex_ in (noise.scalar.reshape(n, 1), noise.vector2, noise.cosine_unit_vector3, noise.unit_vector2, noise.unit_vector3):
+        for value in (0, 255):
+            assert ((tex_ == value).sum(axis=0) * 16 >= n).all()
+    assert noise.blue[:, :2].min() == 0 and noise.blue[:, :2].max() == 1
+    _camera_rays_consume(noise, noise_color, tex=2)
 
 
 def test_noise_texture_index_and_missing_sets_are_rejected():
