@@ -634,6 +634,53 @@ RTOW_API int rtowDenoiseDevice(RtowContext context, const RtowDenoiseParams* par
                                const float* inColor, const float* inNormal, const float* inAlbedo,
                                void* scratch, float* outColor, void* stream);
 
+/* ---- temporal reuse across a camera move: the previous view's accumulators, seen from the new view ----
+ * replaces: the ZeroMemory of the four accumulation buffers in ScheduleSample(firstBatch) (UNITY/Raytracer.cs:616-626) when the reset's only cause is
+ * cameraDirty (:483-489) and the world is static: instead of starting the moved camera's frame from zero, every pixel starts from the sums of the previous
+ * view's pixel that saw the same surface point.  Backward reprojection by the first hit of each pixel's camera ray: `rays` and `hits` are
+ * rtowTraceViewDevice's outputs for the NEW view, `previousHits` those the host kept from the previous view, `previous` the accumulators of the previous view.
+ * A pure function of its buffers: it needs no resident scene.  The batches of the new view then accumulate on top of `out` as on top of any accumulators.
+ * Limits: what a pixel carries is what the previous view saw.  Entities with moving != 0, defocus blur (lensRadius > 0) and view-dependent shading (mirrors,
+ * glass) are carried as they were seen - the host decides when to reset instead (ZeroMemory, as before).  Sampling is nearest-neighbour: one previous
+ * pixel per new pixel, unfiltered (a bilinear variant is not part of this interface).
+ * Added after API version 12 without changing it: a host detects the call by its entry point (C#: EntryPointNotFoundException). */
+typedef enum RtowReprojectFlags { RTOW_REPROJECT_MATCH_ENTITY = 1 } RtowReprojectFlags;
+typedef struct RtowReprojectParams {
+    int32_t  width, height;
+    RtowView previousView;      /* the view `previous` and `previousHits` were made with; lensRadius ignored */
+    float    depthTolerance;    /* >= 0, finite; relative.                 recommended: 0.01 */
+    int32_t  maxHistory;        /* >= 1: most samples (color.w) a pixel carries over.  recommended: 64 */
+    int32_t  flags;             /* RtowReprojectFlags                       recommended: RTOW_REPROJECT_MATCH_ENTITY */
+    int32_t  reserved;          /* 0 */
+} RtowReprojectParams;          /* 112 bytes */
+/* Numeric specification (float32, in this order; no contraction; `/` and sqrt correctly rounded; dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z):
+ *   PV = previousView.  On the host, in float32 with the same dot: LF = dot(PV.lowerLeftCorner, PV.forward), LR = dot(PV.lowerLeftCorner, PV.right),
+ *   LU = dot(PV.lowerLeftCorner, PV.up), HR = dot(PV.horizontal, PV.right), VU = dot(PV.vertical, PV.up).
+ *   Pixel i, with o, d = rays[i].origin, rays[i].direction as stored, t = hits.distance[i], e = hits.entityIndex[i]:
+ *   1. point:    e >= 0: P = (o.x + t*d.x, o.y + t*d.y, o.z + t*d.z), w = P - PV.origin, r = sqrt(dot(w, w));  e < 0 (sky): w = d, a point at infinity.
+ *   2. project:  s = dot(w, PV.forward) / LF; nothing is carried unless s > 0.  u = (dot(w, PV.right) / s - LR) / HR, v = (dot(w, PV.up) / s - LU) / VU,
+ *                fx = u * (float)W, fy = v * (float)H; nothing is carried unless fx >= 0 && fx < (float)W && fy >= 0 && fy < (float)H (NaN fails these)
+ *                [and (int)fx < W && (int)fy < H, which the former imply whenever W and H are exact in float32, i.e. up to 2^24].  q = (int)fy * W + (int)fx.
+ *   3. validate against previousHits at q, pe and pt the entity and distance there:  sky: valid iff pe < 0.  hit: valid iff pe >= 0, and pe == e when
+ *                RTOW_REPROJECT_MATCH_ENTITY is set, and fabs(pt - r) <= depthTolerance * r.
+ *   4. history:  c = previous.color[q] is valid only if its four channels are finite and c.w >= 1.  If c.w > (float)maxHistory: k = (float)maxHistory / c.w;
+ *                colour xyz, normal, albedo and sampleCountWeight of q are written multiplied by k, and color.w = (float)maxHistory exactly (all four buffers are
+ *                sums over color.w samples, JOBS/CombineJob.cs:54,63,69; (int)color.w stays integral).  Otherwise the 11 floats of q are copied bit for bit.
+ *   5. not carried: all 11 floats are +0.  outSource[i] = q, or -1.
+ * Validation (RTOW_ERROR_INVALID_VALUE, nothing enqueued): NULL context, params, rays, hits, previousHits, previous or out; a NULL distance or entityIndex of
+ * either hit set (normal is ignored), a NULL member of previous or out; width or height <= 0 or width * height > INT32_MAX; a negative or non-finite
+ * depthTolerance; maxHistory < 1; unknown flag bits; reserved != 0; LF, HR or VU zero or non-finite; any out buffer, or outSource, overlapping a buffer the
+ * pass gathers from (the four of `previous`, distance and entityIndex of previousHits) or another output.
+ * Enqueued on `stream` (NULL = the context's own stream): one launch, one lane per pixel, a wave per 8 x 8 pixel tile; no allocation, no wait, so the call
+ * may be captured in a graph. */
+RTOW_API int rtowReprojectAccumDevice(RtowContext context, const RtowReprojectParams* params,
+                                      const RtowRay* rays /* device, W*H: rtowTraceViewDevice's outRays of the NEW view */,
+                                      const RtowHitBuffers* hits /* of `rays`: distance and entityIndex required, normal ignored */,
+                                      const RtowHitBuffers* previousHits /* of the previous view: distance and entityIndex required */,
+                                      const RtowAccumBuffers* previous, const RtowAccumBuffers* out /* device, W*H each, all four required */,
+                                      int32_t* outSource /* device, W*H, or NULL: previous pixel index carried, -1 if none */,
+                                      void* stream);
+
 /* dst += src for the four accumulation buffers (device pointers, `pixelCount` elements each).  The reference accumulates
  * successive batches by feeding a batch's outputs to the next one as inputs (UNITY/Raytracer.cs:798-802); when batches run
  * CONCURRENTLY on several GPUs (each from zeroed accumulators, its own Seed) their partial sums are folded with this, in

@@ -201,6 +201,20 @@ class TraceViewParams(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("view", View), ("time", C.c_float), ("reserved", C.c_int32)]
 
 
+# RtowReprojectFlags
+RTOW_REPROJECT_MATCH_ENTITY = 1
+# recommended settings of rtowReprojectAccumDevice (include/rtow.h)
+REPROJECT_DEFAULT_DEPTH_TOLERANCE = 0.01
+REPROJECT_DEFAULT_MAX_HISTORY = 64
+REPROJECT_DEFAULT_FLAGS = RTOW_REPROJECT_MATCH_ENTITY
+
+
+class ReprojectParams(C.Structure):
+    """RtowReprojectParams (112 bytes): previousView is the view the carried accumulators and previousHits were made with."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("previousView", View), ("depthTolerance", C.c_float), ("maxHistory", C.c_int32),
+                ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
 def denoise_scratch_bytes(width, height):
     """RTOW_DENOISE_SCRATCH_BYTES(w, h): the ping-pong float3 colour buffer of the levels"""
     return int(width) * int(height) * 12
@@ -215,5 +229,5 @@ EXPORTED_SYMBOLS = [
     "rtowSampleBatchChainDevice", "rtowSampleBatchChain", "rtowCommSetLibraryPath", "rtowCommGetUniqueId", "rtowCommInit", "rtowCommDestroy", "rtowGatherRowsDevice",
     "rtowHybridPlan", "rtowExchangeAccumDevice", "rtowSampleBatchGroupDevice",
     "rtowCombineFinalizeDevice", "rtowReduceMetricsDeviceAsync", "rtowProbeNearestHit", "rtowSampleBatchChainAdaptiveDevice",
-    "rtowDenoiseDevice", "rtowTraceRaysDevice", "rtowTraceViewDevice",
+    "rtowDenoiseDevice", "rtowTraceRaysDevice", "rtowTraceViewDevice", "rtowReprojectAccumDevice",
 ]

@@ -1598,6 +1598,42 @@ RTOW_API int rtowDenoiseDevice(RtowContext ctx, const RtowDenoiseParams* params,
     return RTOW_SUCCESS;
 }
 
+RTOW_API int rtowReprojectAccumDevice(RtowContext ctx, const RtowReprojectParams* params, const RtowRay* rays, const RtowHitBuffers* hits, const RtowHitBuffers* previousHits,
+                                      const RtowAccumBuffers* previous, const RtowAccumBuffers* out, int32_t* outSource, void* stream)
+{
+    if (!ctx || !params || !rays || !hits || !previousHits || !previous || !out) return RTOW_ERROR_INVALID_VALUE;
+    if (!hits->distance || !hits->entityIndex || !previousHits->distance || !previousHits->entityIndex) return RTOW_ERROR_INVALID_VALUE;
+    if (!previous->color || !previous->normal || !previous->albedo || !previous->sampleCountWeight || !out->color || !out->normal || !out->albedo || !out->sampleCountWeight)
+        return RTOW_ERROR_INVALID_VALUE;
+    const RtowReprojectParams& p = *params;
+    if (p.width <= 0 || p.height <= 0 || (int64_t)p.width * p.height > INT32_MAX) return RTOW_ERROR_INVALID_VALUE;
+    if (!(p.depthTolerance >= 0.0f && p.depthTolerance <= FLT_MAX) || p.maxHistory < 1) return RTOW_ERROR_INVALID_VALUE;      // NaN fails
+    if ((p.flags & ~(int32_t)RTOW_REPROJECT_MATCH_ENTITY) != 0 || p.reserved != 0) return RTOW_ERROR_INVALID_VALUE;
+    const ReprojectConstants k = reprojectConstants(p.previousView);
+    for (const float d : {k.LF, k.HR, k.VU})
+        if (!(d != 0.0f && d >= -FLT_MAX && d <= FLT_MAX)) return RTOW_ERROR_INVALID_VALUE;      // the divisors of the projection
+    // every pixel gathers from an arbitrary pixel of the previous frame: no byte the pass writes may be one it gathers from, or another output's
+    const size_t n = (size_t)p.width * (size_t)p.height;
+    struct Range { const void* base; size_t bytes; };
+    const Range written[5] = {{out->color, n * 16}, {out->normal, n * 12}, {out->albedo, n * 12}, {out->sampleCountWeight, n * 4}, {outSource, n * 4}};
+    const Range gathered[6] = {{previous->color, n * 16}, {previous->normal, n * 12}, {previous->albedo, n * 12}, {previous->sampleCountWeight, n * 4},
+                               {previousHits->distance, n * 4}, {previousHits->entityIndex, n * 4}};
+    const auto overlap = [](const Range& a, const Range& b) {
+        return a.base && b.base && (uintptr_t)a.base < (uintptr_t)b.base + b.bytes && (uintptr_t)b.base < (uintptr_t)a.base + a.bytes;
+    };
+    for (int i = 0; i < 5; ++i) {
+        for (const Range& g : gathered)
+            if (overlap(written[i], g)) return RTOW_ERROR_INVALID_VALUE;
+        for (int j = i + 1; j < 5; ++j)
+            if (overlap(written[i], written[j])) return RTOW_ERROR_INVALID_VALUE;
+    }
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    HIP_TRY(ctx, launchReproject(p, k, rays, *hits, *previousHits, *previous, *out, outSource, s), RTOW_ERROR_LAUNCH_FAILURE);
+    return RTOW_SUCCESS;
+}
+
 RTOW_API int rtowAddAccumDevice(RtowContext ctx, int32_t pixelCount, const RtowAccumBuffers* dst, const RtowAccumBuffers* src, void* stream)
 {
     if (!ctx || !dst || !src || pixelCount <= 0) return RTOW_ERROR_INVALID_VALUE;

@@ -332,6 +332,16 @@ hipError_t launchCombineFinalize(const RtowCombineParams& p, const float* inColo
 // rtowDenoiseDevice (rtow_denoise.hip): one launch per a-trous level on `stream`, ping-pong between scratch and outColor (params validated by the caller)
 hipError_t launchDenoise(const RtowDenoiseParams& p, const float* inColor, const float* inNormal, const float* inAlbedo, float* scratch, float* outColor,
                          hipStream_t stream);
+// rtowReprojectAccumDevice (rtow_reproject.hip): one launch on `stream` (arguments validated by the caller).  The constants of previousView the specification has the
+// host compute, in float32 (this header is compiled without contraction)
+struct ReprojectConstants { float LF, LR, LU, HR, VU; };
+inline ReprojectConstants reprojectConstants(const RtowView& v)
+{
+    const auto dot = [](const RtowFloat3& a, const RtowFloat3& b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; };
+    return ReprojectConstants{dot(v.lowerLeftCorner, v.forward), dot(v.lowerLeftCorner, v.right), dot(v.lowerLeftCorner, v.up), dot(v.horizontal, v.right), dot(v.vertical, v.up)};
+}
+hipError_t launchReproject(const RtowReprojectParams& p, const ReprojectConstants& k, const RtowRay* rays, const RtowHitBuffers& hits, const RtowHitBuffers& previousHits,
+                           const RtowAccumBuffers& previous, const RtowAccumBuffers& out, int32_t* outSource, hipStream_t stream);
 // dst[k] += src[k] for the four accumulators (float4 / float3 / float3 / float per pixel) in one launch
 hipError_t launchAddAccum(size_t pixels, float* const dst[4], const float* const src[4], hipStream_t stream);
 // bits of tieBits -> entries of tieRedo (one per marked pixel; `batches` per pixel, batch index in bits 27.., for a batch group)

@@ -453,6 +453,35 @@ class DenoiseJob:
         return JobHandle(rc)
 
 
+class ReprojectJob:
+    """rtowReprojectAccumDevice: what replaces the ZeroMemory of ScheduleSample(firstBatch) (UNITY/Raytracer.cs:616-626) after a camera move over a static
+    world - the previous view's accumulators gathered to the new view's pixels.  Device buffers (or raw device addresses): Rays / HitDistance / HitEntityIndex
+    are rtowTraceViewDevice's outputs for the NEW view, PreviousHitDistance / PreviousHitEntityIndex those kept from PreviousView; the four Previous* are the
+    accumulators rendered at PreviousView, the four Output* receive the carried sums; OutputSource (optional) the previous pixel each pixel carries, -1 = none."""
+
+    def __init__(self, context, Width, Height, PreviousView, DepthTolerance=abi.REPROJECT_DEFAULT_DEPTH_TOLERANCE, MaxHistory=abi.REPROJECT_DEFAULT_MAX_HISTORY,
+                 Flags=abi.REPROJECT_DEFAULT_FLAGS, Reserved=0):
+        self.context, self.Width, self.Height, self.PreviousView = context, Width, Height, PreviousView
+        self.DepthTolerance, self.MaxHistory, self.Flags, self.Reserved = DepthTolerance, MaxHistory, Flags, Reserved
+        self.Rays = self.HitDistance = self.HitEntityIndex = self.PreviousHitDistance = self.PreviousHitEntityIndex = None
+        self.PreviousColor = self.PreviousNormal = self.PreviousAlbedo = self.PreviousSampleCountWeight = None
+        self.OutputColor = self.OutputNormal = self.OutputAlbedo = self.OutputSampleCountWeight = self.OutputSource = None
+
+    def params(self):
+        return abi.ReprojectParams(int(self.Width), int(self.Height), self.PreviousView, float(self.DepthTolerance), int(self.MaxHistory), int(self.Flags),
+                                   int(self.Reserved))
+
+    def Schedule(self, stream=None):
+        p = self.params()
+        hits = abi.HitBuffers(_device_ptr(self.HitDistance), _device_ptr(self.HitEntityIndex), None)
+        prev_hits = abi.HitBuffers(_device_ptr(self.PreviousHitDistance), _device_ptr(self.PreviousHitEntityIndex), None)
+        prev = _buffers(*[_device_ptr(b) for b in (self.PreviousColor, self.PreviousNormal, self.PreviousAlbedo, self.PreviousSampleCountWeight)])
+        out = _buffers(*[_device_ptr(b) for b in (self.OutputColor, self.OutputNormal, self.OutputAlbedo, self.OutputSampleCountWeight)])
+        rc = load().rtowReprojectAccumDevice(self.context.handle, C.byref(p), _device_ptr(self.Rays), C.byref(hits), C.byref(prev_hits), C.byref(prev), C.byref(out),
+                                             _device_ptr(self.OutputSource), stream)
+        return JobHandle(rc)
+
+
 class ReduceMetricsJob:
     """Mirror of `struct ReduceMetricsJob` (JOBS/ReduceMetricsJob.cs:10-20); device buffers in, scalars out."""
 
