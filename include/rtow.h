@@ -546,6 +546,48 @@ RTOW_API int rtowTraceViewDevice(RtowContext context, const RtowTraceViewParams*
                                  const RtowHitBuffers* hits /* width*height, pixel = row*width+col, row 0 at the bottom */,
                                  RtowRay* outRays /* device, width*height, or NULL */, void* stream);
 
+/* ---- first-hit material AOVs: what the surface a trace call found is made of ----
+ * The trace calls return distance, entity and geometric normal; this call returns the material of that first surface, evaluated as the sample path evaluates it at a hit:
+ * Albedo.SampleColor / Emission.SampleColor / Metallic.SampleScalar / Glossiness.SampleScalar at HitRecord.TexCoords (RT/Material.cs:71,77-78,123,176-196; RT/Texture.cs:51-138;
+ * RT/HitTests.cs:116-150), and on a miss the sky colour the sample path's albedo AOV takes (JOBS/SampleBatchJob.cs:308-328,349-370).  `rays` and `entityIndex` are what
+ * rtowTraceRaysDevice / rtowTraceViewDevice were given / returned (outRays, RtowHitBuffers.entityIndex).  With rtowTraceViewDevice's normal this is a noise-free guide pair for
+ * rtowDenoiseDevice, and the albedo RTOW_DENOISE_DEMODULATE_ALBEDO divides by; materialIndex / materialInfo tell a picking host which material is under the cursor and a
+ * reprojecting host whether two views saw the same material.
+ * Raw surface, no path: the values of the FIRST surface.  Nothing is traced through glass or mirrors; bit 8 of materialInfo marks the surfaces where the sample path's own
+ * albedo AOV looks further (Material.IsPerfectSpecular, JOBS/SampleBatchJob.cs:316).
+ * Added after API version 12 without changing it: a host detects the call by its entry point (C#: EntryPointNotFoundException). */
+typedef struct RtowSurfaceBuffers {     /* device pointers, `count` elements each, tightly packed; any may be NULL (not written), not all */
+    float*    albedo;              /* float3 */
+    float*    emission;            /* float3 */
+    float*    texCoord;            /* float2: HitRecord.TexCoords */
+    float*    metallicGlossiness;  /* float2: Metallic.SampleScalar, Glossiness.SampleScalar */
+    int32_t*  materialIndex;       /* index into RtowSceneDesc.materials, -1 on a miss */
+    uint32_t* materialInfo;        /* bits 0..7 RtowMaterialType, bit 8 Material.IsPerfectSpecular; 0xFFFFFFFF on a miss */
+} RtowSurfaceBuffers;
+typedef struct RtowShadeHitsParams { RtowEnvironment environment; int32_t flags /* 0 */; int32_t reserved /* 0 */; } RtowShadeHitsParams;   /* 36 bytes */
+/* Numeric specification (float32, no contraction; where the sample path has an expression, that expression):
+ *   hit:       element i is a hit when 0 <= entityIndex[i] < entityCount and that entity has a primitive in the resident scene; otherwise it is a miss.
+ *   TexCoords: a Triangle entity: the triangle's own hit test (RT/HitTests.cs:116-150) once more on rays[i] with tMin 0, tMax +inf - what the HIT stage of the textured kernels
+ *              runs for the winner - and mul(TextureCoordinates, barycentricCoords) of it (:148); (0, 0) if that test does not hit (the caller's ray does not meet the entity
+ *              it names).  Every other entity type: (0, 0) (RT/Entity.cs:108).  rays[i].time and rays[i].pad are never read.
+ *   textures:  albedo = Albedo.SampleColor(TexCoords), emission = Emission.SampleColor(TexCoords), metallicGlossiness = (Metallic.SampleScalar, Glossiness.SampleScalar) -
+ *              Constant: MainColor (scalar: its ScalarValueChannel, a channel beyond 1 reads .z); ConstantScalar: the scalar; Image: the texel ((int)(u * width), (int)(v * height))
+ *              clamped into the image, byte / 255 * MainColor per channel, 0 for a null image; None: 0.  The (int) conversions truncate, saturate at the ends of int32 and give 0
+ *              for NaN.  Materials without an Image texture read the constants the upload folded (the same values).
+ *   miss:      albedo = the sky along rays[i].direction AS STORED (not normalised): RTOW_SKY_GRADIENT s = 0.5f * (d.y + 1), bottom + s * (top - bottom) per channel;
+ *              RTOW_SKY_CUBEMAP Cubemap.Sample (RT/Texture.cs:171-210) on the faces of rtowUploadSkyCubemap, black without them; RTOW_SKY_NONE black.  emission, texCoord and
+ *              metallicGlossiness are +0, materialIndex -1, materialInfo 0xFFFFFFFF.  This is `sampleAlbedo = hitSkyColor`: a guide built from this call agrees with
+ *              rtowCombineDevice's on sky pixels.
+ * Memory safety: entity, primitive, material and image numbers are checked before they address anything, texels are clamped: no value of `rays` or `entityIndex` makes the
+ * kernel read outside the scene.
+ * Validation (RTOW_ERROR_INVALID_VALUE, nothing enqueued): NULL context / params / rays / entityIndex / surface, all six output pointers NULL, count < 0, flags or reserved
+ * non-zero, an unknown skyType.  count == 0 succeeds and launches nothing.  RTOW_ERROR_NO_SCENE before rtowUploadScene.
+ * Enqueued on `stream` (NULL = the context's own stream): one launch, one lane per element; no allocation, no wait.  Inputs and outputs may start at any 4-byte aligned
+ * address.  Reads only the resident scene; ordered against rtowUploadScene like the trace calls (an upload waits for the device). */
+RTOW_API int rtowShadeHitsDevice(RtowContext context, const RtowShadeHitsParams* params, int32_t count,
+                                 const RtowRay* rays /* device */, const int32_t* entityIndex /* device: RtowHitBuffers.entityIndex of `rays` */,
+                                 const RtowSurfaceBuffers* surface, void* stream);
+
 /* Device time (ms) of the most recent sample kernel of this context, measured with HIP events recorded on the
  * stream the kernel was launched on (the RecordTimeJob 0/1 bracket, JOBS/UtilJobs.cs:77-86). Synchronises on the end event. */
 RTOW_API int rtowGetLastSampleKernelMs(RtowContext context, float* outMs);

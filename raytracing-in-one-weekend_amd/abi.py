@@ -215,6 +215,26 @@ class ReprojectParams(C.Structure):
                 ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
+class SurfaceBuffers(C.Structure):
+    """RtowSurfaceBuffers (48 bytes): device pointers, any may be NULL (not written), not all six."""
+    _fields_ = [("albedo", C.c_void_p), ("emission", C.c_void_p), ("texCoord", C.c_void_p), ("metallicGlossiness", C.c_void_p),
+                ("materialIndex", C.c_void_p), ("materialInfo", C.c_void_p)]
+
+
+class ShadeHitsParams(C.Structure):
+    """RtowShadeHitsParams (36 bytes): the sky a miss takes its albedo from; flags and reserved are 0."""
+    _fields_ = [("environment", Environment), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+# numpy element type and shape of every RtowSurfaceBuffers member, in the struct's order
+SURFACE_OUTPUTS = {"albedo": ("<f4", 3), "emission": ("<f4", 3), "texCoord": ("<f4", 2), "metallicGlossiness": ("<f4", 2),
+                   "materialIndex": ("<i4", 1), "materialInfo": ("<u4", 1)}
+# RtowSurfaceBuffers.materialInfo
+MATERIAL_INFO_TYPE_MASK = 0xFF
+MATERIAL_INFO_PERFECT_SPECULAR = 0x100
+MATERIAL_INFO_MISS = 0xFFFFFFFF
+
+
 def denoise_scratch_bytes(width, height):
     """RTOW_DENOISE_SCRATCH_BYTES(w, h): the ping-pong float3 colour buffer of the levels"""
     return int(width) * int(height) * 12
@@ -229,5 +249,5 @@ EXPORTED_SYMBOLS = [
     "rtowSampleBatchChainDevice", "rtowSampleBatchChain", "rtowCommSetLibraryPath", "rtowCommGetUniqueId", "rtowCommInit", "rtowCommDestroy", "rtowGatherRowsDevice",
     "rtowHybridPlan", "rtowExchangeAccumDevice", "rtowSampleBatchGroupDevice",
     "rtowCombineFinalizeDevice", "rtowReduceMetricsDeviceAsync", "rtowProbeNearestHit", "rtowSampleBatchChainAdaptiveDevice",
-    "rtowDenoiseDevice", "rtowTraceRaysDevice", "rtowTraceViewDevice", "rtowReprojectAccumDevice",
+    "rtowDenoiseDevice", "rtowTraceRaysDevice", "rtowTraceViewDevice", "rtowReprojectAccumDevice", "rtowShadeHitsDevice",
 ]

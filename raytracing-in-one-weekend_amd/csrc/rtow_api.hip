@@ -1058,6 +1058,7 @@ RTOW_API int rtowDestroyContext(RtowContext ctx)
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->dScene) (void)hipFree(ctx->dScene);
     if (ctx->dEntityOfPrim) (void)hipFree(ctx->dEntityOfPrim);
+    if (ctx->dPrimOfEntity) (void)hipFree(ctx->dPrimOfEntity);
     if (ctx->dWorkCounter) (void)hipFree(ctx->dWorkCounter);
     if (ctx->dChunkCost) { (void)hipFree(ctx->dChunkCost); (void)hipFree(ctx->dChunkOrder); (void)hipFree(ctx->dPixelCost); (void)hipFree(ctx->dTicketMap); }
     if (ctx->dChunkDone) (void)hipFree(ctx->dChunkDone);
@@ -1118,6 +1119,19 @@ RTOW_API int rtowUploadScene(RtowContext ctx, const RtowSceneDesc* scene)
         const size_t n = compiled.entityOfPrim.size();
         RTOW_TRY(growDevice(ctx, ctx->entityOfPrimCapacity, n, {devBuf(ctx->dEntityOfPrim, n * sizeof(int32_t))}));
         HIP_TRY(ctx, hipMemcpy(ctx->dEntityOfPrim, compiled.entityOfPrim.data(), n * sizeof(int32_t), hipMemcpyHostToDevice), RTOW_ERROR_LAUNCH_FAILURE);
+    }
+    // ... and rtowShadeHitsDevice goes the other way, from the entity index the queries reported to the primitive: the inverse map, -1 for an entity without a primitive
+    if (ctx->dPrimOfEntity) { (void)hipFree(ctx->dPrimOfEntity); ctx->dPrimOfEntity = nullptr; }
+    ctx->primOfEntityCount = 0;      // (the device is idle)
+    if (!compiled.entityOfPrim.empty() && compiled.entityCount > 0) {
+        std::vector<int32_t> primOfEntity((size_t)compiled.entityCount, -1);
+        for (size_t prim = 0; prim < compiled.entityOfPrim.size(); prim++) {
+            const int32_t entity = compiled.entityOfPrim[prim];
+            if (entity >= 0 && entity < compiled.entityCount) primOfEntity[(size_t)entity] = (int32_t)prim;
+        }
+        HIP_TRY(ctx, hipMalloc((void**)&ctx->dPrimOfEntity, primOfEntity.size() * sizeof(int32_t)), RTOW_ERROR_MEMORY_ALLOCATION);
+        HIP_TRY(ctx, hipMemcpy(ctx->dPrimOfEntity, primOfEntity.data(), primOfEntity.size() * sizeof(int32_t), hipMemcpyHostToDevice), RTOW_ERROR_LAUNCH_FAILURE);
+        ctx->primOfEntityCount = compiled.entityCount;
     }
     if (!compiled.texBlob.empty()) {
         RTOW_TRY(growDevice(ctx, ctx->texBlobCapacity, compiled.texBlob.size(), {devBuf(ctx->dTexBlob, compiled.texBlob.size())}));
@@ -1517,6 +1531,35 @@ RTOW_API int rtowTraceViewDevice(RtowContext ctx, const RtowTraceViewParams* par
     HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     HIP_TRY(ctx, launchTraceView(ctx->dScene, ctx->scene.layout, ctx->scene.entityOfPrim.empty() ? nullptr : ctx->dEntityOfPrim, *params, *hits, outRays, s), RTOW_ERROR_LAUNCH_FAILURE);
+    return RTOW_SUCCESS;
+}
+
+RTOW_API int rtowShadeHitsDevice(RtowContext ctx, const RtowShadeHitsParams* params, int32_t count, const RtowRay* rays, const int32_t* entityIndex,
+                                 const RtowSurfaceBuffers* surface, void* stream)
+{
+    if (!ctx || !params || !rays || !entityIndex || !surface || count < 0) return RTOW_ERROR_INVALID_VALUE;
+    if (!surface->albedo && !surface->emission && !surface->texCoord && !surface->metallicGlossiness && !surface->materialIndex && !surface->materialInfo)
+        return RTOW_ERROR_INVALID_VALUE;
+    if (params->flags != 0 || params->reserved != 0) return RTOW_ERROR_INVALID_VALUE;
+    const int32_t sky = params->environment.skyType;
+    if (sky != RTOW_SKY_NONE && sky != RTOW_SKY_GRADIENT && sky != RTOW_SKY_CUBEMAP) return RTOW_ERROR_INVALID_VALUE;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
+    if (count == 0) return RTOW_SUCCESS;
+    const bool mapped = !ctx->scene.entityOfPrim.empty();
+    if (mapped && !ctx->dPrimOfEntity) return RTOW_ERROR_INTERNAL;      // (an upload that failed half way: the old scene's description, no map)
+    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    ShadeScene sc{};
+    sc.blob = ctx->dScene;
+    sc.layout = ctx->scene.layout;
+    sc.primOfEntity = mapped ? ctx->dPrimOfEntity : nullptr;
+    sc.entityCount = mapped ? std::min(ctx->scene.entityCount, ctx->primOfEntityCount) : ctx->scene.entityCount;      // never beyond the map on the device
+    sc.texBlob = ctx->scene.texLayout.totalBytes ? ctx->dTexBlob : nullptr;
+    sc.texLayout = ctx->scene.texLayout;
+    sc.cubemapData = ctx->dCubemap;
+    sc.cubemap = ctx->cubemap;
+    HIP_TRY(ctx, launchShadeHits(sc, params->environment, count, rays, entityIndex, *surface, s), RTOW_ERROR_LAUNCH_FAILURE);
     return RTOW_SUCCESS;
 }
 

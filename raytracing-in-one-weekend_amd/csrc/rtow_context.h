@@ -44,6 +44,9 @@ struct RtowContext_t {
     size_t dSceneCapacity = 0;
     int32_t* dEntityOfPrim = nullptr;     // device copy of scene.entityOfPrim for rtowTraceRaysDevice / rtowTraceViewDevice (read only while scene.entityOfPrim is not empty)
     size_t entityOfPrimCapacity = 0;      // in entries
+    int32_t* dPrimOfEntity = nullptr;     // its inverse for rtowShadeHitsDevice: entity -> primitive, -1 for an entity without one; sized by the entity count, allocated under the same
+                                          // condition, freed at every upload and at destroy
+    int32_t primOfEntityCount = 0;        // entries of dPrimOfEntity: what rtowShadeHitsDevice bounds an entity index by, whatever an upload that failed half way left in `scene`
     uint32_t ldsSceneBytes = 0, ldsNodeCount = 0;
     unsigned short* dHistSpill = nullptr; // path-history rows that do not fit LDS (LdsPlan.histSpillRows), [row][workgroup x 1024 + lane]
     size_t histSpillBytes = 0;

@@ -357,6 +357,22 @@ hipError_t launchTraceRays(const uint8_t* blob, const SceneLayout& layout, const
 hipError_t launchTraceView(const uint8_t* blob, const SceneLayout& layout, const int32_t* entityOfPrim, const RtowTraceViewParams& p, const RtowHitBuffers& hits,
                            RtowRay* outRays, hipStream_t stream);
 
+// rtowShadeHitsDevice (rtow_shade.hip): one launch on `stream`, one lane per element (arguments validated by the caller).  What the pass reads of the context, all device
+// memory but the descriptor: primOfEntity = the inverse of CompiledScene.entityOfPrim (-1: no primitive), or null (the same number); texBlob may be null (no Image texture),
+// cubemapData too (no cubemap: black)
+struct ShadeScene {
+    const uint8_t* blob;
+    SceneLayout layout;
+    const int32_t* primOfEntity;
+    int32_t entityCount;
+    const uint8_t* texBlob;
+    TexLayout texLayout;
+    const uint8_t* cubemapData;
+    RtowCubemapDesc cubemap;
+};
+hipError_t launchShadeHits(const ShadeScene& scene, const RtowEnvironment& environment, int32_t count, const RtowRay* rays, const int32_t* entityIndex,
+                           const RtowSurfaceBuffers& surface, hipStream_t stream);
+
 // same-XCD hand-over litmus of the chained launches (rtow_kernels.hip): pairs of workgroups that ran on one XCD, stale dwords seen, waits that timed out
 hipError_t runXcdCoherenceLitmus(int cuCount, hipStream_t stream, unsigned* outPairs, unsigned* outStale, unsigned* outTimeouts);
 

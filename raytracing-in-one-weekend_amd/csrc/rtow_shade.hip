@@ -1,0 +1,166 @@
+// rtow_shade.hip - rtowShadeHitsDevice: the material of every first hit, on the device.
+//
+// The trace calls (rtow_trace.hip) answer WHERE a ray meets the scene: distance, entity, normal.  This pass answers WHAT it meets there: the surface's albedo and emission at
+// the hit's texture coordinates, metallic and glossiness, the material's index and kind - the raw values of the first surface, nothing traced through glass or mirrors - and
+// the sky colour where the ray meets nothing.  Together with rtowTraceViewDevice's normals that is a noise-free G-buffer: guides for rtowDenoiseDevice, a material id under
+// the cursor, a material to match on in rtowReprojectAccumDevice's host.  include/rtow.h holds the numeric specification.
+//
+// Every value is computed by the sample kernel's own helpers (rtow_sample_kernel.hip.h: general_hit's texCoord as the HIT stage of the textured kernels asks for it,
+// texture_color / texture_scalar, cubemap_sample, the SKY stage's gradient expression), so the pass cannot drift from what a sample batch shades with.  Those helpers take the
+// sample kernel's argument block: this kernel's argument begins with one (ShadeArgs::S), of which only the scene, the texture blob and the cubemap fields are filled in -
+// cubemap_sample reads the cubemap's constants through the kernarg segment pointer, which is why the block has to come first.
+//
+// Launch shape: a plain grid of 256-lane workgroups, one lane per element, no LDS, no barrier; a lane without an element leaves at once.  The scene comes
+// from HBM / L2 (general_hit<false>): one primitive record, one material record and at most four texels per element.
+//
+// Memory safety: `rays` and `entityIndex` are the caller's.  An entity index outside [0, entityCount) is a miss; so is an entity whose primitive number (primOfEntity, or the
+// index itself) is not one of the scene's, and a material index beyond the scene's materials.  An Image texture whose image number is not one of the blob's samples as a null
+// image.  Texels are clamped into their image by texture_pixel, after (int) conversions that saturate on this hardware (NaN: 0), as in cubemap_sample, whose face coordinates
+// (u, v) lie in [-1, 1] or are NaN for every direction.  A ray's floats are only ever operands, never addresses.
+#include "rtow_sample_kernel.hip.h"
+
+#include <cstddef>
+
+namespace rtow {
+
+namespace {
+
+constexpr int kShadeBlock = 256;
+
+// a ray at a 4-byte aligned address (a caller may pass a view that starts anywhere in an allocation)
+struct __attribute__((packed, aligned(4))) Ray8 { float ox, oy, oz, time, dx, dy, dz, pad; };
+static_assert(sizeof(Ray8) == sizeof(RtowRay), "RtowRay is eight floats");
+
+struct ShadeArgs {
+    SampleKernelArgs S;             // FIRST (see above): sceneBlob, layout, texBlob, texLayout, environment and the cubemap fields; everything else zero
+    const int32_t* primOfEntity;    // the host's entity index -> primitive, -1 = none; null: the same number
+    const RtowRay* rays;
+    const int32_t* entityIndex;
+    RtowSurfaceBuffers out;
+    int32_t count;
+    int32_t entityCount;
+    uint32_t imageCount;            // GpuImage records in the texture blob
+};
+static_assert(offsetof(ShadeArgs, S) == 0, "cubemap_sample reads the kernarg segment as a SampleKernelArgs");
+
+// texture_color / texture_scalar index the image table with t.image: an image number that is not the blob's samples as the null image does (0).  The record is read where
+// it lies in the blob: a private copy of it would be a per-lane array (texture_scalar selects a channel of mainColor)
+__device__ __forceinline__ bool no_such_image(const GpuTexture& t, uint32_t imageCount)
+{
+    return t.type == RTOW_TEXTURE_IMAGE && t.image >= 0 && (uint32_t)t.image >= imageCount;
+}
+__device__ __forceinline__ V3 color_checked(const SampleKernelArgs& S, const GpuTexture& t, float2 uv, uint32_t imageCount)
+{
+    return no_such_image(t, imageCount) ? v3(0, 0, 0) : texture_color(S, t, uv);
+}
+__device__ __forceinline__ float scalar_checked(const SampleKernelArgs& S, const GpuTexture& t, float2 uv, uint32_t imageCount)
+{
+    return no_such_image(t, imageCount) ? 0.0f : texture_scalar(S, t, uv);
+}
+
+template <int BASE>
+__global__ void __launch_bounds__(kShadeBlock) shade_kernel(ShadeArgs A)
+{
+    const long long i = (long long)blockIdx.x * kShadeBlock + threadIdx.x;
+    if (i >= (long long)A.count) return;
+    const size_t index = (size_t)i;
+    const SceneLayout& L = A.S.layout;
+    const Ray8 r = reinterpret_cast<const Ray8*>(A.rays)[index];
+    const V3 ro = v3(r.ox, r.oy, r.oz), rd = v3(r.dx, r.dy, r.dz);
+    SceneRefs sc;
+    sc.lds = nullptr;
+    sc.glob = A.S.sceneBlob;
+    sc.ldsNodeCount = 0;
+
+    // entity -> primitive -> material, each checked before it is an address
+    const int32_t e = A.entityIndex[index];
+    int prim = -1;
+    if (e >= 0 && e < A.entityCount) prim = A.primOfEntity ? A.primOfEntity[e] : e;
+    if (prim < 0 || (uint32_t)prim >= L.sphereCount) prim = -1;
+    unsigned mi = 0, matIdx = 0;
+    if (prim >= 0) {
+        mi = *reinterpret_cast<const unsigned*>(section<false>(sc, L.matIndexOffset) + (uint32_t)prim * 4u);
+        matIdx = mi & 0xffffu;
+        if (matIdx >= L.materialCount) prim = -1;
+    }
+
+    V3 albedo = v3(0, 0, 0), emission = v3(0, 0, 0);
+    float2 uv = make_float2(0, 0), mg = make_float2(0, 0);
+    int32_t materialIndex = -1;
+    uint32_t materialInfo = 0xffffffffu;
+    if (prim >= 0) {
+        if (BASE >= SCENE_KIND_GENERAL && (mi >> kPrimTypeShift) == RTOW_ENTITY_TRIANGLE) {
+            // HitRecord.TexCoords: the named triangle's own test once more (tMin 0), as HIT does for the winner; a ray that does not meet it leaves (0, 0)
+            float t2; V3 nLocal; float4 rq;
+            (void)general_hit<false>(sc, L, prim, RTOW_ENTITY_TRIANGLE, ro, rd, 0.0f, 0.0f, t2, nLocal, rq, &uv);
+        }
+        const uint8_t* mp = section<false>(sc, L.materialOffset) + matIdx * 64u;
+        const float4 m0 = *reinterpret_cast<const float4*>(mp);       // albedo.xyz emission.x
+        const float4 m1 = *reinterpret_cast<const float4*>(mp + 16);  // emission.yz type metallic
+        const float4 m2 = *reinterpret_cast<const float4*>(mp + 32);  // glossiness parameter flags roughness
+        albedo = v3(m0.x, m0.y, m0.z);
+        emission = v3(m0.w, m1.x, m1.y);
+        mg = make_float2(m1.w, m2.x);
+        const unsigned flags = __float_as_uint(m2.z);
+        if (BASE >= SCENE_KIND_GENERAL && (flags & MAT_FLAG_TEXTURED) && A.S.texBlob && A.S.texLayout.totalBytes != 0u) {
+            // Material.Scatter / Emit evaluate the four textures at rec.TexCoords (RT/Material.cs:71,77-78,123,176-179)
+            const GpuTexMaterial& tm = reinterpret_cast<const GpuTexMaterial*>(A.S.texBlob + A.S.texLayout.materialOffset)[matIdx];
+            albedo = color_checked(A.S, tm.albedo, uv, A.imageCount);
+            emission = color_checked(A.S, tm.emission, uv, A.imageCount);
+            mg = make_float2(scalar_checked(A.S, tm.metallic, uv, A.imageCount), scalar_checked(A.S, tm.glossiness, uv, A.imageCount));
+        }
+        materialIndex = (int32_t)matIdx;
+        materialInfo = (__float_as_uint(m1.z) & 0xffu) | ((flags & MAT_FLAG_PERFECT_SPECULAR) ? 0x100u : 0u);
+    } else {
+        // sampleAlbedo = hitSkyColor (JOBS/SampleBatchJob.cs:349-370): the SKY stage's expressions on the direction as stored
+        const RtowEnvironment& ENV = A.S.environment;
+        if (ENV.skyType == RTOW_SKY_GRADIENT) {
+            const float s = 0.5f * (rd.y + 1);
+            const V3 b = v3(ENV.skyBottomColor), tp = v3(ENV.skyTopColor);
+            albedo = v3(b.x + s * (tp.x - b.x), b.y + s * (tp.y - b.y), b.z + s * (tp.z - b.z));
+        } else if (ENV.skyType == RTOW_SKY_CUBEMAP) {
+            albedo = cubemap_sample(A.S, rd);
+        }
+    }
+
+    if (A.out.albedo) { float* o = A.out.albedo + index * 3u; o[0] = albedo.x; o[1] = albedo.y; o[2] = albedo.z; }
+    if (A.out.emission) { float* o = A.out.emission + index * 3u; o[0] = emission.x; o[1] = emission.y; o[2] = emission.z; }
+    if (A.out.texCoord) { float* o = A.out.texCoord + index * 2u; o[0] = uv.x; o[1] = uv.y; }
+    if (A.out.metallicGlossiness) { float* o = A.out.metallicGlossiness + index * 2u; o[0] = mg.x; o[1] = mg.y; }
+    if (A.out.materialIndex) A.out.materialIndex[index] = materialIndex;
+    if (A.out.materialInfo) A.out.materialInfo[index] = materialInfo;
+}
+
+}  // namespace
+
+hipError_t launchShadeHits(const ShadeScene& scene, const RtowEnvironment& environment, int32_t count, const RtowRay* rays, const int32_t* entityIndex,
+                           const RtowSurfaceBuffers& surface, hipStream_t stream)
+{
+    if (count <= 0) return hipSuccess;
+    ShadeArgs A{};
+    A.S.sceneBlob = scene.blob;
+    A.S.layout = scene.layout;
+    A.S.texBlob = scene.texBlob;
+    A.S.texLayout = scene.texLayout;
+    A.S.environment = environment;
+    A.S.cubemapData = scene.cubemapData;
+    A.S.cubemapHalfW = scene.cubemap.faceWidth / 2; A.S.cubemapHalfH = scene.cubemap.faceHeight / 2;                    // RT/Texture.cs:152-154
+    A.S.cubemapW1 = scene.cubemap.faceWidth - 1; A.S.cubemapH1 = scene.cubemap.faceHeight - 1;
+    A.S.cubemapPixelStride = scene.cubemap.pixelStride; A.S.cubemapRowStride = scene.cubemap.pixelStride * scene.cubemap.faceWidth;      // :167
+    A.S.cubemapFaceStride = scene.cubemap.pixelStride * scene.cubemap.faceWidth * scene.cubemap.faceHeight;             // :168
+    A.S.cubemapChannelType = scene.cubemap.channelType;
+    A.primOfEntity = scene.primOfEntity;
+    A.rays = rays;
+    A.entityIndex = entityIndex;
+    A.out = surface;
+    A.count = count;
+    A.entityCount = scene.entityCount;
+    A.imageCount = scene.texLayout.totalBytes ? (scene.texLayout.pixelOffset - scene.texLayout.imageOffset) / (uint32_t)sizeof(GpuImage) : 0u;
+    const dim3 grid((unsigned)(((long long)count + kShadeBlock - 1) / kShadeBlock)), block(kShadeBlock);
+    if (scene.layout.sceneKind == SCENE_KIND_SPHERES) hipLaunchKernelGGL((shade_kernel<SCENE_KIND_SPHERES>), grid, block, 0, stream, A);
+    else if (scene.layout.sceneKind == SCENE_KIND_SPHERES_MOTION) hipLaunchKernelGGL((shade_kernel<SCENE_KIND_SPHERES_MOTION>), grid, block, 0, stream, A);
+    else hipLaunchKernelGGL((shade_kernel<SCENE_KIND_GENERAL>), grid, block, 0, stream, A);
+    return hipGetLastError();
+}
+
+}  // namespace rtow

@@ -220,6 +220,41 @@ class Context:
         return self._trace(int(width) * int(height),
                            lambda hits, rays: check(load().rtowTraceViewDevice(self.handle, C.byref(p), C.byref(hits), rays, stream), "rtowTraceViewDevice"), want, want_rays)
 
+    def shade_hits(self, rays, entity_index, environment=None, outputs=tuple(abi.SURFACE_OUTPUTS)):
+        """rtowShadeHitsDevice on host data: `rays` as for trace_rays, `entity_index` the (n,) int32 "entityIndex" a trace call returned for them; `environment` an
+        abi.Environment (None: RTOW_SKY_NONE, a miss's albedo is black).  Returns {"albedo": (n, 3) float32, "emission": (n, 3), "texCoord": (n, 2),
+        "metallicGlossiness": (n, 2), "materialIndex": (n,) int32, "materialInfo": (n,) uint32} for the names in `outputs`.  Runs on the context's own stream and waits for it
+        (ShadeHitsJob is the form for device buffers on a caller's stream)."""
+        a = np.ascontiguousarray(rays)
+        if a.dtype != np.dtype(abi.RAY_DTYPE):
+            a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 8)
+        count = int(a.shape[0])
+        ent = np.ascontiguousarray(entity_index, dtype=np.int32).reshape(-1)
+        if ent.shape[0] != count:
+            raise ValueError("entity_index must hold one int32 per ray")
+        unknown = [k for k in outputs if k not in abi.SURFACE_OUTPUTS]
+        if unknown:
+            raise ValueError("unknown surface outputs: %s" % unknown)
+        p = abi.ShadeHitsParams(environment if environment is not None else abi.Environment(abi.SKY_NONE), 0, 0)
+        dev_rays = DeviceBuffer(self, max(1, count) * C.sizeof(abi.Ray))
+        dev_ent = DeviceBuffer(self, max(1, count) * 4)
+        bufs = {k: DeviceBuffer(self, max(1, count) * 4 * abi.SURFACE_OUTPUTS[k][1]) for k in abi.SURFACE_OUTPUTS if k in outputs}
+        try:
+            if count:
+                dev_rays.upload(a)
+                dev_ent.upload(ent)
+            surface = abi.SurfaceBuffers(*[bufs[k].handle.value if k in bufs else None for k in abi.SURFACE_OUTPUTS])
+            check(load().rtowShadeHitsDevice(self.handle, C.byref(p), count, dev_rays.handle, dev_ent.handle, C.byref(surface), None), "rtowShadeHitsDevice")
+            self.synchronize()
+            out = {}
+            for k, b in bufs.items():
+                dtype, width = abi.SURFACE_OUTPUTS[k]
+                out[k] = b.download(np.dtype(dtype), (count, width) if width > 1 else (count,))
+            return out
+        finally:
+            for b in list(bufs.values()) + [dev_rays, dev_ent]:
+                b.free()
+
     def synchronize(self):
         check(load().rtowSynchronize(self.handle), "rtowSynchronize")
 
@@ -479,6 +514,27 @@ class ReprojectJob:
         out = _buffers(*[_device_ptr(b) for b in (self.OutputColor, self.OutputNormal, self.OutputAlbedo, self.OutputSampleCountWeight)])
         rc = load().rtowReprojectAccumDevice(self.context.handle, C.byref(p), _device_ptr(self.Rays), C.byref(hits), C.byref(prev_hits), C.byref(prev), C.byref(out),
                                              _device_ptr(self.OutputSource), stream)
+        return JobHandle(rc)
+
+
+class ShadeHitsJob:
+    """rtowShadeHitsDevice on device buffers (or raw device addresses): Rays / EntityIndex are a trace call's rays and hit entity indices, `Count` elements; the six
+    outputs (Albedo, Emission, TexCoord, MetallicGlossiness, MaterialIndex, MaterialInfo) may each stay None (not written), not all.  Environment: the sky a miss takes
+    its albedo from (abi.Environment; None = RTOW_SKY_NONE)."""
+
+    def __init__(self, context, Count, Environment=None, Flags=0, Reserved=0):
+        self.context, self.Count, self.Environment, self.Flags, self.Reserved = context, Count, Environment, Flags, Reserved
+        self.Rays = self.EntityIndex = None
+        self.Albedo = self.Emission = self.TexCoord = self.MetallicGlossiness = self.MaterialIndex = self.MaterialInfo = None
+
+    def params(self):
+        return abi.ShadeHitsParams(self.Environment if self.Environment is not None else abi.Environment(abi.SKY_NONE), int(self.Flags), int(self.Reserved))
+
+    def Schedule(self, stream=None):
+        p = self.params()
+        ptr = lambda b: _device_ptr(b) if b is not None else None
+        surface = abi.SurfaceBuffers(*[ptr(b) for b in (self.Albedo, self.Emission, self.TexCoord, self.MetallicGlossiness, self.MaterialIndex, self.MaterialInfo)])
+        rc = load().rtowShadeHitsDevice(self.context.handle, C.byref(p), int(self.Count), ptr(self.Rays), ptr(self.EntityIndex), C.byref(surface), stream)
         return JobHandle(rc)
 
 

@@ -68,6 +68,7 @@ def load():
     lib.rtowTraceViewDevice.argtypes = [vp, C.POINTER(abi.TraceViewParams), C.POINTER(abi.HitBuffers), vp, vp]
     lib.rtowReprojectAccumDevice.argtypes = [vp, C.POINTER(abi.ReprojectParams), vp, C.POINTER(abi.HitBuffers), C.POINTER(abi.HitBuffers),
                                              C.POINTER(abi.AccumBuffers), C.POINTER(abi.AccumBuffers), vp, vp]
+    lib.rtowShadeHitsDevice.argtypes = [vp, C.POINTER(abi.ShadeHitsParams), C.c_int32, vp, vp, C.POINTER(abi.SurfaceBuffers), vp]
     lib.rtowReduceMetricsDeviceAsync.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp]
     lib.rtowAddAccumDevice.argtypes = [vp, C.c_int32, AB, AB, vp]
     lib.rtowDeviceAlloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
