@@ -225,8 +225,8 @@ int buildArgs(RtowContext ctx, const RtowSampleParams* p, const RtowAccumBuffers
     a.hitSpill = ctx->hitSpillEntries ? ctx->dHitSpill : nullptr;
     a.hitSpillEntries = ctx->hitSpillEntries;
     a.hitSpillStride = (uint32_t)ctx->cuCount * (uint32_t)kBlockThreads;
-    a.texBlob = ctx->dTexBlob;
-    a.texLayout = ctx->scene.texLayout;
+    a.tex.blob = ctx->dTexBlob;
+    a.tex.layout = ctx->scene.texLayout;
     a.noiseColor = p->noiseColor;
     if (p->noiseColor == RTOW_NOISE_BLUE) {
         if (!ctx->dBlueNoise || p->noiseTextureIndex < 0 || (uint32_t)p->noiseTextureIndex >= ctx->blueTextureCount) return RTOW_ERROR_INVALID_VALUE;
@@ -242,12 +242,7 @@ int buildArgs(RtowContext ctx, const RtowSampleParams* p, const RtowAccumBuffers
         a.stbUnitVector2 = ctx->dStbNoise + all * 8 + t * 3;                 // RGB24
         a.stbUnitVector3 = ctx->dStbNoise + all * 11 + t * 3;                // RGB24
     }
-    a.cubemapData = ctx->dCubemap;
-    a.cubemapHalfW = ctx->cubemap.faceWidth / 2; a.cubemapHalfH = ctx->cubemap.faceHeight / 2;                  // RT/Texture.cs:152-154
-    a.cubemapW1 = ctx->cubemap.faceWidth - 1; a.cubemapH1 = ctx->cubemap.faceHeight - 1;
-    a.cubemapPixelStride = ctx->cubemap.pixelStride; a.cubemapRowStride = ctx->cubemap.pixelStride * ctx->cubemap.faceWidth;   // :167
-    a.cubemapFaceStride = ctx->cubemap.pixelStride * ctx->cubemap.faceWidth * ctx->cubemap.faceHeight;         // :168
-    a.cubemapChannelType = ctx->cubemap.channelType;
+    a.cubemap = cubemapRefs(ctx->cubemap, ctx->dCubemap);
     return RTOW_SUCCESS;
 }
 

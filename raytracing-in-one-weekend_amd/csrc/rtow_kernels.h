@@ -164,6 +164,30 @@ __host__ __device__ inline void owned_pixel_xy(unsigned n, unsigned width, unsig
 }
 // [ticket numbering: end]
 
+// What the texture and the cubemap helpers (rtow_surface.hip.h) read of a launch: part of the sample kernel's arguments and of the shade pass's
+struct TexRefs {
+    const uint8_t* blob;   // Image-texture blob (TexLayout), HBM only; may be null (no Image texture)
+    TexLayout layout;
+};
+// sky cubemap (RT/Texture.cs:141-211); data may be null (-> black)
+struct CubemapRefs {
+    const uint8_t* data;
+    int32_t halfW, halfH, w1, h1;   // halfFaceSize, faceSizeMinusOne
+    int32_t pixelStride, rowStride, faceStride, channelType;
+};
+static_assert(sizeof(TexRefs) == 24 && sizeof(CubemapRefs) == 40, "pointer-aligned blocks without padding: they sit in SampleKernelArgs where their fields used to");
+inline CubemapRefs cubemapRefs(const RtowCubemapDesc& d, const uint8_t* data)
+{
+    CubemapRefs c;
+    c.data = data;
+    c.halfW = d.faceWidth / 2; c.halfH = d.faceHeight / 2;                    // RT/Texture.cs:152-154
+    c.w1 = d.faceWidth - 1; c.h1 = d.faceHeight - 1;
+    c.pixelStride = d.pixelStride; c.rowStride = d.pixelStride * d.faceWidth;   // :167
+    c.faceStride = d.pixelStride * d.faceWidth * d.faceHeight;                  // :168
+    c.channelType = d.channelType;
+    return c;
+}
+
 struct SampleKernelArgs {
     // accumulators (JOBS/SampleBatchJob.cs:41-51)
     const float* inColor;   // float4[N]
@@ -223,8 +247,7 @@ struct SampleKernelArgs {
     int32_t xoroshiro;                    // per-sample policies: 1 = xoroshiro64** (RTOW_RNG_PER_SAMPLE_XOROSHIRO), 0 = Unity's xorshift32 reseeded per sample
 
     // Image textures (SCENE_KIND_TEXTURED): GpuTexMaterial / GpuImage tables and pixels, in HBM
-    const uint8_t* texBlob;
-    TexLayout texLayout;
+    TexRefs tex;
 
     // noise source (RT/RandomSource.cs): the texture of this batch for Blue / SpatioTemporalBlue (null for white)
     int32_t noiseColor;                   // RtowNoiseColor
@@ -236,10 +259,8 @@ struct SampleKernelArgs {
     const uint8_t* stbUnitVector2;        // RGB24
     const uint8_t* stbUnitVector3;        // RGB24
 
-    // sky cubemap (RT/Texture.cs:141-211), used when environment.skyType == RTOW_SKY_CUBEMAP; cubemapData may be null (-> black)
-    const uint8_t* cubemapData;
-    int32_t cubemapHalfW, cubemapHalfH, cubemapW1, cubemapH1;   // halfFaceSize, faceSizeMinusOne
-    int32_t cubemapPixelStride, cubemapRowStride, cubemapFaceStride, cubemapChannelType;
+    // sky cubemap, used when environment.skyType == RTOW_SKY_CUBEMAP
+    CubemapRefs cubemap;
 
     // RTOW_CONTEXT_REFERENCE_DIAGNOSTICS: the reference's own tree (RefTreeNode[], HBM only); when set, BoundsHitCount / CandidateCount of the
     // 16-byte diagnostics count THAT tree's boxes and leaves (JOBS/SampleBatchJob.cs:427-440), one extra unpruned walk per ray

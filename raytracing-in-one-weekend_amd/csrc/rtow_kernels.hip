@@ -1,7 +1,9 @@
 // rtow_kernels.hip - the small kernels around the sample-batch megakernel (rtow_sample_kernel.hip.h): per-sample record fold, camera-ray
 // node lists, chunk ordering, scene preparation and the post passes (CombineJob, FinalizeTexturesJob, ReduceMetricsJob), and the host
 // launchers of all of them.
-#include "rtow_sample_kernel.hip.h"
+#include "rtow_kernels.h"
+#include "rtow_surface.hip.h"
+#include "rtow_vecmath.hip.h"
 #include "rtow_finalize.hip.h"
 
 namespace rtow {

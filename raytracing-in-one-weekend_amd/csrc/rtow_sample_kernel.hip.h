@@ -1,5 +1,6 @@
-// rtow_sample_kernel.hip.h - the sample-batch megakernel (hand-written gfx950 / CDNA4) and the device helpers shared with the small
-// kernels of rtow_kernels.hip.  Included by one translation unit per scene kind (rtow_sample_*.hip): the kernel has 338
+// rtow_sample_kernel.hip.h - the sample-batch megakernel (hand-written gfx950 / CDNA4), what only it uses (random sources, hit-list sorts, path history, the tie
+// resolver) and its launch dispatch.  The helpers it shares with the walk, the shade pass and the small kernels live in rtow_vecmath.hip.h, rtow_hit_tests.hip.h and
+// rtow_surface.hip.h.  Included by one translation unit per scene kind (rtow_sample_*.hip): the kernel has 338
 // template instantiations (240 + 90 with wide codes + 4 pinhole twins + 4 twins with the lanes in a hurry) and compiling them side by side keeps the build at a minute and a half.
 //
 // sample_batch_kernel replaces SampleBatchJob.Execute + Sample + FindHitCandidates + FindHits + Entity.Hit +
@@ -38,16 +39,10 @@
 #include <type_traits>
 
 #include "rtow_detmath.hip.h"
-#include "rtow_exactmath.hip.h"
+#include "rtow_hit_tests.hip.h"
+#include "rtow_surface.hip.h"
+#include "rtow_vecmath.hip.h"
 
-// IEEE 1 / x and sqrt(x) of the path's float program: the exhaustively checked short forms of rtow_exactmath.hip.h (same result for every
-// operand; RTOW_EXACT_MATH=0 builds the compiler's expansions instead, for A/B timing).
-#ifndef RTOW_EXACT_MATH
-#define RTOW_EXACT_MATH 1
-#endif
-#ifndef RTOW_SPLIT_NODE_LOADS
-#define RTOW_SPLIT_NODE_LOADS 1   // 0: A/B build with one flat load per node quad (the base chosen per lane) in the kernels whose tree does not fit LDS
-#endif
 #ifndef RTOW_WHOLE_MATERIAL
 #define RTOW_WHOLE_MATERIAL 1     // 0: A/B build in which the kernels beyond LDS load a hit's material record piece by piece where it is used (HIT)
 #endif
@@ -71,52 +66,10 @@
 #ifndef RTOW_TIE_WATCH
 #define RTOW_TIE_WATCH 1      // 0: A/B build without the nearest-hit tie watch of the sphere kinds
 #endif
-#if RTOW_EXACT_MATH
-#define RTOW_RCP(x) rtow::exact_rcp(x)
-#define RTOW_RCP_NAN_TO_INF(x) rtow::exact_rcp_nan_to_inf(x)
-#define RTOW_SQRT(x) rtow::exact_sqrt(x)
-#ifndef RTOW_EXACT_DIV3
-#define RTOW_EXACT_DIV3 1
-#endif
-#else
-#define RTOW_RCP(x) (1.0f / (x))
-#define RTOW_RCP_NAN_TO_INF(x) ([](float r_) { return r_ != r_ ? __builtin_inff() : r_; }(1.0f / (x)))
-#define RTOW_SQRT(x) __builtin_sqrtf(x)
-#define RTOW_EXACT_DIV3 0
-#endif
 
 namespace rtow {
 
 namespace {
-
-// ------------------------------------------------------------------------------------------------------------
-// small float3 helpers; each spells out the reference's evaluation order
-// ------------------------------------------------------------------------------------------------------------
-struct V3 { float x, y, z; };
-// (the helpers marked __host__ __device__ below - vectors, um_min / um_max, scene access, sphere_at, sphere_hit, general_hit - are also what rtowProbeNearestHit walks its one
-// ray with on the host: rtow_probe.hip; the host pass evaluates the same expressions with the IEEE operations the device's short forms stand for)
-
-__host__ __device__ __forceinline__ V3 v3(float x, float y, float z) { V3 r; r.x = x; r.y = y; r.z = z; return r; }
-__host__ __device__ __forceinline__ V3 v3(const RtowFloat3& a) { return v3(a.x, a.y, a.z); }
-__host__ __device__ __forceinline__ V3 add(V3 a, V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
-__host__ __device__ __forceinline__ V3 sub(V3 a, V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }
-__host__ __device__ __forceinline__ V3 neg(V3 a) { return v3(-a.x, -a.y, -a.z); }
-__host__ __device__ __forceinline__ V3 scale(float s, V3 a) { return v3(s * a.x, s * a.y, s * a.z); }
-__host__ __device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-// math.normalize(v) = rsqrt(dot(v, v)) * v with rsqrt(x) = 1 / sqrt(x)
-__device__ __forceinline__ V3 normalize(V3 v) { const float r = RTOW_RCP(RTOW_SQRT(dot(v, v))); return scale(r, v); }
-// math.reflect(i, n) = i - 2f * n * dot(i, n)
-__device__ __forceinline__ V3 reflect(V3 i, V3 n)
-{
-    const float d = dot(i, n);
-    return v3(i.x - (2.0f * n.x) * d, i.y - (2.0f * n.y) * d, i.z - (2.0f * n.z) * d);
-}
-// math.min / math.max return the FIRST operand when the second is NaN
-__host__ __device__ __forceinline__ float um_min(float x, float y) { return (y != y || x < y) ? x : y; }
-__host__ __device__ __forceinline__ float um_max(float x, float y) { return (y != y || x > y) ? x : y; }
-__device__ __forceinline__ float um_saturate(float x) { return um_max(0.0f, um_min(1.0f, x)); }
-
-constexpr float kPi = 3.14159265f; // math.PI
 
 // x / pow(2, depth) == x * 2^-depth exactly (scaling by a power of two), including the subnormal end of the range;
 // pow(2, depth) overflows to +inf from depth 128 on, where the quotient is 0.
@@ -139,15 +92,6 @@ __device__ __forceinline__ float rng_next(unsigned& state)
     return __uint_as_float(0x3f800000u | (t >> 9)) - 1.0f;
 }
 
-// Unity.Mathematics.half -> float (exact)
-__device__ __forceinline__ float half_bits_to_float(unsigned h)
-{
-    const unsigned sign = (h & 0x8000u) << 16;
-    const unsigned exp = (h >> 10) & 0x1fu, man = h & 0x3ffu;
-    if (exp == 0) return __uint_as_float(__float_as_uint((float)man * 5.9604644775390625e-8f) | sign);   // zero / subnormal: man * 2^-24, exact
-    if (exp == 31) return __uint_as_float(sign | 0x7f800000u | (man << 13));
-    return __uint_as_float(sign | ((exp + 112u) << 23) | (man << 13));
-}
 // Tools.TangentToWorldSpace (UTIL/Tools.cs:19-37): corrected Frisvad / Pixar basis, float3x3(tangent, normal, bitangent) * v, normalized
 __device__ __forceinline__ V3 tangent_to_world(float tx, float ty, float tz, V3 n)
 {
@@ -350,13 +294,7 @@ struct Rng<RTOW_NOISE_SPATIOTEMPORAL_BLUE> {
     __device__ __forceinline__ unsigned trace_value() const { return s; }
 };
 
-// Microfacet.TrowbridgeReitz.RoughnessToAlpha / Lambda, SmithMaskingShadowing (RT/Microfacet.cs:9-12,53-80)
-__device__ __forceinline__ float roughness_to_alpha(float roughness)
-{
-    roughness = um_max(roughness, 1e-3f);
-    const float x = det_log(roughness);
-    return 1.62142f + 0.819955f * x + 0.1734f * x * x + 0.0171201f * x * x * x + 0.000640711f * x * x * x * x;
-}
+// Microfacet.TrowbridgeReitz.Lambda, SmithMaskingShadowing (RT/Microfacet.cs:53-80)
 __device__ __forceinline__ float smith_g1(V3 w, V3 n, float alpha /* = RoughnessToAlpha(roughness), per material */)
 {
     const float cosTheta = dot(n, w);
@@ -373,76 +311,6 @@ __device__ __forceinline__ float smith_g1(V3 w, V3 n, float alpha /* = Roughness
         lambda = (-1 + RTOW_SQRT(1 + a2t2)) / 2;
     }
     return RTOW_RCP(1 + lambda);
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// Cubemap.Sample (RT/Texture.cs:171-210): the face is the first axis whose |component| is the largest (x before y before z), the
-// texel min((int2)((uv + 1) * halfFaceSize), faceSizeMinusOne) of that face, point sampled; RGBA half or byte channels.
-// ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ V3 cubemap_sample(const SampleKernelArgs& hotArgs, V3 d)
-{
-    // the cubemap's nine launch constants are read where they are used - through a laundered pointer to the kernarg segment, like the pixel boundary's (REGEN) - instead of
-    // living in scalar registers (or, spilled, in VGPR lanes and scratch) through every stage of every launch, most of which have a gradient sky
-#if defined(__HIP_DEVICE_COMPILE__)
-    const SampleKernelArgs* coldArgs = (const SampleKernelArgs*)__builtin_amdgcn_kernarg_segment_ptr();   // the struct is the kernel's only argument
-    asm volatile("" : "+s"(coldArgs));
-    const SampleKernelArgs& A = *coldArgs;
-#else
-    const SampleKernelArgs& A = hotArgs;                                                                   // host pass of the HIP compiler: never executed
-#endif
-    (void)hotArgs;
-    if (!A.cubemapData) return v3(0, 0, 0);
-    const float ax = __builtin_fabsf(d.x), ay = __builtin_fabsf(d.y), az = __builtin_fabsf(d.z);
-    const float m = um_max(um_max(um_max(ax, ay), az), 0.0f);                  // cmax(float4(abs(vector), 0))
-    int lane;
-    if (m == ax) lane = 0; else if (m == ay) lane = 1; else if (m == az) lane = 2; else return v3(0, 0, 0);   // NaN direction
-    const float major = lane == 0 ? d.x : lane == 1 ? d.y : d.z;
-    const float amajor = lane == 0 ? ax : lane == 1 ? ay : az;
-    const bool positive = major >= 0;
-    float u, v;
-    if (lane == 0) { u = positive ? -d.z : d.z; v = -d.y; }
-    else if (lane == 1) { u = d.x; v = positive ? d.z : -d.z; }
-    else { u = positive ? d.x : -d.x; v = -d.y; }
-    u = u / amajor;
-    v = v / amajor;
-    int cx = (int)((u + 1) * (float)A.cubemapHalfW), cy = (int)((v + 1) * (float)A.cubemapHalfH);
-    cx = cx < A.cubemapW1 ? cx : A.cubemapW1;
-    cy = cy < A.cubemapH1 ? cy : A.cubemapH1;
-    const uint8_t* px = A.cubemapData + (size_t)(lane * 2 + (positive ? 0 : 1)) * (size_t)A.cubemapFaceStride + cx * A.cubemapPixelStride + cy * A.cubemapRowStride;
-    if (A.cubemapChannelType == RTOW_CUBEMAP_UNSIGNED_BYTE) return v3((float)px[0] / 255.0f, (float)px[1] / 255.0f, (float)px[2] / 255.0f);
-    const unsigned short* hp = reinterpret_cast<const unsigned short*>(px);
-    return v3(half_bits_to_float(hp[0]), half_bits_to_float(hp[1]), half_bits_to_float(hp[2]));
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// Texture.SampleColor / SampleScalar (RT/Texture.cs:51-138) for the per-hit evaluation of textured materials.  Image: the texel
-// (int2)(uv * ImageSize) - clamped into the image, where the reference would read out of bounds - as bytes / 255 * MainColor.
-// ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ const uint8_t* texture_pixel(const SampleKernelArgs& A, const GpuTexture& t, float2 uv)
-{
-    const GpuImage im = reinterpret_cast<const GpuImage*>(A.texBlob + A.texLayout.imageOffset)[t.image];
-    int x = (int)(uv.x * (float)im.width), y = (int)(uv.y * (float)im.height);
-    x = x < 0 ? 0 : x > im.width - 1 ? im.width - 1 : x;
-    y = y < 0 ? 0 : y > im.height - 1 ? im.height - 1 : y;
-    return A.texBlob + A.texLayout.pixelOffset + im.offset + ((size_t)y * (size_t)im.width + (size_t)x) * (size_t)im.pixelStride;
-}
-__device__ __forceinline__ V3 texture_color(const SampleKernelArgs& A, const GpuTexture& t, float2 uv)
-{
-    if (t.type == RTOW_TEXTURE_CONSTANT) return v3(t.mainColor[0], t.mainColor[1], t.mainColor[2]);
-    if (t.type == RTOW_TEXTURE_CONSTANT_SCALAR) return v3(t.parameter, t.parameter, t.parameter);
-    if (t.type == RTOW_TEXTURE_IMAGE && t.image >= 0) {
-        const uint8_t* px = texture_pixel(A, t, uv);
-        return v3((float)px[0] / 255.0f * t.mainColor[0], (float)px[1] / 255.0f * t.mainColor[1], (float)px[2] / 255.0f * t.mainColor[2]);
-    }
-    return v3(0, 0, 0);
-}
-__device__ __forceinline__ float texture_scalar(const SampleKernelArgs& A, const GpuTexture& t, float2 uv)
-{
-    const float main = t.channel == 0 ? t.mainColor[0] : t.channel == 1 ? t.mainColor[1] : t.mainColor[2];
-    if (t.type == RTOW_TEXTURE_CONSTANT) return main;
-    if (t.type == RTOW_TEXTURE_CONSTANT_SCALAR) return t.parameter;
-    if (t.type == RTOW_TEXTURE_IMAGE && t.image >= 0) return (float)texture_pixel(A, t, uv)[t.channel] / 255.0f * main;
-    return 0.0f;
 }
 
 // [hit-list sorts: begin]  (tests/test_hitsort_host.py compiles the text between the two markers for the host and checks it against the oracle)
@@ -633,287 +501,6 @@ __device__ __noinline__ __attribute__((unused)) void sort_hit_list_spilled(float
 }
 
 // [hit-list sorts: end]
-// ------------------------------------------------------------------------------------------------------------
-// scene access: LDS image first, HBM/L2 for whatever did not fit
-// ------------------------------------------------------------------------------------------------------------
-struct SceneRefs {
-    const uint8_t* lds;     // LDS copy of the blob prefix
-    const uint8_t* glob;    // full blob in HBM
-    uint32_t ldsNodeCount;
-};
-
-template <bool ALL_LDS, bool SPLIT = false>
-__host__ __device__ __forceinline__ void load_node(const SceneRefs& sc, const SceneLayout& L, int idx, float4& q0, float4& q1, float4& q2, int& c0, int& c1)
-{
-    const uint32_t off = L.nodeOffset + (uint32_t)idx * 64u;
-#if defined(__HIP_DEVICE_COMPILE__) && RTOW_SPLIT_NODE_LOADS
-    if (!ALL_LDS && SPLIT) {
-        // A tree that does not fit LDS keeps its first ldsNodeCount nodes (the top levels) there; the blob in memory holds every node.  Selecting the BASE per lane makes
-        // every node load a flat_load (address-space check per lane, both memory counters, seven instructions to build the generic pointer), and a wave waits for its
-        // slowest lane anyway: so the wave reads from LDS when ALL its walking lanes are in the top levels and through L1 / L2 otherwise - ds_read or global_load
-        // (scalar base + 32-bit offset), never flat.  (Per-lane branches - ds_read under one EXEC mask, global_load under the other - make the compiler wait for the
-        // first group before it issues the second: both write the same registers.)  SPLIT = the walk of the kernels with 16-bit codes: 10 000 spheres +0.6 %, same box,
-        // three alternating runs each, every run above the other side's best.  The wide-code kernels keep the flat loads: their trees' lower levels miss L1 and L2, and
-        // the lanes in the top levels are better off in LDS whatever the others do (250 882 triangles: -5 % with the split; profiles/r05q_node_loads.json).
-        typedef __attribute__((address_space(3))) const uint8_t* LdsBytes;
-        typedef __attribute__((address_space(1))) const uint8_t* GlobalBytes;
-        if (__ballot((uint32_t)idx >= sc.ldsNodeCount) == 0ull) {      // wave-uniform: every lane that walks right now is in the top levels
-            LdsBytes b = (LdsBytes)sc.lds + off;
-            q0 = *(__attribute__((address_space(3))) const float4*)(b);
-            q1 = *(__attribute__((address_space(3))) const float4*)(b + 16);
-            q2 = *(__attribute__((address_space(3))) const float4*)(b + 32);
-            // the two child codes through an asm statement (with its own wait: the compiler's wait-count bookkeeping does not see into it): as an ordinary load the
-            // compiler sinks one of the two dwords behind the branch - as a flat load through a phi of both pointers, one more memory instruction per node visit
-            typedef int i2 __attribute__((ext_vector_type(2)));
-            i2 c;
-            asm volatile("ds_read_b64 %0, %1 offset:48\n\ts_waitcnt lgkmcnt(0)" : "=v"(c) : "v"((unsigned)(uintptr_t)b) : "memory");
-            c0 = c.x; c1 = c.y;
-        } else {
-            GlobalBytes b = (GlobalBytes)sc.glob + off;
-            q0 = *(__attribute__((address_space(1))) const float4*)(b);
-            q1 = *(__attribute__((address_space(1))) const float4*)(b + 16);
-            q2 = *(__attribute__((address_space(1))) const float4*)(b + 32);
-            const int2 c = *(__attribute__((address_space(1))) const int2*)(b + 48);
-            c0 = c.x; c1 = c.y;
-        }
-        return;
-    }
-#endif
-    const uint8_t* base = (ALL_LDS || (uint32_t)idx < sc.ldsNodeCount) ? sc.lds : sc.glob;
-    const float4* p = reinterpret_cast<const float4*>(base + off);
-    q0 = p[0];
-    q1 = p[1];
-    q2 = p[2];
-    const int2 c = *reinterpret_cast<const int2*>(base + off + 48);
-    c0 = c.x;
-    c1 = c.y;
-}
-
-template <bool ALL_LDS>
-__host__ __device__ __forceinline__ const uint8_t* section(const SceneRefs& sc, uint32_t offset)
-{
-    return (ALL_LDS ? sc.lds : sc.glob) + offset;
-}
-
-// centre of primitive `i` at ray time `time` (Entity.TransformAtTime, RT/Entity.cs:124-127) and its signed radius
-template <bool ALL_LDS, bool HAS_MOTION>
-__host__ __device__ __forceinline__ void sphere_at(const SceneRefs& sc, const SceneLayout& L, int i, float time, V3& c, float& radius)
-{
-    const float4 s = *reinterpret_cast<const float4*>(section<ALL_LDS>(sc, L.sphereOffset) + (uint32_t)i * 16u);
-    c = v3(s.x, s.y, s.z);
-    radius = s.w;
-    if (HAS_MOTION) {
-        const uint8_t* mp = section<ALL_LDS>(sc, L.motionOffset) + (uint32_t)i * 32u;
-        const float4 m0 = *reinterpret_cast<const float4*>(mp);      // dx dy dz t0
-        const float2 m1 = *reinterpret_cast<const float2*>(mp + 16); // t1 moving
-        if (__builtin_bit_cast(int, m1.y) != 0) {
-            // clamp(unlerp(t0, t1, t), 0, 1); when every moving entity shares one TimeRange (L.commonTimeRange) `time` already IS that value:
-            // the sample's ray time goes through the expression once, in REGEN, instead of once per sphere test (same operands, same result)
-            const float f = L.commonTimeRange ? time : um_max(0.0f, um_min(1.0f, (time - m0.w) / (m1.x - m0.w)));
-            c = v3(c.x + m0.x * f, c.y + m0.y * f, c.z + m0.z * f);
-        }
-    }
-}
-
-// (p.x / d, p.y / d, p.z / d): three IEEE divisions by one divisor (a sphere's outward normal, r.GetPoint(t) / radius, RT/HitTests.cs:56)
-__host__ __device__ __forceinline__ V3 div3(V3 p, float d)
-{
-#if RTOW_EXACT_DIV3
-    V3 q;
-    rtow::exact_div3(p.x, p.y, p.z, d, q.x, q.y, q.z);
-    return q;
-#else
-    return v3(p.x / d, p.y / d, p.z / d);
-#endif
-}
-
-// HitTests.Hit(Sphere) (RT/HitTests.cs:23-60) in entity space (oc = origin - centre), tMin = 0, tMax = +inf
-__host__ __device__ __forceinline__ bool sphere_hit(V3 oc, V3 d, float a, float radius, float& tOut)
-{
-    const float b = dot(oc, d);
-    const float c = dot(oc, oc) - radius * radius;
-    const float disc = b * b - a * c;
-    if (disc > 0) {
-        // t = (-b -+ sq) / a with a = dot(d, d) >= 0: a numerator that is not positive gives a quotient that is not positive (or NaN) and
-        // fails `t > 0` whatever a is, so its IEEE division is skipped - bit-identical, and the common "sphere behind the origin" case
-        // (every ray leaving the ground sphere) costs no division at all.
-        const float sq = RTOW_SQRT(disc);
-        const float n0 = -b - sq;
-        if (n0 > 0) {
-            const float t = n0 / a;
-            if (t < __builtin_inff() && t > 0) { tOut = t; return true; }
-        }
-        const float n1 = -b + sq;
-        if (n1 > 0) {
-            const float t = n1 / a;
-            if (t < __builtin_inff() && t > 0) { tOut = t; return true; }
-        }
-    }
-    return false;
-}
-
-// the same test with an arbitrary tMin (strict: t > tMin), RT/HitTests.cs:40,49
-__host__ __device__ __forceinline__ bool sphere_hit_tmin(V3 oc, V3 d, float a, float radius, float tMin, float& tOut)
-{
-    const float b = dot(oc, d);
-    const float c = dot(oc, oc) - radius * radius;
-    const float disc = b * b - a * c;
-    if (disc > 0) {
-        const float sq = RTOW_SQRT(disc);                    // tMin >= 0 here: the numerator shortcut of sphere_hit applies unchanged
-        const float n0 = -b - sq;
-        if (n0 > 0) {
-            const float t = n0 / a;
-            if (t < __builtin_inff() && t > tMin) { tOut = t; return true; }
-        }
-        const float n1 = -b + sq;
-        if (n1 > 0) {
-            const float t = n1 / a;
-            if (t < __builtin_inff() && t > tMin) { tOut = t; return true; }
-        }
-    }
-    return false;
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// general entities (SCENE_KIND_GENERAL): Rect / Box / Triangle and rotated or moving transforms, RT/Entity.cs:58-127
-// ------------------------------------------------------------------------------------------------------------
-__host__ __device__ __forceinline__ V3 cross(V3 a, V3 b) { return v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
-// math.mul(quaternion q, float3 v): t = 2 * cross(q.xyz, v); v + q.w * t + cross(q.xyz, t)
-__host__ __device__ __forceinline__ V3 rotate(float4 q, V3 v)
-{
-    const V3 qv = v3(q.x, q.y, q.z);
-    const V3 t = scale(2.0f, cross(qv, v));
-    const V3 c = cross(qv, t);
-    return v3(v.x + q.w * t.x + c.x, v.y + q.w * t.y + c.y, v.z + q.w * t.z + c.z);
-}
-__host__ __device__ __forceinline__ float um_sign(float x) { return (x > 0.0f ? 1.0f : 0.0f) - (x < 0.0f ? 1.0f : 0.0f); }
-
-// Entity.HitInternal + HitContent for primitive `i` (RT/Entity.cs:74-122) with tMax = +inf (tMin = 0 except for the exit-hit
-// probe of volume hulls, JOBS/SampleBatchJob.cs:465).
-// Returns the distance, the entity-space normal and the rotation that takes it to world space.
-template <bool ALL_LDS, bool TRIANGLES_ONLY = false>
-__host__ __device__ __forceinline__ bool general_hit(const SceneRefs& sc, const SceneLayout& L, int i, unsigned type, V3 ro, V3 rd, float time, float tMin,
-                                            float& tOut, V3& nLocal, float4& rot, float2* texCoord = nullptr)
-{
-    const float4* p = reinterpret_cast<const float4*>(section<ALL_LDS>(sc, L.primOffset) + (uint32_t)i * 128u);
-    if (texCoord) *texCoord = make_float2(0, 0);       // only triangles have texture coordinates (RT/Entity.cs:108, RT/HitTests.cs:123)
-    if (TRIANGLES_ONLY || type == RTOW_ENTITY_TRIANGLE) {       // TRIANGLES_ONLY (SCENE_KIND_TRIANGLES): the other primitives' code is not compiled in
-        // HitTests.Hit(Triangle) (RT/HitTests.cs:115-150); triangles are tested in world space (RT/Entity.cs:91-93)
-        // the first three quads (edges, v0, first normal) decide the test; the rest of the record - its second cache line when it is read from HBM -
-        // is only fetched for a hit
-        const float4 a0 = p[0], a1 = p[1], a2 = p[2];
-        const V3 e0 = v3(a0.x, a0.y, a0.z), e1 = v3(a0.w, a1.x, a1.y), v0 = v3(a1.z, a1.w, a2.x);
-        const V3 pvec = cross(rd, e0);
-        const float det = dot(e1, pvec);
-        if (det == 0) return false;
-        const float invDet = RTOW_RCP(det);
-        const V3 tvec = sub(ro, v0);
-        const float u = dot(tvec, pvec) * invDet;
-        if (u < 0 || u > 1) return false;
-        const V3 qvec = cross(tvec, e1);
-        const float v = dot(rd, qvec) * invDet;
-        if (v < 0 || u + v > 1) return false;
-        const float dist = dot(e0, qvec) * invDet;
-        if (dist < tMin || dist > __builtin_inff()) return false;
-        const float b0 = 1 - u - v;
-        const float4 a3 = p[3], a4 = p[4];
-        rot = p[6];
-        const V3 n0 = v3(a2.y, a2.z, a2.w), n1 = v3(a3.x, a3.y, a3.z), n2 = v3(a3.w, a4.x, a4.y);
-        nLocal = v3(n0.x * b0 + n1.x * u + n2.x * v, n0.y * b0 + n1.y * u + n2.y * v, n0.z * b0 + n1.z * u + n2.z * v);
-        if (texCoord) {                                  // mul(tri.TextureCoordinates, barycentricCoords) (:148): float2x3 columns t0 t1 t2
-            const float4 a5 = p[5];
-            *texCoord = make_float2(a4.z * b0 + a5.x * u + a5.z * v, a4.w * b0 + a5.y * u + a5.w * v);
-        }
-        tOut = dist;
-        return true;
-    }
-    rot = p[0];
-    const float4 invRot = p[1], q2 = p[2], q3 = p[3], q4 = p[4], q5 = p[5];
-    V3 invT = v3(q4.y, q4.z, q4.w);
-    if (__builtin_bit_cast(int, q2.w) != 0) {
-        // TransformAtTime (RT/Entity.cs:124-127) and its inverse (:87-88): invTranslation = mul(invRot, -pos(t))
-        const float f = um_max(0.0f, um_min(1.0f, (time - q3.w) / (q4.x - q3.w)));
-        const V3 pt = v3(q2.x + q3.x * f, q2.y + q3.y * f, q2.z + q3.z * f);
-        invT = rotate(invRot, neg(pt));
-    }
-    const V3 oL = add(rotate(invRot, ro), invT);     // transform(inverseTransform, ray.Origin)
-    const V3 dL = rotate(invRot, rd);                // rotate(inverseTransform, ray.Direction)
-    if (type == RTOW_ENTITY_SPHERE) {
-        float t;
-        if (!sphere_hit_tmin(oL, dL, dot(dL, dL), q5.x, tMin, t)) return false;
-        nLocal = div3(v3(oL.x + t * dL.x, oL.y + t * dL.y, oL.z + t * dL.z), q5.x);
-        tOut = t;
-        return true;
-    }
-    if (type == RTOW_ENTITY_RECT) {
-        // HitTests.Hit(Rect) (RT/HitTests.cs:62-78)
-        if (dL.z >= 0) return false;
-        const float t = -oL.z / dL.z;
-        if (t < tMin || t > __builtin_inff()) return false;
-        const float x = oL.x + t * dL.x, y = oL.y + t * dL.y;
-        if (x < q5.x || y < q5.y || x > q5.z || y > q5.w) return false;
-        nLocal = v3(0, 0, 1);
-        tOut = t;
-        return true;
-    }
-    // HitTests.Hit(Box) (RT/HitTests.cs:80-113): the origin is first advanced by tMin (origin + direction * tMin)
-    const float4 q6 = p[6];
-    const V3 ext = v3(q5.x, q5.y, q5.z), invExt = v3(q5.w, q6.x, q6.y);
-    const V3 o = v3(oL.x + dL.x * tMin, oL.y + dL.y * tMin, oL.z + dL.z * tMin);
-    const float winding = um_max(um_max(__builtin_fabsf(o.x) * invExt.x, __builtin_fabsf(o.y) * invExt.y), __builtin_fabsf(o.z) * invExt.z) < 1 ? -1.0f : 1.0f;
-    V3 sgn = v3(-um_sign(dL.x), -um_sign(dL.y), -um_sign(dL.z));
-    const V3 dtp = v3((ext.x * winding * sgn.x - o.x) / dL.x, (ext.y * winding * sgn.y - o.y) / dL.y, (ext.z * winding * sgn.z - o.z) / dL.z);
-    const bool tx = dtp.x >= 0 && __builtin_fabsf(o.y + dL.y * dtp.x) < ext.y && __builtin_fabsf(o.z + dL.z * dtp.x) < ext.z;
-    const bool ty = dtp.y >= 0 && __builtin_fabsf(o.z + dL.z * dtp.y) < ext.z && __builtin_fabsf(o.x + dL.x * dtp.y) < ext.x;
-    const bool tz = dtp.z >= 0 && __builtin_fabsf(o.x + dL.x * dtp.z) < ext.x && __builtin_fabsf(o.y + dL.y * dtp.z) < ext.y;
-    sgn = tx ? v3(sgn.x, 0, 0) : ty ? v3(0, sgn.y, 0) : v3(0, 0, tz ? sgn.z : 0);
-    if (!(sgn.x != 0 || sgn.y != 0 || sgn.z != 0)) return false;
-    float dist = sgn.x != 0 ? dtp.x : sgn.y != 0 ? dtp.y : dtp.z;
-    dist += tMin;
-    if (dist > __builtin_inff()) return false;
-    nLocal = sgn;
-    tOut = dist;
-    return true;
-}
-
-// HitTests.Hit(Triangle) (RT/HitTests.cs:115-150) on the compact record of an all-triangle scene (GpuTriHot, rtow_scene.h): the same expressions as general_hit's triangle
-// branch on the same operands, up to the distance; the barycentric (u, v) are handed back instead of the blended normal, which only the ray's nearest hit needs (tri_normal_cold)
-template <bool ALL_LDS>
-__host__ __device__ __forceinline__ bool tri_hit_hot(const SceneRefs& sc, const SceneLayout& L, int i, V3 ro, V3 rd, float tMin, float& tOut, float& uOut, float& vOut)
-{
-    const float4* p = reinterpret_cast<const float4*>(section<ALL_LDS>(sc, L.triHotOffset) + (uint32_t)i * (uint32_t)sizeof(GpuTriHot));
-    const float4 a0 = p[0], a1 = p[1];
-    const float a2x = *reinterpret_cast<const float*>(p + 2);
-    const V3 e0 = v3(a0.x, a0.y, a0.z), e1 = v3(a0.w, a1.x, a1.y), v0 = v3(a1.z, a1.w, a2x);
-    const V3 pvec = cross(rd, e0);
-    const float det = dot(e1, pvec);
-    if (det == 0) return false;
-    const float invDet = RTOW_RCP(det);
-    const V3 tvec = sub(ro, v0);
-    const float u = dot(tvec, pvec) * invDet;
-    if (u < 0 || u > 1) return false;
-    const V3 qvec = cross(tvec, e1);
-    const float v = dot(rd, qvec) * invDet;
-    if (v < 0 || u + v > 1) return false;
-    const float dist = dot(e0, qvec) * invDet;
-    if (dist < tMin || dist > __builtin_inff()) return false;
-    tOut = dist;
-    uOut = u;
-    vOut = v;
-    return true;
-}
-// the rest of that test for the hit that won: mul(tri.Normals, barycentricCoords) (RT/HitTests.cs:140-146) from the GpuTriCold record, and the entity's rotation
-template <bool ALL_LDS>
-__host__ __device__ __forceinline__ V3 tri_normal_cold(const SceneRefs& sc, const SceneLayout& L, int i, float u, float v, float4& rot)
-{
-    const float4* p = reinterpret_cast<const float4*>(section<ALL_LDS>(sc, L.triColdOffset) + (uint32_t)i * (uint32_t)sizeof(GpuTriCold));
-    const float4 c0 = p[0], c1 = p[1];
-    const float c2x = *reinterpret_cast<const float*>(p + 2);
-    rot = p[3];
-    const float b0 = 1 - u - v;
-    const V3 n0 = v3(c0.x, c0.y, c0.z), n1 = v3(c0.w, c1.x, c1.y), n2 = v3(c1.z, c1.w, c2x);
-    return v3(n0.x * b0 + n1.x * u + n2.x * v, n0.y * b0 + n1.y * u + n2.y * v, n0.z * b0 + n1.z * u + n2.z * v);
-}
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 
@@ -980,7 +567,7 @@ __device__ __forceinline__ unsigned short* hist_row_slot(unsigned short* ldsLane
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     if (SPILL) {
-        const SampleKernelArgs* A = (const SampleKernelArgs*)__builtin_amdgcn_kernarg_segment_ptr();      // the struct is the kernel's only argument
+        const SampleKernelArgs* A = (const SampleKernelArgs*)__builtin_amdgcn_kernarg_segment_ptr();      // the struct is the kernel's only argument (not cold_args: the kernel's copy does not come this far)
         asm volatile("" : "+s"(A));
         if (row >= (int)A->ldsHistRows) return A->histSpill + (size_t)(row - (int)A->ldsHistRows) * (size_t)A->histSpillStride + (size_t)blockIdx.x * kBlockThreads + threadIdx.x;
     }
@@ -1480,6 +1067,7 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
                     // Pixel boundaries are rare (one per `spp` samples) and touch two dozen launch constants nothing else needs - buffer pointers,
                     // slice and sample-count parameters.  Read through a laundered pointer to the kernarg segment they are s_load-ed here, on
                     // use, instead of sitting in SGPRs (and, past 102 of them, in VGPR lanes read back with v_readlane) through every stage.
+                    // (Written out instead of cold_args(A): through the helper the register allocation of the whole spheres kernel comes out differently.)
 #if defined(__HIP_DEVICE_COMPILE__)
                     const SampleKernelArgs* coldArgs = (const SampleKernelArgs*)__builtin_amdgcn_kernarg_segment_ptr();   // the struct is the kernel's only argument
                     asm volatile("" : "+s"(coldArgs));
@@ -1788,11 +1376,7 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
                     // LDS - their waves wait for memory anyway - gain from both: 10 000 spheres +1.2 % (kernarg) / +2.0 % (LDS), 250 882 triangles +2.2 / +2.4 %: they read the LDS
                     // copy.  Kernels with the scene in LDS LOSE with both (cover -1.1 / -1.7 %, depth 32 groups -2.8 %: their REGEN and SKY runs are short and the round trip
                     // shows): they keep the registers.  (The cubemap's nine constants are read on use in every kernel: cubemap_sample.)
-                    const SampleKernelArgs* viewArgs = &A;
-#if defined(__HIP_DEVICE_COMPILE__)
-                    if (COLD_VIEW) { viewArgs = (const SampleKernelArgs*)__builtin_amdgcn_kernarg_segment_ptr(); asm volatile("" : "+s"(viewArgs)); }
-#endif
-                    const SampleKernelArgs& VA = *viewArgs;
+                    const SampleKernelArgs& VA = COLD_VIEW ? cold_args(A) : A;
                     const RtowView& VW = LDS_VIEW ? *reinterpret_cast<const RtowView*>(ldsConst) : VA.view;
                     const float frameX = LDS_VIEW ? ldsConst[29] : VA.sizeX, frameY = LDS_VIEW ? ldsConst[30] : VA.sizeY;
                     const V3 viewRight = PINHOLE ? v3(0, 0, 0) : v3(VW.right), viewUp = PINHOLE ? v3(0, 0, 0) : v3(VW.up);
@@ -2028,13 +1612,7 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
                             if (TIE_WATCH) {
                                 // the watch of the all-triangle kinds (see TIE_WATCH above): same mark as the sphere kinds' below
                                 if (tie) {
-#if defined(__HIP_DEVICE_COMPILE__)
-                                    const SampleKernelArgs* rareArgs = (const SampleKernelArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-                                    asm volatile("" : "+s"(rareArgs));
-#else
-                                    const SampleKernelArgs* rareArgs = &A;
-#endif
-                                    unsigned* const bits = rareArgs->tieBits;
+                                    unsigned* const bits = cold_args(A).tieBits;
                                     if (bits) atomicOr(bits + ((unsigned)pix >> 5), 1u << ((unsigned)pix & 31u));
                                 }
                             }
@@ -2061,13 +1639,7 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
                                 bool take = t < best;
                                 if (!take && prim >= 0) {
                                     take = rank[i] < rank[prim];
-#if defined(__HIP_DEVICE_COMPILE__)
-                                    const SampleKernelArgs* rareArgs = (const SampleKernelArgs*)__builtin_amdgcn_kernarg_segment_ptr();      // loaded here, on use: no register holds the bitmap's address through the stages
-                                    asm volatile("" : "+s"(rareArgs));
-#else
-                                    const SampleKernelArgs* rareArgs = &A;
-#endif
-                                    unsigned* const bits = rareArgs->tieBits;
+                                    unsigned* const bits = cold_args(A).tieBits;      // loaded here, on use: no register holds the bitmap's address through the stages
                                     if (bits) atomicOr(bits + ((unsigned)pix >> 5), 1u << ((unsigned)pix & 31u));
                                 }
                                 if (take) { best = t; prim = i; }
@@ -2093,7 +1665,7 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
                     // two surfaces at exactly this distance: let the reference's own procedure pick (rare; see resolve_nearest_tie)
                     tieAtBest = false;
 #if defined(__HIP_DEVICE_COMPILE__)
-                    const SampleKernelArgs* argsInKernarg = (const SampleKernelArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+                    const SampleKernelArgs* argsInKernarg = (const SampleKernelArgs*)__builtin_amdgcn_kernarg_segment_ptr();      // (not cold_args(A): only an address for the callee is formed here; with the helper's laundering the exact-tie kernels come out differently)
 #else
                     const SampleKernelArgs* argsInKernarg = &A;                                                           // host pass of the HIP compiler: never executed
 #endif
@@ -2175,13 +1747,13 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
                     if (__float_as_uint(m2hit.z) & MAT_FLAG_TEXTURED) {
                         // Material.Scatter / Emit evaluate the four textures at rec.TexCoords (RT/Material.cs:71,77-78,123,176-179), and
                         // everything derived from metallic / glossiness (prepare_materials_kernel's program) follows per hit
-                        const GpuTexMaterial tm = reinterpret_cast<const GpuTexMaterial*>(A.texBlob + A.texLayout.materialOffset)[matIdx];
-                        reflectance = texture_color(A, tm.albedo, hitUv);
-                        emission = texture_color(A, tm.emission, hitUv);
-                        const float glossiness = texture_scalar(A, tm.glossiness, hitUv);
+                        const GpuTexMaterial tm = reinterpret_cast<const GpuTexMaterial*>(A.tex.blob + A.tex.layout.materialOffset)[matIdx];
+                        reflectance = texture_color(A.tex, tm.albedo, hitUv);
+                        emission = texture_color(A.tex, tm.emission, hitUv);
+                        const float glossiness = texture_scalar(A.tex, tm.glossiness, hitUv);
                         float roughness, ior, invIor = 0.0f, alpha = 0.0f;
                         if (__float_as_int(m1.z) == RTOW_MATERIAL_STANDARD) {
-                            metallicHit = texture_scalar(A, tm.metallic, hitUv);
+                            metallicHit = texture_scalar(A.tex, tm.metallic, hitUv);
                             roughness = det_sq(1 - glossiness);
                             ior = 1.5f + metallicHit * (1.1f - 1.5f);
                             alpha = roughness_to_alpha(roughness);
@@ -2444,18 +2016,14 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
             if (st == ST_SKY) {
                 DBG_TRACE(2, 0xffff, 0.0f);
                 V3 sky = v3(0, 0, 0);
-                const SampleKernelArgs* skyArgs = &A;                      // the sky's seven constants: read on use in the kernels that read the view's so (REGEN)
-#if defined(__HIP_DEVICE_COMPILE__)
-                if (COLD_VIEW) { skyArgs = (const SampleKernelArgs*)__builtin_amdgcn_kernarg_segment_ptr(); asm volatile("" : "+s"(skyArgs)); }
-#endif
-                const SampleKernelArgs& EA = *skyArgs;
+                const SampleKernelArgs& EA = COLD_VIEW ? cold_args(A) : A;     // the sky's seven constants: read on use in the kernels that read the view's so (REGEN)
                 const RtowEnvironment& ENV = LDS_VIEW ? *reinterpret_cast<const RtowEnvironment*>(ldsConst + 22) : EA.environment;
                 if (ENV.skyType == RTOW_SKY_GRADIENT) {
                     const float s = 0.5f * (rd.y + 1);
                     const V3 b = v3(ENV.skyBottomColor), tp = v3(ENV.skyTopColor);
                     sky = v3(b.x + s * (tp.x - b.x), b.y + s * (tp.y - b.y), b.z + s * (tp.z - b.z));
                 } else if (ENV.skyType == RTOW_SKY_CUBEMAP) {
-                    sky = cubemap_sample(A, rd);
+                    sky = cubemap_sample(cold_args(A).cubemap, rd);       // its nine constants are read on use in every kernel: most launches have a gradient sky
                 }
                 // randomEventsLocalAcc += rng.RandomEvents / pow(2, depth) (:363): RandomEvents is 0 here unless a ProbabilisticHit
                 // that found nothing left its increment pending

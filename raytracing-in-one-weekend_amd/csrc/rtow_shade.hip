@@ -5,10 +5,8 @@
 // the sky colour where the ray meets nothing.  Together with rtowTraceViewDevice's normals that is a noise-free G-buffer: guides for rtowDenoiseDevice, a material id under
 // the cursor, a material to match on in rtowReprojectAccumDevice's host.  include/rtow.h holds the numeric specification.
 //
-// Every value is computed by the sample kernel's own helpers (rtow_sample_kernel.hip.h: general_hit's texCoord as the HIT stage of the textured kernels asks for it,
-// texture_color / texture_scalar, cubemap_sample, the SKY stage's gradient expression), so the pass cannot drift from what a sample batch shades with.  Those helpers take the
-// sample kernel's argument block: this kernel's argument begins with one (ShadeArgs::S), of which only the scene, the texture blob and the cubemap fields are filled in -
-// cubemap_sample reads the cubemap's constants through the kernarg segment pointer, which is why the block has to come first.
+// Every value is computed by the sample kernel's own helpers (rtow_hit_tests.hip.h: general_hit's texCoord as the HIT stage of the textured kernels asks for it;
+// rtow_surface.hip.h: texture_color / texture_scalar, cubemap_sample; the SKY stage's gradient expression), so the pass cannot drift from what a sample batch shades with.
 //
 // Launch shape: a plain grid of 256-lane workgroups, one lane per element, no LDS, no barrier; a lane without an element leaves at once.  The scene comes
 // from HBM / L2 (general_hit<false>): one primitive record, one material record and at most four texels per element.
@@ -17,9 +15,8 @@
 // index itself) is not one of the scene's, and a material index beyond the scene's materials.  An Image texture whose image number is not one of the blob's samples as a null
 // image.  Texels are clamped into their image by texture_pixel, after (int) conversions that saturate on this hardware (NaN: 0), as in cubemap_sample, whose face coordinates
 // (u, v) lie in [-1, 1] or are NaN for every direction.  A ray's floats are only ever operands, never addresses.
-#include "rtow_sample_kernel.hip.h"
-
-#include <cstddef>
+#include "rtow_hit_tests.hip.h"
+#include "rtow_surface.hip.h"
 
 namespace rtow {
 
@@ -32,7 +29,11 @@ struct __attribute__((packed, aligned(4))) Ray8 { float ox, oy, oz, time, dx, dy
 static_assert(sizeof(Ray8) == sizeof(RtowRay), "RtowRay is eight floats");
 
 struct ShadeArgs {
-    SampleKernelArgs S;             // FIRST (see above): sceneBlob, layout, texBlob, texLayout, environment and the cubemap fields; everything else zero
+    const uint8_t* sceneBlob;
+    SceneLayout layout;
+    TexRefs tex;
+    CubemapRefs cubemap;
+    RtowEnvironment environment;
     const int32_t* primOfEntity;    // the host's entity index -> primitive, -1 = none; null: the same number
     const RtowRay* rays;
     const int32_t* entityIndex;
@@ -41,7 +42,6 @@ struct ShadeArgs {
     int32_t entityCount;
     uint32_t imageCount;            // GpuImage records in the texture blob
 };
-static_assert(offsetof(ShadeArgs, S) == 0, "cubemap_sample reads the kernarg segment as a SampleKernelArgs");
 
 // texture_color / texture_scalar index the image table with t.image: an image number that is not the blob's samples as the null image does (0).  The record is read where
 // it lies in the blob: a private copy of it would be a per-lane array (texture_scalar selects a channel of mainColor)
@@ -49,13 +49,13 @@ __device__ __forceinline__ bool no_such_image(const GpuTexture& t, uint32_t imag
 {
     return t.type == RTOW_TEXTURE_IMAGE && t.image >= 0 && (uint32_t)t.image >= imageCount;
 }
-__device__ __forceinline__ V3 color_checked(const SampleKernelArgs& S, const GpuTexture& t, float2 uv, uint32_t imageCount)
+__device__ __forceinline__ V3 color_checked(const TexRefs& tex, const GpuTexture& t, float2 uv, uint32_t imageCount)
 {
-    return no_such_image(t, imageCount) ? v3(0, 0, 0) : texture_color(S, t, uv);
+    return no_such_image(t, imageCount) ? v3(0, 0, 0) : texture_color(tex, t, uv);
 }
-__device__ __forceinline__ float scalar_checked(const SampleKernelArgs& S, const GpuTexture& t, float2 uv, uint32_t imageCount)
+__device__ __forceinline__ float scalar_checked(const TexRefs& tex, const GpuTexture& t, float2 uv, uint32_t imageCount)
 {
-    return no_such_image(t, imageCount) ? 0.0f : texture_scalar(S, t, uv);
+    return no_such_image(t, imageCount) ? 0.0f : texture_scalar(tex, t, uv);
 }
 
 template <int BASE>
@@ -64,12 +64,12 @@ __global__ void __launch_bounds__(kShadeBlock) shade_kernel(ShadeArgs A)
     const long long i = (long long)blockIdx.x * kShadeBlock + threadIdx.x;
     if (i >= (long long)A.count) return;
     const size_t index = (size_t)i;
-    const SceneLayout& L = A.S.layout;
+    const SceneLayout& L = A.layout;
     const Ray8 r = reinterpret_cast<const Ray8*>(A.rays)[index];
     const V3 ro = v3(r.ox, r.oy, r.oz), rd = v3(r.dx, r.dy, r.dz);
     SceneRefs sc;
     sc.lds = nullptr;
-    sc.glob = A.S.sceneBlob;
+    sc.glob = A.sceneBlob;
     sc.ldsNodeCount = 0;
 
     // entity -> primitive -> material, each checked before it is an address
@@ -102,24 +102,24 @@ __global__ void __launch_bounds__(kShadeBlock) shade_kernel(ShadeArgs A)
         emission = v3(m0.w, m1.x, m1.y);
         mg = make_float2(m1.w, m2.x);
         const unsigned flags = __float_as_uint(m2.z);
-        if (BASE >= SCENE_KIND_GENERAL && (flags & MAT_FLAG_TEXTURED) && A.S.texBlob && A.S.texLayout.totalBytes != 0u) {
+        if (BASE >= SCENE_KIND_GENERAL && (flags & MAT_FLAG_TEXTURED) && A.tex.blob && A.tex.layout.totalBytes != 0u) {
             // Material.Scatter / Emit evaluate the four textures at rec.TexCoords (RT/Material.cs:71,77-78,123,176-179)
-            const GpuTexMaterial& tm = reinterpret_cast<const GpuTexMaterial*>(A.S.texBlob + A.S.texLayout.materialOffset)[matIdx];
-            albedo = color_checked(A.S, tm.albedo, uv, A.imageCount);
-            emission = color_checked(A.S, tm.emission, uv, A.imageCount);
-            mg = make_float2(scalar_checked(A.S, tm.metallic, uv, A.imageCount), scalar_checked(A.S, tm.glossiness, uv, A.imageCount));
+            const GpuTexMaterial& tm = reinterpret_cast<const GpuTexMaterial*>(A.tex.blob + A.tex.layout.materialOffset)[matIdx];
+            albedo = color_checked(A.tex, tm.albedo, uv, A.imageCount);
+            emission = color_checked(A.tex, tm.emission, uv, A.imageCount);
+            mg = make_float2(scalar_checked(A.tex, tm.metallic, uv, A.imageCount), scalar_checked(A.tex, tm.glossiness, uv, A.imageCount));
         }
         materialIndex = (int32_t)matIdx;
         materialInfo = (__float_as_uint(m1.z) & 0xffu) | ((flags & MAT_FLAG_PERFECT_SPECULAR) ? 0x100u : 0u);
     } else {
         // sampleAlbedo = hitSkyColor (JOBS/SampleBatchJob.cs:349-370): the SKY stage's expressions on the direction as stored
-        const RtowEnvironment& ENV = A.S.environment;
+        const RtowEnvironment& ENV = A.environment;
         if (ENV.skyType == RTOW_SKY_GRADIENT) {
             const float s = 0.5f * (rd.y + 1);
             const V3 b = v3(ENV.skyBottomColor), tp = v3(ENV.skyTopColor);
             albedo = v3(b.x + s * (tp.x - b.x), b.y + s * (tp.y - b.y), b.z + s * (tp.z - b.z));
         } else if (ENV.skyType == RTOW_SKY_CUBEMAP) {
-            albedo = cubemap_sample(A.S, rd);
+            albedo = cubemap_sample(A.cubemap, rd);
         }
     }
 
@@ -138,17 +138,12 @@ hipError_t launchShadeHits(const ShadeScene& scene, const RtowEnvironment& envir
 {
     if (count <= 0) return hipSuccess;
     ShadeArgs A{};
-    A.S.sceneBlob = scene.blob;
-    A.S.layout = scene.layout;
-    A.S.texBlob = scene.texBlob;
-    A.S.texLayout = scene.texLayout;
-    A.S.environment = environment;
-    A.S.cubemapData = scene.cubemapData;
-    A.S.cubemapHalfW = scene.cubemap.faceWidth / 2; A.S.cubemapHalfH = scene.cubemap.faceHeight / 2;                    // RT/Texture.cs:152-154
-    A.S.cubemapW1 = scene.cubemap.faceWidth - 1; A.S.cubemapH1 = scene.cubemap.faceHeight - 1;
-    A.S.cubemapPixelStride = scene.cubemap.pixelStride; A.S.cubemapRowStride = scene.cubemap.pixelStride * scene.cubemap.faceWidth;      // :167
-    A.S.cubemapFaceStride = scene.cubemap.pixelStride * scene.cubemap.faceWidth * scene.cubemap.faceHeight;             // :168
-    A.S.cubemapChannelType = scene.cubemap.channelType;
+    A.sceneBlob = scene.blob;
+    A.layout = scene.layout;
+    A.tex.blob = scene.texBlob;
+    A.tex.layout = scene.texLayout;
+    A.cubemap = cubemapRefs(scene.cubemap, scene.cubemapData);
+    A.environment = environment;
     A.primOfEntity = scene.primOfEntity;
     A.rays = rays;
     A.entityIndex = entityIndex;

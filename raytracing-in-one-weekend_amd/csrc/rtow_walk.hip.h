@@ -5,14 +5,14 @@
 // leaves it reaches, and it reaches a leaf iff the ray passes the box of every node above it under AxisAlignedBoundingBox.Hit (RT/HitTests.cs:9-21).  A box that encloses
 // another passes whenever the inner one does (subtraction, multiplication, min and max are monotone in binary32), so that set is "the entities whose own box the ray passes" -
 // what the leaf children of this library's tree carry (the reference's own entity boxes under the reference's own slab test; the leaf's box where the host forced a leaf at
-// MaxBvhDepth).  The walk visits them with the sample kernel's own hit tests (sphere_at / sphere_hit / general_hit of rtow_sample_kernel.hip.h: the same expressions in the
+// MaxBvhDepth).  The walk visits them with the sample kernel's own hit tests (sphere_at / sphere_hit / general_hit of rtow_hit_tests.hip.h: the same expressions in the
 // same order, IEEE division and square root, no contraction), pruning inner boxes by the best distance so far with the kernel's 2^-12 of slack.
 // Hits at bit-identical distance: the entity that comes first in the reference tree's leaf order (what the sample path shades).
 //
 // Stack: where the pending far children live.  `bool push(int)` (false: no room - the walk then reports overflow instead of dropping a subtree silently), `int pop()`,
 // `bool empty()`.  The host keeps a growing array; the device a column of an LDS array (rtow_trace.hip).
 #pragma once
-#include "rtow_sample_kernel.hip.h"
+#include "rtow_hit_tests.hip.h"
 
 namespace rtow {
 

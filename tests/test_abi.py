@@ -92,8 +92,12 @@ def test_comm_library_path_selects_the_rccl_build_once_per_process():
     loaded once)."""
     import subprocess
     import sys
-    fake = os.path.join(ROOT, "tests", "build", "libfake_rccl.so")
-    assert os.path.exists(fake), "python __graft_entry__.py builds tests/build/libfake_rccl.so"
+    # the stand-in is built by python __graft_entry__.py; a tests/build that lacks it gets it here, by the same command (as tests/test_gpu_comm.py does)
+    fake, src = os.path.join(ROOT, "tests", "build", "libfake_rccl.so"), os.path.join(ROOT, "tests", "native", "fake_rccl.cpp")
+    if not os.path.exists(fake) or os.path.getmtime(fake) < os.path.getmtime(src):
+        os.makedirs(os.path.dirname(fake), exist_ok=True)
+        subprocess.run(["/opt/rocm/bin/hipcc", "-std=c++17", "-O2", "-fPIC", "-shared", "-x", "c++", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", src, "-o", fake,
+                        "-L/opt/rocm/lib", "-lamdhip64", "-pthread"], check=True, capture_output=True)
     code = r'''
 import importlib, sys
 sys.path.insert(0, sys.argv[1])

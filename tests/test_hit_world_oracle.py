@@ -99,7 +99,7 @@ def probe_shim():
     os.makedirs(out_dir, exist_ok=True)
     so, obj = os.path.join(out_dir, "libprobe_shim.so"), os.path.join(out_dir, "probe_host.o")
     srcs = [os.path.join(ROOT, "tests", "native", "probe_shim.cpp"), os.path.join(csrc, "rtow_bvh.cpp"), os.path.join(csrc, "rtow_reforder.cpp")]
-    deps = srcs + [os.path.join(csrc, n) for n in ("rtow_probe.hip", "rtow_sample_kernel.hip.h", "rtow_exactmath.hip.h", "rtow_scene.h", "rtow_kernels.h")]
+    deps = srcs + [os.path.join(csrc, n) for n in ("rtow_probe.hip", "rtow_walk.hip.h", "rtow_hit_tests.hip.h", "rtow_vecmath.hip.h", "rtow_exactmath.hip.h", "rtow_scene.h", "rtow_kernels.h")]
     if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
         subprocess.run(["/opt/rocm/bin/hipcc", "-std=c++17", "-O2", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "--offload-host-only", "-x", "hip", "-c",
                         os.path.join(csrc, "rtow_probe.hip"), "-o", obj], check=True, capture_output=True)
