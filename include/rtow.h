@@ -546,6 +546,46 @@ RTOW_API int rtowTraceViewDevice(RtowContext context, const RtowTraceViewParams*
                                  const RtowHitBuffers* hits /* width*height, pixel = row*width+col, row 0 at the bottom */,
                                  RtowRay* outRays /* device, width*height, or NULL */, void* stream);
 
+/* ---- interval ray queries: the nearest hit within (tMin, tMax), and any-hit ----
+ * The queries above are fixed at tMin 0, tMax +inf and always walk to the nearest hit.  These pass the reference's own bounds on - Entity.Hit(r, tMin, tMax), RT/Entity.cs:58-127 -
+ * for the two questions that cannot be asked that way: "is anything between A and B" (visibility of a light or a gizmo, line of sight, an ambient-occlusion guide, disocclusion
+ * by visibility from the previous camera: a walk that stops at the first occluder, with no distance to compare afterwards and no origin to offset by hand) and "what lies
+ * behind the first surface" (the thing behind the glass ball that rtowShadeHitsDevice marks with bit 8 of materialInfo; a second layer for a guide).
+ * Added after API version 12 without changing it: a host detects the calls by their entry points (C#: EntryPointNotFoundException). */
+typedef struct RtowRayInterval { float tMin, tMax; } RtowRayInterval;   /* 8 bytes, parameter units of the ray's direction AS STORED */
+/* Numeric specification (float32, no contraction; the walk is csrc/rtow_walk.hip.h: walk_interval, one text for the host and the device):
+ *   hit set:   an entity counts for a ray iff the ray passes the entity's own reference box under AxisAlignedBoundingBox.Hit (RT/HitTests.cs:9-21; the test the walk of
+ *              rtowTraceRaysDevice applies at its leaves - it knows nothing of the interval) and Entity.Hit(ray, tMin, tMax) is true, per primitive type (RT/HitTests.cs):
+ *              Sphere: the near root if tMin < t < tMax (both strict), else the far root under the same test; Rect and Triangle: rejected iff t < tMin || t > tMax (both ends
+ *              inclusive); Box: the origin is advanced by tMin (origin + direction * tMin), the distance is that ray's plus tMin, rejected iff it is > tMax.  Volume entities
+ *              are hit as their hull; moving entities at rays[i].time, as in rtowTraceRaysDevice.  A distance that is not below +INFINITY (the reference's Triangle comparisons
+ *              let +inf and NaN through) never counts, as it never wins in rtowTraceRaysDevice.
+ *   nearest:   distance = the smallest such distance, entityIndex and normal that entity's (the normal is HitRecord.Normal of Entity.Hit(ray, tMin, tMax): a sphere's far
+ *              root and a box's exit face have theirs); of several entities at the bit-identical smallest distance the one first in the reference tree's leaf order, as in
+ *              rtowTraceRaysDevice.  A miss gives +INFINITY, -1 and (0, 0, 0).
+ *   NULL:      intervals == NULL means (0, +inf) for every ray; all three outputs are then bit for bit those of rtowTraceRaysDevice.
+ *   occlusion: occluded[i] = 1 if the hit set of ray i is not empty, else 0 - (entityIndex >= 0) of the nearest form on the same ray and interval; the walk returns at the
+ *              first hit it accepts.
+ *   not traced: a ray whose interval does not satisfy 0 <= tMin && tMin <= tMax (NaN fails) is not traced: it reports a miss / occluded = 0.  tMax may be +INFINITY.
+ *   peeling:   a Sphere at exactly tMin is excluded, a Triangle, Rect or Box at exactly tMin is NOT: a host that asks for the layer behind a hit at distance d passes
+ *              tMin = the next float above d (C: nextafterf(d, INFINITY)), which excludes that hit for every type; the result is a miss or strictly farther than d.
+ *              For a segment from A to B with direction = B - A the interval is (tMin, 1): a Sphere that touches B exactly does not occlude, a Triangle that does, does.
+ * Enqueued on `stream` (NULL = the context's own stream): one launch, one lane per ray; no allocation, no wait; stream order and queueing as rtowTraceRaysDevice.  Rays
+ * and intervals may start at any 4-byte aligned address, `occluded` at any address.
+ * Validation (RTOW_ERROR_INVALID_VALUE, nothing enqueued): that of rtowTraceRaysDevice (NULL context / rays / hits, all three hit pointers NULL, count < 0), for the
+ * occlusion call NULL context / rays / occluded, count < 0.  count == 0 succeeds and launches nothing.  RTOW_ERROR_NO_SCENE before rtowUploadScene. */
+/* nearest Entity.Hit(r, tMin, tMax) per ray; intervals == NULL means (0, +inf) for every ray */
+RTOW_API int rtowTraceRaysIntervalDevice(RtowContext context, int32_t count, const RtowRay* rays /* device */, const RtowRayInterval* intervals /* device or NULL */,
+                                         const RtowHitBuffers* hits, void* stream);
+/* occluded[i] = 1 if ANY entity has Entity.Hit(r, tMin, tMax), else 0; intervals == NULL as above */
+RTOW_API int rtowTraceOcclusionDevice(RtowContext context, int32_t count, const RtowRay* rays /* device */, const RtowRayInterval* intervals /* device or NULL */,
+                                      uint8_t* occluded /* device, count bytes, any address */, void* stream);
+/* One ray on the host, the interval form of rtowProbeNearestHit (the same host walk under the same lock: it never waits for a batch); one ray of
+ * rtowTraceRaysIntervalDevice bit for bit, an interval that is not traced included.  occluded == (*entityIndex >= 0).  Either output pointer may be NULL.
+ * Validation: NULL context / origin / direction -> RTOW_ERROR_INVALID_VALUE; RTOW_ERROR_NO_SCENE before rtowUploadScene. */
+RTOW_API int rtowProbeNearestHitInterval(RtowContext context, const RtowFloat3* origin, const RtowFloat3* direction, float time, float tMin, float tMax,
+                                         float* distance, int32_t* entityIndex);
+
 /* ---- first-hit material AOVs: what the surface a trace call found is made of ----
  * The trace calls return distance, entity and geometric normal; this call returns the material of that first surface, evaluated as the sample path evaluates it at a hit:
  * Albedo.SampleColor / Emission.SampleColor / Metallic.SampleScalar / Glossiness.SampleScalar at HitRecord.TexCoords (RT/Material.cs:71,77-78,123,176-196; RT/Texture.cs:51-138;

@@ -192,6 +192,15 @@ class Ray(C.Structure):
 RAY_DTYPE = [("origin", "<f4", (3,)), ("time", "<f4"), ("direction", "<f4", (3,)), ("pad", "<f4")]
 
 
+class RayInterval(C.Structure):
+    """RtowRayInterval (8 bytes): tMin, tMax in parameter units of the ray's direction as stored."""
+    _fields_ = [("tMin", C.c_float), ("tMax", C.c_float)]
+
+
+# numpy view of an RtowRayInterval array
+RAY_INTERVAL_DTYPE = [("tMin", "<f4"), ("tMax", "<f4")]
+
+
 class HitBuffers(C.Structure):
     """RtowHitBuffers: device pointers, any may be NULL (not written), not all three."""
     _fields_ = [("distance", C.c_void_p), ("entityIndex", C.c_void_p), ("normal", C.c_void_p)]
@@ -250,4 +259,5 @@ EXPORTED_SYMBOLS = [
     "rtowHybridPlan", "rtowExchangeAccumDevice", "rtowSampleBatchGroupDevice",
     "rtowCombineFinalizeDevice", "rtowReduceMetricsDeviceAsync", "rtowProbeNearestHit", "rtowSampleBatchChainAdaptiveDevice",
     "rtowDenoiseDevice", "rtowTraceRaysDevice", "rtowTraceViewDevice", "rtowReprojectAccumDevice", "rtowShadeHitsDevice",
+    "rtowTraceRaysIntervalDevice", "rtowTraceOcclusionDevice", "rtowProbeNearestHitInterval",
 ]

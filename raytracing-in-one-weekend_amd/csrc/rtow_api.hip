@@ -1503,6 +1503,21 @@ RTOW_API int rtowProbeNearestHit(RtowContext ctx, const RtowFloat3* origin, cons
     return RTOW_SUCCESS;
 }
 
+RTOW_API int rtowProbeNearestHitInterval(RtowContext ctx, const RtowFloat3* origin, const RtowFloat3* direction, float time, float tMin, float tMax, float* distance,
+                                         int32_t* entityIndex)
+{
+    if (!ctx || !origin || !direction) return RTOW_ERROR_INVALID_VALUE;
+    std::lock_guard<std::mutex> lock(ctx->sceneMu);          // the probe's own lock, as rtowProbeNearestHit
+    if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
+    const float o[3] = {origin->x, origin->y, origin->z}, d[3] = {direction->x, direction->y, direction->z};
+    float t = 0.0f;
+    int prim = -1;
+    (void)probeIntervalHost(ctx->scene.blob.data(), ctx->scene.layout, ctx->scene.entityOfPrim.empty() ? nullptr : ctx->scene.entityOfPrim.data(), o, d, time, tMin, tMax, false, &t, &prim);
+    if (distance) *distance = t;
+    if (entityIndex) *entityIndex = prim;
+    return RTOW_SUCCESS;
+}
+
 RTOW_API int rtowTraceRaysDevice(RtowContext ctx, int32_t count, const RtowRay* rays, const RtowHitBuffers* hits, void* stream)
 {
     if (!ctx || !rays || !hits || count < 0) return RTOW_ERROR_INVALID_VALUE;
@@ -1526,6 +1541,32 @@ RTOW_API int rtowTraceViewDevice(RtowContext ctx, const RtowTraceViewParams* par
     HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     HIP_TRY(ctx, launchTraceView(ctx->dScene, ctx->scene.layout, ctx->scene.entityOfPrim.empty() ? nullptr : ctx->dEntityOfPrim, *params, *hits, outRays, s), RTOW_ERROR_LAUNCH_FAILURE);
+    return RTOW_SUCCESS;
+}
+
+RTOW_API int rtowTraceRaysIntervalDevice(RtowContext ctx, int32_t count, const RtowRay* rays, const RtowRayInterval* intervals, const RtowHitBuffers* hits, void* stream)
+{
+    if (!ctx || !rays || !hits || count < 0) return RTOW_ERROR_INVALID_VALUE;
+    if (!hits->distance && !hits->entityIndex && !hits->normal) return RTOW_ERROR_INVALID_VALUE;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
+    if (count == 0) return RTOW_SUCCESS;
+    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    HIP_TRY(ctx, launchTraceRaysInterval(ctx->dScene, ctx->scene.layout, ctx->scene.entityOfPrim.empty() ? nullptr : ctx->dEntityOfPrim, count, rays, intervals, *hits, s),
+            RTOW_ERROR_LAUNCH_FAILURE);
+    return RTOW_SUCCESS;
+}
+
+RTOW_API int rtowTraceOcclusionDevice(RtowContext ctx, int32_t count, const RtowRay* rays, const RtowRayInterval* intervals, uint8_t* occluded, void* stream)
+{
+    if (!ctx || !rays || !occluded || count < 0) return RTOW_ERROR_INVALID_VALUE;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
+    if (count == 0) return RTOW_SUCCESS;
+    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    HIP_TRY(ctx, launchTraceOcclusion(ctx->dScene, ctx->scene.layout, count, rays, intervals, occluded, s), RTOW_ERROR_LAUNCH_FAILURE);
     return RTOW_SUCCESS;
 }
 

@@ -371,12 +371,23 @@ hipError_t launchCollectTiedPixels(const unsigned* tieBits, unsigned words, unsi
 // rtowProbeNearestHit (rtow_probe.hip): one ray walked on the host through the scene's host image (derived entity transforms included); false = miss
 bool probeNearestHitHost(const uint8_t* blob, const SceneLayout& L, const int32_t* entityOfPrim, const float origin[3], const float direction[3], float time, float* distance, int* entity);
 
+// rtowProbeNearestHitInterval: the same with Entity.Hit(r, tMin, tMax) (walk_interval); any: the first accepted hit instead of the nearest; an interval that is not traced: a miss
+bool probeIntervalHost(const uint8_t* blob, const SceneLayout& L, const int32_t* entityOfPrim, const float origin[3], const float direction[3], float time, float tMin, float tMax,
+                       bool any, float* distance, int* entity);
+
 // rtowTraceRaysDevice / rtowTraceViewDevice (rtow_trace.hip): one launch on `stream`, one lane per ray, through the DEVICE image of the scene (arguments validated by the caller);
 // entityOfPrim: the device copy of CompiledScene.entityOfPrim, or null
 hipError_t launchTraceRays(const uint8_t* blob, const SceneLayout& layout, const int32_t* entityOfPrim, int64_t count, const RtowRay* rays, const RtowHitBuffers& hits,
                            hipStream_t stream);
 hipError_t launchTraceView(const uint8_t* blob, const SceneLayout& layout, const int32_t* entityOfPrim, const RtowTraceViewParams& p, const RtowHitBuffers& hits,
                            RtowRay* outRays, hipStream_t stream);
+
+// rtowTraceRaysIntervalDevice / rtowTraceOcclusionDevice (rtow_trace_interval.hip): one launch on `stream`, one lane per ray, as launchTraceRays; intervals: device, or null
+// = (0, +inf) for every ray; occluded: one byte per ray
+hipError_t launchTraceRaysInterval(const uint8_t* blob, const SceneLayout& layout, const int32_t* entityOfPrim, int64_t count, const RtowRay* rays,
+                                   const RtowRayInterval* intervals, const RtowHitBuffers& hits, hipStream_t stream);
+hipError_t launchTraceOcclusion(const uint8_t* blob, const SceneLayout& layout, int64_t count, const RtowRay* rays, const RtowRayInterval* intervals, uint8_t* occluded,
+                                hipStream_t stream);
 
 // rtowShadeHitsDevice (rtow_shade.hip): one launch on `stream`, one lane per element (arguments validated by the caller).  What the pass reads of the context, all device
 // memory but the descriptor: primOfEntity = the inverse of CompiledScene.entityOfPrim (-1: no primitive), or null (the same number); texBlob may be null (no Image texture),

@@ -1,4 +1,4 @@
-// rtow_probe.hip - rtowProbeNearestHit: one ray against the resident scene, walked on the HOST.
+// rtow_probe.hip - rtowProbeNearestHit / rtowProbeNearestHitInterval: one ray against the resident scene, walked on the HOST.
 //
 // Replaces the host's HitWorld (UNITY/Raytracer.cs:1353: BvhRoot->Hit(r, 0, +inf, out hitRec) -> the recursive HitTests.Hit(BvhNode), RT/HitTests.cs:152-196), which
 // ScheduleSample calls with the camera's centre ray before every batch to set the focus distance (UNITY/Raytracer.cs:608-609) - the one reason a host that has handed
@@ -38,6 +38,15 @@ void walk(const uint8_t* blob, const SceneLayout& L, V3 ro, V3 rd, float time, f
     (void)walk_nearest<BASE>(blob, L, ro, rd, time, stack, bestT, bestPrim, rtime);
 }
 
+template <int BASE>
+void walkInterval(const uint8_t* blob, const SceneLayout& L, V3 ro, V3 rd, float time, float tMin, float tMax, bool any, float& bestT, int& bestPrim)
+{
+    HostStack stack((size_t)L.bvhDepth + 2u);
+    float rtime;
+    if (any) (void)walk_interval<BASE, true>(blob, L, ro, rd, time, tMin, tMax, stack, bestT, bestPrim, rtime);
+    else (void)walk_interval<BASE, false>(blob, L, ro, rd, time, tMin, tMax, stack, bestT, bestPrim, rtime);
+}
+
 } // namespace
 
 // blob: the HOST image of the scene, derived entity transforms included (rtowUploadScene copies them back).  entityOfPrim: CompiledScene.entityOfPrim (all-triangle scenes
@@ -50,6 +59,25 @@ bool probeNearestHitHost(const uint8_t* blob, const SceneLayout& L, const int32_
     if (L.sceneKind == SCENE_KIND_SPHERES) walk<SCENE_KIND_SPHERES>(blob, L, ro, rd, time, t, prim);
     else if (L.sceneKind == SCENE_KIND_SPHERES_MOTION) walk<SCENE_KIND_SPHERES_MOTION>(blob, L, ro, rd, time, t, prim);
     else walk<SCENE_KIND_GENERAL>(blob, L, ro, rd, time, t, prim);
+    *distance = t;
+    *entity = prim >= 0 && entityOfPrim ? entityOfPrim[prim] : prim;
+    return prim >= 0;
+}
+
+
+// The interval form (rtowProbeNearestHitInterval): Entity.Hit(r, tMin, tMax) through walk_interval.  any: stop at the first accepted hit - *distance and *entity are then
+// that hit's, not the nearest's.  An interval that is not traced (interval_is_traced) is a miss.
+bool probeIntervalHost(const uint8_t* blob, const SceneLayout& L, const int32_t* entityOfPrim, const float origin[3], const float direction[3], float time, float tMin, float tMax,
+                       bool any, float* distance, int* entity)
+{
+    const V3 ro = v3(origin[0], origin[1], origin[2]), rd = v3(direction[0], direction[1], direction[2]);
+    float t = __builtin_inff();
+    int prim = -1;
+    if (interval_is_traced(tMin, tMax)) {
+        if (L.sceneKind == SCENE_KIND_SPHERES) walkInterval<SCENE_KIND_SPHERES>(blob, L, ro, rd, time, tMin, tMax, any, t, prim);
+        else if (L.sceneKind == SCENE_KIND_SPHERES_MOTION) walkInterval<SCENE_KIND_SPHERES_MOTION>(blob, L, ro, rd, time, tMin, tMax, any, t, prim);
+        else walkInterval<SCENE_KIND_GENERAL>(blob, L, ro, rd, time, tMin, tMax, any, t, prim);
+    }
     *distance = t;
     *entity = prim >= 0 && entityOfPrim ? entityOfPrim[prim] : prim;
     return prim >= 0;

@@ -13,35 +13,11 @@
 //    tests/test_trace_rays_isa.py prints the counts);
 //  * the view form maps a wave's 64 lanes to an 8 x 8 pixel tile, so that the rays of a wave stay together in the tree; its rays are the sample kernel's REGEN expressions with
 //    SubPixelJitter off and LensRadius 0.
-#include "rtow_walk.hip.h"
-
-#include "rtow_bvh.h"
+#include "rtow_trace_lanes.hip.h"
 
 namespace rtow {
 
 namespace {
-
-constexpr int kTraceBlock = 256;
-constexpr int kTraceStackEntries = RTOW_STACK_CAPACITY + 2;
-
-// a lane's column of the workgroup's [entry][lane] LDS array
-struct LdsStack {
-    int* col;
-    int sp;
-    __device__ __forceinline__ bool push(int x)
-    {
-        if (sp >= kTraceStackEntries) return false;
-        col[sp * kTraceBlock] = x;
-        sp++;
-        return true;
-    }
-    __device__ __forceinline__ int pop() { sp--; return col[sp * kTraceBlock]; }
-    __device__ __forceinline__ bool empty() const { return sp == 0; }
-};
-
-// a ray at a 4-byte aligned address (a caller may pass a view that starts anywhere in an allocation)
-struct __attribute__((packed, aligned(4))) Ray8 { float ox, oy, oz, time, dx, dy, dz, pad; };
-static_assert(sizeof(Ray8) == sizeof(RtowRay), "RtowRay is eight floats");
 
 struct TraceArgs {
     const uint8_t* blob;            // device image of the scene
@@ -70,24 +46,6 @@ __device__ __forceinline__ V3 view_direction(const RtowView& VW, int cx, int cy,
     return normalize(v3(viewLLC.x + u * viewH.x + v * viewV.x,
                         viewLLC.y + u * viewH.y + v * viewV.y,
                         viewLLC.z + u * viewH.z + v * viewV.z));
-}
-
-// HitRecord.Normal of primitive `prim` hit at distance t: what the sample kernel's HIT stage derives (RT/Entity.cs:62-66) - the winner's test once more for its entity-space
-// normal, rotated out and normalised; spheres of the sphere kinds: r.GetPoint(t) / radius, normalised
-template <int BASE>
-__device__ __forceinline__ V3 hit_normal(const SceneRefs& sc, const SceneLayout& L, int prim, V3 ro, V3 rd, float rtime, float t)
-{
-    if (BASE >= SCENE_KIND_GENERAL) {
-        const unsigned mi = *reinterpret_cast<const unsigned*>(section<false>(sc, L.matIndexOffset) + (uint32_t)prim * 4u);
-        float t2; V3 nLocal; float4 rq;
-        (void)general_hit<false>(sc, L, prim, mi >> kPrimTypeShift, ro, rd, rtime, 0.0f, t2, nLocal, rq);
-        return normalize(rotate(rq, nLocal));
-    }
-    V3 c; float radius;
-    sphere_at<false, BASE == SCENE_KIND_SPHERES_MOTION>(sc, L, prim, rtime, c, radius);
-    const V3 oc = sub(ro, c);
-    const V3 nLocal = div3(v3(oc.x + t * rd.x, oc.y + t * rd.y, oc.z + t * rd.z), radius);
-    return normalize(nLocal);
 }
 
 template <int BASE, bool VIEW>
@@ -135,7 +93,7 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(TraceArgs A)
             sc.lds = nullptr;
             sc.glob = A.blob;
             sc.ldsNodeCount = 0;
-            n = hit_normal<BASE>(sc, A.layout, prim, ro, rd, rtime, t);
+            n = hit_normal<BASE>(sc, A.layout, prim, ro, rd, rtime, 0.0f, t);
         }
         float* o = A.hits.normal + index * 3u;
         o[0] = n.x; o[1] = n.y; o[2] = n.z;

@@ -1,0 +1,118 @@
+// rtow_trace_interval.hip - rtowTraceRaysIntervalDevice / rtowTraceOcclusionDevice: ray queries with a parameter interval (tMin, tMax) against the resident scene, on the device.
+//
+// The many-ray form of rtowProbeNearestHitInterval: walk_interval (rtow_walk.hip.h, the text the host probe compiles), one lane per ray, on the device image of the scene.
+//  * nearest (ANY = false): distance, the host's entity index and the world-space normal of the nearest Entity.Hit(r, tMin, tMax) - with (0, +inf) what rtow_trace.hip's
+//    ray form stores, bit for bit;
+//  * occlusion (ANY = true): one byte per ray, 1 if any entity has Entity.Hit(r, tMin, tMax) - the walk returns at the first accepted hit.
+// A ray whose interval is not traced (interval_is_traced: 0 <= tMin <= tMax, NaN fails) reports a miss / 0 without a walk.
+//
+// Launch shape: rtow_trace.hip's ray form - 256-lane workgroups, one lane per ray, no barrier, no scratch, tree and primitives from HBM / L2, the
+// [entry][lane] LDS stack of rtow_trace_lanes.hip.h (26 x 256 x 4 B).  A lane that has its answer leaves the loop; its wave goes on until its last lane has.
+#include "rtow_trace_lanes.hip.h"
+
+namespace rtow {
+
+namespace {
+
+// an interval at a 4-byte aligned address
+struct __attribute__((packed, aligned(4))) Interval2 { float tMin, tMax; };
+static_assert(sizeof(Interval2) == sizeof(RtowRayInterval), "RtowRayInterval is two floats");
+
+struct IntervalArgs {
+    const uint8_t* blob;            // device image of the scene
+    const int32_t* entityOfPrim;    // primitive -> the host's entity index, or null (the same number)
+    SceneLayout layout;
+    const RtowRay* rays;
+    const RtowRayInterval* intervals;   // null: (0, +inf) for every ray
+    long long count;
+    RtowHitBuffers hits;            // nearest form
+    uint8_t* occluded;              // occlusion form
+};
+
+template <int BASE, bool ANY>
+__global__ void __launch_bounds__(kTraceBlock) interval_kernel(IntervalArgs A)
+{
+    __shared__ int stackRows[kTraceStackEntries * kTraceBlock];
+    const long long i = (long long)blockIdx.x * kTraceBlock + threadIdx.x;
+    if (i >= A.count) return;
+    const size_t index = (size_t)i;
+    const Ray8 r = reinterpret_cast<const Ray8*>(A.rays)[index];
+    const V3 ro = v3(r.ox, r.oy, r.oz), rd = v3(r.dx, r.dy, r.dz);
+    float tMin = 0.0f, tMax = __builtin_inff();
+    if (A.intervals) {
+        const Interval2 iv = reinterpret_cast<const Interval2*>(A.intervals)[index];
+        tMin = iv.tMin;
+        tMax = iv.tMax;
+    }
+    float t = __builtin_inff(), rtime = r.time;
+    int prim = -1;
+    if (interval_is_traced(tMin, tMax)) {
+        LdsStack stack;
+        stack.col = stackRows + threadIdx.x;
+        stack.sp = 0;
+        (void)walk_interval<BASE, ANY>(A.blob, A.layout, ro, rd, r.time, tMin, tMax, stack, t, prim, rtime);      // (the launcher refuses a tree deeper than the stack: push cannot fail)
+    }
+    if (ANY) {
+        A.occluded[index] = prim >= 0 ? 1 : 0;
+        return;
+    }
+    if (A.hits.distance) A.hits.distance[index] = t;
+    if (A.hits.entityIndex) A.hits.entityIndex[index] = prim >= 0 && A.entityOfPrim ? A.entityOfPrim[prim] : prim;
+    if (A.hits.normal) {
+        V3 n = v3(0, 0, 0);
+        if (prim >= 0) {
+            SceneRefs sc;
+            sc.lds = nullptr;
+            sc.glob = A.blob;
+            sc.ldsNodeCount = 0;
+            n = hit_normal<BASE>(sc, A.layout, prim, ro, rd, rtime, tMin, t);
+        }
+        float* o = A.hits.normal + index * 3u;
+        o[0] = n.x; o[1] = n.y; o[2] = n.z;
+    }
+}
+
+template <bool ANY>
+hipError_t launch(const IntervalArgs& A, hipStream_t stream)
+{
+    if (A.layout.bvhDepth + 2u > (unsigned)kTraceStackEntries) return hipErrorInvalidValue;      // compileScene builds to RTOW_STACK_CAPACITY: not reachable
+    const unsigned long long blocks = ((unsigned long long)A.count + kTraceBlock - 1) / kTraceBlock;
+    if (blocks == 0ull) return hipSuccess;
+    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)blocks), block(kTraceBlock);
+    if (A.layout.sceneKind == SCENE_KIND_SPHERES) hipLaunchKernelGGL((interval_kernel<SCENE_KIND_SPHERES, ANY>), grid, block, 0, stream, A);
+    else if (A.layout.sceneKind == SCENE_KIND_SPHERES_MOTION) hipLaunchKernelGGL((interval_kernel<SCENE_KIND_SPHERES_MOTION, ANY>), grid, block, 0, stream, A);
+    else hipLaunchKernelGGL((interval_kernel<SCENE_KIND_GENERAL, ANY>), grid, block, 0, stream, A);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launchTraceRaysInterval(const uint8_t* blob, const SceneLayout& layout, const int32_t* entityOfPrim, int64_t count, const RtowRay* rays,
+                                   const RtowRayInterval* intervals, const RtowHitBuffers& hits, hipStream_t stream)
+{
+    IntervalArgs A{};
+    A.blob = blob;
+    A.entityOfPrim = entityOfPrim;
+    A.layout = layout;
+    A.rays = rays;
+    A.intervals = intervals;
+    A.count = count;
+    A.hits = hits;
+    return launch<false>(A, stream);
+}
+
+hipError_t launchTraceOcclusion(const uint8_t* blob, const SceneLayout& layout, int64_t count, const RtowRay* rays, const RtowRayInterval* intervals, uint8_t* occluded,
+                                hipStream_t stream)
+{
+    IntervalArgs A{};
+    A.blob = blob;
+    A.layout = layout;
+    A.rays = rays;
+    A.intervals = intervals;
+    A.count = count;
+    A.occluded = occluded;
+    return launch<true>(A, stream);
+}
+
+}  // namespace rtow

@@ -220,6 +220,61 @@ class Context:
         return self._trace(int(width) * int(height),
                            lambda hits, rays: check(load().rtowTraceViewDevice(self.handle, C.byref(p), C.byref(hits), rays, stream), "rtowTraceViewDevice"), want, want_rays)
 
+    def hit_world_interval(self, origin, direction, time, tmin, tmax):
+        """rtowProbeNearestHitInterval: the nearest Entity.Hit(r, tmin, tmax) of one ray, walked on the host: (hit, distance, entity index); `hit` is the ray's
+        occlusion bit.  An interval that does not satisfy 0 <= tmin <= tmax is a miss."""
+        d, e = C.c_float(), C.c_int32()
+        o3, d3 = abi.Float3(*[float(x) for x in origin]), abi.Float3(*[float(x) for x in direction])
+        check(load().rtowProbeNearestHitInterval(self.handle, C.byref(o3), C.byref(d3), float(time), float(tmin), float(tmax), C.byref(d), C.byref(e)),
+              "rtowProbeNearestHitInterval")
+        return e.value >= 0, d.value, e.value
+
+    def _upload_rays_intervals(self, rays, intervals):
+        """Device copies of `rays` (as for trace_rays) and of `intervals` (abi.RAY_INTERVAL_DTYPE or (n, 2) float32; None: no buffer): (count, rays, intervals or None)"""
+        a = np.ascontiguousarray(rays)
+        if a.dtype != np.dtype(abi.RAY_DTYPE):
+            a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 8)
+        count = int(a.shape[0])
+        iv = None
+        if intervals is not None:
+            iv = np.ascontiguousarray(intervals)
+            if iv.dtype != np.dtype(abi.RAY_INTERVAL_DTYPE):
+                iv = np.ascontiguousarray(iv, dtype=np.float32).reshape(-1, 2)
+            if int(iv.shape[0]) != count:
+                raise ValueError("intervals must hold one (tMin, tMax) pair per ray")
+        dev = DeviceBuffer(self, max(1, count) * C.sizeof(abi.Ray))
+        dev_iv = DeviceBuffer(self, max(1, count) * C.sizeof(abi.RayInterval)) if iv is not None else None
+        if count:
+            dev.upload(a)
+            if dev_iv:
+                dev_iv.upload(iv)
+        return count, dev, dev_iv
+
+    def trace_rays_interval(self, rays, intervals=None, want=("distance", "entityIndex", "normal"), stream=None):
+        """rtowTraceRaysIntervalDevice on host data: the nearest Entity.Hit(r, tMin, tMax) per ray.  `rays` as for trace_rays; `intervals` an array of
+        abi.RAY_INTERVAL_DTYPE (or (n, 2) float32), None = (0, +inf) for every ray (then trace_rays' result).  Returns the arrays of trace_rays."""
+        count, dev, dev_iv = self._upload_rays_intervals(rays, intervals)
+        try:
+            return self._trace(count, lambda hits, _: check(load().rtowTraceRaysIntervalDevice(self.handle, count, dev.handle, dev_iv.handle if dev_iv else None, C.byref(hits),
+                                                                                                stream), "rtowTraceRaysIntervalDevice"), want)
+        finally:
+            for b in (dev, dev_iv):
+                if b:
+                    b.free()
+
+    def trace_occlusion(self, rays, intervals=None, stream=None):
+        """rtowTraceOcclusionDevice on host data: (n,) uint8, 1 where any entity has Entity.Hit(r, tMin, tMax).  Arguments as for trace_rays_interval."""
+        count, dev, dev_iv = self._upload_rays_intervals(rays, intervals)
+        out = DeviceBuffer(self, max(1, count))
+        try:
+            check(load().rtowTraceOcclusionDevice(self.handle, count, dev.handle, dev_iv.handle if dev_iv else None, out.handle, stream), "rtowTraceOcclusionDevice")
+            self.synchronize()
+            return out.download(np.uint8, (count,))
+        finally:
+            for b in (dev, dev_iv, out):
+                if b:
+                    b.free()
+
     def shade_hits(self, rays, entity_index, environment=None, outputs=tuple(abi.SURFACE_OUTPUTS)):
         """rtowShadeHitsDevice on host data: `rays` as for trace_rays, `entity_index` the (n,) int32 "entityIndex" a trace call returned for them; `environment` an
         abi.Environment (None: RTOW_SKY_NONE, a miss's albedo is black).  Returns {"albedo": (n, 3) float32, "emission": (n, 3), "texCoord": (n, 2),

@@ -66,6 +66,9 @@ def load():
     lib.rtowDenoiseDevice.argtypes = [vp, C.POINTER(abi.DenoiseParams), vp, vp, vp, vp, vp, vp]
     lib.rtowTraceRaysDevice.argtypes = [vp, C.c_int32, vp, C.POINTER(abi.HitBuffers), vp]
     lib.rtowTraceViewDevice.argtypes = [vp, C.POINTER(abi.TraceViewParams), C.POINTER(abi.HitBuffers), vp, vp]
+    lib.rtowTraceRaysIntervalDevice.argtypes = [vp, C.c_int32, vp, vp, C.POINTER(abi.HitBuffers), vp]
+    lib.rtowTraceOcclusionDevice.argtypes = [vp, C.c_int32, vp, vp, vp, vp]
+    lib.rtowProbeNearestHitInterval.argtypes = [vp, C.POINTER(abi.Float3), C.POINTER(abi.Float3), C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
     lib.rtowReprojectAccumDevice.argtypes = [vp, C.POINTER(abi.ReprojectParams), vp, C.POINTER(abi.HitBuffers), C.POINTER(abi.HitBuffers),
                                              C.POINTER(abi.AccumBuffers), C.POINTER(abi.AccumBuffers), vp, vp]
     lib.rtowShadeHitsDevice.argtypes = [vp, C.POINTER(abi.ShadeHitsParams), C.c_int32, vp, vp, C.POINTER(abi.SurfaceBuffers), vp]

@@ -1,0 +1,90 @@
+"""CPU: the product's host walk with an interval (csrc/rtow_walk.hip.h: walk_interval, through csrc/rtow_probe.hip: probeIntervalHost - what rtowProbeNearestHitInterval
+runs, and the text the device kernels compile) against the brute-force reference of tests/trace_interval_reference.py, nearest and any-hit, on the scene kinds whose host
+image is complete without a device.  Every ray gets every interval family; no ray is left out of any assertion."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import test_gpu_trace_rays as tr  # noqa: E402  (its ray generators)
+import trace_interval_reference as ir  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SCENES = ["cover", "moving", "twins", "mesh", "coplanar"]
+
+
+@pytest.fixture(scope="module")
+def shim():
+    """built as tests/test_hit_world_oracle.py builds probe_shim.cpp; the shim itself is a host-only hipcc object too (it derives the entities' inverse transforms with the
+    library's own vector helpers, see its header)"""
+    csrc = os.path.join(ROOT, "raytracing-in-one-weekend_amd", "csrc")
+    out_dir = os.path.join(ROOT, "tests", "build")
+    os.makedirs(out_dir, exist_ok=True)
+    so, objs = os.path.join(out_dir, "libinterval_shim.so"), [os.path.join(out_dir, n) for n in ("interval_probe_host.o", "interval_shim_host.o")]
+    host = [os.path.join(csrc, "rtow_probe.hip"), os.path.join(ROOT, "tests", "native", "interval_shim.cpp")]
+    srcs = [os.path.join(csrc, "rtow_bvh.cpp"), os.path.join(csrc, "rtow_reforder.cpp")]
+    deps = srcs + host + [os.path.join(csrc, n) for n in ("rtow_probe.hip", "rtow_walk.hip.h", "rtow_hit_tests.hip.h", "rtow_vecmath.hip.h", "rtow_exactmath.hip.h", "rtow_scene.h", "rtow_kernels.h", "rtow_bvh.h")]
+    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
+        for src, obj in zip(host, objs):
+            subprocess.run(["/opt/rocm/bin/hipcc", "-std=c++17", "-O2", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "--offload-host-only", "-x", "hip", "-c", src, "-o", obj],
+                           check=True, capture_output=True)
+        subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-shared", "-fPIC"] + srcs + objs + ["-o", so], check=True, capture_output=True)
+    lib = C.CDLL(so)
+    fp = C.POINTER(C.c_float)
+    lib.shim_interval_probe.argtypes = [fp, fp, C.c_float, C.c_float, C.c_float, C.c_int, fp, C.POINTER(C.c_int)]
+    lib.shim_nearest_probe.argtypes = [fp, fp, C.c_float, fp, C.POINTER(C.c_int)]
+    return lib
+
+
+def _bits(x):
+    return np.float32(x).view(np.uint32)
+
+
+@pytest.mark.parametrize("name", SCENES)
+def test_the_host_walk_equals_the_brute_force_reference(rt, oracle, shim, name):
+    scene = tr._scene(rt, name)
+    desc = scene.desc()
+    kind = shim.shim_interval_compile(C.byref(desc))
+    assert kind in (0, 1, 2, 6), kind                                                # spheres, moving spheres, general (the shim derives the transforms), triangles
+    ref = ir.IntervalReference(oracle, desc)
+    pairs, times = ir.interval_rays(tr, rt, scene, name)
+    try:
+        cands = ref.rays(pairs, times)                                               # (the reference's own self-check against HitWorld runs here)
+    finally:
+        ref.close()
+    draws = np.random.default_rng(29).random(len(pairs)).astype(np.float32)
+    dist, ent = C.c_float(), C.c_int()
+    seen = {"hit": 0, "miss": 0, "occluded": 0, "clear": 0, "later": 0}
+    for k, ((o, d), t, rc) in enumerate(zip(pairs, times, cands)):
+        o3, d3 = (C.c_float * 3)(*o), (C.c_float * 3)(*d)
+        later = False
+        for fam in ir.FAMILIES:
+            tmin, tmax = ir.family_interval(fam, rc.first, draws[k])
+            want_t, want_set, want_any = rc.query(tmin, tmax)
+            hit = shim.shim_interval_probe(o3, d3, t, tmin, tmax, 0, C.byref(dist), C.byref(ent))
+            assert bool(hit) == want_any == (ent.value >= 0), (name, k, fam)
+            assert _bits(dist.value) == _bits(want_t), (name, k, fam, dist.value, want_t)
+            assert (ent.value in want_set) if want_any else ent.value == -1, (name, k, fam, ent.value, sorted(want_set))
+            if fam == "null":
+                d0, e0 = C.c_float(), C.c_int()
+                shim.shim_nearest_probe(o3, d3, t, C.byref(d0), C.byref(e0))
+                assert _bits(d0.value) == _bits(dist.value) and e0.value == ent.value, (name, k)
+                seen["hit" if want_any else "miss"] += 1
+            if fam in ir.INVALID:
+                assert not hit and np.isposinf(dist.value), (name, k, fam)
+            # any-hit: the bit, and a hit it names is one of the interval's
+            occluded = shim.shim_interval_probe(o3, d3, t, tmin, tmax, 1, C.byref(dist), C.byref(ent))
+            assert bool(occluded) == want_any, (name, k, fam)
+            if fam not in ir.INVALID and fam != "null":
+                seen["occluded" if want_any else "clear"] += 1
+            # an interval that excludes the nearest hit and admits a later one
+            if want_any and np.isfinite(rc.first) and want_t > rc.first and tmin >= rc.first:
+                later = True
+        seen["later"] += later
+    print(name, seen)
+    assert seen["hit"] > 0 and seen["miss"] > 0 and seen["occluded"] > 0 and seen["clear"] > 0, (name, seen)
+    assert seen["later"] >= 50, (name, seen)
