@@ -763,6 +763,73 @@ RTOW_API int rtowReprojectAccumDevice(RtowContext context, const RtowReprojectPa
                                       int32_t* outSource /* device, W*H, or NULL: previous pixel index carried, -1 if none */,
                                       void* stream);
 
+/* ---- from the rendered size to the displayed size: guided upsampling of a scaled-down frame ----
+ * replaces: the raster blit that brings the host's scaled buffer to the screen.  resolutionScaling (UNITY/Raytracer.cs:86, two of the four scenes run at 0.5) makes
+ * bufferSize = ceil(pixelWidth * s) x ceil(pixelHeight * s) (:478-480, :1095-1096), and the frame reaches the camera's size through a texture whose filter is
+ * FilterMode.Point, or Bilinear above 1 (:1123): at 0.5, blocks of 2 x 2 identical pixels.  RTOW_UPSAMPLE_POINT and RTOW_UPSAMPLE_BILINEAR are those two reads on the
+ * float3 colour, before rtowFinalizeDevice.  RTOW_UPSAMPLE_GUIDED is a joint bilateral upsampling (Kopf et al., SIGGRAPH 2007): the bilinear taps weighted by whether
+ * the first hit of the src pixel (rtowTraceViewDevice at srcW x srcH) is the surface the dst pixel sees (rtowTraceViewDevice at dstW x dstH with the SAME RtowView - the
+ * view is in world units, so the denser grid samples the same image rectangle), so silhouettes stay at the displayed resolution; with
+ * RTOW_UPSAMPLE_DEMODULATE_ALBEDO the albedo (rtowShadeHitsDevice at both sizes) is divided out of the taps and the dst pixel's own multiplied back, so texture detail
+ * does too.  A pure function of its buffers: it needs no resident scene, and entity indices are only compared, never used as addresses.
+ * Added after API version 12 without changing it: a host detects the call by its entry point (C#: EntryPointNotFoundException). */
+typedef enum RtowUpsampleMode  { RTOW_UPSAMPLE_POINT = 0, RTOW_UPSAMPLE_BILINEAR = 1, RTOW_UPSAMPLE_GUIDED = 2 } RtowUpsampleMode;
+typedef enum RtowUpsampleFlags { RTOW_UPSAMPLE_MATCH_ENTITY = 1, RTOW_UPSAMPLE_DEMODULATE_ALBEDO = 2 } RtowUpsampleFlags;
+typedef struct RtowUpsampleParams {
+    int32_t srcWidth, srcHeight;   /* the rendered size (the host's bufferSize)                 */
+    int32_t dstWidth, dstHeight;   /* the displayed size (the camera's pixelWidth/Height)       */
+    int32_t mode;                  /* RtowUpsampleMode                                          recommended: RTOW_UPSAMPLE_GUIDED */
+    int32_t normalSharpness;       /* 0..8, as RtowDenoiseParams                                recommended: 0 */
+    float   depthTolerance;        /* >= 0, finite; relative, as RtowReprojectParams            recommended: 0.2 */
+    int32_t flags;                 /* RtowUpsampleFlags      recommended: RTOW_UPSAMPLE_MATCH_ENTITY | RTOW_UPSAMPLE_DEMODULATE_ALBEDO */
+    int32_t reserved;              /* 0 */
+} RtowUpsampleParams;              /* 36 bytes */
+/* The recommended sharpness and tolerance are the best point of a grid (0 / 2 / 4 / 6 x 0.01 / 0.05 / 0.2, both flags set) on the cover scene at resolutionScaling 0.5:
+ * 16 spp at 96 x 54 brought to 192 x 108 against 1024 spp rendered there (tests/test_gpu_upsample.py, profiles/r09_upsample.json).  Squared error over that of the
+ * POINT read, which is what the host shows today: GUIDED 0.62 (0.66 at the starting point 4 / 0.05, 0.73 at 6 / 0.01), BILINEAR 0.70.  At 16 spp the error is mostly
+ * noise, so the point that averages most wins; both flags off leaves 0.61 there and gives up the entity edges.  The cover scene has one albedo per entity, so
+ * DEMODULATE_ALBEDO changes its figures by less than 1e-4 - but only next to MATCH_ENTITY: without it taps cross entities, one surface's albedo is divided out and
+ * another's multiplied back, and the error is 2 to 24 times the POINT read's (likewise BILINEAR with the flag: 60 times).  Set it with MATCH_ENTITY or not at all. */
+/* Numeric specification (float32, in this order; no contraction; `/` correctly rounded; dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z).  Pixel = row * width + col, row 0
+ * at the bottom, in every buffer.
+ *   Position, in integers (int32 holds every term for sizes up to 16384).  For the dst pixel p = (X, Y):
+ *     point pixel:    px = ((2X+1) * srcW) / (2 * dstW), py likewise: the texel a Point filter reads at the pixel centre, floor((X + 0.5) / dstW * srcW); always inside.
+ *     bilinear base:  Nx = (2X+1) * srcW - dstW (may be negative); x0 = floor(Nx / (2 * dstW)) (a floor division: -1 is possible), rx = Nx - x0 * 2 * dstW in
+ *                     [0, 2 * dstW), fx = (float)rx / (float)(2 * dstW); y0, fy likewise.  x1 = x0 + 1, y1 = y0 + 1.
+ *     Tap coordinates outside the image are clamped to its edge (min(max(x, 0), srcW - 1)): the texture's clamp wrap mode.
+ *   Tap colour: c_q = srcColor[q]; with DEMODULATE_ALBEDO per channel c_q = a_q >= 2^-10 ? c_q / a_q : c_q, a = srcAlbedo[q] (the rule of rtowDenoiseDevice).  A tap
+ *     whose c_q (after this) has a non-finite channel is skipped.
+ *   Guide weight g(p, q) (GUIDED; g = 1 in BILINEAR): e, t, n = entityIndex, distance, normal of dstHits at p; e', t', n' of srcHits at q.
+ *     e < 0 (sky):  g = e' < 0 ? 1 : 0.
+ *     otherwise:    g = 0 if e' < 0; g = 0 if MATCH_ENTITY is set and e' != e; g = 0 unless fabs(t' - t) <= depthTolerance * t (NaN fails); else d = dot(n, n'),
+ *                   d = d > 0 ? d : 0, then d = d * d, normalSharpness times, and g = d.
+ *   Stages.  acc and wsum start at +0; a tap whose weight is not > 0 (NaN included) is skipped; skipped taps add nothing.
+ *     A (BILINEAR, GUIDED): the four taps (x0,y0), (x1,y0), (x0,y1), (x1,y1) in this order, w = (bx * by) * g with bx = 1 - fx for x0 and fx for x1, by likewise;
+ *        acc += w * c_q, wsum += w.  If wsum > 0: r = acc / wsum per channel.
+ *     B (GUIDED only, when A ends with wsum not > 0): the twelve outer taps of the 4 x 4 block x0-1 .. x0+2, y0-1 .. y0+2, j outer, i inner, the inner 2 x 2 left out,
+ *        w = g; the same accumulation, the same result.
+ *     C (when no earlier stage answered, and the whole of POINT): outColor[p] = srcColor[py * srcW + px], the three channels bit for bit (non-finite values included), no
+ *        demodulation either way.
+ *     With DEMODULATE_ALBEDO a result of stage A or B is multiplied back: r = a_p >= 2^-10 ? r * a_p : r per channel, a_p = dstAlbedo[p].
+ *   outStage[p] (optional) = 0, 1 or 2: the stage that answered (A, B, C).
+ *   Consequences: with srcW == dstW, srcH == dstH and no demodulation every mode returns srcColor bit for bit wherever the colour is finite (a channel of -0 comes back
+ *   as +0 from stage A) and, in GUIDED, g of the pixel with itself is > 0; GUIDED with guides that are the same everywhere (and g = 1) equals BILINEAR bit for bit.
+ * Validation (RTOW_ERROR_INVALID_VALUE, nothing enqueued): NULL context, params, srcColor or outColor; any size < 1 or > 16384; an unknown mode; normalSharpness
+ * outside 0..8; a negative or non-finite depthTolerance; unknown flag bits, reserved != 0; any flag in POINT mode, MATCH_ENTITY outside GUIDED; GUIDED with a NULL
+ * srcHits or dstHits or a NULL distance, entityIndex or normal in either; DEMODULATE_ALBEDO with a NULL srcAlbedo or dstAlbedo; outColor or outStage overlapping an
+ * input the mode reads, or each other.  Pointers a mode does not read are ignored.
+ * Enqueued on `stream` (NULL = the context's own stream): one launch, one lane per dst pixel, a wave per 8 x 8 dst tile; no allocation, no wait, so the call may be
+ * captured in a graph.  All arrays may start at any 4-byte aligned address, outStage at any address. */
+RTOW_API int rtowUpsampleDevice(RtowContext context, const RtowUpsampleParams* params,
+                                const float* srcColor /* device float3[srcW*srcH]: rtowCombineDevice's or rtowDenoiseDevice's colour */,
+                                const RtowHitBuffers* srcHits /* rtowTraceViewDevice at srcW x srcH: distance, entityIndex, normal (GUIDED) */,
+                                const float* srcAlbedo /* float3[srcW*srcH], DEMODULATE_ALBEDO only */,
+                                const RtowHitBuffers* dstHits /* rtowTraceViewDevice at dstW x dstH with the SAME RtowView (GUIDED) */,
+                                const float* dstAlbedo /* float3[dstW*dstH], DEMODULATE_ALBEDO only */,
+                                float* outColor /* float3[dstW*dstH], for rtowFinalizeDevice */,
+                                uint8_t* outStage /* dstW*dstH bytes or NULL: which stage answered (0 A, 1 B, 2 C) */,
+                                void* stream);
+
 /* dst += src for the four accumulation buffers (device pointers, `pixelCount` elements each).  The reference accumulates
  * successive batches by feeding a batch's outputs to the next one as inputs (UNITY/Raytracer.cs:798-802); when batches run
  * CONCURRENTLY on several GPUs (each from zeroed accumulators, its own Seed) their partial sums are folded with this, in

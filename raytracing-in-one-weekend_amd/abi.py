@@ -224,6 +224,26 @@ class ReprojectParams(C.Structure):
                 ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
+# RtowUpsampleMode
+RTOW_UPSAMPLE_POINT, RTOW_UPSAMPLE_BILINEAR, RTOW_UPSAMPLE_GUIDED = 0, 1, 2
+# RtowUpsampleFlags
+RTOW_UPSAMPLE_MATCH_ENTITY = 1
+RTOW_UPSAMPLE_DEMODULATE_ALBEDO = 2
+# recommended settings of rtowUpsampleDevice (include/rtow.h; sharpness and tolerance are the best point of profiles/upsample_timing.py's grid on
+# tests/test_gpu_upsample.py's quality test, profiles/r09_upsample.json)
+UPSAMPLE_DEFAULT_MODE = RTOW_UPSAMPLE_GUIDED
+UPSAMPLE_DEFAULT_NORMAL_SHARPNESS = 0
+UPSAMPLE_DEFAULT_DEPTH_TOLERANCE = 0.2
+UPSAMPLE_DEFAULT_FLAGS = RTOW_UPSAMPLE_MATCH_ENTITY | RTOW_UPSAMPLE_DEMODULATE_ALBEDO
+UPSAMPLE_MAX_SIZE = 16384
+
+
+class UpsampleParams(C.Structure):
+    """RtowUpsampleParams (36 bytes): src = the rendered size, dst = the displayed size."""
+    _fields_ = [("srcWidth", C.c_int32), ("srcHeight", C.c_int32), ("dstWidth", C.c_int32), ("dstHeight", C.c_int32), ("mode", C.c_int32),
+                ("normalSharpness", C.c_int32), ("depthTolerance", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
 class SurfaceBuffers(C.Structure):
     """RtowSurfaceBuffers (48 bytes): device pointers, any may be NULL (not written), not all six."""
     _fields_ = [("albedo", C.c_void_p), ("emission", C.c_void_p), ("texCoord", C.c_void_p), ("metallicGlossiness", C.c_void_p),
@@ -259,5 +279,5 @@ EXPORTED_SYMBOLS = [
     "rtowHybridPlan", "rtowExchangeAccumDevice", "rtowSampleBatchGroupDevice",
     "rtowCombineFinalizeDevice", "rtowReduceMetricsDeviceAsync", "rtowProbeNearestHit", "rtowSampleBatchChainAdaptiveDevice",
     "rtowDenoiseDevice", "rtowTraceRaysDevice", "rtowTraceViewDevice", "rtowReprojectAccumDevice", "rtowShadeHitsDevice",
-    "rtowTraceRaysIntervalDevice", "rtowTraceOcclusionDevice", "rtowProbeNearestHitInterval",
+    "rtowTraceRaysIntervalDevice", "rtowTraceOcclusionDevice", "rtowProbeNearestHitInterval", "rtowUpsampleDevice",
 ]

@@ -1713,6 +1713,50 @@ RTOW_API int rtowReprojectAccumDevice(RtowContext ctx, const RtowReprojectParams
     return RTOW_SUCCESS;
 }
 
+RTOW_API int rtowUpsampleDevice(RtowContext ctx, const RtowUpsampleParams* params, const float* srcColor, const RtowHitBuffers* srcHits, const float* srcAlbedo,
+                                const RtowHitBuffers* dstHits, const float* dstAlbedo, float* outColor, uint8_t* outStage, void* stream)
+{
+    if (!ctx || !params || !srcColor || !outColor) return RTOW_ERROR_INVALID_VALUE;
+    const RtowUpsampleParams& p = *params;
+    for (const int32_t size : {p.srcWidth, p.srcHeight, p.dstWidth, p.dstHeight})
+        if (size < 1 || size > 16384) return RTOW_ERROR_INVALID_VALUE;
+    if (p.mode != RTOW_UPSAMPLE_POINT && p.mode != RTOW_UPSAMPLE_BILINEAR && p.mode != RTOW_UPSAMPLE_GUIDED) return RTOW_ERROR_INVALID_VALUE;
+    if (p.normalSharpness < 0 || p.normalSharpness > 8 || !(p.depthTolerance >= 0.0f && p.depthTolerance <= FLT_MAX)) return RTOW_ERROR_INVALID_VALUE;      // NaN fails
+    if ((p.flags & ~(int32_t)(RTOW_UPSAMPLE_MATCH_ENTITY | RTOW_UPSAMPLE_DEMODULATE_ALBEDO)) != 0 || p.reserved != 0) return RTOW_ERROR_INVALID_VALUE;
+    const bool guided = p.mode == RTOW_UPSAMPLE_GUIDED, demod = (p.flags & RTOW_UPSAMPLE_DEMODULATE_ALBEDO) != 0;
+    if (p.mode == RTOW_UPSAMPLE_POINT && p.flags != 0) return RTOW_ERROR_INVALID_VALUE;
+    if (!guided && (p.flags & RTOW_UPSAMPLE_MATCH_ENTITY) != 0) return RTOW_ERROR_INVALID_VALUE;
+    if (guided) {
+        if (!srcHits || !dstHits) return RTOW_ERROR_INVALID_VALUE;
+        if (!srcHits->distance || !srcHits->entityIndex || !srcHits->normal || !dstHits->distance || !dstHits->entityIndex || !dstHits->normal) return RTOW_ERROR_INVALID_VALUE;
+    }
+    if (demod && (!srcAlbedo || !dstAlbedo)) return RTOW_ERROR_INVALID_VALUE;
+    // a dst pixel reads src pixels and dst guides of other lanes' neighbourhoods: no byte the pass writes may be one the mode reads, or the other output's
+    const size_t ns = (size_t)p.srcWidth * (size_t)p.srcHeight, nd = (size_t)p.dstWidth * (size_t)p.dstHeight;
+    struct Range { const void* base; size_t bytes; };
+    const Range written[2] = {{outColor, nd * 12}, {outStage, nd}};
+    Range read[9] = {{srcColor, ns * 12}};
+    int reads = 1;
+    if (guided) {
+        read[reads++] = {srcHits->distance, ns * 4}; read[reads++] = {srcHits->entityIndex, ns * 4}; read[reads++] = {srcHits->normal, ns * 12};
+        read[reads++] = {dstHits->distance, nd * 4}; read[reads++] = {dstHits->entityIndex, nd * 4}; read[reads++] = {dstHits->normal, nd * 12};
+    }
+    if (demod) { read[reads++] = {srcAlbedo, ns * 12}; read[reads++] = {dstAlbedo, nd * 12}; }
+    const auto overlap = [](const Range& a, const Range& b) {
+        return a.base && b.base && (uintptr_t)a.base < (uintptr_t)b.base + b.bytes && (uintptr_t)b.base < (uintptr_t)a.base + a.bytes;
+    };
+    for (const Range& w : written)
+        for (int i = 0; i < reads; ++i)
+            if (overlap(w, read[i])) return RTOW_ERROR_INVALID_VALUE;
+    if (overlap(written[0], written[1])) return RTOW_ERROR_INVALID_VALUE;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    const RtowHitBuffers none{};
+    HIP_TRY(ctx, launchUpsample(p, srcColor, guided ? *srcHits : none, srcAlbedo, guided ? *dstHits : none, dstAlbedo, outColor, outStage, s), RTOW_ERROR_LAUNCH_FAILURE);
+    return RTOW_SUCCESS;
+}
+
 RTOW_API int rtowAddAccumDevice(RtowContext ctx, int32_t pixelCount, const RtowAccumBuffers* dst, const RtowAccumBuffers* src, void* stream)
 {
     if (!ctx || !dst || !src || pixelCount <= 0) return RTOW_ERROR_INVALID_VALUE;

@@ -363,6 +363,10 @@ inline ReprojectConstants reprojectConstants(const RtowView& v)
 }
 hipError_t launchReproject(const RtowReprojectParams& p, const ReprojectConstants& k, const RtowRay* rays, const RtowHitBuffers& hits, const RtowHitBuffers& previousHits,
                            const RtowAccumBuffers& previous, const RtowAccumBuffers& out, int32_t* outSource, hipStream_t stream);
+// rtowUpsampleDevice (rtow_upsample.hip): one launch on `stream` (arguments validated by the caller); the hit sets are read in GUIDED mode only, the albedos with
+// RTOW_UPSAMPLE_DEMODULATE_ALBEDO only
+hipError_t launchUpsample(const RtowUpsampleParams& p, const float* srcColor, const RtowHitBuffers& srcHits, const float* srcAlbedo, const RtowHitBuffers& dstHits,
+                          const float* dstAlbedo, float* outColor, uint8_t* outStage, hipStream_t stream);
 // dst[k] += src[k] for the four accumulators (float4 / float3 / float3 / float per pixel) in one launch
 hipError_t launchAddAccum(size_t pixels, float* const dst[4], const float* const src[4], hipStream_t stream);
 // bits of tieBits -> entries of tieRedo (one per marked pixel; `batches` per pixel, batch index in bits 27.., for a batch group)

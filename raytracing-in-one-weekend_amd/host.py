@@ -572,6 +572,34 @@ class ReprojectJob:
         return JobHandle(rc)
 
 
+class UpsampleJob:
+    """rtowUpsampleDevice: a frame rendered at SrcWidth x SrcHeight (the host's bufferSize under resolutionScaling, UNITY/Raytracer.cs:478-480) brought to the displayed
+    DstWidth x DstHeight before FinalizeTexturesJob - what replaces the Point / Bilinear raster blit of the scaled texture (:1123).  Device buffers (or raw device
+    addresses): SrcColor is combine's or the denoiser's float3 colour; Src* / Dst* HitDistance, HitEntityIndex, HitNormal are rtowTraceViewDevice's outputs at the two
+    sizes with the batch's view (GUIDED mode), SrcAlbedo / DstAlbedo rtowShadeHitsDevice's at the two sizes (RTOW_UPSAMPLE_DEMODULATE_ALBEDO); OutputColor receives
+    float3 per dst pixel, OutputStage (optional) one byte per dst pixel: the stage that answered."""
+
+    def __init__(self, context, SrcWidth, SrcHeight, DstWidth, DstHeight, Mode=abi.UPSAMPLE_DEFAULT_MODE, NormalSharpness=abi.UPSAMPLE_DEFAULT_NORMAL_SHARPNESS,
+                 DepthTolerance=abi.UPSAMPLE_DEFAULT_DEPTH_TOLERANCE, Flags=abi.UPSAMPLE_DEFAULT_FLAGS, Reserved=0):
+        self.context, self.SrcWidth, self.SrcHeight, self.DstWidth, self.DstHeight = context, SrcWidth, SrcHeight, DstWidth, DstHeight
+        self.Mode, self.NormalSharpness, self.DepthTolerance, self.Flags, self.Reserved = Mode, NormalSharpness, DepthTolerance, Flags, Reserved
+        self.SrcColor = self.SrcHitDistance = self.SrcHitEntityIndex = self.SrcHitNormal = self.SrcAlbedo = None
+        self.DstHitDistance = self.DstHitEntityIndex = self.DstHitNormal = self.DstAlbedo = None
+        self.OutputColor = self.OutputStage = None
+
+    def params(self):
+        return abi.UpsampleParams(int(self.SrcWidth), int(self.SrcHeight), int(self.DstWidth), int(self.DstHeight), int(self.Mode), int(self.NormalSharpness),
+                                  float(self.DepthTolerance), int(self.Flags), int(self.Reserved))
+
+    def Schedule(self, stream=None):
+        p = self.params()
+        src_hits = abi.HitBuffers(_device_ptr(self.SrcHitDistance), _device_ptr(self.SrcHitEntityIndex), _device_ptr(self.SrcHitNormal))
+        dst_hits = abi.HitBuffers(_device_ptr(self.DstHitDistance), _device_ptr(self.DstHitEntityIndex), _device_ptr(self.DstHitNormal))
+        rc = load().rtowUpsampleDevice(self.context.handle, C.byref(p), _device_ptr(self.SrcColor), C.byref(src_hits), _device_ptr(self.SrcAlbedo), C.byref(dst_hits),
+                                       _device_ptr(self.DstAlbedo), _device_ptr(self.OutputColor), _device_ptr(self.OutputStage), stream)
+        return JobHandle(rc)
+
+
 class ShadeHitsJob:
     """rtowShadeHitsDevice on device buffers (or raw device addresses): Rays / EntityIndex are a trace call's rays and hit entity indices, `Count` elements; the six
     outputs (Albedo, Emission, TexCoord, MetallicGlossiness, MaterialIndex, MaterialInfo) may each stay None (not written), not all.  Environment: the sky a miss takes

@@ -71,6 +71,7 @@ def load():
     lib.rtowProbeNearestHitInterval.argtypes = [vp, C.POINTER(abi.Float3), C.POINTER(abi.Float3), C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
     lib.rtowReprojectAccumDevice.argtypes = [vp, C.POINTER(abi.ReprojectParams), vp, C.POINTER(abi.HitBuffers), C.POINTER(abi.HitBuffers),
                                              C.POINTER(abi.AccumBuffers), C.POINTER(abi.AccumBuffers), vp, vp]
+    lib.rtowUpsampleDevice.argtypes = [vp, C.POINTER(abi.UpsampleParams), vp, C.POINTER(abi.HitBuffers), vp, C.POINTER(abi.HitBuffers), vp, vp, vp, vp]
     lib.rtowShadeHitsDevice.argtypes = [vp, C.POINTER(abi.ShadeHitsParams), C.c_int32, vp, vp, C.POINTER(abi.SurfaceBuffers), vp]
     lib.rtowReduceMetricsDeviceAsync.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp]
     lib.rtowAddAccumDevice.argtypes = [vp, C.c_int32, AB, AB, vp]
