@@ -553,7 +553,7 @@ RTOW_API int rtowTraceViewDevice(RtowContext context, const RtowTraceViewParams*
  * behind the first surface" (the thing behind the glass ball that rtowShadeHitsDevice marks with bit 8 of materialInfo; a second layer for a guide).
  * Added after API version 12 without changing it: a host detects the calls by their entry points (C#: EntryPointNotFoundException). */
 typedef struct RtowRayInterval { float tMin, tMax; } RtowRayInterval;   /* 8 bytes, parameter units of the ray's direction AS STORED */
-/* Numeric specification (float32, no contraction; the walk is csrc/rtow_walk.hip.h: walk_interval, one text for the host and the device):
+/* Numeric specification (float32, no contraction; the walk is csrc/rtow_walk.hip.h: the interval forms of walk, one text for the host and the device):
  *   hit set:   an entity counts for a ray iff the ray passes the entity's own reference box under AxisAlignedBoundingBox.Hit (RT/HitTests.cs:9-21; the test the walk of
  *              rtowTraceRaysDevice applies at its leaves - it knows nothing of the interval) and Entity.Hit(ray, tMin, tMax) is true, per primitive type (RT/HitTests.cs):
  *              Sphere: the near root if tMin < t < tMax (both strict), else the far root under the same test; Rect and Triangle: rejected iff t < tMin || t > tMax (both ends

@@ -853,6 +853,29 @@ int enqueueBatches(RtowContext ctx, int count, const RtowSampleParams* params, c
     return rc;
 }
 
+// What the entry points do once they hold their lock: this thread on the context's device (calls come from a different worker thread each time) and the stream the work
+// goes to (null: the context's)
+int useDevice(RtowContext ctx, void* stream, hipStream_t* s)
+{
+    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
+    *s = stream ? (hipStream_t)stream : ctx->stream;
+    return RTOW_SUCCESS;
+}
+
+// primitive -> the host's entity index (all-triangle scenes number their primitives in leaf order), on the device and on the host; null: the same number
+const int32_t* entityMapDevice(RtowContext ctx) { return ctx->scene.entityOfPrim.empty() ? nullptr : ctx->dEntityOfPrim; }
+const int32_t* entityMapHost(RtowContext ctx) { return ctx->scene.entityOfPrim.empty() ? nullptr : ctx->scene.entityOfPrim.data(); }
+
+// a query has to be asked for at least one of distance / entityIndex / normal
+bool anyHitBuffer(const RtowHitBuffers& h) { return h.distance || h.entityIndex || h.normal; }
+
+// the aliasing checks of the post passes: a caller's buffer, and whether two of them share a byte (a null buffer shares none)
+struct Range { const void* base; size_t bytes; };
+bool overlaps(const Range& a, const Range& b)
+{
+    return a.base && b.base && (uintptr_t)a.base < (uintptr_t)b.base + b.bytes && (uintptr_t)b.base < (uintptr_t)a.base + a.bytes;
+}
+
 // The sample entry points' common start, in this order (the same bad input gets the same code): every batch's params - validateParams, where a trace depth beyond 64
 // is RTOW_ERROR_CAPACITY - each followed by the call's own per-batch check; the four input buffers and, unless `out` is null (groups check theirs per batch), the four
 // output buffers; then the lock, the scene, the device (calls come from a different worker thread each time), the stream (null: the context's) and a clear cancel word.
@@ -870,8 +893,7 @@ int beginSample(RtowContext ctx, std::unique_lock<std::mutex>& lock, int count, 
     if (out && (!out->color || !out->normal || !out->albedo || !out->sampleCountWeight)) return RTOW_ERROR_INVALID_VALUE;
     lock = std::unique_lock<std::mutex>(ctx->mu);
     if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
-    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
-    *s = stream ? (hipStream_t)stream : ctx->stream;
+    RTOW_TRY(useDevice(ctx, stream, s));
     *ctx->hCancel = 0u;
     return RTOW_SUCCESS;
 }
@@ -1497,7 +1519,7 @@ RTOW_API int rtowProbeNearestHit(RtowContext ctx, const RtowFloat3* origin, cons
     const float o[3] = {origin->x, origin->y, origin->z}, d[3] = {direction->x, direction->y, direction->z};
     float t = 0.0f;
     int prim = -1;
-    (void)probeNearestHitHost(ctx->scene.blob.data(), ctx->scene.layout, ctx->scene.entityOfPrim.empty() ? nullptr : ctx->scene.entityOfPrim.data(), o, d, time, &t, &prim);      // no device work: batches in flight are neither waited for nor disturbed
+    (void)probeNearestHitHost(ctx->scene.blob.data(), ctx->scene.layout, entityMapHost(ctx), o, d, time, &t, &prim);      // no device work: batches in flight are neither waited for nor disturbed
     if (distance) *distance = t;
     if (entityIndex) *entityIndex = prim;
     return RTOW_SUCCESS;
@@ -1512,7 +1534,7 @@ RTOW_API int rtowProbeNearestHitInterval(RtowContext ctx, const RtowFloat3* orig
     const float o[3] = {origin->x, origin->y, origin->z}, d[3] = {direction->x, direction->y, direction->z};
     float t = 0.0f;
     int prim = -1;
-    (void)probeIntervalHost(ctx->scene.blob.data(), ctx->scene.layout, ctx->scene.entityOfPrim.empty() ? nullptr : ctx->scene.entityOfPrim.data(), o, d, time, tMin, tMax, false, &t, &prim);
+    (void)probeIntervalHost(ctx->scene.blob.data(), ctx->scene.layout, entityMapHost(ctx), o, d, time, tMin, tMax, false, &t, &prim);
     if (distance) *distance = t;
     if (entityIndex) *entityIndex = prim;
     return RTOW_SUCCESS;
@@ -1521,39 +1543,39 @@ RTOW_API int rtowProbeNearestHitInterval(RtowContext ctx, const RtowFloat3* orig
 RTOW_API int rtowTraceRaysDevice(RtowContext ctx, int32_t count, const RtowRay* rays, const RtowHitBuffers* hits, void* stream)
 {
     if (!ctx || !rays || !hits || count < 0) return RTOW_ERROR_INVALID_VALUE;
-    if (!hits->distance && !hits->entityIndex && !hits->normal) return RTOW_ERROR_INVALID_VALUE;
+    if (!anyHitBuffer(*hits)) return RTOW_ERROR_INVALID_VALUE;
     std::lock_guard<std::mutex> lock(ctx->mu);
     if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
     if (count == 0) return RTOW_SUCCESS;
-    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    HIP_TRY(ctx, launchTraceRays(ctx->dScene, ctx->scene.layout, ctx->scene.entityOfPrim.empty() ? nullptr : ctx->dEntityOfPrim, count, rays, *hits, s), RTOW_ERROR_LAUNCH_FAILURE);
+    hipStream_t s;
+    RTOW_TRY(useDevice(ctx, stream, &s));
+    HIP_TRY(ctx, launchTraceRays(ctx->dScene, ctx->scene.layout, entityMapDevice(ctx), count, rays, *hits, s), RTOW_ERROR_LAUNCH_FAILURE);
     return RTOW_SUCCESS;
 }
 
 RTOW_API int rtowTraceViewDevice(RtowContext ctx, const RtowTraceViewParams* params, const RtowHitBuffers* hits, RtowRay* outRays, void* stream)
 {
     if (!ctx || !params || !hits) return RTOW_ERROR_INVALID_VALUE;
-    if (!hits->distance && !hits->entityIndex && !hits->normal) return RTOW_ERROR_INVALID_VALUE;
+    if (!anyHitBuffer(*hits)) return RTOW_ERROR_INVALID_VALUE;
     if (params->width <= 0 || params->height <= 0 || (int64_t)params->width * params->height > INT32_MAX || params->reserved != 0) return RTOW_ERROR_INVALID_VALUE;
     std::lock_guard<std::mutex> lock(ctx->mu);
     if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
-    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    HIP_TRY(ctx, launchTraceView(ctx->dScene, ctx->scene.layout, ctx->scene.entityOfPrim.empty() ? nullptr : ctx->dEntityOfPrim, *params, *hits, outRays, s), RTOW_ERROR_LAUNCH_FAILURE);
+    hipStream_t s;
+    RTOW_TRY(useDevice(ctx, stream, &s));
+    HIP_TRY(ctx, launchTraceView(ctx->dScene, ctx->scene.layout, entityMapDevice(ctx), *params, *hits, outRays, s), RTOW_ERROR_LAUNCH_FAILURE);
     return RTOW_SUCCESS;
 }
 
 RTOW_API int rtowTraceRaysIntervalDevice(RtowContext ctx, int32_t count, const RtowRay* rays, const RtowRayInterval* intervals, const RtowHitBuffers* hits, void* stream)
 {
     if (!ctx || !rays || !hits || count < 0) return RTOW_ERROR_INVALID_VALUE;
-    if (!hits->distance && !hits->entityIndex && !hits->normal) return RTOW_ERROR_INVALID_VALUE;
+    if (!anyHitBuffer(*hits)) return RTOW_ERROR_INVALID_VALUE;
     std::lock_guard<std::mutex> lock(ctx->mu);
     if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
     if (count == 0) return RTOW_SUCCESS;
-    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    HIP_TRY(ctx, launchTraceRaysInterval(ctx->dScene, ctx->scene.layout, ctx->scene.entityOfPrim.empty() ? nullptr : ctx->dEntityOfPrim, count, rays, intervals, *hits, s),
+    hipStream_t s;
+    RTOW_TRY(useDevice(ctx, stream, &s));
+    HIP_TRY(ctx, launchTraceRaysInterval(ctx->dScene, ctx->scene.layout, entityMapDevice(ctx), count, rays, intervals, *hits, s),
             RTOW_ERROR_LAUNCH_FAILURE);
     return RTOW_SUCCESS;
 }
@@ -1564,8 +1586,8 @@ RTOW_API int rtowTraceOcclusionDevice(RtowContext ctx, int32_t count, const Rtow
     std::lock_guard<std::mutex> lock(ctx->mu);
     if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
     if (count == 0) return RTOW_SUCCESS;
-    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    hipStream_t s;
+    RTOW_TRY(useDevice(ctx, stream, &s));
     HIP_TRY(ctx, launchTraceOcclusion(ctx->dScene, ctx->scene.layout, count, rays, intervals, occluded, s), RTOW_ERROR_LAUNCH_FAILURE);
     return RTOW_SUCCESS;
 }
@@ -1584,8 +1606,8 @@ RTOW_API int rtowShadeHitsDevice(RtowContext ctx, const RtowShadeHitsParams* par
     if (count == 0) return RTOW_SUCCESS;
     const bool mapped = !ctx->scene.entityOfPrim.empty();
     if (mapped && !ctx->dPrimOfEntity) return RTOW_ERROR_INTERNAL;      // (an upload that failed half way: the old scene's description, no map)
-    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    hipStream_t s;
+    RTOW_TRY(useDevice(ctx, stream, &s));
     ShadeScene sc{};
     sc.blob = ctx->dScene;
     sc.layout = ctx->scene.layout;
@@ -1616,8 +1638,8 @@ RTOW_API int rtowReduceMetricsDevice(RtowContext ctx, int32_t pixelCount, const 
     if (!ctx || !diagnostics || !color || !sampleCountWeight || !outMetrics || pixelCount <= 0) return RTOW_ERROR_INVALID_VALUE;
     if (diagnosticsStride != 4 && diagnosticsStride != 16) return RTOW_ERROR_INVALID_VALUE;
     std::lock_guard<std::mutex> lock(ctx->mu);
-    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    hipStream_t s;
+    RTOW_TRY(useDevice(ctx, stream, &s));
     if (ctx->haveMetricsDone) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->evMetricsDone, 0), RTOW_ERROR_LAUNCH_FAILURE);      // an asynchronous reduction may still be folding the partials
     HIP_TRY(ctx, launchReduceMetrics(pixelCount, (const uint8_t*)diagnostics, diagnosticsStride, color, sampleCountWeight, ctx->dPartials, s),
             RTOW_ERROR_LAUNCH_FAILURE);
@@ -1635,8 +1657,8 @@ RTOW_API int rtowCombineDevice(RtowContext ctx, const RtowCombineParams* params,
     if (!ctx || !params || !inColor || !inNormal || !inAlbedo || !outColor || !outNormal || !outAlbedo) return RTOW_ERROR_INVALID_VALUE;
     if (params->width <= 0 || params->height <= 0) return RTOW_ERROR_INVALID_VALUE;
     std::lock_guard<std::mutex> lock(ctx->mu);
-    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    hipStream_t s;
+    RTOW_TRY(useDevice(ctx, stream, &s));
     HIP_TRY(ctx, launchCombine(*params, inColor, inNormal, inAlbedo, outColor, outNormal, outAlbedo, s), RTOW_ERROR_LAUNCH_FAILURE);
     return RTOW_SUCCESS;
 }
@@ -1646,8 +1668,8 @@ RTOW_API int rtowFinalizeDevice(RtowContext ctx, int32_t pixelCount, const float
 {
     if (!ctx || pixelCount <= 0 || !inColor || !inNormal || !inAlbedo || !outColor || !outNormal || !outAlbedo) return RTOW_ERROR_INVALID_VALUE;
     std::lock_guard<std::mutex> lock(ctx->mu);
-    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    hipStream_t s;
+    RTOW_TRY(useDevice(ctx, stream, &s));
     HIP_TRY(ctx, launchFinalize(pixelCount, inColor, inNormal, inAlbedo, outColor, outNormal, outAlbedo, ctx->dByteThresholds, s), RTOW_ERROR_LAUNCH_FAILURE);
     return RTOW_SUCCESS;
 }
@@ -1663,16 +1685,14 @@ RTOW_API int rtowDenoiseDevice(RtowContext ctx, const RtowDenoiseParams* params,
     if ((p.flags & ~(int32_t)RTOW_DENOISE_DEMODULATE_ALBEDO) != 0 || p.reserved != 0) return RTOW_ERROR_INVALID_VALUE;
     if (!scratch && p.iterations > 1) return RTOW_ERROR_INVALID_VALUE;
     // the levels write outColor and scratch while they read the inputs and each other: no byte of a written buffer may be another buffer's
-    const size_t bytes = RTOW_DENOISE_SCRATCH_BYTES(p.width, p.height);
-    const auto overlap = [bytes](const void* a, const void* b) {
-        return a && b && (uintptr_t)a < (uintptr_t)b + bytes && (uintptr_t)b < (uintptr_t)a + bytes;
-    };
+    const size_t bytes = RTOW_DENOISE_SCRATCH_BYTES(p.width, p.height);      // the one length every buffer is checked with
+    const Range out{outColor, bytes}, work{scratch, bytes};
     for (const void* in : {(const void*)inColor, (const void*)inNormal, (const void*)inAlbedo})
-        if (overlap(outColor, in) || overlap(scratch, in)) return RTOW_ERROR_INVALID_VALUE;
-    if (overlap(outColor, scratch)) return RTOW_ERROR_INVALID_VALUE;
+        if (overlaps(out, Range{in, bytes}) || overlaps(work, Range{in, bytes})) return RTOW_ERROR_INVALID_VALUE;
+    if (overlaps(out, work)) return RTOW_ERROR_INVALID_VALUE;
     std::lock_guard<std::mutex> lock(ctx->mu);
-    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    hipStream_t s;
+    RTOW_TRY(useDevice(ctx, stream, &s));
     HIP_TRY(ctx, launchDenoise(p, inColor, inNormal, inAlbedo, (float*)scratch, outColor, s), RTOW_ERROR_LAUNCH_FAILURE);
     return RTOW_SUCCESS;
 }
@@ -1693,22 +1713,18 @@ RTOW_API int rtowReprojectAccumDevice(RtowContext ctx, const RtowReprojectParams
         if (!(d != 0.0f && d >= -FLT_MAX && d <= FLT_MAX)) return RTOW_ERROR_INVALID_VALUE;      // the divisors of the projection
     // every pixel gathers from an arbitrary pixel of the previous frame: no byte the pass writes may be one it gathers from, or another output's
     const size_t n = (size_t)p.width * (size_t)p.height;
-    struct Range { const void* base; size_t bytes; };
     const Range written[5] = {{out->color, n * 16}, {out->normal, n * 12}, {out->albedo, n * 12}, {out->sampleCountWeight, n * 4}, {outSource, n * 4}};
     const Range gathered[6] = {{previous->color, n * 16}, {previous->normal, n * 12}, {previous->albedo, n * 12}, {previous->sampleCountWeight, n * 4},
                                {previousHits->distance, n * 4}, {previousHits->entityIndex, n * 4}};
-    const auto overlap = [](const Range& a, const Range& b) {
-        return a.base && b.base && (uintptr_t)a.base < (uintptr_t)b.base + b.bytes && (uintptr_t)b.base < (uintptr_t)a.base + a.bytes;
-    };
     for (int i = 0; i < 5; ++i) {
         for (const Range& g : gathered)
-            if (overlap(written[i], g)) return RTOW_ERROR_INVALID_VALUE;
+            if (overlaps(written[i], g)) return RTOW_ERROR_INVALID_VALUE;
         for (int j = i + 1; j < 5; ++j)
-            if (overlap(written[i], written[j])) return RTOW_ERROR_INVALID_VALUE;
+            if (overlaps(written[i], written[j])) return RTOW_ERROR_INVALID_VALUE;
     }
     std::lock_guard<std::mutex> lock(ctx->mu);
-    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    hipStream_t s;
+    RTOW_TRY(useDevice(ctx, stream, &s));
     HIP_TRY(ctx, launchReproject(p, k, rays, *hits, *previousHits, *previous, *out, outSource, s), RTOW_ERROR_LAUNCH_FAILURE);
     return RTOW_SUCCESS;
 }
@@ -1733,7 +1749,6 @@ RTOW_API int rtowUpsampleDevice(RtowContext ctx, const RtowUpsampleParams* param
     if (demod && (!srcAlbedo || !dstAlbedo)) return RTOW_ERROR_INVALID_VALUE;
     // a dst pixel reads src pixels and dst guides of other lanes' neighbourhoods: no byte the pass writes may be one the mode reads, or the other output's
     const size_t ns = (size_t)p.srcWidth * (size_t)p.srcHeight, nd = (size_t)p.dstWidth * (size_t)p.dstHeight;
-    struct Range { const void* base; size_t bytes; };
     const Range written[2] = {{outColor, nd * 12}, {outStage, nd}};
     Range read[9] = {{srcColor, ns * 12}};
     int reads = 1;
@@ -1742,16 +1757,13 @@ RTOW_API int rtowUpsampleDevice(RtowContext ctx, const RtowUpsampleParams* param
         read[reads++] = {dstHits->distance, nd * 4}; read[reads++] = {dstHits->entityIndex, nd * 4}; read[reads++] = {dstHits->normal, nd * 12};
     }
     if (demod) { read[reads++] = {srcAlbedo, ns * 12}; read[reads++] = {dstAlbedo, nd * 12}; }
-    const auto overlap = [](const Range& a, const Range& b) {
-        return a.base && b.base && (uintptr_t)a.base < (uintptr_t)b.base + b.bytes && (uintptr_t)b.base < (uintptr_t)a.base + a.bytes;
-    };
     for (const Range& w : written)
         for (int i = 0; i < reads; ++i)
-            if (overlap(w, read[i])) return RTOW_ERROR_INVALID_VALUE;
-    if (overlap(written[0], written[1])) return RTOW_ERROR_INVALID_VALUE;
+            if (overlaps(w, read[i])) return RTOW_ERROR_INVALID_VALUE;
+    if (overlaps(written[0], written[1])) return RTOW_ERROR_INVALID_VALUE;
     std::lock_guard<std::mutex> lock(ctx->mu);
-    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    hipStream_t s;
+    RTOW_TRY(useDevice(ctx, stream, &s));
     const RtowHitBuffers none{};
     HIP_TRY(ctx, launchUpsample(p, srcColor, guided ? *srcHits : none, srcAlbedo, guided ? *dstHits : none, dstAlbedo, outColor, outStage, s), RTOW_ERROR_LAUNCH_FAILURE);
     return RTOW_SUCCESS;
@@ -1763,8 +1775,8 @@ RTOW_API int rtowAddAccumDevice(RtowContext ctx, int32_t pixelCount, const RtowA
     if (!dst->color || !dst->normal || !dst->albedo || !dst->sampleCountWeight || !src->color || !src->normal || !src->albedo || !src->sampleCountWeight)
         return RTOW_ERROR_INVALID_VALUE;
     std::lock_guard<std::mutex> lock(ctx->mu);
-    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    hipStream_t s;
+    RTOW_TRY(useDevice(ctx, stream, &s));
     float* const d[4] = {dst->color, dst->normal, dst->albedo, dst->sampleCountWeight};
     const float* const q[4] = {src->color, src->normal, src->albedo, src->sampleCountWeight};
     HIP_TRY(ctx, launchAddAccum((size_t)pixelCount, d, q, s), RTOW_ERROR_LAUNCH_FAILURE);      // one launch for the four buffers
@@ -1777,8 +1789,8 @@ RTOW_API int rtowCombineFinalizeDevice(RtowContext ctx, const RtowCombineParams*
     if (!ctx || !params || !inColor || !inNormal || !inAlbedo || !outColor || !outNormal || !outAlbedo) return RTOW_ERROR_INVALID_VALUE;
     if (params->width <= 0 || params->height <= 0) return RTOW_ERROR_INVALID_VALUE;
     std::lock_guard<std::mutex> lock(ctx->mu);
-    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    hipStream_t s;
+    RTOW_TRY(useDevice(ctx, stream, &s));
     HIP_TRY(ctx, launchCombineFinalize(*params, inColor, inNormal, inAlbedo, outColor, outNormal, outAlbedo, ctx->dByteThresholds, s), RTOW_ERROR_LAUNCH_FAILURE);
     return RTOW_SUCCESS;
 }
@@ -1789,8 +1801,8 @@ RTOW_API int rtowReduceMetricsDeviceAsync(RtowContext ctx, int32_t pixelCount, c
     if (!ctx || !diagnostics || !color || !sampleCountWeight || !outMetrics || pixelCount <= 0) return RTOW_ERROR_INVALID_VALUE;
     if (diagnosticsStride != 4 && diagnosticsStride != 16) return RTOW_ERROR_INVALID_VALUE;
     std::lock_guard<std::mutex> lock(ctx->mu);
-    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    hipStream_t s;
+    RTOW_TRY(useDevice(ctx, stream, &s));
     // where the record goes: memory registered with rtowRegisterHostBuffer (the device writes it over PCIe), else a device pointer (any HIP allocation)
     RtowMetrics* target = (RtowMetrics*)mappedHost(ctx, outMetrics, sizeof(RtowMetrics));
     if (!target) {

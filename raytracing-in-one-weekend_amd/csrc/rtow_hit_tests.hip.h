@@ -23,6 +23,8 @@ struct SceneRefs {
     const uint8_t* glob;    // full blob in HBM
     uint32_t ldsNodeCount;
 };
+// the scene from global memory only (the probe's host image; the device queries and post passes, which stage nothing)
+__host__ __device__ __forceinline__ SceneRefs global_scene(const uint8_t* blob) { return SceneRefs{nullptr, blob, 0u}; }
 
 template <bool ALL_LDS, bool SPLIT = false>
 __host__ __device__ __forceinline__ void load_node(const SceneRefs& sc, const SceneLayout& L, int idx, float4& q0, float4& q1, float4& q2, int& c0, int& c1)

@@ -375,7 +375,7 @@ hipError_t launchCollectTiedPixels(const unsigned* tieBits, unsigned words, unsi
 // rtowProbeNearestHit (rtow_probe.hip): one ray walked on the host through the scene's host image (derived entity transforms included); false = miss
 bool probeNearestHitHost(const uint8_t* blob, const SceneLayout& L, const int32_t* entityOfPrim, const float origin[3], const float direction[3], float time, float* distance, int* entity);
 
-// rtowProbeNearestHitInterval: the same with Entity.Hit(r, tMin, tMax) (walk_interval); any: the first accepted hit instead of the nearest; an interval that is not traced: a miss
+// rtowProbeNearestHitInterval: the same with Entity.Hit(r, tMin, tMax) (the interval forms of rtow_walk.hip.h's walk); any: the first accepted hit instead of the nearest; an interval that is not traced: a miss
 bool probeIntervalHost(const uint8_t* blob, const SceneLayout& L, const int32_t* entityOfPrim, const float origin[3], const float direction[3], float time, float tMin, float tMax,
                        bool any, float* distance, int* entity);
 

@@ -30,21 +30,18 @@ struct HostStack {
     bool empty() const { return sp == 0; }
 };
 
-template <int BASE>
-void walk(const uint8_t* blob, const SceneLayout& L, V3 ro, V3 rd, float time, float& bestT, int& bestPrim)
+// the walk of rtow_walk.hip.h in the form and for the scene kind that are known at run time only
+template <bool BOUNDED>
+void walkHost(const uint8_t* blob, const SceneLayout& L, V3 ro, V3 rd, float time, float tMin, float tMax, bool any, float& bestT, int& bestPrim)
 {
-    HostStack stack((size_t)L.bvhDepth + 2u);
-    float rtime;
-    (void)walk_nearest<BASE>(blob, L, ro, rd, time, stack, bestT, bestPrim, rtime);
-}
-
-template <int BASE>
-void walkInterval(const uint8_t* blob, const SceneLayout& L, V3 ro, V3 rd, float time, float tMin, float tMax, bool any, float& bestT, int& bestPrim)
-{
-    HostStack stack((size_t)L.bvhDepth + 2u);
-    float rtime;
-    if (any) (void)walk_interval<BASE, true>(blob, L, ro, rd, time, tMin, tMax, stack, bestT, bestPrim, rtime);
-    else (void)walk_interval<BASE, false>(blob, L, ro, rd, time, tMin, tMax, stack, bestT, bestPrim, rtime);
+    for_scene_base(L.sceneKind, [&](auto base) {
+        constexpr int BASE = decltype(base)::value;
+        HostStack stack((size_t)L.bvhDepth + 2u);
+        float rtime;
+        if (!BOUNDED) (void)walk<BASE, WALK_OPEN>(blob, L, ro, rd, time, tMin, tMax, stack, bestT, bestPrim, rtime);
+        else if (any) (void)walk<BASE, WALK_ANY>(blob, L, ro, rd, time, tMin, tMax, stack, bestT, bestPrim, rtime);
+        else (void)walk<BASE, WALK_NEAREST>(blob, L, ro, rd, time, tMin, tMax, stack, bestT, bestPrim, rtime);
+    });
 }
 
 } // namespace
@@ -56,16 +53,14 @@ bool probeNearestHitHost(const uint8_t* blob, const SceneLayout& L, const int32_
     const V3 ro = v3(origin[0], origin[1], origin[2]), rd = v3(direction[0], direction[1], direction[2]);
     float t = __builtin_inff();
     int prim = -1;
-    if (L.sceneKind == SCENE_KIND_SPHERES) walk<SCENE_KIND_SPHERES>(blob, L, ro, rd, time, t, prim);
-    else if (L.sceneKind == SCENE_KIND_SPHERES_MOTION) walk<SCENE_KIND_SPHERES_MOTION>(blob, L, ro, rd, time, t, prim);
-    else walk<SCENE_KIND_GENERAL>(blob, L, ro, rd, time, t, prim);
+    walkHost<false>(blob, L, ro, rd, time, 0.0f, 0.0f, false, t, prim);
     *distance = t;
     *entity = prim >= 0 && entityOfPrim ? entityOfPrim[prim] : prim;
     return prim >= 0;
 }
 
 
-// The interval form (rtowProbeNearestHitInterval): Entity.Hit(r, tMin, tMax) through walk_interval.  any: stop at the first accepted hit - *distance and *entity are then
+// The interval form (rtowProbeNearestHitInterval): Entity.Hit(r, tMin, tMax) through the walk's interval forms.  any: stop at the first accepted hit - *distance and *entity are then
 // that hit's, not the nearest's.  An interval that is not traced (interval_is_traced) is a miss.
 bool probeIntervalHost(const uint8_t* blob, const SceneLayout& L, const int32_t* entityOfPrim, const float origin[3], const float direction[3], float time, float tMin, float tMax,
                        bool any, float* distance, int* entity)
@@ -73,11 +68,7 @@ bool probeIntervalHost(const uint8_t* blob, const SceneLayout& L, const int32_t*
     const V3 ro = v3(origin[0], origin[1], origin[2]), rd = v3(direction[0], direction[1], direction[2]);
     float t = __builtin_inff();
     int prim = -1;
-    if (interval_is_traced(tMin, tMax)) {
-        if (L.sceneKind == SCENE_KIND_SPHERES) walkInterval<SCENE_KIND_SPHERES>(blob, L, ro, rd, time, tMin, tMax, any, t, prim);
-        else if (L.sceneKind == SCENE_KIND_SPHERES_MOTION) walkInterval<SCENE_KIND_SPHERES_MOTION>(blob, L, ro, rd, time, tMin, tMax, any, t, prim);
-        else walkInterval<SCENE_KIND_GENERAL>(blob, L, ro, rd, time, tMin, tMax, any, t, prim);
-    }
+    if (interval_is_traced(tMin, tMax)) walkHost<true>(blob, L, ro, rd, time, tMin, tMax, any, t, prim);
     *distance = t;
     *entity = prim >= 0 && entityOfPrim ? entityOfPrim[prim] : prim;
     return prim >= 0;

@@ -6,17 +6,11 @@
 // previous frame land in a few rows of it; a workgroup is four tiles, and tiles beyond the grid limit are walked by a grid-stride loop.  No LDS, no barrier.
 #include "rtow_kernels.h"
 
-#include "rtow_exactmath.hip.h"
+#include "rtow_vecmath.hip.h"
 
 namespace rtow {
 
 namespace {
-
-// buffers at 4-byte aligned addresses (tightly packed; a caller may pass views that start 4 bytes into an allocation)
-struct __attribute__((packed, aligned(4))) P3 { float x, y, z; };
-struct __attribute__((packed, aligned(4))) P4 { float x, y, z, w; };
-struct __attribute__((packed, aligned(4))) Ray8 { float ox, oy, oz, time, dx, dy, dz, pad; };
-static_assert(sizeof(Ray8) == sizeof(RtowRay), "RtowRay is eight floats");
 
 constexpr int kReprojectBlock = 256;                      // four 8 x 8 tiles
 constexpr unsigned kReprojectMaxBlocks = 4096;            // two rounds of the 2048 workgroups an MI355X holds at 8 waves per SIMD; tile groups beyond this (frames from

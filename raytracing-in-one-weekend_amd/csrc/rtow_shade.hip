@@ -24,10 +24,6 @@ namespace {
 
 constexpr int kShadeBlock = 256;
 
-// a ray at a 4-byte aligned address (a caller may pass a view that starts anywhere in an allocation)
-struct __attribute__((packed, aligned(4))) Ray8 { float ox, oy, oz, time, dx, dy, dz, pad; };
-static_assert(sizeof(Ray8) == sizeof(RtowRay), "RtowRay is eight floats");
-
 struct ShadeArgs {
     const uint8_t* sceneBlob;
     SceneLayout layout;
@@ -67,10 +63,7 @@ __global__ void __launch_bounds__(kShadeBlock) shade_kernel(ShadeArgs A)
     const SceneLayout& L = A.layout;
     const Ray8 r = reinterpret_cast<const Ray8*>(A.rays)[index];
     const V3 ro = v3(r.ox, r.oy, r.oz), rd = v3(r.dx, r.dy, r.dz);
-    SceneRefs sc;
-    sc.lds = nullptr;
-    sc.glob = A.sceneBlob;
-    sc.ldsNodeCount = 0;
+    const SceneRefs sc = global_scene(A.sceneBlob);
 
     // entity -> primitive -> material, each checked before it is an address
     const int32_t e = A.entityIndex[index];

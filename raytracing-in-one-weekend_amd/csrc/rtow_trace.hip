@@ -83,34 +83,14 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(TraceArgs A)
     stack.sp = 0;
     float t, rtime;
     int prim;
-    (void)walk_nearest<BASE>(A.blob, A.layout, ro, rd, time, stack, t, prim, rtime);      // (the launcher refuses a tree deeper than the stack: push cannot fail)
-    if (A.hits.distance) A.hits.distance[index] = t;
-    if (A.hits.entityIndex) A.hits.entityIndex[index] = prim >= 0 && A.entityOfPrim ? A.entityOfPrim[prim] : prim;
-    if (A.hits.normal) {
-        V3 n = v3(0, 0, 0);
-        if (prim >= 0) {
-            SceneRefs sc;
-            sc.lds = nullptr;
-            sc.glob = A.blob;
-            sc.ldsNodeCount = 0;
-            n = hit_normal<BASE>(sc, A.layout, prim, ro, rd, rtime, 0.0f, t);
-        }
-        float* o = A.hits.normal + index * 3u;
-        o[0] = n.x; o[1] = n.y; o[2] = n.z;
-    }
+    (void)walk<BASE, WALK_OPEN>(A.blob, A.layout, ro, rd, time, 0.0f, 0.0f, stack, t, prim, rtime);      // (the launcher refuses a tree deeper than the stack: push cannot fail)
+    store_hit<BASE>(A, index, ro, rd, rtime, 0.0f, t, prim);
 }
 
 template <bool VIEW>
 hipError_t launch(const TraceArgs& A, unsigned long long blocks, hipStream_t stream)
 {
-    if (A.layout.bvhDepth + 2u > (unsigned)kTraceStackEntries) return hipErrorInvalidValue;      // compileScene builds to RTOW_STACK_CAPACITY: not reachable
-    if (blocks == 0ull) return hipSuccess;
-    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)blocks), block(kTraceBlock);
-    if (A.layout.sceneKind == SCENE_KIND_SPHERES) hipLaunchKernelGGL((trace_kernel<SCENE_KIND_SPHERES, VIEW>), grid, block, 0, stream, A);
-    else if (A.layout.sceneKind == SCENE_KIND_SPHERES_MOTION) hipLaunchKernelGGL((trace_kernel<SCENE_KIND_SPHERES_MOTION, VIEW>), grid, block, 0, stream, A);
-    else hipLaunchKernelGGL((trace_kernel<SCENE_KIND_GENERAL, VIEW>), grid, block, 0, stream, A);
-    return hipGetLastError();
+    return launch_query(A.layout, blocks, [&](auto base, dim3 grid, dim3 block) { hipLaunchKernelGGL((trace_kernel<decltype(base)::value, VIEW>), grid, block, 0, stream, A); });
 }
 
 }  // namespace

@@ -1,6 +1,6 @@
 // rtow_trace_interval.hip - rtowTraceRaysIntervalDevice / rtowTraceOcclusionDevice: ray queries with a parameter interval (tMin, tMax) against the resident scene, on the device.
 //
-// The many-ray form of rtowProbeNearestHitInterval: walk_interval (rtow_walk.hip.h, the text the host probe compiles), one lane per ray, on the device image of the scene.
+// The many-ray form of rtowProbeNearestHitInterval: the interval forms of `walk` (rtow_walk.hip.h, the text the host probe compiles), one lane per ray, on the device image of the scene.
 //  * nearest (ANY = false): distance, the host's entity index and the world-space normal of the nearest Entity.Hit(r, tMin, tMax) - with (0, +inf) what rtow_trace.hip's
 //    ray form stores, bit for bit;
 //  * occlusion (ANY = true): one byte per ray, 1 if any entity has Entity.Hit(r, tMin, tMax) - the walk returns at the first accepted hit.
@@ -50,40 +50,20 @@ __global__ void __launch_bounds__(kTraceBlock) interval_kernel(IntervalArgs A)
         LdsStack stack;
         stack.col = stackRows + threadIdx.x;
         stack.sp = 0;
-        (void)walk_interval<BASE, ANY>(A.blob, A.layout, ro, rd, r.time, tMin, tMax, stack, t, prim, rtime);      // (the launcher refuses a tree deeper than the stack: push cannot fail)
+        (void)walk<BASE, ANY ? WALK_ANY : WALK_NEAREST>(A.blob, A.layout, ro, rd, r.time, tMin, tMax, stack, t, prim, rtime);      // (the launcher refuses a tree deeper than the stack: push cannot fail)
     }
     if (ANY) {
         A.occluded[index] = prim >= 0 ? 1 : 0;
         return;
     }
-    if (A.hits.distance) A.hits.distance[index] = t;
-    if (A.hits.entityIndex) A.hits.entityIndex[index] = prim >= 0 && A.entityOfPrim ? A.entityOfPrim[prim] : prim;
-    if (A.hits.normal) {
-        V3 n = v3(0, 0, 0);
-        if (prim >= 0) {
-            SceneRefs sc;
-            sc.lds = nullptr;
-            sc.glob = A.blob;
-            sc.ldsNodeCount = 0;
-            n = hit_normal<BASE>(sc, A.layout, prim, ro, rd, rtime, tMin, t);
-        }
-        float* o = A.hits.normal + index * 3u;
-        o[0] = n.x; o[1] = n.y; o[2] = n.z;
-    }
+    store_hit<BASE>(A, index, ro, rd, rtime, tMin, t, prim);
 }
 
 template <bool ANY>
 hipError_t launch(const IntervalArgs& A, hipStream_t stream)
 {
-    if (A.layout.bvhDepth + 2u > (unsigned)kTraceStackEntries) return hipErrorInvalidValue;      // compileScene builds to RTOW_STACK_CAPACITY: not reachable
-    const unsigned long long blocks = ((unsigned long long)A.count + kTraceBlock - 1) / kTraceBlock;
-    if (blocks == 0ull) return hipSuccess;
-    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)blocks), block(kTraceBlock);
-    if (A.layout.sceneKind == SCENE_KIND_SPHERES) hipLaunchKernelGGL((interval_kernel<SCENE_KIND_SPHERES, ANY>), grid, block, 0, stream, A);
-    else if (A.layout.sceneKind == SCENE_KIND_SPHERES_MOTION) hipLaunchKernelGGL((interval_kernel<SCENE_KIND_SPHERES_MOTION, ANY>), grid, block, 0, stream, A);
-    else hipLaunchKernelGGL((interval_kernel<SCENE_KIND_GENERAL, ANY>), grid, block, 0, stream, A);
-    return hipGetLastError();
+    return launch_query(A.layout, ((unsigned long long)A.count + kTraceBlock - 1) / kTraceBlock,
+                        [&](auto base, dim3 grid, dim3 block) { hipLaunchKernelGGL((interval_kernel<decltype(base)::value, ANY>), grid, block, 0, stream, A); });
 }
 
 }  // namespace

@@ -1,6 +1,6 @@
-// rtow_trace_lanes.hip.h - what one lane of a device ray query needs besides the walk: its column of the workgroup's LDS stack, the ray record at a 4-byte aligned
-// address and the winner's world-space normal.  Shared by rtow_trace.hip (rtowTraceRaysDevice / rtowTraceViewDevice) and rtow_trace_interval.hip
-// (rtowTraceRaysIntervalDevice / rtowTraceOcclusionDevice): one launch shape, DESIGN.md 4.2.
+// rtow_trace_lanes.hip.h - what one lane of a device ray query needs besides the walk: its column of the workgroup's LDS stack, the winner's world-space normal and the
+// store of its result - and the launcher's part that does not depend on the kernel.  Shared by rtow_trace.hip (rtowTraceRaysDevice / rtowTraceViewDevice) and
+// rtow_trace_interval.hip (rtowTraceRaysIntervalDevice / rtowTraceOcclusionDevice): one launch shape, DESIGN.md 4.2.
 #pragma once
 #include "rtow_walk.hip.h"
 
@@ -28,10 +28,6 @@ struct LdsStack {
     __device__ __forceinline__ bool empty() const { return sp == 0; }
 };
 
-// a ray at a 4-byte aligned address (a caller may pass a view that starts anywhere in an allocation)
-struct __attribute__((packed, aligned(4))) Ray8 { float ox, oy, oz, time, dx, dy, dz, pad; };
-static_assert(sizeof(Ray8) == sizeof(RtowRay), "RtowRay is eight floats");
-
 // HitRecord.Normal of primitive `prim` hit at distance t: what the sample kernel's HIT stage derives (RT/Entity.cs:62-66) - the winner's test once more (with the tMin the
 // walk gave it: a sphere's far root or a box's exit face are the winner's only under that tMin) for its entity-space normal, rotated out and normalised; spheres of the
 // sphere kinds: r.GetPoint(t) / radius, normalised
@@ -49,6 +45,33 @@ __device__ __forceinline__ V3 hit_normal(const SceneRefs& sc, const SceneLayout&
     const V3 oc = sub(ro, c);
     const V3 nLocal = div3(v3(oc.x + t * rd.x, oc.y + t * rd.y, oc.z + t * rd.z), radius);
     return normalize(nLocal);
+}
+
+// A lane's result into the caller's buffers A.hits: the distance, the host's entity index (A.entityOfPrim: primitive -> entity, or null for the same number) and the normal
+// of the hit the walk found in A.blob / A.layout under `tMin` (0 for the open form); a miss stores +inf, -1 and a zero normal.  Args: the kernel's argument struct.
+template <int BASE, typename Args>
+__device__ __forceinline__ void store_hit(const Args& A, size_t index, V3 ro, V3 rd, float rtime, float tMin, float t, int prim)
+{
+    if (A.hits.distance) A.hits.distance[index] = t;
+    if (A.hits.entityIndex) A.hits.entityIndex[index] = prim >= 0 && A.entityOfPrim ? A.entityOfPrim[prim] : prim;
+    if (A.hits.normal) {
+        V3 n = v3(0, 0, 0);
+        if (prim >= 0) n = hit_normal<BASE>(global_scene(A.blob), A.layout, prim, ro, rd, rtime, tMin, t);
+        float* o = A.hits.normal + index * 3u;
+        o[0] = n.x; o[1] = n.y; o[2] = n.z;
+    }
+}
+
+// The launch of a query kernel on `blocks` workgroups of kTraceBlock lanes: launchKernel(base, grid, block) launches the unit's kernel for BASE = decltype(base)::value
+template <typename F>
+hipError_t launch_query(const SceneLayout& L, unsigned long long blocks, F&& launchKernel)
+{
+    if (L.bvhDepth + 2u > (unsigned)kTraceStackEntries) return hipErrorInvalidValue;      // compileScene builds to RTOW_STACK_CAPACITY: not reachable
+    if (blocks == 0ull) return hipSuccess;
+    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)blocks), block(kTraceBlock);
+    for_scene_base(L.sceneKind, [&](auto base) { launchKernel(base, grid, block); });
+    return hipGetLastError();
 }
 
 } // namespace

@@ -8,12 +8,12 @@
 // parameters: the POINT and BILINEAR kernels carry no guide loads, and only the DEMODULATE kernels the albedo loads and divisions.
 #include "rtow_kernels.h"
 
+#include "rtow_vecmath.hip.h"
+
 namespace rtow {
 
 namespace {
 
-// buffers at 4-byte aligned addresses (tightly packed float3; a caller may pass views that start 4 bytes into an allocation)
-struct __attribute__((packed, aligned(4))) P3 { float x, y, z; };
 __device__ __forceinline__ P3 ld3(const float* p, size_t index) { return reinterpret_cast<const P3*>(p)[index]; }
 
 constexpr int kUpsampleBlock = 256;                      // four 8 x 8 tiles

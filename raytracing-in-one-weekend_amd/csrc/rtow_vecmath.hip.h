@@ -1,7 +1,8 @@
 // rtow_vecmath.hip.h - the float3 helpers and the exact-math macros of the path's float program: V3 and its operations, normalize / reflect, Unity.Mathematics' min / max /
 // saturate / sign, half -> float, quaternion rotation, the three-way IEEE division.  Each helper spells out the reference's evaluation order (-ffp-contract=off, IEEE
 // division and square root through the exhaustively checked short forms of rtow_exactmath.hip.h).
-// Included by rtow_hit_tests.hip.h and rtow_surface.hip.h (and through them by the sample kernel, the walk and the shade pass) and by rtow_kernels.hip.
+// Included by rtow_hit_tests.hip.h and rtow_surface.hip.h (and through them by the sample kernel, the walk and the shade pass), by rtow_kernels.hip, and by
+// rtow_reproject.hip / rtow_upsample.hip for the packed buffer records at its end.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -92,6 +93,12 @@ __host__ __device__ __forceinline__ V3 rotate(float4 q, V3 v)
     return v3(v.x + q.w * t.x + c.x, v.y + q.w * t.y + c.y, v.z + q.w * t.z + c.z);
 }
 __host__ __device__ __forceinline__ float um_sign(float x) { return (x > 0.0f ? 1.0f : 0.0f) - (x < 0.0f ? 1.0f : 0.0f); }
+
+// the callers' tightly packed buffers at 4-byte aligned addresses (a caller may pass a view that starts anywhere in an allocation): float3, float4 and RtowRay
+struct __attribute__((packed, aligned(4))) P3 { float x, y, z; };
+struct __attribute__((packed, aligned(4))) P4 { float x, y, z, w; };
+struct __attribute__((packed, aligned(4))) Ray8 { float ox, oy, oz, time, dx, dy, dz, pad; };
+static_assert(sizeof(Ray8) == sizeof(RtowRay), "RtowRay is eight floats");
 
 } // namespace
 

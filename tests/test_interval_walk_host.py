@@ -1,4 +1,4 @@
-"""CPU: the product's host walk with an interval (csrc/rtow_walk.hip.h: walk_interval, through csrc/rtow_probe.hip: probeIntervalHost - what rtowProbeNearestHitInterval
+"""CPU: the product's host walk with an interval (csrc/rtow_walk.hip.h: the interval forms of walk, through csrc/rtow_probe.hip: probeIntervalHost - what rtowProbeNearestHitInterval
 runs, and the text the device kernels compile) against the brute-force reference of tests/trace_interval_reference.py, nearest and any-hit, on the scene kinds whose host
 image is complete without a device.  Every ray gets every interval family; no ray is left out of any assertion."""
 import ctypes as C
