@@ -554,8 +554,9 @@ RTOW_API int rtowTraceViewDevice(RtowContext context, const RtowTraceViewParams*
  * Added after API version 12 without changing it: a host detects the calls by their entry points (C#: EntryPointNotFoundException). */
 typedef struct RtowRayInterval { float tMin, tMax; } RtowRayInterval;   /* 8 bytes, parameter units of the ray's direction AS STORED */
 /* Numeric specification (float32, no contraction; the walk is csrc/rtow_walk.hip.h: the interval forms of walk, one text for the host and the device):
- *   hit set:   an entity counts for a ray iff the ray passes the entity's own reference box under AxisAlignedBoundingBox.Hit (RT/HitTests.cs:9-21; the test the walk of
- *              rtowTraceRaysDevice applies at its leaves - it knows nothing of the interval) and Entity.Hit(ray, tMin, tMax) is true, per primitive type (RT/HitTests.cs):
+ *   hit set:   an entity counts for a ray iff the ray passes, under AxisAlignedBoundingBox.Hit (RT/HitTests.cs:9-21; the test the walk of rtowTraceRaysDevice applies at
+ *              its leaves - it knows nothing of the interval), the box of the reference tree's leaf that holds the entity - the entity's own box, except in a leaf forced at
+ *              RtowSceneDesc.maxBvhDepth, where it is the union of that leaf's boxes - and Entity.Hit(ray, tMin, tMax) is true, per primitive type (RT/HitTests.cs):
  *              Sphere: the near root if tMin < t < tMax (both strict), else the far root under the same test; Rect and Triangle: rejected iff t < tMin || t > tMax (both ends
  *              inclusive); Box: the origin is advanced by tMin (origin + direction * tMin), the distance is that ray's plus tMin, rejected iff it is > tMax.  Volume entities
  *              are hit as their hull; moving entities at rays[i].time, as in rtowTraceRaysDevice.  A distance that is not below +INFINITY (the reference's Triangle comparisons

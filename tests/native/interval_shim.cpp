@@ -42,6 +42,9 @@ extern "C" int shim_interval_compile(const RtowSceneDesc* desc)
     return (int)g_scene.layout.sceneKind;
 }
 
+// 1: the scene compiler found one TimeRange on every moving entity and the walk maps the ray time once (csrc/rtow_walk.hip.h); 0: sphere_at clamps per test
+extern "C" int shim_interval_common_time_range() { return (int)g_scene.layout.commonTimeRange; }
+
 static const int32_t* entity_map() { return g_scene.entityOfPrim.empty() ? nullptr : g_scene.entityOfPrim.data(); }
 
 extern "C" int shim_interval_probe(const float* origin, const float* direction, float time, float tMin, float tMax, int any, float* distance, int* entity)

@@ -1,6 +1,11 @@
 """Brute-force reference of the interval ray queries (include/rtow.h: rtowTraceRaysIntervalDevice / rtowTraceOcclusionDevice / rtowProbeNearestHitInterval), made of
-oracle calls only: per ray, the entities e with oracle_kat_aabb_hit(oracle_kat_entity_bounds(e), ray) and oracle_kat_entity_hit(e, ray, time, tMin, tMax); of these the
+oracle calls only: per ray, the entities e with oracle_kat_aabb_hit(gate box of e, ray) and oracle_kat_entity_hit(e, ray, time, tMin, tMax); of these the
 minimum distance, the set of entities at that minimum (by bits) and any-hit.  No tree, no pruning, no tie rule: what every walk of the product must agree with.
+
+The gate box of an entity is the box of the reference tree's leaf that holds it (oracle_kat_leaf_boxes): the entity's own box (oracle_kat_entity_bounds), except in a
+leaf forced at RtowSceneDesc.maxBvhDepth, where it is the union of that leaf's boxes - Raytracer.HitWorld tests every entity of a leaf whose box the ray passes, so a ray
+that lies in a face plane of an entity's own box (and fails that box) still meets the entity through the wider one.  Built at depth 32 no scene of the suite has a forced
+leaf, and the two are the same bits: asserted below.
 
 A float64 slab test, vectorised over the entities and widened so that it can only over-include, thins the entities out before the oracle's own box test decides
 (needed for the meshes).  The module checks itself once per scene: with (0, +inf) its distance bits equal OracleScene.hit_world's on every test ray."""
@@ -53,7 +58,7 @@ def interval_is_traced(tmin, tmax):
 
 
 class RayCandidates:
-    """The entities whose own reference box the ray passes (the interval plays no part in that), ready for any number of intervals."""
+    """The entities whose gate box (the box of their reference leaf) the ray passes (the interval plays no part in that), ready for any number of intervals."""
 
     def __init__(self, ref, origin, direction, time, entities):
         self.ref, self.time, self.entities = ref, float(time), entities
@@ -98,11 +103,15 @@ class IntervalReference:
         self.desc = desc
         self.osc = oracle.OracleScene(desc)
         n = desc.entityCount
-        self.bounds = np.zeros((n, 6), np.float32)
+        self.own_bounds = np.zeros((n, 6), np.float32)                                        # every entity's own box
         out = (C.c_float * 6)()
         for e in range(n):
             assert self.lib.oracle_kat_entity_bounds(C.byref(desc.entities[e]), desc.triangles, desc.triangleCount, out) == 0, e
-            self.bounds[e] = out[:]
+            self.own_bounds[e] = out[:]
+        self.bounds = np.zeros((n, 6), np.float32)                                            # the gate: the box of the reference leaf the entity sits in
+        assert self.lib.oracle_kat_leaf_boxes(C.byref(desc), self.bounds.ctypes.data_as(C.POINTER(C.c_float))) == n
+        if desc.maxBvhDepth in (0, 32):
+            assert np.array_equal(self.bounds.view(np.uint32), self.own_bounds.view(np.uint32)), "a leaf forced at depth 32"
         self._lo, self._hi = self.bounds[:, :3].astype(np.float64), self.bounds[:, 3:].astype(np.float64)
 
     def close(self):
