@@ -323,6 +323,8 @@ typedef enum RtowContextFlags {
     RTOW_CONTEXT_NO_CHAIN_FUSION = 1u << 7,        /* run chained batches (rtowSampleBatchChain*) one launch per batch - what a context does by itself when its same-XCD hand-over
                                                     * litmus fails (rtowCreateContext measures, on the device it runs on, that plain stores + sc1 loads hand data over inside an XCD
                                                     * the way a chained launch relies on; logged at level 4, a failure at level 3).  Same results either way */
+    RTOW_CONTEXT_NODE_IMAGE_64 = 1u << 8,          /* development: keep the 64-byte tree nodes in LDS in the static-sphere kernels that would walk the 80-byte image with sign-ordered
+                                                    * planes (DESIGN.md 4.1 TRAV).  Same results either way */
     RTOW_CONTEXT_NO_THRESHOLD_TUNING = 1u << 6     /* keep the built-in stage thresholds of the scene's kernel kind.  By default a scene that has been asked for 64 samples per pixel
                                                     * since its upload gets three (volume scenes: six) threshold sets measured with 4-sample probes of the batch's own frame, enqueued in front
                                                     * of that batch and timed with events that a LATER call reads - no call waits for them - and the fastest set runs from then on; a re-upload of
@@ -341,7 +343,7 @@ typedef struct RtowContextOptions {
                                      * through the kernels that read the tree from HBM */
     int32_t schedulerTune[9];       /* development: stage thresholds in 64ths of the live lanes (REGEN TRAV TEST HIT SKY VOL; values below 1 mean 1 = any lane), the number of
                                      * candidates at which a box walk hands over to the exact tests (1 .. 7; 0 = the built-in 3), the pixel regrouping (below), and the box-walk slice (node visits
-                                     * per trip; 0 = the built-in value of the scene); all zero = everything built in, thresholds measured per scene.
+                                     * per trip; 0 = the built-in value of the scene; values beyond 65 535 run as 65 535, which no walk reaches); all zero = everything built in, thresholds measured per scene.
                                      * [7], which pixel a ticket stands for, is a knob of its own (setting it says nothing about the thresholds): 0 = the default (3); 1 = a wave's 64 tickets are
                                      * an 8 x 8 tile of the image in row order; 3 = the same tile, its tickets ordered most expensive pixel first by the ray counts of the previous launch
                                      * (a wave's lanes take a chunk's tickets one by one as they finish their previous pixels, so a chunk's expensive pixel should not be its last ticket:

@@ -191,6 +191,7 @@ int buildArgs(RtowContext ctx, const RtowSampleParams* p, const RtowAccumBuffers
     a.layout = ctx->scene.layout;
     a.ldsSceneBytes = ctx->ldsSceneBytes;
     a.ldsNodeCount = ctx->ldsNodeCount;
+    a.ldsNodeImageBytes = ctx->ldsPlan.nodeImageBytes;
     a.ldsStackRows = ctx->ldsPlan.stackRows; a.ldsHistOffset = 0u; a.ldsFrontBytes = ctx->ldsPlan.frontBytes;      // (launches of the generic variants plan again: planHistory)
     a.workCounter = ctx->dWorkCounter;
     a.cancelFlag = useCancelFlag ? ctx->hCancel : nullptr;
@@ -259,7 +260,7 @@ int planHistory(RtowContext ctx, const RtowSampleParams* p, SampleKernelArgs& a)
     if (hw != 32 || a.traceDepth <= kHistoryInRegisters) return RTOW_SUCCESS;
     const LdsPlan plan = planLds(ctx->wideCodes, ctx->scene.layout, (uint32_t)(a.traceDepth - kHistoryInRegisters), ctx->ldsSceneBudget);
     a.ldsStackRows = plan.stackRows; a.ldsHistOffset = plan.histOffset; a.ldsFrontBytes = plan.frontBytes; a.ldsHistRows = plan.histRows;
-    a.ldsSceneBytes = plan.sceneBytes; a.ldsNodeCount = plan.nodeCount;
+    a.ldsSceneBytes = plan.sceneBytes; a.ldsNodeCount = plan.nodeCount; a.ldsNodeImageBytes = plan.nodeImageBytes;      // (0: the deep-path variants keep 64-byte nodes)
     if (plan.histSpillRows) {
         // the rows that do not fit LDS (32-bit stack rows of a deep tree next to a deep trace depth; a scene kept whole in LDS): 2 bytes per lane and row in HBM
         const size_t stride = (size_t)ctx->cuCount * (size_t)kBlockThreads, need = (size_t)plan.histSpillRows * stride * sizeof(unsigned short);
@@ -274,7 +275,7 @@ int planHistory(RtowContext ctx, const RtowSampleParams* p, SampleKernelArgs& a)
 void setSchedulerValues(const RtowContext_t* ctx, const RtowSampleParams* p, SampleKernelArgs& a)
 {
     for (int i = 0; i < 8; i++) a.tune[i] = ctx->tune[i] < 1 ? 1 : ctx->tune[i];
-    a.travSlice = ctx->tune[8] < 1 ? 1 : ctx->tune[8];
+    a.travSlice = travSliceOf(ctx->tune[8]);      // 1 .. 65 535: bit 16 belongs to the launcher (kNodeImageFlag)
     // Lanes that wait for company at a pixel boundary (kernel: A.tune[7]; schedulerTune[7] bits 12 .. 15 override).  Measured (profiles/r06d_pixel_boundaries_in_company.json):
     // worth it only where boundaries are frequent - the reference host's 50 samples per batch: groups +2.5 % with 3 - 4 lanes, the per-sample policies' 16-sample units +1.6 % -
     // (the adaptive {1, 50} schedule +0.5 ... 1 %) and a loss of 1 - 3 % where a pixel takes hundreds of samples (the wait costs more than the shared instructions save):
@@ -1199,7 +1200,12 @@ RTOW_API int rtowUploadScene(RtowContext ctx, const RtowSceneDesc* scene)
     std::lock_guard<std::mutex> sceneLock(ctx->sceneMu);          // rtowProbeNearestHit reads the host image under this lock only
     ctx->scene = std::move(compiled);
     // LDS of a launch: a traversal-stack row per inner level of THIS tree, then the scene image - whole, or the top of the node array (planLds, rtow_kernels.h)
-    ctx->ldsPlan = planLds(wide, ctx->scene.layout, 0u, ctx->ldsSceneBudget);
+    // (static spheres: with the 80-byte node image of the sign-ordered walk when the tree allows it and the image fits next to the whole scene; the variants that walk it are the
+    // launcher's business - launchVariant - the others stage the 64-byte nodes in the same plan)
+    const SceneLayout& sl = ctx->scene.layout;
+    const bool nodeImage = !wide && sl.sceneKind == SCENE_KIND_SPHERES && !(ctx->flags & RTOW_CONTEXT_NODE_IMAGE_64) &&
+                           node_planes_ordered(reinterpret_cast<const GpuNode*>(ctx->scene.blob.data() + sl.nodeOffset), sl.nodeCount, sl.sphereCount > 1u);
+    ctx->ldsPlan = planLds(wide, sl, 0u, ctx->ldsSceneBudget, nodeImage);
     ctx->ldsSceneBytes = ctx->ldsPlan.sceneBytes;
     ctx->ldsNodeCount = ctx->ldsPlan.nodeCount;
     ctx->haveScene = true;
@@ -1218,9 +1224,9 @@ RTOW_API int rtowUploadScene(RtowContext ctx, const RtowSceneDesc* scene)
                 ctx->tunedCandidate = e.winner;
                 ctx->tunedScene = ctx->sceneSerial;
             }
-    logf(ctx, 4, "scene", "%d entities, %u BVH nodes, depth %u, %u bytes (%u in LDS)%s", ctx->scene.entityCount, ctx->scene.layout.nodeCount,
+    logf(ctx, 4, "scene", "%d entities, %u BVH nodes, depth %u, %u bytes (%u in LDS)%s%s", ctx->scene.entityCount, ctx->scene.layout.nodeCount,
          ctx->scene.layout.bvhDepth, ctx->scene.layout.totalBytes, ctx->ldsSceneBytes,
-         ctx->scene.layout.exactTies ? ", exact-tie kernels" : "");
+         ctx->scene.layout.exactTies ? ", exact-tie kernels" : "", ctx->ldsPlan.nodeImageBytes ? ", 80-byte node image" : "");
     return RTOW_SUCCESS;
 }
 
@@ -1308,7 +1314,7 @@ RTOW_API int rtowGetSceneInfo(RtowContext ctx, RtowSceneInfo* info)
     info->materialCount = ctx->scene.materialCount;
     info->bvhNodeCount = (int32_t)ctx->scene.layout.nodeCount;
     info->bvhDepth = (int32_t)ctx->scene.layout.bvhDepth;
-    info->ldsBytesScene = (int32_t)ctx->ldsSceneBytes;
+    info->ldsBytesScene = (int32_t)(ctx->ldsSceneBytes + ctx->ldsPlan.nodeImageBytes);      // with the 80-byte node image where the register-history kernels stage it
     info->sceneInLds = ctx->ldsSceneBytes == ctx->scene.layout.totalBytes ? 1 : 0;
     info->sceneBytesDevice = ctx->scene.layout.totalBytes;
     info->hitSpillBytes = (uint64_t)ctx->hitSpillEntries * (uint64_t)ctx->cuCount * (uint64_t)kBlockThreads * sizeof(uint4);

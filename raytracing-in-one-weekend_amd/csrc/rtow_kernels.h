@@ -30,6 +30,39 @@ constexpr int kHistoryInRegisters = 8;   // path-history codes (one per surface 
 //   [scene image: the whole blob, or the top of the node array]
 // The cover scene's tree is 11 levels deep: 26 KB come back, which is where the reference host's committed traceDepth 32 keeps its path history (48 KB) - rounds 1 - 5 kept it in a
 // 448-byte private segment per lane, cleared per sample: 186 GB of HBM writes per 10-batch launch (profiles/r05_hostdefault_pmc_summary.json).
+// The 80-byte LDS node image of the sign-ordered box walk (rtow_sample_kernel.hip.h, "sign-ordered box walk"): per axis [lo0 lo1][hi0 hi1][lo0 lo1] (24 bytes), three
+// axes, then the two children.  A 16-byte read at axis + 8 returns (hi, lo) pairs, at axis + 0 (lo, hi): the ray's sign picks (near, far) by address.  The image exists in
+// LDS only - the kernel expands the blob's 64-byte nodes while it stages the scene - and only when it fits next to the whole scene (planLds).
+constexpr uint32_t kNodeImageBytes = 80u;
+constexpr uint32_t kNodeImageFlag = 1u << 16;      // SampleKernelArgs.travSlice: the launch stages the 80-byte image (set by the launcher of a variant that has the walk)
+// The slice a launch runs with: RtowContextOptions.schedulerTune[8] is a caller's value, so it is confined to [1, 65 535] here - the one place a slice enters the kernel's
+// arguments (rtow_api.hip setSchedulerValues).  65 535 visits per trip is "never slice" for every tree the 16-bit kernels walk, and a caller's value can neither reach the
+// flag bit nor leave a slice whose low 16 bits are zero (a walk that never advances)
+inline int32_t travSliceOf(int32_t requested) { return requested < 1 ? 1 : requested >= (int32_t)kNodeImageFlag ? (int32_t)kNodeImageFlag - 1 : requested; }
+// ... and what the launcher of a variant WITH the sign-ordered walk hands its kernel: the slice again confined (whatever built the arguments), bit 16 set exactly when this
+// launch's LDS was sized for the image
+inline int32_t travSliceForImage(int32_t slice, bool imageGranted) { return travSliceOf(slice & (int32_t)(kNodeImageFlag - 1u)) | (imageGranted ? (int32_t)kNodeImageFlag : 0); }
+// dwords of a GpuNode (lo.x lo.y lo.z hi.x hi.y hi.z as (child0, child1) pairs, c0, c1, -, -) -> the 20 dwords of the image
+__host__ __device__ inline void node_image(const uint32_t n[16], uint32_t o[20])
+{
+    for (int axis = 0; axis < 3; axis++) {
+        uint32_t* b = o + 6 * axis;
+        b[0] = n[2 * axis]; b[1] = n[2 * axis + 1];
+        b[2] = n[6 + 2 * axis]; b[3] = n[6 + 2 * axis + 1];
+        b[4] = n[2 * axis]; b[5] = n[2 * axis + 1];
+    }
+    o[18] = n[12]; o[19] = n[13];
+}
+// What the sign-ordered walk assumes of a tree: lo <= hi in every plane pair of every child (no NaN either).  True of every tree the scene compiler builds from finite
+// entities - the one-entity scene's placeholder second child (lo = +FLT_MAX, hi = -FLT_MAX) is masked in the kernel and exempt here; a scene that fails keeps 64-byte nodes.
+inline bool node_planes_ordered(const GpuNode* nodes, uint32_t nodeCount, bool twoChildren)
+{
+    for (uint32_t i = 0; i < nodeCount; i++)
+        for (int c = 0; c < (twoChildren ? 2 : 1); c++)
+            if (!(nodes[i].lox[c] <= nodes[i].hix[c] && nodes[i].loy[c] <= nodes[i].hiy[c] && nodes[i].loz[c] <= nodes[i].hiz[c])) return false;
+    return true;
+}
+
 struct LdsPlan {
     uint32_t stackRows;      // >= 1
     uint32_t histOffset;     // byte offset of the history rows (0: none in LDS)
@@ -39,11 +72,14 @@ struct LdsPlan {
     uint32_t sceneBytes;     // bytes of the blob staged behind the queues
     uint32_t nodeCount;      // nodes [0, nodeCount) are LDS resident
     bool allLds;
+    uint32_t nodeImageBytes; // what the 80-byte node image adds to sceneBytes behind the queues (0: the nodes stay 64 bytes)
 };
 // histRowsNeeded = traceDepth - kHistoryInRegisters for the variants that keep codes in rows (else 0).  A scene stays whole in LDS only if ALL the rows fit next to it (the
 // scene-in-LDS kernels carry no code for rows elsewhere: it cost them their freedom from a private segment); otherwise the top of the tree is staged - at least 256 nodes - the
 // history gets the rows that fit, and the rest of the rows live in HBM: paths that deep are rare (2.5 segments on average) and rows are only touched beyond depth 8.
-inline LdsPlan planLds(bool wide, const SceneLayout& L, uint32_t histRowsNeeded, uint32_t budgetOverride)
+// nodeImage: the launch's variant can walk the 80-byte node image (kNodeImageBytes).  It gets it when the scene stays whole in LDS WITH the image (and every history row); a scene
+// that fits whole with 64-byte nodes only keeps them - the image never decides whether a scene is whole.
+inline LdsPlan planLds(bool wide, const SceneLayout& L, uint32_t histRowsNeeded, uint32_t budgetOverride, bool nodeImage = false)
 {
     LdsPlan p{};
     const uint32_t codeBytes = wide ? 4u : 2u, rowBytes = (uint32_t)kBlockThreads * 2u;
@@ -64,6 +100,9 @@ inline LdsPlan planLds(bool wide, const SceneLayout& L, uint32_t histRowsNeeded,
     if (budget > sceneBudget) budget = sceneBudget;
     if (whole) {
         p.sceneBytes = L.totalBytes; p.nodeCount = L.nodeCount; p.allLds = true;
+        const uint64_t growth = (uint64_t)L.nodeCount * (kNodeImageBytes - (uint32_t)sizeof(GpuNode));
+        if (nodeImage && L.nodeOffset == 0u && (uint64_t)L.totalBytes + growth <= sceneBudget && (uint64_t)L.totalBytes + growth + (uint64_t)histRowsNeeded * rowBytes <= (uint64_t)room)
+            p.nodeImageBytes = (uint32_t)growth;
     } else {
         // too large for LDS: stage the top of the (breadth-first) node array, read the rest through L2
         uint32_t nodes = budget / (uint32_t)sizeof(GpuNode);
@@ -299,7 +338,8 @@ struct SampleKernelArgs {
     // pixel boundary before the boundary block runs; bits 8 .. 31 = the float bits (low eight dropped) of the rate - rays per sample done so far - beyond which a pixel's lane stops
     // waiting for company (kernel: HURRY; 0 = none: the launch runs the variants without that code, which read tune[7] as the gate alone)
     int32_t tune[8];
-    int32_t travSlice;
+    int32_t travSlice;                    // node visits per TRAV slice, 1 .. 65 535 (travSliceOf); bit 16 (kNodeImageFlag), set by launchVariant alone: the kernel stages the 80-byte node image
+    uint32_t ldsNodeImageBytes;           // LdsPlan.nodeImageBytes of this launch: LDS the 80-byte node image takes on top of ldsSceneBytes, for the variants that walk it (0: none)
 };
 
 struct KernelInfo {

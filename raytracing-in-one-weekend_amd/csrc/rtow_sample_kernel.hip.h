@@ -63,6 +63,9 @@
 #ifndef RTOW_PINHOLE
 #define RTOW_PINHOLE 1        // 0: A/B build without the pinhole twins (kGeoPinhole)
 #endif
+#ifndef RTOW_SIGNED_WALK
+#define RTOW_SIGNED_WALK 1   // 0: A/B build without the sign-ordered box walk and its 80-byte node image (signed_walk_variant)
+#endif
 #ifndef RTOW_TIE_WATCH
 #define RTOW_TIE_WATCH 1      // 0: A/B build without the nearest-hit tie watch of the sphere kinds
 #endif
@@ -786,6 +789,50 @@ __device__ __noinline__ __attribute__((unused)) float2 reference_counts(const ui
     return make_float2(bh, cc);
 }
 
+// ---- sign-ordered box walk ----
+// The slab test sorts tl = (lo - o) * inv against th = (hi - o) * inv per axis and child: twelve of a visit's min / max.  For a ray whose origin is finite and whose three
+// inv components are finite and not zero the order is known beforehand: lo <= hi (node_planes_ordered, rtow_kernels.h), so lo - o <= hi - o (rounding is monotone), and one
+// finite non-zero factor keeps that order or reverses it by its sign - no NaN can arise (no inf - inf, no 0 x inf).  min(tl, th) is then the product with the plane the
+// sign names, max the other one: the same values up to the sign of a zero, which nothing downstream tells apart (max with +0, <=, <, the near-first swap).
+// The choice costs no select and no load: the LDS image keeps the planes of an axis as [lo0 lo1][hi0 hi1][lo0 lo1] (node_image, rtow_kernels.h), and ONE 16-byte read
+// at axis + 8 * (inv < 0) returns (near0 near1 far0 far1).  Offset 0 of every block is (lo, hi): the generic expressions read the same image.
+// Which kernels carry the visit: static spheres, scene whole in LDS, the reference stream with its history in registers (the headline kernels, 128 VGPRs, nothing spilled).
+// The moving-sphere kernels of the same shape do not: with the visit in, every form tried left them a private segment (two to eight spilled VGPRs, or 36 bytes of dead
+// spill slots: profiles/r10_signed_walk.json), which tests/test_isa_guards.py rules out.  Whether a launch has the image is bit 16 of travSlice, which the walk reads per
+// slice anyway (launchVariant sets it; kNodeImageFlag).
+template <bool ALL_LDS, int KIND, int HW, int DIAG, int NOISE, bool PER_SAMPLE, int GEO>
+constexpr bool signed_walk_variant() { return RTOW_SIGNED_WALK && ALL_LDS && KIND == SCENE_KIND_SPHERES && (HW == 4 || HW == 8) && DIAG == 0 && NOISE == RTOW_NOISE_WHITE && !PER_SAMPLE && GEO == 0; }
+// byte offset of (near, far) inside an axis block: 8 when the ray runs down the axis
+__device__ __forceinline__ uint32_t near_plane_offset(float invAxis) { return (__float_as_uint(invAxis) >> 28) & 8u; }
+// finite, and (inv) not zero: v_cmp_class_f32 masks (-normal -denormal [-0 +0] +denormal +normal)
+__device__ __forceinline__ bool finite_value(float x) { return __builtin_amdgcn_classf(x, 0x1f8); }
+__device__ __forceinline__ bool finite_nonzero(float x) { return __builtin_amdgcn_classf(x, 0x198); }
+// (planes - o) * inv for the two children of an axis with o and inv in ONE register pair oi = (o, inv): the packed operations broadcast the half they need (op_sel), so the
+// walk holds three pairs instead of the six pairs (o, o), (inv, inv) that the vector expressions copy together in front of the loop - what pays for the three offsets
+__device__ __forceinline__ f2 axis_distances(f2 planes, f2 oi)
+{
+    f2 d, t;
+    asm("v_pk_add_f32 %0, %1, %2 op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,1]" : "=v"(d) : "v"(planes), "v"(oi));
+    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(t) : "v"(d), "v"(oi));
+    return t;
+}
+// node `idx` of the 80-byte image: the three axis blocks at the given offsets (0: (lo0 lo1 hi0 hi1)), and the children.  The reads are 8-byte aligned.
+__device__ __forceinline__ void load_node_image(const uint8_t* image, int idx, uint32_t offx, uint32_t offy, uint32_t offz, float4& px, float4& py, float4& pz, int& c0, int& c1)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef __attribute__((address_space(3))) const uint8_t* LdsBytes;
+    typedef float4 PlaneQuad __attribute__((aligned(8)));
+    LdsBytes b = (LdsBytes)image + __umul24((uint32_t)idx, kNodeImageBytes);      // (16-bit node codes: one full-rate multiply-add with the base)
+    px = *(__attribute__((address_space(3))) const PlaneQuad*)(b + offx);
+    py = *(__attribute__((address_space(3))) const PlaneQuad*)(b + 24u + offy);
+    pz = *(__attribute__((address_space(3))) const PlaneQuad*)(b + 48u + offz);
+    const int2 c = *(__attribute__((address_space(3))) const int2*)(b + 72u);
+    c0 = c.x; c1 = c.y;
+#else
+    (void)image; (void)idx; (void)offx; (void)offy; (void)offz; px = py = pz = make_float4(0, 0, 0, 0); c0 = c1 = -1;
+#endif
+}
+
 // Launch geometry of a variant (template parameter GEO): one workgroup of 1024 lanes per CU (four waves per SIMD: the throughput shape; 512- and
 // 256-lane workgroups for launches that own about one pixel per resident lane were built in round 3, measured - a lone wave gains 1.55 x, the machine
 // loses 2.6 x - and removed in round 4); bit 2 = 32-bit traversal-stack / candidate codes (scenes of more than 65 535 entities or tree
@@ -823,6 +870,7 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
     constexpr bool LDS_VIEW = (RTOW_LDS_VIEW & (ALL_LDS ? 1 : 2)) != 0;   // ... or read from an LDS copy (bit 0: kernels with the scene in LDS, bit 1: the others)
     constexpr bool COLD_VIEW __attribute__((unused)) = RTOW_COLD_VIEW && !ALL_LDS && !LDS_VIEW;    // the view's and the sky's launch constants are read on use instead of held in scalar registers (REGEN)
     constexpr bool SPLIT_NODES = !ALL_LDS && !WIDE;      // node loads as ds_read / global_load behind a wave-uniform branch instead of flat loads (load_node)
+    constexpr bool SIGNED_WALK = signed_walk_variant<ALL_LDS, KIND, HW, DIAG, NOISE, PER_SAMPLE, GEO>();      // the sign-ordered visit and the 80-byte node image (above)
     using Code = typename std::conditional<WIDE, unsigned, unsigned short>::type;
     const uint32_t ldsFront = A.ldsFrontBytes;          // this launch's LDS plan (LdsPlan, rtow_kernels.h): where the wave queues start
 
@@ -851,7 +899,21 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
         ldsConst[tid] = *reinterpret_cast<const float*>(ka + from);
     }
 #endif
-    {
+    uint32_t imageGrowth = 0;       // the 80-byte node image (SIGNED_WALK) pushes every other section 16 bytes per node back
+    if (SIGNED_WALK && (A.travSlice & (int)kNodeImageFlag) != 0) {
+        // nodes are the blob's first section: expanded node by node (one per lane and turn), the rest of the blob copied behind the image
+        const uint4* src = reinterpret_cast<const uint4*>(A.sceneBlob);
+        const uint32_t nodes = A.layout.nodeCount, n16 = A.ldsSceneBytes >> 4;
+        imageGrowth = nodes * (kNodeImageBytes - (uint32_t)sizeof(GpuNode));
+        uint4* img = reinterpret_cast<uint4*>(ldsScene);
+        for (uint32_t i = (uint32_t)tid; i < nodes; i += BT) {
+            uint4 in[4] = {src[4u * i], src[4u * i + 1u], src[4u * i + 2u], src[4u * i + 3u]}, out[5];
+            node_image(reinterpret_cast<const uint32_t*>(in), reinterpret_cast<uint32_t*>(out));
+            for (int k = 0; k < 5; k++) img[5u * i + (uint32_t)k] = out[k];
+        }
+        uint4* dst = reinterpret_cast<uint4*>(ldsScene + imageGrowth);
+        for (uint32_t i = 4u * nodes + (uint32_t)tid; i < n16; i += BT) dst[i] = src[i];
+    } else {
         const uint4* src = reinterpret_cast<const uint4*>(A.sceneBlob);
         uint4* dst = reinterpret_cast<uint4*>(ldsScene);
         const uint32_t n16 = A.ldsSceneBytes >> 4;
@@ -860,7 +922,7 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
     __syncthreads();
 
     SceneRefs sc;
-    sc.lds = ldsScene;
+    sc.lds = ldsScene + imageGrowth;      // sections by their blob offsets (with the 80-byte image the nodes are NOT at theirs: loadNode)
     sc.glob = A.sceneBlob;
     sc.ldsNodeCount = A.ldsNodeCount;
     const SceneLayout L = A.layout;
@@ -984,6 +1046,51 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
         }
         smp++;
         st = ST_REGEN;
+    };
+    // ---- node access of the walk and of the camera-ray lists ----
+    // May this wave's walking lanes take the sign-ordered visit?  One ballot (wave-uniform: no divergence inside the loops): the launch has the 80-byte image and every lane
+    // that takes part has a finite origin and three finite non-zero inv components.  Otherwise the whole wave runs the generic expressions.
+    auto signOrderedWave = [&]() -> bool {
+        if (!SIGNED_WALK || (A.travSlice & (int)kNodeImageFlag) == 0) return false;
+        const bool ok = finite_value(ro.x) && finite_value(ro.y) && finite_value(ro.z) && finite_nonzero(inv.x) && finite_nonzero(inv.y) && finite_nonzero(inv.z);
+        return __ballot(!ok) == 0ull;
+    };
+    // a node in the 64-byte layout, whichever image the launch staged
+    auto loadNode = [&](int idx, float4& q0, float4& q1, float4& q2, int& c0, int& c1) {
+        if (SIGNED_WALK && (A.travSlice & (int)kNodeImageFlag) != 0) {
+            float4 px, py, pz;
+            load_node_image(ldsScene, idx, 0u, 0u, 0u, px, py, pz, c0, c1);
+            q0 = make_float4(px.x, px.y, py.x, py.y); q1 = make_float4(pz.x, pz.y, px.z, px.w); q2 = make_float4(py.z, py.w, pz.z, pz.w);
+        } else {
+            load_node<ALL_LDS, SPLIT_NODES>(sc, L, idx, q0, q1, q2, c0, c1);
+        }
+    };
+    // slab distances of both children of a node, for the camera-ray lists - the walk's own expressions: sign-ordered (ordered = signOrderedWave() of this list) or generic
+    // (COPIES, to be kept in step by hand: the generic expressions below = the `else` of `if constexpr (SIGNED_WALK)` in the REGEN list, in the TEST list and in both TRAV
+    // loops; the sign-ordered ones = the first TRAV loop.  Sharing them with the variants without the walk moved those variants' register allocation: HISTORY.md)
+    auto nodeSlabs = [&](int idx, bool ordered, float& tmin0, float& tfar0, float& tmin1, float& tfar1, int& c0, int& c1) {
+        const f2 invx = {inv.x, inv.x}, invy = {inv.y, inv.y}, invz = {inv.z, inv.z};
+        const f2 ox = {ro.x, ro.x}, oy = {ro.y, ro.y}, oz = {ro.z, ro.z};
+        if (SIGNED_WALK && ordered) {
+            float4 px, py, pz;
+            load_node_image(ldsScene, idx, near_plane_offset(inv.x), near_plane_offset(inv.y), near_plane_offset(inv.z), px, py, pz, c0, c1);
+            const f2 oix = {ro.x, inv.x}, oiy = {ro.y, inv.y}, oiz = {ro.z, inv.z};
+            const f2 tnx = axis_distances(f2{px.x, px.y}, oix), tfx = axis_distances(f2{px.z, px.w}, oix);
+            const f2 tny = axis_distances(f2{py.x, py.y}, oiy), tfy = axis_distances(f2{py.z, py.w}, oiy);
+            const f2 tnz = axis_distances(f2{pz.x, pz.y}, oiz), tfz = axis_distances(f2{pz.z, pz.w}, oiz);
+            tmin0 = vmax3(tnx.x, tny.x, vmax(tnz.x, 0.0f)); tfar0 = vmin3(tfx.x, tfy.x, tfz.x);
+            tmin1 = vmax3(tnx.y, tny.y, vmax(tnz.y, 0.0f)); tfar1 = vmin3(tfx.y, tfy.y, tfz.y);
+        } else {
+            float4 q0, q1, q2;
+            loadNode(idx, q0, q1, q2, c0, c1);
+            const f2 tlx = (f2{q0.x, q0.y} - ox) * invx, thx = (f2{q1.z, q1.w} - ox) * invx;
+            const f2 tly = (f2{q0.z, q0.w} - oy) * invy, thy = (f2{q2.x, q2.y} - oy) * invy;
+            const f2 tlz = (f2{q1.x, q1.y} - oz) * invz, thz = (f2{q2.z, q2.w} - oz) * invz;
+            tmin0 = vmax3(vmin(tlx.x, thx.x), vmin(tly.x, thy.x), vmax(vmin(tlz.x, thz.x), 0.0f));
+            tfar0 = vmin3(vmax(tlx.x, thx.x), vmax(tly.x, thy.x), vmax(tlz.x, thz.x));
+            tmin1 = vmax3(vmin(tlx.y, thx.y), vmin(tly.y, thy.y), vmax(vmin(tlz.y, thz.y), 0.0f));
+            tfar1 = vmin3(vmax(tlx.y, thx.y), vmax(tly.y, thy.y), vmax(tlz.y, thz.y));
+        }
     };
     // a new ray segment starts: reset the traversal state
     auto startRay = [&]() {
@@ -1420,21 +1527,28 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
                         // box must not reach that leaf's exact test, whose rounding can report a hit for a far, small sphere it passes closely).
                         const f2 invx = {inv.x, inv.x}, invy = {inv.y, inv.y}, invz = {inv.z, inv.z};
                         const f2 ox = {ro.x, ro.x}, oy = {ro.y, ro.y}, oz = {ro.z, ro.z};
+                        const bool ordered = signOrderedWave();      // (SIGNED_WALK) one ballot per list, not per node
                         cur = -1;
                         for (int k = 0; k < 4; k++) {
                             const unsigned node = WIDE ? (k == 0 ? pcand.x : k == 1 ? pcand.y : k == 2 ? pcand.z : pcand.w)
                                                        : ((k < 2 ? pcand.x >> (16 * k) : pcand.y >> (16 * (k - 2))) & 0xffffu);
                             if (node == (WIDE ? 0xffffffffu : 0xffffu)) break;
-                            float4 q0, q1, q2;
+                            float tmin0, tfar0, tmin1, tfar1;
                             int c0, c1;
-                            load_node<ALL_LDS, SPLIT_NODES>(sc, L, (int)node, q0, q1, q2, c0, c1);
-                            const f2 tlx = (f2{q0.x, q0.y} - ox) * invx, thx = (f2{q1.z, q1.w} - ox) * invx;
-                            const f2 tly = (f2{q0.z, q0.w} - oy) * invy, thy = (f2{q2.x, q2.y} - oy) * invy;
-                            const f2 tlz = (f2{q1.x, q1.y} - oz) * invz, thz = (f2{q2.z, q2.w} - oz) * invz;
-                            const float tmin0 = vmax3(vmin(tlx.x, thx.x), vmin(tly.x, thy.x), vmax(vmin(tlz.x, thz.x), 0.0f));
-                            const float tfar0 = vmin3(vmax(tlx.x, thx.x), vmax(tly.x, thy.x), vmax(tlz.x, thz.x));
-                            const float tmin1 = vmax3(vmin(tlx.y, thx.y), vmin(tly.y, thy.y), vmax(vmin(tlz.y, thz.y), 0.0f));
-                            const float tfar1 = vmin3(vmax(tlx.y, thx.y), vmax(tly.y, thy.y), vmax(tlz.y, thz.y));
+                            if constexpr (SIGNED_WALK) {
+                                nodeSlabs((int)node, ordered, tmin0, tfar0, tmin1, tfar1, c0, c1);
+                            } else {
+                                // (the parent's text for the variants without the walk; twins: nodeSlabs' generic branch, the other list loop, TRAV)
+                                float4 q0, q1, q2;
+                                load_node<ALL_LDS, SPLIT_NODES>(sc, L, (int)node, q0, q1, q2, c0, c1);
+                                const f2 tlx = (f2{q0.x, q0.y} - ox) * invx, thx = (f2{q1.z, q1.w} - ox) * invx;
+                                const f2 tly = (f2{q0.z, q0.w} - oy) * invy, thy = (f2{q2.x, q2.y} - oy) * invy;
+                                const f2 tlz = (f2{q1.x, q1.y} - oz) * invz, thz = (f2{q2.z, q2.w} - oz) * invz;
+                                tmin0 = vmax3(vmin(tlx.x, thx.x), vmin(tly.x, thy.x), vmax(vmin(tlz.x, thz.x), 0.0f));
+                                tfar0 = vmin3(vmax(tlx.x, thx.x), vmax(tly.x, thy.x), vmax(tlz.x, thz.x));
+                                tmin1 = vmax3(vmin(tlx.y, thx.y), vmin(tly.y, thy.y), vmax(vmin(tlz.y, thz.y), 0.0f));
+                                tfar1 = vmin3(vmax(tlx.y, thx.y), vmax(tly.y, thy.y), vmax(tlz.y, thz.y));
+                            }
                             const bool leaf0 = c0 < 0 && tmin0 < tfar0;                        // AxisAlignedBoundingBox.Hit on the entity's own box
                             const bool leaf1 = c1 < 0 && tmin1 < tfar1 && twoChildren;
                             if (FULL_DIAG && !refDiag) boundsHits += (leaf0 ? 1.0f : 0.0f) + (leaf1 ? 1.0f : 0.0f);
@@ -1457,7 +1571,7 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
             if (st == ST_TRAV) {
                 const f2 invx = {inv.x, inv.x}, invy = {inv.y, inv.y}, invz = {inv.z, inv.z};
                 const f2 ox = {ro.x, ro.x}, oy = {ro.y, ro.y}, oz = {ro.z, ro.z};
-                int budget = A.travSlice;
+                int budget = SIGNED_WALK ? A.travSlice & (int)(kNodeImageFlag - 1u) : A.travSlice;
                 // Pruning bound.  A subtree whose box the ray enters beyond the nearest hit so far cannot hold a nearer one - but it can hold an
                 // EQUAL one: the twin of the sphere that set `best`.  The two distances come from different float programs (slab entry of the
                 // twin's box against the quadratic's root), and where the ray meets the sphere at a point that touches its box they differ by
@@ -1476,53 +1590,131 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
                 // 250 k-triangle mesh 1.84 / 1.90 / 1.98 / 1.96 / 1.84 (gpurun_out/r03bb; "1" = the 7 of before in that run's encoding)
                 // (volume scenes keep every hit of a ray and prune nothing: their lists fill up as before)
                 const int candExit = VOLUMES ? kCandCapacity - 2 : (A.tune[6] < kCandCapacity - 1 ? A.tune[6] : kCandCapacity - 1) - 1;
-                while (budget > 0 && cur >= 0 && nc <= candExit) {
-                    budget--;
-                    STAT_ADD(3, (threadIdx.x & 63) == __builtin_ctzll(__ballot(1)) ? 1 : 0);
-                    STAT_LANES(4);
-                    float4 q0, q1, q2;
-                    int c0, c1;
-                    load_node<ALL_LDS, SPLIT_NODES>(sc, L, cur, q0, q1, q2, c0, c1);
-                    const int spm1 = sp > 0 ? sp - 1 : 0;
-                    const int popped = (int)stack[spm1 * BT];
-                    // q0 = (lo0.x lo1.x lo0.y lo1.y)  q1 = (lo0.z lo1.z hi0.x hi1.x)  q2 = (hi0.y hi1.y hi0.z hi1.z): pairs = (child0, child1)
-                    const f2 tlx = (f2{q0.x, q0.y} - ox) * invx, thx = (f2{q1.z, q1.w} - ox) * invx;
-                    const f2 tly = (f2{q0.z, q0.w} - oy) * invy, thy = (f2{q2.x, q2.y} - oy) * invy;
-                    const f2 tlz = (f2{q1.x, q1.y} - oz) * invz, thz = (f2{q2.z, q2.w} - oz) * invz;
-                    const float tmin0 = vmax3(vmin(tlx.x, thx.x), vmin(tly.x, thy.x), vmax(vmin(tlz.x, thz.x), 0.0f));
-                    const float tfar0 = vmin3(vmax(tlx.x, thx.x), vmax(tly.x, thy.x), vmax(tlz.x, thz.x));
-                    const float tmin1 = vmax3(vmin(tlx.y, thx.y), vmin(tly.y, thy.y), vmax(vmin(tlz.y, thz.y), 0.0f));
-                    const float tfar1 = vmin3(vmax(tlx.y, thx.y), vmax(tly.y, thy.y), vmax(tlz.y, thz.y));
-                    // inner child (padded box): conservative, pruned by the nearest hit so far.  Leaf child (the reference's own entity box):
-                    // AxisAlignedBoundingBox.Hit itself, tMin < tMax (RT/HitTests.cs:15-20) - pruning by `best` on top (<=, so that a tie at
-                    // exactly `best` is still tested) cannot change which hit is nearest.
-                    const bool hit0 = tmin0 <= vmin(tfar0, bestPrune);
-                    const bool hit1 = tmin1 <= vmin(tfar1, bestPrune) && twoChildren;
-                    const bool leaf0 = c0 < 0 && hit0 && tmin0 < tfar0, leaf1 = c1 < 0 && hit1 && tmin1 < tfar1;
-                    if (FULL_DIAG && !refDiag) boundsHits += ((c0 < 0 ? leaf0 : hit0) ? 1.0f : 0.0f) + ((c1 < 0 ? leaf1 : hit1) ? 1.0f : 0.0f);
-                    cand[nc * BT] = (Code)~c0;
-                    nc += leaf0 ? 1 : 0;
-                    cand[nc * BT] = (Code)~c1;
-                    nc += leaf1 ? 1 : 0;
-                    if (PREFETCH_TRI) {
-                        // the listed triangle's record is on its way while the walk goes on; both leaves of one parent are neighbours in leaf order
-                        if (leaf0) prefetch_sector(sc.glob, L.triHotOffset + (uint32_t)~c0 * (uint32_t)sizeof(GpuTriHot), ldsDump);
-                        if (leaf1) prefetch_sector(sc.glob, L.triHotOffset + (uint32_t)~c1 * (uint32_t)sizeof(GpuTriHot), ldsDump);
+                if constexpr (SIGNED_WALK) {
+                    // (finishVisit = the tail of the loop in the `else` below, which is the parent's text for the variants without the walk: two copies to keep in step)
+                    // the rest of a visit once the four slab distances are known: pruning, leaf test, candidate and stack stores, near child first
+                    auto finishVisit = [&](float tmin0, float tfar0, float tmin1, float tfar1, int c0, int c1, int popped, int spm1) {
+                        // inner child (padded box): conservative, pruned by the nearest hit so far.  Leaf child (the reference's own entity box):
+                        // AxisAlignedBoundingBox.Hit itself, tMin < tMax (RT/HitTests.cs:15-20) - pruning by `best` on top (<=, so that a tie at
+                        // exactly `best` is still tested) cannot change which hit is nearest.
+                        const bool hit0 = tmin0 <= vmin(tfar0, bestPrune);
+                        const bool hit1 = tmin1 <= vmin(tfar1, bestPrune) && twoChildren;
+                        const bool leaf0 = c0 < 0 && hit0 && tmin0 < tfar0, leaf1 = c1 < 0 && hit1 && tmin1 < tfar1;
+                        if (FULL_DIAG && !refDiag) boundsHits += ((c0 < 0 ? leaf0 : hit0) ? 1.0f : 0.0f) + ((c1 < 0 ? leaf1 : hit1) ? 1.0f : 0.0f);
+                        cand[nc * BT] = (Code)~c0;
+                        nc += leaf0 ? 1 : 0;
+                        cand[nc * BT] = (Code)~c1;
+                        nc += leaf1 ? 1 : 0;
+                        if (PREFETCH_TRI) {
+                            // the listed triangle's record is on its way while the walk goes on; both leaves of one parent are neighbours in leaf order
+                            if (leaf0) prefetch_sector(sc.glob, L.triHotOffset + (uint32_t)~c0 * (uint32_t)sizeof(GpuTriHot), ldsDump);
+                            if (leaf1) prefetch_sector(sc.glob, L.triHotOffset + (uint32_t)~c1 * (uint32_t)sizeof(GpuTriHot), ldsDump);
+                        }
+                        const bool in0 = hit0 && c0 >= 0;
+                        const bool in1 = hit1 && c1 >= 0;
+                        const bool both = in0 && in1;
+                        const bool swap = tmin1 < tmin0;                         // near child first
+                        if (PREFETCH_FAR) {
+                            // every pushed node is visited later (nothing is dropped at the pop): ask for it now
+                            const uint32_t farNode = (uint32_t)(swap ? c0 : c1);
+                            if (both && farNode >= sc.ldsNodeCount) prefetch_sector(sc.glob, L.nodeOffset + farNode * 64u, ldsDump);
+                        }
+                        stack[sp * BT] = (Code)(swap ? c0 : c1);
+                        const int next = both ? (swap ? c1 : c0) : (in0 ? c0 : c1);
+                        const bool any = in0 || in1;
+                        cur = any ? next : (sp > 0 ? popped : -1);
+                        sp = any ? sp + (both ? 1 : 0) : spm1;
+                    };
+                    if (signOrderedWave()) {
+                        // ---- sign-ordered visit (see SIGNED_WALK): near and far planes come out of the 80-byte image by address, nothing is sorted ----
+                        const uint32_t offx = near_plane_offset(inv.x), offy = near_plane_offset(inv.y), offz = near_plane_offset(inv.z);
+                        const f2 oix = {ro.x, inv.x}, oiy = {ro.y, inv.y}, oiz = {ro.z, inv.z};
+                        while (budget > 0 && cur >= 0 && nc <= candExit) {
+                            budget--;
+                            STAT_ADD(3, (threadIdx.x & 63) == __builtin_ctzll(__ballot(1)) ? 1 : 0);
+                            STAT_LANES(4);
+                            float4 px, py, pz;
+                            int c0, c1;
+                            load_node_image(ldsScene, cur, offx, offy, offz, px, py, pz, c0, c1);
+                            const int spm1 = sp > 0 ? sp - 1 : 0;
+                            const int popped = (int)stack[spm1 * BT];
+                            // p = (near0 near1 far0 far1) of the axis
+                            const f2 tnx = axis_distances(f2{px.x, px.y}, oix), tfx = axis_distances(f2{px.z, px.w}, oix);
+                            const f2 tny = axis_distances(f2{py.x, py.y}, oiy), tfy = axis_distances(f2{py.z, py.w}, oiy);
+                            const f2 tnz = axis_distances(f2{pz.x, pz.y}, oiz), tfz = axis_distances(f2{pz.z, pz.w}, oiz);
+                            finishVisit(vmax3(tnx.x, tny.x, vmax(tnz.x, 0.0f)), vmin3(tfx.x, tfy.x, tfz.x), vmax3(tnx.y, tny.y, vmax(tnz.y, 0.0f)), vmin3(tfx.y, tfy.y, tfz.y), c0, c1, popped, spm1);
+                        }
+                    } else {
+                        while (budget > 0 && cur >= 0 && nc <= candExit) {
+                            budget--;
+                            STAT_ADD(3, (threadIdx.x & 63) == __builtin_ctzll(__ballot(1)) ? 1 : 0);
+                            STAT_LANES(4);
+                            float4 q0, q1, q2;
+                            int c0, c1;
+                            loadNode(cur, q0, q1, q2, c0, c1);
+                            const int spm1 = sp > 0 ? sp - 1 : 0;
+                            const int popped = (int)stack[spm1 * BT];
+                            // q0 = (lo0.x lo1.x lo0.y lo1.y)  q1 = (lo0.z lo1.z hi0.x hi1.x)  q2 = (hi0.y hi1.y hi0.z hi1.z): pairs = (child0, child1)
+                            const f2 tlx = (f2{q0.x, q0.y} - ox) * invx, thx = (f2{q1.z, q1.w} - ox) * invx;
+                            const f2 tly = (f2{q0.z, q0.w} - oy) * invy, thy = (f2{q2.x, q2.y} - oy) * invy;
+                            const f2 tlz = (f2{q1.x, q1.y} - oz) * invz, thz = (f2{q2.z, q2.w} - oz) * invz;
+                            const float tmin0 = vmax3(vmin(tlx.x, thx.x), vmin(tly.x, thy.x), vmax(vmin(tlz.x, thz.x), 0.0f));
+                            const float tfar0 = vmin3(vmax(tlx.x, thx.x), vmax(tly.x, thy.x), vmax(tlz.x, thz.x));
+                            const float tmin1 = vmax3(vmin(tlx.y, thx.y), vmin(tly.y, thy.y), vmax(vmin(tlz.y, thz.y), 0.0f));
+                            const float tfar1 = vmin3(vmax(tlx.y, thx.y), vmax(tly.y, thy.y), vmax(tlz.y, thz.y));
+                            finishVisit(tmin0, tfar0, tmin1, tfar1, c0, c1, popped, spm1);
+                        }
                     }
-                    const bool in0 = hit0 && c0 >= 0;
-                    const bool in1 = hit1 && c1 >= 0;
-                    const bool both = in0 && in1;
-                    const bool swap = tmin1 < tmin0;                         // near child first
-                    if (PREFETCH_FAR) {
-                        // every pushed node is visited later (nothing is dropped at the pop): ask for it now
-                        const uint32_t farNode = (uint32_t)(swap ? c0 : c1);
-                        if (both && farNode >= sc.ldsNodeCount) prefetch_sector(sc.glob, L.nodeOffset + farNode * 64u, ldsDump);
+                } else {
+                    // (twin of the generic loop + finishVisit above)
+                    while (budget > 0 && cur >= 0 && nc <= candExit) {
+                        budget--;
+                        STAT_ADD(3, (threadIdx.x & 63) == __builtin_ctzll(__ballot(1)) ? 1 : 0);
+                        STAT_LANES(4);
+                        float4 q0, q1, q2;
+                        int c0, c1;
+                        load_node<ALL_LDS, SPLIT_NODES>(sc, L, cur, q0, q1, q2, c0, c1);
+                        const int spm1 = sp > 0 ? sp - 1 : 0;
+                        const int popped = (int)stack[spm1 * BT];
+                        // q0 = (lo0.x lo1.x lo0.y lo1.y)  q1 = (lo0.z lo1.z hi0.x hi1.x)  q2 = (hi0.y hi1.y hi0.z hi1.z): pairs = (child0, child1)
+                        const f2 tlx = (f2{q0.x, q0.y} - ox) * invx, thx = (f2{q1.z, q1.w} - ox) * invx;
+                        const f2 tly = (f2{q0.z, q0.w} - oy) * invy, thy = (f2{q2.x, q2.y} - oy) * invy;
+                        const f2 tlz = (f2{q1.x, q1.y} - oz) * invz, thz = (f2{q2.z, q2.w} - oz) * invz;
+                        const float tmin0 = vmax3(vmin(tlx.x, thx.x), vmin(tly.x, thy.x), vmax(vmin(tlz.x, thz.x), 0.0f));
+                        const float tfar0 = vmin3(vmax(tlx.x, thx.x), vmax(tly.x, thy.x), vmax(tlz.x, thz.x));
+                        const float tmin1 = vmax3(vmin(tlx.y, thx.y), vmin(tly.y, thy.y), vmax(vmin(tlz.y, thz.y), 0.0f));
+                        const float tfar1 = vmin3(vmax(tlx.y, thx.y), vmax(tly.y, thy.y), vmax(tlz.y, thz.y));
+                        // inner child (padded box): conservative, pruned by the nearest hit so far.  Leaf child (the reference's own entity box):
+                        // AxisAlignedBoundingBox.Hit itself, tMin < tMax (RT/HitTests.cs:15-20) - pruning by `best` on top (<=, so that a tie at
+                        // exactly `best` is still tested) cannot change which hit is nearest.
+                        const bool hit0 = tmin0 <= vmin(tfar0, bestPrune);
+                        const bool hit1 = tmin1 <= vmin(tfar1, bestPrune) && twoChildren;
+                        const bool leaf0 = c0 < 0 && hit0 && tmin0 < tfar0, leaf1 = c1 < 0 && hit1 && tmin1 < tfar1;
+                        if (FULL_DIAG && !refDiag) boundsHits += ((c0 < 0 ? leaf0 : hit0) ? 1.0f : 0.0f) + ((c1 < 0 ? leaf1 : hit1) ? 1.0f : 0.0f);
+                        cand[nc * BT] = (Code)~c0;
+                        nc += leaf0 ? 1 : 0;
+                        cand[nc * BT] = (Code)~c1;
+                        nc += leaf1 ? 1 : 0;
+                        if (PREFETCH_TRI) {
+                            // the listed triangle's record is on its way while the walk goes on; both leaves of one parent are neighbours in leaf order
+                            if (leaf0) prefetch_sector(sc.glob, L.triHotOffset + (uint32_t)~c0 * (uint32_t)sizeof(GpuTriHot), ldsDump);
+                            if (leaf1) prefetch_sector(sc.glob, L.triHotOffset + (uint32_t)~c1 * (uint32_t)sizeof(GpuTriHot), ldsDump);
+                        }
+                        const bool in0 = hit0 && c0 >= 0;
+                        const bool in1 = hit1 && c1 >= 0;
+                        const bool both = in0 && in1;
+                        const bool swap = tmin1 < tmin0;                         // near child first
+                        if (PREFETCH_FAR) {
+                            // every pushed node is visited later (nothing is dropped at the pop): ask for it now
+                            const uint32_t farNode = (uint32_t)(swap ? c0 : c1);
+                            if (both && farNode >= sc.ldsNodeCount) prefetch_sector(sc.glob, L.nodeOffset + farNode * 64u, ldsDump);
+                        }
+                        stack[sp * BT] = (Code)(swap ? c0 : c1);
+                        const int next = both ? (swap ? c1 : c0) : (in0 ? c0 : c1);
+                        const bool any = in0 || in1;
+                        cur = any ? next : (sp > 0 ? popped : -1);
+                        sp = any ? sp + (both ? 1 : 0) : spm1;
                     }
-                    stack[sp * BT] = (Code)(swap ? c0 : c1);
-                    const int next = both ? (swap ? c1 : c0) : (in0 ? c0 : c1);
-                    const bool any = in0 || in1;
-                    cur = any ? next : (sp > 0 ? popped : -1);
-                    sp = any ? sp + (both ? 1 : 0) : spm1;
                 }
                 if (cur < 0 || nc > candExit) {
                     if (nc > 0) st = ST_TEST;      // exact tests pending (walk finished, or the list is full)
@@ -1542,6 +1734,7 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
                         // ---- the rest of a camera ray's long list: as many nodes at a time as the candidate list has room for (see REGEN) ----
                         const f2 invx = {inv.x, inv.x}, invy = {inv.y, inv.y}, invz = {inv.z, inv.z};
                         const f2 ox = {ro.x, ro.x}, oy = {ro.y, ro.y}, oz = {ro.z, ro.z};
+                        const bool ordered = signOrderedWave();      // (SIGNED_WALK) one ballot per list, not per node
                         int k = -2 - cur;
                         cur = -1;
                         for (; k < 8; k++) {
@@ -1549,16 +1742,22 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
                             const unsigned word = k < 6 ? pcand.z : pcand.w;
                             const unsigned node = (word >> (16 * (k & 1))) & 0xffffu;
                             if (node == 0xffffu) break;
-                            float4 q0, q1, q2;
+                            float tmin0, tfar0, tmin1, tfar1;
                             int c0, c1;
-                            load_node<ALL_LDS, SPLIT_NODES>(sc, L, (int)node, q0, q1, q2, c0, c1);
-                            const f2 tlx = (f2{q0.x, q0.y} - ox) * invx, thx = (f2{q1.z, q1.w} - ox) * invx;
-                            const f2 tly = (f2{q0.z, q0.w} - oy) * invy, thy = (f2{q2.x, q2.y} - oy) * invy;
-                            const f2 tlz = (f2{q1.x, q1.y} - oz) * invz, thz = (f2{q2.z, q2.w} - oz) * invz;
-                            const float tmin0 = vmax3(vmin(tlx.x, thx.x), vmin(tly.x, thy.x), vmax(vmin(tlz.x, thz.x), 0.0f));
-                            const float tfar0 = vmin3(vmax(tlx.x, thx.x), vmax(tly.x, thy.x), vmax(tlz.x, thz.x));
-                            const float tmin1 = vmax3(vmin(tlx.y, thx.y), vmin(tly.y, thy.y), vmax(vmin(tlz.y, thz.y), 0.0f));
-                            const float tfar1 = vmin3(vmax(tlx.y, thx.y), vmax(tly.y, thy.y), vmax(tlz.y, thz.y));
+                            if constexpr (SIGNED_WALK) {
+                                nodeSlabs((int)node, ordered, tmin0, tfar0, tmin1, tfar1, c0, c1);
+                            } else {
+                                // (the parent's text for the variants without the walk; twins: nodeSlabs' generic branch, the other list loop, TRAV)
+                                float4 q0, q1, q2;
+                                load_node<ALL_LDS, SPLIT_NODES>(sc, L, (int)node, q0, q1, q2, c0, c1);
+                                const f2 tlx = (f2{q0.x, q0.y} - ox) * invx, thx = (f2{q1.z, q1.w} - ox) * invx;
+                                const f2 tly = (f2{q0.z, q0.w} - oy) * invy, thy = (f2{q2.x, q2.y} - oy) * invy;
+                                const f2 tlz = (f2{q1.x, q1.y} - oz) * invz, thz = (f2{q2.z, q2.w} - oz) * invz;
+                                tmin0 = vmax3(vmin(tlx.x, thx.x), vmin(tly.x, thy.x), vmax(vmin(tlz.x, thz.x), 0.0f));
+                                tfar0 = vmin3(vmax(tlx.x, thx.x), vmax(tly.x, thy.x), vmax(tlz.x, thz.x));
+                                tmin1 = vmax3(vmin(tlx.y, thx.y), vmin(tly.y, thy.y), vmax(vmin(tlz.y, thz.y), 0.0f));
+                                tfar1 = vmin3(vmax(tlx.y, thx.y), vmax(tly.y, thy.y), vmax(tlz.y, thz.y));
+                            }
                             const bool leaf0 = c0 < 0 && tmin0 < tfar0;
                             const bool leaf1 = c1 < 0 && tmin1 < tfar1 && twoChildren;
                             if (FULL_DIAG && !refDiag) boundsHits += (leaf0 ? 1.0f : 0.0f) + (leaf1 ? 1.0f : 0.0f);
@@ -2078,7 +2277,19 @@ template <bool ALL_LDS, int KIND, int HW, int DIAG, int NOISE, bool PER_SAMPLE, 
 hipError_t launchVariant(const SampleKernelArgs& args, int numBlocks, hipStream_t stream)
 {
     auto k = sample_batch_kernel<ALL_LDS, KIND, HW, DIAG, NOISE, PER_SAMPLE, GEO>;
-    const size_t ldsBytes = (size_t)args.ldsFrontBytes + (size_t)kQueueBytes + args.ldsSceneBytes;
+    // The 80-byte node image the plan has room for (LdsPlan.nodeImageBytes) is staged by the variants with the sign-ordered walk only.  They read the grant from bit 16 of
+    // travSlice, so THEIR launches always get a slice of this launcher's making (travSliceForImage): the bit is set exactly when the LDS below is sized for the image and is
+    // clear otherwise, whatever the arguments came in with; the other variants read travSlice as a plain count and get the arguments as they are
+    constexpr bool SIGNED_WALK = signed_walk_variant<ALL_LDS, KIND, HW, DIAG, NOISE, PER_SAMPLE, GEO>();
+    const bool imageGranted = SIGNED_WALK && args.ldsNodeImageBytes != 0u && args.ldsNodeImageBytes == args.layout.nodeCount * (kNodeImageBytes - (uint32_t)sizeof(GpuNode));
+    SampleKernelArgs ownSlice;
+    const SampleKernelArgs* launchArgs = &args;
+    if (SIGNED_WALK) {
+        ownSlice = args;
+        ownSlice.travSlice = travSliceForImage(args.travSlice, imageGranted);
+        launchArgs = &ownSlice;
+    }
+    const size_t ldsBytes = (size_t)args.ldsFrontBytes + (size_t)kQueueBytes + args.ldsSceneBytes + (imageGranted ? args.ldsNodeImageBytes : 0u);
     // the launch's LDS plan must be the plan of THIS variant: history rows where the codes beyond the registers go, a stack row per level of the tree
     if (args.ldsStackRows < 1u || ldsBytes > (size_t)kLdsBytesMax) return hipErrorInvalidValue;
     if (HW == 32 && args.traceDepth > kHistoryInRegisters) {
@@ -2087,7 +2298,7 @@ hipError_t launchVariant(const SampleKernelArgs& args, int numBlocks, hipStream_
     }
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(numBlocks), dim3(geo_block_threads(GEO)), ldsBytes, stream, args);
+    hipLaunchKernelGGL(k, dim3(numBlocks), dim3(geo_block_threads(GEO)), ldsBytes, stream, *launchArgs);
     return hipGetLastError();
 }
 
