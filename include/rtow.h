@@ -833,6 +833,76 @@ RTOW_API int rtowUpsampleDevice(RtowContext context, const RtowUpsampleParams* p
                                 uint8_t* outStage /* dstW*dstH bytes or NULL: which stage answered (0 A, 1 B, 2 C) */,
                                 void* stream);
 
+/* ---- samples where the host wants them: sample batches over a device list of pixels ----
+ * replaces: nothing the reference can do.  Its one sample operator runs SampleBatchJob.Execute for EVERY pixel index of the frame (JOBS/SampleBatchJob.cs:59-164,
+ * scheduled over totalBufferSize at UNITY/Raytracer.cs:729-738); the only per-pixel choices it has are the slice test (:69-70), the adaptive {min, max} count from the
+ * pixel's weight (:118-126) and the one pixel DebugCoordinates names for path drawing (:54, :97; the frame's centre, UNITY/Raytracer.cs:709).  A list launch runs
+ * that same Execute for the pixels of a device list and for no other: the holes rtowReprojectAccumDevice leaves (all 11 floats +0, color.w == 0) next to
+ * neighbours that carry up to maxHistory samples, an editor's render region, one pixel for picking or a bug report.
+ * A pixel list is device memory of 4 + capacity uint32 words:
+ *   words[0]      how many pixels qualified (a builder's total: it may EXCEED capacity; a host reads it later to learn of an overflow)
+ *   words[1..3]   reserved; the builder writes 0
+ *   words[4 + i]  frame pixel index row * W + col, row 0 at the bottom, for i < min(words[0], capacity)
+ * A host may fill a list itself (rtowDeviceCopy).  Frames of a list are limited to W * H <= 2^27: the sample kernel's list entries keep a batch number above bit 27.
+ * Added after API version 12 without changing it: a host detects the calls by their entry points (C#: EntryPointNotFoundException). */
+#define RTOW_PIXEL_LIST_BYTES(capacity) (((size_t)4 + (size_t)(capacity)) * sizeof(uint32_t))
+#define RTOW_PIXEL_LIST_MAX_PIXELS ((int64_t)1 << 27)
+typedef struct RtowPixelList { uint32_t* words /* device, RTOW_PIXEL_LIST_BYTES(capacity) */; uint32_t capacity; } RtowPixelList;   /* 16 bytes */
+typedef struct RtowPixelListParams {
+    int32_t width, height;             /* the frame                                                             */
+    int32_t x0, y0, x1, y1;            /* the rectangle [x0, x1) x [y0, y1); it may stick out of the frame or be empty */
+    int32_t sliceOffset, sliceDivider; /* rows with y % sliceDivider == sliceOffset (JOBS/SampleBatchJob.cs:69-70); 0 / 1: every row */
+    float   minSampleCount;            /* with `color`: pixels whose color.w is not >= this                     */
+    int32_t flags;                     /* 0 */
+    int32_t reserved;                  /* 0 */
+} RtowPixelListParams;                 /* 44 bytes */
+#define RTOW_PIXEL_LIST_SCRATCH_BYTES(w, h) ((((size_t)(w) + 7) / 8) * (((size_t)(h) + 7) / 8) * sizeof(uint32_t))
+/* Numeric specification (integers, and one float comparison).  p = y * W + x.  Pixel (x, y) qualifies iff
+ *     max(x0, 0) <= x < min(x1, W)  and  max(y0, 0) <= y < min(y1, H)         (an empty rectangle is valid and lists nothing)
+ *     y % sliceDivider == sliceOffset
+ *     mask == NULL  or  mask[p] != 0                                          (one byte per pixel)
+ *     color == NULL or  !(color[4 p + 3] >= minSampleCount)                   (float4 per pixel; a NaN count qualifies, -0 is 0)
+ *   Order: tiles of 8 x 8 pixels anchored at (0, 0), row of tiles by row of tiles from the bottom, left to right in a row; inside a tile row by row from the bottom,
+ *   left to right - the 64 pixels a wave of the sample kernel pulls at a time are then one tile's (or, in sparse lists, neighbouring tiles').
+ *   The first `capacity` qualifiers in that order are written to words[4 ...]; words[0] = the number of ALL qualifiers, words[1..3] = 0; capacity == 0 is valid.
+ *   Words behind min(words[0], capacity) are not written.  No index appears twice.
+ * Validation (RTOW_ERROR_INVALID_VALUE, nothing enqueued): NULL context, params, list, list->words or scratch; width or height <= 0 or width * height > 2^27;
+ * sliceDivider < 1 or sliceOffset outside [0, sliceDivider); with `color`, a negative or NaN minSampleCount; flags or reserved != 0; the list or the scratch
+ * overlapping `color` or `mask`, or each other.
+ * `scratch`: RTOW_PIXEL_LIST_SCRATCH_BYTES(width, height) of device memory, the caller's (as RTOW_DENOISE_SCRATCH_BYTES); its contents afterwards are unspecified.
+ * Enqueued on `stream` (NULL = the context's own stream): a count per tile (one wave per tile), an exclusive scan of the counts, a write at base + rank - plain
+ * launches in stream order, none waits for another workgroup; no allocation, no wait, so the call may be captured in a graph.  A pure function of its buffers: it
+ * needs no resident scene.  `color` may start at any 4-byte aligned address, `mask` at any address. */
+RTOW_API int rtowBuildPixelListDevice(RtowContext context, const RtowPixelListParams* params,
+                                      const float* color /* device float4[W*H] or NULL: the accumulated colour, .w = sample count */,
+                                      const uint8_t* mask /* device, W*H bytes, or NULL */,
+                                      void* scratch /* device, RTOW_PIXEL_LIST_SCRATCH_BYTES(width, height) */,
+                                      const RtowPixelList* list, void* stream);
+
+/* `count` successive batches of one frame for the pixels of `list` only: for every listed pixel p, the four `out` buffers at p - and every diagnostics[k] record at
+ * p - hold exactly what rtowSampleBatchChainDevice(count, params, in, out, diagnostics, ...) would store there, bit for bit (count == 1: rtowSampleBatchDevice).
+ * NO other element of any output is written.  `in` and `out` may alias element for element.  Batches that differ in nothing but `seed` run as one launch that
+ * carries each pixel through the chain in registers; other sequences run batch by batch.  count is 1 .. 16.
+ * min(words[0], capacity) entries are rendered.  The call first copies the caller's list into one the context owns (in stream order: `list` may be reused or
+ * rewritten as soon as the call returns), and an entry >= W * H is dropped there - it is never used as an address.  An index listed TWICE is the caller's error
+ * when `in` aliases `out` (the pixel is then read and stored by two lanes in no order); rtowBuildPixelListDevice never produces one.  An empty list costs a
+ * launch that leaves at once.
+ * What runs: the exact-tie kernel of the scene's kind over the list (the kernel that renders the tie watch's marked pixels), min(CU count,
+ * ceil(capacity / 1024)) workgroups; no cost map, chunk order or ticket map is read or left behind, and the launch neither counts towards nor triggers the per-scene
+ * threshold measurement.  It IS the context's most recent sample batch for rtowGetLastSampleKernelMs, rtowGetBatchStatus and rtowSynchronize; hit-list growth,
+ * RTOW_ERROR_CAPACITY and `cancel` behave as for rtowSampleBatchDevice.
+ * params[k].sliceOffset / sliceDivider must be 0 / 1: the list alone says which pixels (a multi-GPU host builds one list per rank with the builder's slice fields).
+ * Not supported (RTOW_ERROR_UNSUPPORTED, nothing enqueued, no output touched):
+ *   - scenes whose kind has no list-capable kernel: any entity that is not a sphere in a scene that is not all triangles, and any scene with volumes
+ *     (the GENERAL, TEXTURED, VOLUMES and VOLUMES_TEXTURED kernels; image-textured spheres among them);
+ *   - params[k].rngPolicy other than RTOW_RNG_REFERENCE;
+ *   - a context created with RTOW_CONTEXT_EXACT_TIES_NEVER (the exact-tie kernels may differ from its frames on rays of more than 16 hits).
+ * Validation (RTOW_ERROR_INVALID_VALUE, nothing enqueued): as rtowSampleBatchChainDevice, and count > 16, a NULL list or list->words, W * H > 2^27, slice fields
+ * other than 0 / 1, batches that differ in size.  RTOW_ERROR_NO_SCENE before rtowUploadScene. */
+RTOW_API int rtowSamplePixelsDevice(RtowContext context, int32_t count, const RtowSampleParams* params /* [count] */, const RtowPixelList* list,
+                                    const RtowAccumBuffers* in, const RtowAccumBuffers* out,
+                                    void* const* diagnostics /* [count] or NULL */, void* stream, const volatile uint8_t* cancel);
+
 /* dst += src for the four accumulation buffers (device pointers, `pixelCount` elements each).  The reference accumulates
  * successive batches by feeding a batch's outputs to the next one as inputs (UNITY/Raytracer.cs:798-802); when batches run
  * CONCURRENTLY on several GPUs (each from zeroed accumulators, its own Seed) their partial sums are folded with this, in

@@ -245,6 +245,33 @@ class UpsampleParams(C.Structure):
                 ("normalSharpness", C.c_int32), ("depthTolerance", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
+# rtowBuildPixelListDevice / rtowSamplePixelsDevice (include/rtow.h): a pixel list is 4 + capacity uint32 words of device memory
+PIXEL_LIST_HEADER_WORDS = 4
+PIXEL_LIST_MAX_PIXELS = 1 << 27          # RTOW_PIXEL_LIST_MAX_PIXELS: the largest W * H a list may name pixels of
+SAMPLE_PIXELS_MAX_BATCHES = 16           # batches one rtowSamplePixelsDevice call may chain
+
+
+class PixelList(C.Structure):
+    """RtowPixelList (16 bytes): words[0] = how many pixels qualified (may exceed capacity), words[1..3] = 0, words[4 + i] = row * W + col."""
+    _fields_ = [("words", C.c_void_p), ("capacity", C.c_uint32)]
+
+
+class PixelListParams(C.Structure):
+    """RtowPixelListParams (44 bytes): the frame, the rectangle [x0, x1) x [y0, y1), the row slice, and the sample count below which a pixel qualifies."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32),
+                ("sliceOffset", C.c_int32), ("sliceDivider", C.c_int32), ("minSampleCount", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+def pixel_list_bytes(capacity):
+    """RTOW_PIXEL_LIST_BYTES(capacity)"""
+    return (PIXEL_LIST_HEADER_WORDS + int(capacity)) * 4
+
+
+def pixel_list_scratch_bytes(width, height):
+    """RTOW_PIXEL_LIST_SCRATCH_BYTES(w, h): one word per 8 x 8 tile of the frame"""
+    return ((int(width) + 7) // 8) * ((int(height) + 7) // 8) * 4
+
+
 class SurfaceBuffers(C.Structure):
     """RtowSurfaceBuffers (48 bytes): device pointers, any may be NULL (not written), not all six."""
     _fields_ = [("albedo", C.c_void_p), ("emission", C.c_void_p), ("texCoord", C.c_void_p), ("metallicGlossiness", C.c_void_p),
@@ -281,4 +308,5 @@ EXPORTED_SYMBOLS = [
     "rtowCombineFinalizeDevice", "rtowReduceMetricsDeviceAsync", "rtowProbeNearestHit", "rtowSampleBatchChainAdaptiveDevice",
     "rtowDenoiseDevice", "rtowTraceRaysDevice", "rtowTraceViewDevice", "rtowReprojectAccumDevice", "rtowShadeHitsDevice",
     "rtowTraceRaysIntervalDevice", "rtowTraceOcclusionDevice", "rtowProbeNearestHitInterval", "rtowUpsampleDevice",
+    "rtowBuildPixelListDevice", "rtowSamplePixelsDevice",
 ]

@@ -633,18 +633,78 @@ int enqueueLaunch(RtowContext ctx, const RtowSampleParams* p, SampleKernelArgs& 
     return RTOW_SUCCESS;
 }
 
+// rtowSamplePixelsDevice: the caller's list (device memory of 4 + capacity words) a launch renders instead of the frame
+struct ListSpec { const unsigned* words; uint32_t capacity; };
+
+// A list launch (rtow.h: rtowSamplePixelsDevice): the exact-tie kernel of the scene's kind in redoMode - as launchTieFixup sets it up, the only launch there is - over
+// the context's own copy of the caller's list.  The copy (launchFilterPixelList) clamps the count, drops entries beyond the frame - the kernel turns an entry into an
+// address without a look - and frees the caller's list in stream order.  No tie bitmap (these kernels resolve their ties themselves), no cost map, chunk order or ticket
+// map read or left behind, no threshold probes and no samples counted towards them, no lanes in a hurry; camera-ray lists as for a batch of that view.
+int enqueueListLaunch(RtowContext ctx, SampleKernelArgs& a, const ChainSpec* chain, const ListSpec& list, hipStream_t stream)
+{
+    const uint32_t ownedPixels = a.totalWork;                                        // the whole frame (slice 0 / 1)
+    a.wideCodes = ctx->wideCodes ? 1 : 0;
+    a.blockThreads = kBlockThreads;
+    // persistent workgroups as for a frame, but no more than the list can occupy
+    const int blocks = (int)std::max<uint64_t>(1u, std::min<uint64_t>((uint64_t)ctx->cuCount, ((uint64_t)list.capacity + (uint32_t)kBlockThreads - 1u) / (uint32_t)kBlockThreads));
+    if (!ctx->scene.layout.exactTies) {
+        // a scene that runs on the rank-rule kernels has no hit-list spill of its own: the area of these workgroups, sized the way sizeHitSpill sizes an exact-tie scene's
+        const uint32_t most = (uint32_t)std::min<uint64_t>((uint64_t)ctx->scene.entityCount, listCapacity(ctx, false));
+        const uint32_t entries = most > (uint32_t)kLocalHitEntries ? most - (uint32_t)kLocalHitEntries : 0u;
+        const uint64_t slots = (uint64_t)entries * (uint64_t)blocks;
+        RTOW_TRY(growDevice(ctx, ctx->listSpillSlots, slots, {devBuf(ctx->dListSpill, (size_t)slots * kBlockThreads * sizeof(uint4))}));
+        a.hitSpill = entries ? ctx->dListSpill : nullptr;
+        a.hitSpillEntries = entries;
+        a.hitSpillStride = (uint32_t)blocks * (uint32_t)kBlockThreads;
+    }   // (else buildArgs gave the scene's own area: one slice per CU, and blocks <= cuCount)
+    if (!ctx->havePixelList || list.capacity > ctx->pixelListCapacity) {
+        // grow-only, allocated on first use (hipFree waits for a launch that still reads the smaller list)
+        if (ctx->dPixelList) (void)hipFree(ctx->dPixelList);
+        if (ctx->dPixelListScratch) (void)hipFree(ctx->dPixelListScratch);
+        ctx->dPixelList = nullptr; ctx->dPixelListScratch = nullptr; ctx->havePixelList = false;
+        HIP_TRY(ctx, hipMalloc(&ctx->dPixelList, RTOW_PIXEL_LIST_BYTES(list.capacity)), RTOW_ERROR_MEMORY_ALLOCATION);
+        HIP_TRY(ctx, hipMalloc(&ctx->dPixelListScratch, (((size_t)list.capacity + 63u) / 64u + 1u) * sizeof(unsigned)), RTOW_ERROR_MEMORY_ALLOCATION);
+        ctx->pixelListCapacity = list.capacity;
+        ctx->havePixelList = true;
+    }
+    // the context's list, ticket counter, batch table and candidate lists are the previous batch's until it has finished (launchSample)
+    if (ctx->haveBatchDone) HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->evBatchDone, 0), RTOW_ERROR_LAUNCH_FAILURE);
+    HIP_TRY(ctx, launchFilterPixelList(list.words, list.capacity, ownedPixels, ctx->dPixelListScratch, ctx->dPixelList, stream), RTOW_ERROR_LAUNCH_FAILURE);
+    RTOW_TRY(refreshCameraRays(ctx, a, ownedPixels, stream));
+    a.chunkCount = (a.totalWork + 63u) / 64u;            // (what writeBatchTable sizes a chain's hand-over state by; a list launch hands over in registers and reads none of it)
+    RTOW_TRY(writeBatchTable(ctx, chain, a, stream));
+    a.redoMode = 1;
+    a.tune[7] &= 255;                                    // the pixel gate alone
+    a.tieBits = nullptr;
+    a.tieRedo = ctx->dPixelList;
+    a.tieRedoCapacity = list.capacity;
+    a.pixelCost = nullptr; a.chunkOrder = nullptr; a.ticketMap = nullptr;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->dWorkCounter, 0, sizeof(unsigned int), stream), RTOW_ERROR_LAUNCH_FAILURE);
+    HIP_TRY(ctx, hipEventRecord(ctx->evStart, stream), RTOW_ERROR_LAUNCH_FAILURE);
+    HIP_TRY(ctx, launchSampleBatch(a, blocks, stream), RTOW_ERROR_LAUNCH_FAILURE);
+    logf(ctx, 4, "launch", "%s: %u batch%s over a pixel list of up to %u, %d workgroups", sampleKernelName(a.layout), a.chainCount, a.chainCount > 1u ? "es" : "", list.capacity, blocks);
+    HIP_TRY(ctx, hipEventRecord(ctx->evStop, stream), RTOW_ERROR_LAUNCH_FAILURE);
+    HIP_TRY(ctx, hipEventRecord(ctx->evBatchDone, stream), RTOW_ERROR_LAUNCH_FAILURE);
+    ctx->haveBatchDone = true;
+    ctx->haveTiming = true;
+    return RTOW_SUCCESS;
+}
+
 // One launch of one batch, a chain or a group (chain), enqueued on `stream` behind everything the context's previous batch enqueued.
 // extremaIn (optional): device memory the kernel reads the SampleCountWeightExtrema from instead of p's (rtowSampleBatchChainAdaptiveDevice)
+// list (optional): the launch renders the pixels of this list instead of the frame (rtowSamplePixelsDevice; the caller has checked that the scene's kind can)
 int launchSample(RtowContext ctx, const RtowSampleParams* p, const RtowAccumBuffers* in, const RtowAccumBuffers* out, void* diag,
-                 hipStream_t stream, bool useCancelFlag, const ChainSpec* chain = nullptr, const RtowFloat2* extremaIn = nullptr)
+                 hipStream_t stream, bool useCancelFlag, const ChainSpec* chain = nullptr, const RtowFloat2* extremaIn = nullptr, const ListSpec* list = nullptr)
 {
     SampleKernelArgs a{};
     RTOW_TRY(buildArgs(ctx, p, in, out, diag, useCancelFlag, chain, extremaIn, a));
+    if (list) a.layout.exactTies = 1u;                   // (before the plan: these kernels have no "lanes in a hurry" twin)
     RTOW_TRY(planHistory(ctx, p, a));
     setSchedulerValues(ctx, p, a);                       // (the hurry rate reads a.layout.exactTies before the triangle tie watch clears it)
     const uint32_t ownedPixels = a.totalWork;
     if (ownedPixels == 0) return recordEmptyBatch(ctx, stream);
     RTOW_TRY(planUnits(ctx, p, a));
+    if (list) return enqueueListLaunch(ctx, a, chain, *list, stream);
     TieWatch tie;
     RTOW_TRY(prepareTieWatch(ctx, p, in, out, a, tie));
 
@@ -831,9 +891,10 @@ bool canFuse(const RtowContext_t* ctx, int count, const RtowSampleParams* params
 
 // `count` batches enqueued on `s`: one launch per kMaxChain of them when `fuse`, else one per batch.  A chain: batch 0 reads `in`, every later one what its
 // predecessor stored to `out` (what the chain is defined to equal).  A group: every batch reads `in` and stores to out[b].  With `cancel` every launch is waited for.
+// list (optional): every launch renders the pixels of this list instead of the frame (rtowSamplePixelsDevice).
 // The caller holds ctx->mu and has validated params / buffers.
 int enqueueBatches(RtowContext ctx, int count, const RtowSampleParams* params, const RtowAccumBuffers* in, const RtowAccumBuffers* out, void* const* diagnostics,
-                   bool group, bool fuse, hipStream_t s, const volatile uint8_t* cancel)
+                   bool group, bool fuse, hipStream_t s, const volatile uint8_t* cancel, const ListSpec* list = nullptr)
 {
     int rc = RTOW_SUCCESS;
     for (int first = 0; first < count && rc == RTOW_SUCCESS;) {
@@ -841,12 +902,12 @@ int enqueueBatches(RtowContext ctx, int count, const RtowSampleParams* params, c
         const RtowAccumBuffers* src = (group || first == 0) ? in : out;
         const RtowAccumBuffers* dst = group ? &out[first] : out;
         if (n == 1) {
-            rc = launchSample(ctx, &params[first], src, dst, diagnostics ? diagnostics[first] : nullptr, s, cancel != nullptr);
+            rc = launchSample(ctx, &params[first], src, dst, diagnostics ? diagnostics[first] : nullptr, s, cancel != nullptr, nullptr, nullptr, list);
         } else {
             uint32_t seeds[kMaxChain];
             for (int b = 0; b < n; b++) seeds[b] = params[first + b].seed;
             const ChainSpec spec{n, seeds, diagnostics ? diagnostics + first : nullptr, group ? out + first : nullptr};
-            rc = launchSample(ctx, &params[first], src, dst, nullptr, s, cancel != nullptr, &spec);
+            rc = launchSample(ctx, &params[first], src, dst, nullptr, s, cancel != nullptr, &spec, nullptr, list);
         }
         if (rc == RTOW_SUCCESS && cancel) rc = waitWithCancel(ctx, cancel);
         first += n;
@@ -1101,6 +1162,9 @@ RTOW_API int rtowDestroyContext(RtowContext ctx)
     if (ctx->dTieInputs) (void)hipFree(ctx->dTieInputs);
     if (ctx->dHistSpill) (void)hipFree(ctx->dHistSpill);
     if (ctx->dRedoSpill) (void)hipFree(ctx->dRedoSpill);
+    if (ctx->dPixelList) (void)hipFree(ctx->dPixelList);
+    if (ctx->dPixelListScratch) (void)hipFree(ctx->dPixelListScratch);
+    if (ctx->dListSpill) (void)hipFree(ctx->dListSpill);
     if (ctx->hCancel) (void)hipHostFree((void*)ctx->hCancel);
     if (ctx->dColor) { (void)hipFree(ctx->dColor); (void)hipFree(ctx->dNormal); (void)hipFree(ctx->dAlbedo); (void)hipFree(ctx->dScw); }
     if (ctx->dDiag) (void)hipFree(ctx->dDiag);
@@ -1773,6 +1837,52 @@ RTOW_API int rtowUpsampleDevice(RtowContext ctx, const RtowUpsampleParams* param
     const RtowHitBuffers none{};
     HIP_TRY(ctx, launchUpsample(p, srcColor, guided ? *srcHits : none, srcAlbedo, guided ? *dstHits : none, dstAlbedo, outColor, outStage, s), RTOW_ERROR_LAUNCH_FAILURE);
     return RTOW_SUCCESS;
+}
+
+RTOW_API int rtowBuildPixelListDevice(RtowContext ctx, const RtowPixelListParams* params, const float* color, const uint8_t* mask, void* scratch, const RtowPixelList* list,
+                                      void* stream)
+{
+    if (!ctx || !params || !list || !list->words || !scratch) return RTOW_ERROR_INVALID_VALUE;
+    const RtowPixelListParams& p = *params;
+    if (p.width <= 0 || p.height <= 0 || (int64_t)p.width * p.height > RTOW_PIXEL_LIST_MAX_PIXELS) return RTOW_ERROR_INVALID_VALUE;
+    if (p.sliceDivider < 1 || p.sliceOffset < 0 || p.sliceOffset >= p.sliceDivider) return RTOW_ERROR_INVALID_VALUE;
+    if (color && !(p.minSampleCount >= 0.0f)) return RTOW_ERROR_INVALID_VALUE;                                  // NaN fails
+    if (p.flags != 0 || p.reserved != 0) return RTOW_ERROR_INVALID_VALUE;
+    // the launches write the list and the scratch while they read the inputs and each other
+    const size_t n = (size_t)p.width * (size_t)p.height;
+    const Range words{list->words, RTOW_PIXEL_LIST_BYTES(list->capacity)}, work{scratch, RTOW_PIXEL_LIST_SCRATCH_BYTES(p.width, p.height)};
+    for (const Range& in : {Range{color, n * 16}, Range{mask, n}})
+        if (overlaps(words, in) || overlaps(work, in)) return RTOW_ERROR_INVALID_VALUE;
+    if (overlaps(words, work)) return RTOW_ERROR_INVALID_VALUE;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    hipStream_t s;
+    RTOW_TRY(useDevice(ctx, stream, &s));
+    HIP_TRY(ctx, launchBuildPixelList(p, color, mask, (unsigned*)scratch, list->words, list->capacity, s), RTOW_ERROR_LAUNCH_FAILURE);
+    return RTOW_SUCCESS;
+}
+
+RTOW_API int rtowSamplePixelsDevice(RtowContext ctx, int32_t count, const RtowSampleParams* params, const RtowPixelList* list, const RtowAccumBuffers* in,
+                                    const RtowAccumBuffers* out, void* const* diagnostics, void* stream, const volatile uint8_t* cancel)
+{
+    if (!out || !list || !list->words || count > kMaxChain) return RTOW_ERROR_INVALID_VALUE;
+    std::unique_lock<std::mutex> lock;
+    hipStream_t s;
+    const auto check = [&](int b) {
+        const RtowSampleParams& q = params[b];
+        if ((int64_t)(int)q.size.x * (int)q.size.y > RTOW_PIXEL_LIST_MAX_PIXELS) return (int)RTOW_ERROR_INVALID_VALUE;     // an entry keeps the batch number above bit 27
+        if (q.sliceOffset != 0 || q.sliceDivider != 1) return (int)RTOW_ERROR_INVALID_VALUE;                                // the list alone says which pixels
+        if ((int)q.size.x != (int)params[0].size.x || (int)q.size.y != (int)params[0].size.y) return (int)RTOW_ERROR_INVALID_VALUE;      // one list, one frame
+        return (int)RTOW_SUCCESS;
+    };
+    RTOW_TRY(beginSample(ctx, lock, count, params, in, out, check, stream, &s));
+    // what has no list-capable kernel (REDO_CAPABLE, rtow_sample_kernel.hip.h), and what those kernels would not reproduce: nothing is enqueued
+    const uint32_t kind = ctx->scene.layout.sceneKind;
+    if (kind > SCENE_KIND_SPHERES_MOTION && !triangleKind(kind)) return RTOW_ERROR_UNSUPPORTED;
+    if (ctx->flags & RTOW_CONTEXT_EXACT_TIES_NEVER) return RTOW_ERROR_UNSUPPORTED;
+    for (int b = 0; b < count; b++)
+        if (params[b].rngPolicy != RTOW_RNG_REFERENCE) return RTOW_ERROR_UNSUPPORTED;
+    const ListSpec spec{list->words, list->capacity};
+    return enqueueBatches(ctx, count, params, in, out, diagnostics, false, canFuse(ctx, count, params, diagnostics, /*handOver*/ false, false), s, cancel, &spec);
 }
 
 RTOW_API int rtowAddAccumDevice(RtowContext ctx, int32_t pixelCount, const RtowAccumBuffers* dst, const RtowAccumBuffers* src, void* stream)

@@ -122,6 +122,14 @@ struct RtowContext_t {
     size_t tieInputPixels = 0;
     uint4* dRedoSpill = nullptr;
     uint32_t redoSpillEntries = 0;
+    // rtowSamplePixelsDevice: the context's own copy of the caller's list (4 + capacity words, entries beyond the frame dropped) with the filter's scan scratch, and the
+    // hit-list spill area of a list launch's workgroups.  Not dTieRedo / dRedoSpill: those belong to watched launches in flight
+    unsigned* dPixelList = nullptr;
+    unsigned* dPixelListScratch = nullptr;
+    uint32_t pixelListCapacity = 0;
+    bool havePixelList = false;           // (a capacity of 0 is a valid list: the four header words)
+    uint4* dListSpill = nullptr;
+    uint64_t listSpillSlots = 0;          // entries x workgroups the area holds
 
     // RtowContextOptions: behaviour switches and development knobs (nothing is read from the environment)
     bool wideCodes = false;               // current scene: more than 65 535 entities or tree nodes (32-bit candidate / stack codes, tree read from HBM)

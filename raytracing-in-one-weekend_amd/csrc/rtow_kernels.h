@@ -407,6 +407,11 @@ hipError_t launchReproject(const RtowReprojectParams& p, const ReprojectConstant
 // RTOW_UPSAMPLE_DEMODULATE_ALBEDO only
 hipError_t launchUpsample(const RtowUpsampleParams& p, const float* srcColor, const RtowHitBuffers& srcHits, const float* srcAlbedo, const RtowHitBuffers& dstHits,
                           const float* dstAlbedo, float* outColor, uint8_t* outStage, hipStream_t stream);
+// rtowBuildPixelListDevice (rtow_pixel_list.hip): count, scan and write launches on `stream` (arguments validated by the caller); scratch: one word per 8 x 8 tile of the frame
+hipError_t launchBuildPixelList(const RtowPixelListParams& p, const float* color, const uint8_t* mask, unsigned* scratch, unsigned* words, unsigned capacity, hipStream_t stream);
+// rtowSamplePixelsDevice: the first min(source[0], capacity) entries of a caller's list that are below framePixels, in their order, into `words` (4 + capacity words;
+// words[0] = how many, never more than capacity); scratch: one word per 64 entries of capacity
+hipError_t launchFilterPixelList(const unsigned* source, unsigned capacity, unsigned framePixels, unsigned* scratch, unsigned* words, hipStream_t stream);
 // dst[k] += src[k] for the four accumulators (float4 / float3 / float3 / float per pixel) in one launch
 hipError_t launchAddAccum(size_t pixels, float* const dst[4], const float* const src[4], hipStream_t stream);
 // bits of tieBits -> entries of tieRedo (one per marked pixel; `batches` per pixel, batch index in bits 27.., for a batch group)

@@ -416,6 +416,21 @@ def sample_batch_chain_device(context, params_list, ins, outs, diags=None, strea
     return load().rtowSampleBatchChainDevice(context.handle, count, arr, C.byref(bi), C.byref(bo), dptr, stream, cancel)
 
 
+def sample_pixels_device(context, params_list, pixel_list, capacity, ins, outs, diags=None, stream=None, cancel=None):
+    """rtowSamplePixelsDevice: the chain above for the pixels of a device list only (pixel_list: a DeviceBuffer or device address of 4 + capacity uint32 words,
+    as build_pixel_list leaves it or as the host filled it); no other element of `outs` or `diags` is written.  params_list: 1 .. 16 batches, slice 0 / 1."""
+    count = len(params_list)
+    arr = (abi.SampleParams * count)(*params_list)
+    bi = _buffers(*[b.ptr for b in ins])
+    bo = _buffers(*[b.ptr for b in outs])
+    dptr = None
+    if diags is not None:
+        dptr = (C.c_void_p * count)(*[d.ptr if d is not None else None for d in diags])
+    words = pixel_list.ptr if isinstance(pixel_list, DeviceBuffer) else pixel_list
+    lst = abi.PixelList(words, int(capacity))
+    return load().rtowSamplePixelsDevice(context.handle, count, arr, C.byref(lst), C.byref(bi), C.byref(bo), dptr, stream, cancel)
+
+
 def sample_batch_chain_adaptive_device(context, params_list, ins, outs, extrema_out, lag=2, extrema_in=None, diags=None, stream=None, cancel=None):
     """rtowSampleBatchChainAdaptiveDevice: the chain above, batch k >= lag deciding its sample counts from the SampleCountWeightExtrema the device reduced
     after batch k - lag (extrema_out: a DeviceBuffer of len(params_list) float2, or a device address); batches k < lag from extrema_in (a DeviceBuffer or device
@@ -570,6 +585,41 @@ class ReprojectJob:
         rc = load().rtowReprojectAccumDevice(self.context.handle, C.byref(p), _device_ptr(self.Rays), C.byref(hits), C.byref(prev_hits), C.byref(prev), C.byref(out),
                                              _device_ptr(self.OutputSource), stream)
         return JobHandle(rc)
+
+
+class PixelListJob:
+    """rtowBuildPixelListDevice: the pixels of a Width x Height frame that lie in the rectangle [X0, X1) x [Y0, Y1) and in the row slice, whose Mask byte (optional) is
+    not 0 and whose accumulated sample count Color[4 p + 3] (optional) is not >= MinSampleCount, as a device list in 8 x 8 tile order for rtowSamplePixelsDevice.
+    Device buffers (or raw device addresses): List holds abi.pixel_list_bytes(Capacity) bytes, Scratch abi.pixel_list_scratch_bytes(Width, Height).  The rectangle
+    defaults to the frame, the slice to every row."""
+
+    def __init__(self, context, Width, Height, Capacity, X0=0, Y0=0, X1=None, Y1=None, SliceOffset=0, SliceDivider=1, MinSampleCount=0.0, Flags=0, Reserved=0):
+        self.context, self.Width, self.Height, self.Capacity = context, Width, Height, Capacity
+        self.X0, self.Y0, self.X1, self.Y1 = X0, Y0, Width if X1 is None else X1, Height if Y1 is None else Y1
+        self.SliceOffset, self.SliceDivider, self.MinSampleCount, self.Flags, self.Reserved = SliceOffset, SliceDivider, MinSampleCount, Flags, Reserved
+        self.Color = self.Mask = self.Scratch = self.List = None
+
+    def params(self):
+        return abi.PixelListParams(int(self.Width), int(self.Height), int(self.X0), int(self.Y0), int(self.X1), int(self.Y1), int(self.SliceOffset),
+                                   int(self.SliceDivider), float(self.MinSampleCount), int(self.Flags), int(self.Reserved))
+
+    def Schedule(self, stream=None):
+        p = self.params()
+        lst = abi.PixelList(_device_ptr(self.List), int(self.Capacity))
+        rc = load().rtowBuildPixelListDevice(self.context.handle, C.byref(p), _device_ptr(self.Color), _device_ptr(self.Mask), _device_ptr(self.Scratch), C.byref(lst), stream)
+        return JobHandle(rc)
+
+
+def build_pixel_list(context, width, height, capacity, color=None, mask=None, min_sample_count=0.0, rect=None, slice_offset=0, slice_divider=1, stream=None):
+    """One PixelListJob with buffers of its own: returns (list DeviceBuffer of 4 + capacity uint32 words, the scratch DeviceBuffer - keep it alive until the stream has
+    run the call).  rect: (x0, y0, x1, y1), default the frame; color / mask: DeviceBuffers or device addresses, or None."""
+    x0, y0, x1, y1 = rect if rect is not None else (0, 0, width, height)
+    job = PixelListJob(context, width, height, capacity, x0, y0, x1, y1, slice_offset, slice_divider, min_sample_count)
+    job.Color, job.Mask = color, mask
+    job.List = DeviceBuffer(context, abi.pixel_list_bytes(capacity))
+    job.Scratch = DeviceBuffer(context, max(4, abi.pixel_list_scratch_bytes(width, height)))
+    check(job.Schedule(stream).Complete(), "rtowBuildPixelListDevice")
+    return job.List, job.Scratch
 
 
 class UpsampleJob:

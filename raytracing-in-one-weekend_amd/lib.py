@@ -72,6 +72,8 @@ def load():
     lib.rtowReprojectAccumDevice.argtypes = [vp, C.POINTER(abi.ReprojectParams), vp, C.POINTER(abi.HitBuffers), C.POINTER(abi.HitBuffers),
                                              C.POINTER(abi.AccumBuffers), C.POINTER(abi.AccumBuffers), vp, vp]
     lib.rtowUpsampleDevice.argtypes = [vp, C.POINTER(abi.UpsampleParams), vp, C.POINTER(abi.HitBuffers), vp, C.POINTER(abi.HitBuffers), vp, vp, vp, vp]
+    lib.rtowBuildPixelListDevice.argtypes = [vp, C.POINTER(abi.PixelListParams), vp, vp, vp, C.POINTER(abi.PixelList), vp]
+    lib.rtowSamplePixelsDevice.argtypes = [vp, C.c_int32, C.POINTER(abi.SampleParams), C.POINTER(abi.PixelList), AB, AB, C.POINTER(vp), vp, vp]
     lib.rtowShadeHitsDevice.argtypes = [vp, C.POINTER(abi.ShadeHitsParams), C.c_int32, vp, vp, C.POINTER(abi.SurfaceBuffers), vp]
     lib.rtowReduceMetricsDeviceAsync.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp]
     lib.rtowAddAccumDevice.argtypes = [vp, C.c_int32, AB, AB, vp]
