@@ -596,7 +596,8 @@ RTOW_API int rtowProbeNearestHitInterval(RtowContext context, const RtowFloat3* 
  * rtowTraceRaysDevice / rtowTraceViewDevice were given / returned (outRays, RtowHitBuffers.entityIndex).  With rtowTraceViewDevice's normal this is a noise-free guide pair for
  * rtowDenoiseDevice, and the albedo RTOW_DENOISE_DEMODULATE_ALBEDO divides by; materialIndex / materialInfo tell a picking host which material is under the cursor and a
  * reprojecting host whether two views saw the same material.
- * Raw surface, no path: the values of the FIRST surface.  Nothing is traced through glass or mirrors; bit 8 of materialInfo marks the surfaces where the sample path's own
+ * Raw surface, no path: the values of the FIRST surface.  Nothing is traced through glass or mirrors here (rtowTraceGuide*Device below walks there and hands this call
+ * the chain's last ray and entity); bit 8 of materialInfo marks the surfaces where the sample path's own
  * albedo AOV looks further (Material.IsPerfectSpecular, JOBS/SampleBatchJob.cs:316).
  * Added after API version 12 without changing it: a host detects the call by its entry point (C#: EntryPointNotFoundException). */
 typedef struct RtowSurfaceBuffers {     /* device pointers, `count` elements each, tightly packed; any may be NULL (not written), not all */
@@ -630,6 +631,62 @@ typedef struct RtowShadeHitsParams { RtowEnvironment environment; int32_t flags 
 RTOW_API int rtowShadeHitsDevice(RtowContext context, const RtowShadeHitsParams* params, int32_t count,
                                  const RtowRay* rays /* device */, const int32_t* entityIndex /* device: RtowHitBuffers.entityIndex of `rays` */,
                                  const RtowSurfaceBuffers* surface, void* stream);
+
+/* ---- guides seen through mirrors and glass: the end of the specular chain ----
+ * The trace calls and rtowShadeHitsDevice stop at the FIRST surface.  On a perfectly specular one (a mirror, glass: bit 8 of materialInfo) the sample path's own albedo and
+ * normal AOVs look further, to the first hit whose material is not Material.IsPerfectSpecular (JOBS/SampleBatchJob.cs:316-328).  These calls walk there deterministically:
+ * mirrors by reflection, glass by refraction (reflection on total internal reflection), no random numbers - and report the END of the chain in the form the trace calls use,
+ * so that rtowShadeHitsDevice (on `rays` / hits.entityIndex), rtowDenoiseDevice and rtowUpsampleDevice work on it unchanged: a noise-free albedo / normal guide pair that shows
+ * what is seen IN a mirror and THROUGH a glass ball instead of a featureless ball.  rtowCombineDevice's guides look as far but follow the random path (the coin at glass
+ * included), so they are noisy.
+ * Measured (profiles/r11_guides.json; tests/test_gpu_denoise.py's protocol: 4-spp cover frame, 192 x 108, against 1024 spp, recommended RtowDenoiseParams; squared error of
+ * the denoised frame relative to the noisy frame's, on the whole frame / on the 24 % of the pixels whose first hit is perfectly specular): combine's guides 0.433 / 0.629,
+ * first-hit guides (rtowTraceViewDevice + rtowShadeHitsDevice) 0.414 / 0.565, chain guides (this call's normal, rtowShadeHitsDevice on its rays) 0.384 / 0.466 - chain
+ * over first-hit 0.92 - 0.94 over three seeds.  Recommended where the frame shows mirrors or glass: maxBounces 8 (no chain of the cover frame is longer than 4).  The pass
+ * costs 1.3 - 1.4 x rtowTraceViewDevice at 3840 x 2160 on the cover scene (1.7 x at 1920 x 1080), 2.0 x on a textured triangle mesh with a glass icosphere, where the long chains are total internal reflections inside the faceted ball (3.4 x at 1920 x 1080).
+ * Added after API version 12 without changing it: a host detects the calls by their entry points (C#: EntryPointNotFoundException). */
+#define RTOW_GUIDE_MAX_BOUNCES 64
+typedef struct RtowGuideParams { int32_t maxBounces; int32_t flags /* 0 */; int32_t reserved /* 0 */; } RtowGuideParams;   /* 12 bytes; maxBounces 0..RTOW_GUIDE_MAX_BOUNCES, recommended 8 */
+typedef struct RtowGuideBuffers {       /* device pointers, `count` elements each, tightly packed; any may be NULL (not written), not all */
+    RtowHitBuffers hits;                /* the END of the chain: distance of the LAST segment, entityIndex, normal - as rtowTraceRaysDevice reports that segment (+inf, -1, (0,0,0) on a miss) */
+    RtowRay*  rays;                     /* the last segment's ray (origin, time, direction, pad 0): with hits.entityIndex the input of rtowShadeHitsDevice */
+    float*    throughput;               /* float3: product of the tints of the surfaces followed, (1,1,1) when none */
+    float*    pathDistance;             /* sum of the segment distances up to the end point, in segment order; a final miss adds nothing */
+    int32_t*  bounces;                  /* surfaces followed, 0..maxBounces */
+    uint8_t*  end;                      /* 0 sky, 1 a surface that is not perfectly specular, 2 cut: a perfectly specular surface met with bounces == maxBounces */
+} RtowGuideBuffers;
+/* Numeric specification (float32, no contraction, the helpers of csrc/rtow_vecmath.hip.h; where the sample kernel has an expression, that expression).  Segment k has the
+ * ray (ro, rd, time); b = surfaces followed so far (0), T = (1, 1, 1), D = +0.
+ *   1 nearest hit: one ray of rtowTraceRaysDevice, bit for bit (distance t, entity; volume entities count as their hull).  Of several entities at the bit-identical
+ *                  nearest distance it is, as there, the one first in the reference tree's leaf order - FindHits[0] of the sample path as long as that path's sort is
+ *                  stable (up to 16 hits on the ray), possibly another of the tied entities beyond that.  A miss: end = 0, stop.
+ *   2 hit record:  D = D + t; P = (ro.x + t * rd.x, ro.y + t * rd.y, ro.z + t * rd.z); N = the normal rtowTraceRaysDevice reports; M = the entity's material.
+ *                  M not Material.IsPerfectSpecular: end = 1, stop.  b == maxBounces: end = 2, stop.
+ *   3 scatter:     Material.Scatter at roughness 0 with the coin taken out (RT/Material.cs:75-161).
+ *                  Standard (a mirror): sdir = reflect(rd, N) = rd - (2 * N) * dot(rd, N); tint = Albedo.
+ *                  Dielectric: rn = normalize(N); dn = dot(rd, rn); dn > 0: on = -rn, nn = ior, otherwise on = rn, nn = 1 / ior (as the upload derived it);
+ *                  dt = dot(rd, on); disc = 1 - nn * nn * (1 - dt * dt); disc > 0: sdir = nn * (rd - on * dt) - on * sqrt(disc) per component, tint = Albedo;
+ *                  otherwise (NaN included) total internal reflection: sdir = reflect(rd, rn), tint = (1, 1, 1).
+ *                  Albedo = Albedo.SampleColor(TexCoords) exactly as rtowShadeHitsDevice returns it for (this segment's ray, this entity).  T = T * tint per channel.
+ *                  Left out on purpose: the untinted glossy branch of a metal (reflectionChance; r0 = 0.0023 at metallic 1) and the Schlick reflection of glass - the chain
+ *                  follows the branch that carries what is seen in or through the surface.  A frosted dielectric (glossiness < 1) is followed along its mean direction.
+ *   4 next ray:    offN = dot(sdir, N) >= 0 ? N : -N; ro = P + 0.001f * offN per component; rd = sdir (not normalised); time unchanged; b = b + 1; go to 1
+ *                  (JOBS/SampleBatchJob.cs:335-336, RT/Ray.cs:18).
+ * At the stop: hits = those of the last segment (on end = 2 the specular surface itself), rays = the last segment's ray, throughput = T, pathDistance = D, bounces = b.
+ * Consequences: maxBounces == 0 gives hits bit for bit those of rtowTraceRaysDevice, rays = the input with pad 0, T = (1, 1, 1), b = 0; a scene without perfectly specular
+ * materials gives the same for any maxBounces.  A lane runs at most maxBounces + 1 <= RTOW_GUIDE_MAX_BOUNCES + 1 = 65 walks, so the kernel always ends.  On a scene of mirrors and lambert surfaces
+ * rtowShadeHitsDevice on (rays, hits.entityIndex) and hits.normal equal the albedo and normal AOVs of a one-sample batch (jitter off, lens 0) bit for bit wherever end != 2
+ * (tests/test_gpu_guides.py).
+ * Enqueued on `stream` (NULL = the context's own stream): one launch, one lane per ray (view form: a wave per 8 x 8 pixel tile, the rays of rtowTraceViewDevice); no
+ * allocation, no wait; stream order, queueing and ordering against rtowUploadScene as rtowTraceRaysDevice.  `rays` (input) may alias out->rays element for element: a lane
+ * reads its ray before it writes.  All arrays may start at any 4-byte aligned address, `end` at any address.
+ * Validation (RTOW_ERROR_INVALID_VALUE, nothing enqueued): that of the corresponding trace call (NULL context / rays, count < 0; NULL view, width or height <= 0 or
+ * width * height > INT32_MAX, view->reserved != 0), NULL params or out, every output pointer NULL, maxBounces outside 0..RTOW_GUIDE_MAX_BOUNCES, flags or reserved non-zero.  count == 0
+ * succeeds and launches nothing.  RTOW_ERROR_NO_SCENE before rtowUploadScene. */
+RTOW_API int rtowTraceGuideRaysDevice(RtowContext context, const RtowGuideParams* params, int32_t count, const RtowRay* rays /* device */,
+                                      const RtowGuideBuffers* out, void* stream);
+RTOW_API int rtowTraceGuideViewDevice(RtowContext context, const RtowGuideParams* params, const RtowTraceViewParams* view,
+                                      const RtowGuideBuffers* out /* width*height, pixel = row*width+col, row 0 at the bottom */, void* stream);
 
 /* Device time (ms) of the most recent sample kernel of this context, measured with HIP events recorded on the
  * stream the kernel was launched on (the RecordTimeJob 0/1 bracket, JOBS/UtilJobs.cs:77-86). Synchronises on the end event. */

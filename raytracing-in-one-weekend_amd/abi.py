@@ -292,6 +292,34 @@ MATERIAL_INFO_PERFECT_SPECULAR = 0x100
 MATERIAL_INFO_MISS = 0xFFFFFFFF
 
 
+# rtowTraceGuideRaysDevice / rtowTraceGuideViewDevice (include/rtow.h)
+GUIDE_MAX_BOUNCES = 64          # RTOW_GUIDE_MAX_BOUNCES
+GUIDE_DEFAULT_MAX_BOUNCES = 8
+# RtowGuideBuffers.end
+GUIDE_END_SKY, GUIDE_END_SURFACE, GUIDE_END_CUT = 0, 1, 2
+
+
+class GuideParams(C.Structure):
+    """RtowGuideParams (12 bytes): maxBounces 0..64; flags and reserved are 0."""
+    _fields_ = [("maxBounces", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GuideBuffers(C.Structure):
+    """RtowGuideBuffers (64 bytes): device pointers, any may be NULL (not written), not all.  hits / rays: the last segment of the specular chain."""
+    _fields_ = [("hits", HitBuffers), ("rays", C.c_void_p), ("throughput", C.c_void_p), ("pathDistance", C.c_void_p), ("bounces", C.c_void_p), ("end", C.c_void_p)]
+
+
+# numpy element type and shape of every RtowGuideBuffers member, in the struct's order ("rays": abi.RAY_DTYPE)
+GUIDE_OUTPUTS = {"distance": ("<f4", 1), "entityIndex": ("<i4", 1), "normal": ("<f4", 3), "rays": (RAY_DTYPE, 1), "throughput": ("<f4", 3),
+                 "pathDistance": ("<f4", 1), "bounces": ("<i4", 1), "end": ("u1", 1)}
+
+
+def guide_buffers(pointers):
+    """RtowGuideBuffers from {name of GUIDE_OUTPUTS: device address}; a name that is missing (or None) is NULL"""
+    at = lambda k: pointers.get(k) or None
+    return GuideBuffers(HitBuffers(at("distance"), at("entityIndex"), at("normal")), at("rays"), at("throughput"), at("pathDistance"), at("bounces"), at("end"))
+
+
 def denoise_scratch_bytes(width, height):
     """RTOW_DENOISE_SCRATCH_BYTES(w, h): the ping-pong float3 colour buffer of the levels"""
     return int(width) * int(height) * 12
@@ -308,5 +336,5 @@ EXPORTED_SYMBOLS = [
     "rtowCombineFinalizeDevice", "rtowReduceMetricsDeviceAsync", "rtowProbeNearestHit", "rtowSampleBatchChainAdaptiveDevice",
     "rtowDenoiseDevice", "rtowTraceRaysDevice", "rtowTraceViewDevice", "rtowReprojectAccumDevice", "rtowShadeHitsDevice",
     "rtowTraceRaysIntervalDevice", "rtowTraceOcclusionDevice", "rtowProbeNearestHitInterval", "rtowUpsampleDevice",
-    "rtowBuildPixelListDevice", "rtowSamplePixelsDevice",
+    "rtowBuildPixelListDevice", "rtowSamplePixelsDevice", "rtowTraceGuideRaysDevice", "rtowTraceGuideViewDevice",
 ]

@@ -931,6 +931,25 @@ const int32_t* entityMapHost(RtowContext ctx) { return ctx->scene.entityOfPrim.e
 // a query has to be asked for at least one of distance / entityIndex / normal
 bool anyHitBuffer(const RtowHitBuffers& h) { return h.distance || h.entityIndex || h.normal; }
 
+// what both guide calls check of their parameters and outputs
+bool guideArgumentsValid(const RtowGuideParams* params, const RtowGuideBuffers* out)
+{
+    if (!params || !out) return false;
+    if (params->maxBounces < 0 || params->maxBounces > RTOW_GUIDE_MAX_BOUNCES || params->flags != 0 || params->reserved != 0) return false;
+    return anyHitBuffer(out->hits) || out->rays || out->throughput || out->pathDistance || out->bounces || out->end;
+}
+
+GuideScene guideScene(RtowContext ctx)
+{
+    GuideScene sc{};
+    sc.blob = ctx->dScene;
+    sc.layout = ctx->scene.layout;
+    sc.entityOfPrim = entityMapDevice(ctx);
+    sc.texBlob = ctx->scene.texLayout.totalBytes ? ctx->dTexBlob : nullptr;
+    sc.texLayout = ctx->scene.texLayout;
+    return sc;
+}
+
 // the aliasing checks of the post passes: a caller's buffer, and whether two of them share a byte (a null buffer shares none)
 struct Range { const void* base; size_t bytes; };
 bool overlaps(const Range& a, const Range& b)
@@ -1688,6 +1707,30 @@ RTOW_API int rtowShadeHitsDevice(RtowContext ctx, const RtowShadeHitsParams* par
     sc.cubemapData = ctx->dCubemap;
     sc.cubemap = ctx->cubemap;
     HIP_TRY(ctx, launchShadeHits(sc, params->environment, count, rays, entityIndex, *surface, s), RTOW_ERROR_LAUNCH_FAILURE);
+    return RTOW_SUCCESS;
+}
+
+RTOW_API int rtowTraceGuideRaysDevice(RtowContext ctx, const RtowGuideParams* params, int32_t count, const RtowRay* rays, const RtowGuideBuffers* out, void* stream)
+{
+    if (!ctx || !rays || count < 0 || !guideArgumentsValid(params, out)) return RTOW_ERROR_INVALID_VALUE;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
+    if (count == 0) return RTOW_SUCCESS;
+    hipStream_t s;
+    RTOW_TRY(useDevice(ctx, stream, &s));
+    HIP_TRY(ctx, launchTraceGuideRays(guideScene(ctx), params->maxBounces, count, rays, *out, s), RTOW_ERROR_LAUNCH_FAILURE);
+    return RTOW_SUCCESS;
+}
+
+RTOW_API int rtowTraceGuideViewDevice(RtowContext ctx, const RtowGuideParams* params, const RtowTraceViewParams* view, const RtowGuideBuffers* out, void* stream)
+{
+    if (!ctx || !view || !guideArgumentsValid(params, out)) return RTOW_ERROR_INVALID_VALUE;
+    if (view->width <= 0 || view->height <= 0 || (int64_t)view->width * view->height > INT32_MAX || view->reserved != 0) return RTOW_ERROR_INVALID_VALUE;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
+    hipStream_t s;
+    RTOW_TRY(useDevice(ctx, stream, &s));
+    HIP_TRY(ctx, launchTraceGuideView(guideScene(ctx), params->maxBounces, *view, *out, s), RTOW_ERROR_LAUNCH_FAILURE);
     return RTOW_SUCCESS;
 }
 

@@ -454,6 +454,18 @@ struct ShadeScene {
 hipError_t launchShadeHits(const ShadeScene& scene, const RtowEnvironment& environment, int32_t count, const RtowRay* rays, const int32_t* entityIndex,
                            const RtowSurfaceBuffers& surface, hipStream_t stream);
 
+// rtowTraceGuideRaysDevice / rtowTraceGuideViewDevice (rtow_guides.hip): one launch on `stream`, one lane per ray, as launchTraceRays / launchTraceView (arguments validated
+// by the caller).  What the pass reads of the context, all device memory: entityOfPrim as for launchTraceRays; texBlob may be null (no Image texture)
+struct GuideScene {
+    const uint8_t* blob;
+    SceneLayout layout;
+    const int32_t* entityOfPrim;
+    const uint8_t* texBlob;
+    TexLayout texLayout;
+};
+hipError_t launchTraceGuideRays(const GuideScene& scene, int32_t maxBounces, int64_t count, const RtowRay* rays, const RtowGuideBuffers& out, hipStream_t stream);
+hipError_t launchTraceGuideView(const GuideScene& scene, int32_t maxBounces, const RtowTraceViewParams& p, const RtowGuideBuffers& out, hipStream_t stream);
+
 // same-XCD hand-over litmus of the chained launches (rtow_kernels.hip): pairs of workgroups that ran on one XCD, stale dwords seen, waits that timed out
 hipError_t runXcdCoherenceLitmus(int cuCount, hipStream_t stream, unsigned* outPairs, unsigned* outStale, unsigned* outTimeouts);
 

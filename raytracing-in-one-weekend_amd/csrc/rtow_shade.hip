@@ -7,6 +7,7 @@
 //
 // Every value is computed by the sample kernel's own helpers (rtow_hit_tests.hip.h: general_hit's texCoord as the HIT stage of the textured kernels asks for it;
 // rtow_surface.hip.h: texture_color / texture_scalar, cubemap_sample; the SKY stage's gradient expression), so the pass cannot drift from what a sample batch shades with.
+// The albedo comes through rtow_albedo.hip.h, which rtow_guides.hip tints the surfaces it follows with: one evaluation for both.
 //
 // Launch shape: a plain grid of 256-lane workgroups, one lane per element, no LDS, no barrier; a lane without an element leaves at once.  The scene comes
 // from HBM / L2 (general_hit<false>): one primitive record, one material record and at most four texels per element.
@@ -15,8 +16,7 @@
 // index itself) is not one of the scene's, and a material index beyond the scene's materials.  An Image texture whose image number is not one of the blob's samples as a null
 // image.  Texels are clamped into their image by texture_pixel, after (int) conversions that saturate on this hardware (NaN: 0), as in cubemap_sample, whose face coordinates
 // (u, v) lie in [-1, 1] or are NaN for every direction.  A ray's floats are only ever operands, never addresses.
-#include "rtow_hit_tests.hip.h"
-#include "rtow_surface.hip.h"
+#include "rtow_albedo.hip.h"
 
 namespace rtow {
 
@@ -38,21 +38,6 @@ struct ShadeArgs {
     int32_t entityCount;
     uint32_t imageCount;            // GpuImage records in the texture blob
 };
-
-// texture_color / texture_scalar index the image table with t.image: an image number that is not the blob's samples as the null image does (0).  The record is read where
-// it lies in the blob: a private copy of it would be a per-lane array (texture_scalar selects a channel of mainColor)
-__device__ __forceinline__ bool no_such_image(const GpuTexture& t, uint32_t imageCount)
-{
-    return t.type == RTOW_TEXTURE_IMAGE && t.image >= 0 && (uint32_t)t.image >= imageCount;
-}
-__device__ __forceinline__ V3 color_checked(const TexRefs& tex, const GpuTexture& t, float2 uv, uint32_t imageCount)
-{
-    return no_such_image(t, imageCount) ? v3(0, 0, 0) : texture_color(tex, t, uv);
-}
-__device__ __forceinline__ float scalar_checked(const TexRefs& tex, const GpuTexture& t, float2 uv, uint32_t imageCount)
-{
-    return no_such_image(t, imageCount) ? 0.0f : texture_scalar(tex, t, uv);
-}
 
 template <int BASE>
 __global__ void __launch_bounds__(kShadeBlock) shade_kernel(ShadeArgs A)
@@ -82,11 +67,7 @@ __global__ void __launch_bounds__(kShadeBlock) shade_kernel(ShadeArgs A)
     int32_t materialIndex = -1;
     uint32_t materialInfo = 0xffffffffu;
     if (prim >= 0) {
-        if (BASE >= SCENE_KIND_GENERAL && (mi >> kPrimTypeShift) == RTOW_ENTITY_TRIANGLE) {
-            // HitRecord.TexCoords: the named triangle's own test once more (tMin 0), as HIT does for the winner; a ray that does not meet it leaves (0, 0)
-            float t2; V3 nLocal; float4 rq;
-            (void)general_hit<false>(sc, L, prim, RTOW_ENTITY_TRIANGLE, ro, rd, 0.0f, 0.0f, t2, nLocal, rq, &uv);
-        }
+        uv = hit_tex_coord<BASE>(sc, L, prim, mi, ro, rd);
         const uint8_t* mp = section<false>(sc, L.materialOffset) + matIdx * 64u;
         const float4 m0 = *reinterpret_cast<const float4*>(mp);       // albedo.xyz emission.x
         const float4 m1 = *reinterpret_cast<const float4*>(mp + 16);  // emission.yz type metallic
@@ -95,10 +76,9 @@ __global__ void __launch_bounds__(kShadeBlock) shade_kernel(ShadeArgs A)
         emission = v3(m0.w, m1.x, m1.y);
         mg = make_float2(m1.w, m2.x);
         const unsigned flags = __float_as_uint(m2.z);
-        if (BASE >= SCENE_KIND_GENERAL && (flags & MAT_FLAG_TEXTURED) && A.tex.blob && A.tex.layout.totalBytes != 0u) {
-            // Material.Scatter / Emit evaluate the four textures at rec.TexCoords (RT/Material.cs:71,77-78,123,176-179)
-            const GpuTexMaterial& tm = reinterpret_cast<const GpuTexMaterial*>(A.tex.blob + A.tex.layout.materialOffset)[matIdx];
-            albedo = color_checked(A.tex, tm.albedo, uv, A.imageCount);
+        if (textures_evaluated<BASE>(A.tex, flags)) {
+            const GpuTexMaterial& tm = tex_material(A.tex, matIdx);
+            albedo = textured_albedo(A.tex, A.imageCount, matIdx, uv);
             emission = color_checked(A.tex, tm.emission, uv, A.imageCount);
             mg = make_float2(scalar_checked(A.tex, tm.metallic, uv, A.imageCount), scalar_checked(A.tex, tm.glossiness, uv, A.imageCount));
         }
@@ -143,7 +123,7 @@ hipError_t launchShadeHits(const ShadeScene& scene, const RtowEnvironment& envir
     A.out = surface;
     A.count = count;
     A.entityCount = scene.entityCount;
-    A.imageCount = scene.texLayout.totalBytes ? (scene.texLayout.pixelOffset - scene.texLayout.imageOffset) / (uint32_t)sizeof(GpuImage) : 0u;
+    A.imageCount = image_count(scene.texLayout);
     const dim3 grid((unsigned)(((long long)count + kShadeBlock - 1) / kShadeBlock)), block(kShadeBlock);
     if (scene.layout.sceneKind == SCENE_KIND_SPHERES) hipLaunchKernelGGL((shade_kernel<SCENE_KIND_SPHERES>), grid, block, 0, stream, A);
     else if (scene.layout.sceneKind == SCENE_KIND_SPHERES_MOTION) hipLaunchKernelGGL((shade_kernel<SCENE_KIND_SPHERES_MOTION>), grid, block, 0, stream, A);

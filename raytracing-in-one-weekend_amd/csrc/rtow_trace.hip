@@ -36,18 +36,6 @@ struct TraceArgs {
     unsigned long long tiles;
 };
 
-// The camera ray of pixel (cx, cy): REGEN of the sample kernel (JOBS/SampleBatchJob.cs:134, RT/View.cs:38-47) with the jitter at the pixel centre and no lens offset
-__device__ __forceinline__ V3 view_direction(const RtowView& VW, int cx, int cy, float frameX, float frameY)
-{
-    const V3 viewLLC = v3(VW.lowerLeftCorner), viewH = v3(VW.horizontal), viewV = v3(VW.vertical);
-    const float jx = 0.5f, jy = 0.5f;
-    const float u = ((float)cx + jx) / frameX;
-    const float v = ((float)cy + jy) / frameY;
-    return normalize(v3(viewLLC.x + u * viewH.x + v * viewV.x,
-                        viewLLC.y + u * viewH.y + v * viewV.y,
-                        viewLLC.z + u * viewH.z + v * viewV.z));
-}
-
 template <int BASE, bool VIEW>
 __global__ void __launch_bounds__(kTraceBlock) trace_kernel(TraceArgs A)
 {
@@ -56,16 +44,12 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(TraceArgs A)
     V3 ro, rd;
     float time;
     if (VIEW) {
-        // wave = 8 x 8 pixel tile, lane = (lane & 7, lane >> 3) inside it
-        const unsigned long long tile = (unsigned long long)blockIdx.x * (kTraceBlock / 64) + (threadIdx.x >> 6);
+        const unsigned long long tile = view_tile();
         if (tile >= A.tiles) return;
-        const int cx = (int)(tile % A.tilesX) * 8 + (int)(threadIdx.x & 7u);
-        const int cy = (int)(tile / A.tilesX) * 8 + (int)((threadIdx.x >> 3) & 7u);
+        int cx, cy;
+        view_pixel(A, tile, cx, cy);
         if (cx >= A.width || cy >= A.height) return;
-        index = (size_t)cy * (size_t)A.width + (size_t)cx;
-        ro = v3(A.view.origin);
-        rd = view_direction(A.view, cx, cy, A.sizeX, A.sizeY);
-        time = A.time;
+        view_ray(A, cx, cy, index, ro, rd, time);
         if (A.outRays) {
             reinterpret_cast<Ray8*>(A.outRays)[index] = Ray8{ro.x, ro.y, ro.z, time, rd.x, rd.y, rd.z, 0.0f};
         }
@@ -117,15 +101,7 @@ hipError_t launchTraceView(const uint8_t* blob, const SceneLayout& layout, const
     A.layout = layout;
     A.hits = hits;
     A.outRays = outRays;
-    A.view = p.view;
-    A.time = p.time;
-    A.sizeX = (float)p.width;       // SampleBatchJob.Size is a float2 (JOBS/SampleBatchJob.cs:24)
-    A.sizeY = (float)p.height;
-    A.width = p.width;
-    A.height = p.height;
-    A.tilesX = ((unsigned)p.width + 7u) / 8u;
-    A.tiles = (unsigned long long)A.tilesX * (((unsigned long long)p.height + 7u) / 8u);
-    return launch<true>(A, (A.tiles + kTraceBlock / 64 - 1) / (kTraceBlock / 64), stream);
+    return launch<true>(A, set_view(A, p), stream);
 }
 
 }  // namespace rtow

@@ -1,6 +1,7 @@
-// rtow_trace_lanes.hip.h - what one lane of a device ray query needs besides the walk: its column of the workgroup's LDS stack, the winner's world-space normal and the
-// store of its result - and the launcher's part that does not depend on the kernel.  Shared by rtow_trace.hip (rtowTraceRaysDevice / rtowTraceViewDevice) and
-// rtow_trace_interval.hip (rtowTraceRaysIntervalDevice / rtowTraceOcclusionDevice): one launch shape, DESIGN.md 4.2.
+// rtow_trace_lanes.hip.h - what one lane of a device ray query needs besides the walk: its column of the workgroup's LDS stack, the camera ray of its pixel (view forms), the
+// winner's world-space normal and the store of its result - and the launcher's part that does not depend on the kernel.  Shared by rtow_trace.hip (rtowTraceRaysDevice /
+// rtowTraceViewDevice), rtow_trace_interval.hip (rtowTraceRaysIntervalDevice / rtowTraceOcclusionDevice) and rtow_guides.hip (rtowTraceGuideRaysDevice /
+// rtowTraceGuideViewDevice): one launch shape, DESIGN.md 4.2.
 #pragma once
 #include "rtow_walk.hip.h"
 
@@ -28,6 +29,52 @@ struct LdsStack {
     __device__ __forceinline__ bool empty() const { return sp == 0; }
 };
 
+// The camera ray of pixel (cx, cy): REGEN of the sample kernel (JOBS/SampleBatchJob.cs:134, RT/View.cs:38-47) with the jitter at the pixel centre and no lens offset
+__device__ __forceinline__ V3 view_direction(const RtowView& VW, int cx, int cy, float frameX, float frameY)
+{
+    const V3 viewLLC = v3(VW.lowerLeftCorner), viewH = v3(VW.horizontal), viewV = v3(VW.vertical);
+    const float jx = 0.5f, jy = 0.5f;
+    const float u = ((float)cx + jx) / frameX;
+    const float v = ((float)cy + jy) / frameY;
+    return normalize(v3(viewLLC.x + u * viewH.x + v * viewV.x,
+                        viewLLC.y + u * viewH.y + v * viewV.y,
+                        viewLLC.z + u * viewH.z + v * viewV.z));
+}
+
+// The view forms' lane -> pixel map: wave = 8 x 8 pixel tile (view_tile: the wave's; a kernel leaves when it is not below A.tiles), lane = (lane & 7, lane >> 3) inside
+// it (view_pixel; a kernel leaves when the pixel is outside the frame), and that pixel's index and ray (view_ray).  Args: the kernel's argument struct with the fields
+// set_view fills.  (Three steps with the two exits left to the kernel: as one function that returns "no pixel" the view kernels compile to more registers.)
+__device__ __forceinline__ unsigned long long view_tile() { return (unsigned long long)blockIdx.x * (kTraceBlock / 64) + (threadIdx.x >> 6); }
+template <typename Args>
+__device__ __forceinline__ void view_pixel(const Args& A, unsigned long long tile, int& cx, int& cy)
+{
+    cx = (int)(tile % A.tilesX) * 8 + (int)(threadIdx.x & 7u);
+    cy = (int)(tile / A.tilesX) * 8 + (int)((threadIdx.x >> 3) & 7u);
+}
+template <typename Args>
+__device__ __forceinline__ void view_ray(const Args& A, int cx, int cy, size_t& index, V3& ro, V3& rd, float& time)
+{
+    index = (size_t)cy * (size_t)A.width + (size_t)cx;
+    ro = v3(A.view.origin);
+    rd = view_direction(A.view, cx, cy, A.sizeX, A.sizeY);
+    time = A.time;
+}
+
+// the view fields of a view form's argument struct; returns the workgroups of its launch
+template <typename Args>
+unsigned long long set_view(Args& A, const RtowTraceViewParams& p)
+{
+    A.view = p.view;
+    A.time = p.time;
+    A.sizeX = (float)p.width;       // SampleBatchJob.Size is a float2 (JOBS/SampleBatchJob.cs:24)
+    A.sizeY = (float)p.height;
+    A.width = p.width;
+    A.height = p.height;
+    A.tilesX = ((unsigned)p.width + 7u) / 8u;
+    A.tiles = (unsigned long long)A.tilesX * (((unsigned long long)p.height + 7u) / 8u);
+    return (A.tiles + kTraceBlock / 64 - 1) / (kTraceBlock / 64);
+}
+
 // HitRecord.Normal of primitive `prim` hit at distance t: what the sample kernel's HIT stage derives (RT/Entity.cs:62-66) - the winner's test once more (with the tMin the
 // walk gave it: a sphere's far root or a box's exit face are the winner's only under that tMin) for its entity-space normal, rotated out and normalised; spheres of the
 // sphere kinds: r.GetPoint(t) / radius, normalised
@@ -47,18 +94,32 @@ __device__ __forceinline__ V3 hit_normal(const SceneRefs& sc, const SceneLayout&
     return normalize(nLocal);
 }
 
-// A lane's result into the caller's buffers A.hits: the distance, the host's entity index (A.entityOfPrim: primitive -> entity, or null for the same number) and the normal
-// of the hit the walk found in A.blob / A.layout under `tMin` (0 for the open form); a miss stores +inf, -1 and a zero normal.  Args: the kernel's argument struct.
-template <int BASE, typename Args>
-__device__ __forceinline__ void store_hit(const Args& A, size_t index, V3 ro, V3 rd, float rtime, float tMin, float t, int prim)
+// A lane's result into the caller's buffers A.hits: the distance and the host's entity index (A.entityOfPrim: primitive -> entity, or null for the same number) of the hit
+// the walk found; a miss stores +inf and -1.  Args: the kernel's argument struct.
+template <typename Args>
+__device__ __forceinline__ void store_hit_place(const Args& A, size_t index, float t, int prim)
 {
     if (A.hits.distance) A.hits.distance[index] = t;
     if (A.hits.entityIndex) A.hits.entityIndex[index] = prim >= 0 && A.entityOfPrim ? A.entityOfPrim[prim] : prim;
+}
+// ... and its normal, for a caller who asked for it (A.hits.normal is not null)
+template <typename Args>
+__device__ __forceinline__ void store_hit_normal(const Args& A, size_t index, V3 n)
+{
+    float* o = A.hits.normal + index * 3u;
+    o[0] = n.x; o[1] = n.y; o[2] = n.z;
+}
+
+// The whole result of a query lane: the hit the walk found in A.blob / A.layout under `tMin` (0 for the open form), the normal derived only where the caller asks for
+// it; a miss stores +inf, -1 and a zero normal
+template <int BASE, typename Args>
+__device__ __forceinline__ void store_hit(const Args& A, size_t index, V3 ro, V3 rd, float rtime, float tMin, float t, int prim)
+{
+    store_hit_place(A, index, t, prim);
     if (A.hits.normal) {
         V3 n = v3(0, 0, 0);
         if (prim >= 0) n = hit_normal<BASE>(global_scene(A.blob), A.layout, prim, ro, rd, rtime, tMin, t);
-        float* o = A.hits.normal + index * 3u;
-        o[0] = n.x; o[1] = n.y; o[2] = n.z;
+        store_hit_normal(A, index, n);
     }
 }
 

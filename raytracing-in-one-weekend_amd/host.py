@@ -310,6 +310,46 @@ class Context:
             for b in list(bufs.values()) + [dev_rays, dev_ent]:
                 b.free()
 
+    def _trace_guide(self, count, launch, want):
+        """The buffers of one guide query: allocate those named in `want` (abi.GUIDE_OUTPUTS), run `launch(out)`, wait, download."""
+        unknown = [k for k in want if k not in abi.GUIDE_OUTPUTS]
+        if unknown:
+            raise ValueError("unknown guide outputs: %s" % unknown)
+        shape = {k: (np.dtype(d), (count, w) if w > 1 else (count,)) for k, (d, w) in abi.GUIDE_OUTPUTS.items()}
+        bufs = {k: DeviceBuffer(self, max(1, count) * shape[k][0].itemsize * abi.GUIDE_OUTPUTS[k][1]) for k in abi.GUIDE_OUTPUTS if k in want}
+        try:
+            launch(abi.guide_buffers({k: b.handle.value for k, b in bufs.items()}))
+            self.synchronize()
+            return {k: b.download(*shape[k]) for k, b in bufs.items()}
+        finally:
+            for b in bufs.values():
+                b.free()
+
+    def trace_guide_rays(self, rays, max_bounces=abi.GUIDE_DEFAULT_MAX_BOUNCES, want=tuple(abi.GUIDE_OUTPUTS), stream=None):
+        """rtowTraceGuideRaysDevice on host data: every ray followed through mirrors and glass to the first surface that is not perfectly specular (or the sky, or
+        `max_bounces` surfaces).  `rays` as for trace_rays.  Returns, for the names in `want`, trace_rays' arrays for the LAST segment plus "rays" (that segment's rays,
+        abi.RAY_DTYPE: with "entityIndex" the input of shade_hits), "throughput" (n, 3), "pathDistance" (n,), "bounces" (n,) int32 and "end" (n,) uint8 (abi.GUIDE_END_*)."""
+        a = np.ascontiguousarray(rays)
+        if a.dtype != np.dtype(abi.RAY_DTYPE):
+            a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 8)
+        count = int(a.shape[0])
+        p = abi.GuideParams(int(max_bounces), 0, 0)
+        dev = DeviceBuffer(self, max(1, count) * C.sizeof(abi.Ray))
+        try:
+            if count:
+                dev.upload(a)
+            return self._trace_guide(count, lambda out: check(load().rtowTraceGuideRaysDevice(self.handle, C.byref(p), count, dev.handle, C.byref(out), stream),
+                                                              "rtowTraceGuideRaysDevice"), want)
+        finally:
+            dev.free()
+
+    def trace_guide_view(self, view, width, height, max_bounces=abi.GUIDE_DEFAULT_MAX_BOUNCES, time=0.0, want=tuple(abi.GUIDE_OUTPUTS), stream=None):
+        """rtowTraceGuideViewDevice: trace_guide_rays on trace_view's rays (pixel = row * width + col, row 0 at the bottom)."""
+        p = abi.GuideParams(int(max_bounces), 0, 0)
+        v = abi.TraceViewParams(int(width), int(height), view, float(time), 0)
+        return self._trace_guide(int(width) * int(height),
+                                 lambda out: check(load().rtowTraceGuideViewDevice(self.handle, C.byref(p), C.byref(v), C.byref(out), stream), "rtowTraceGuideViewDevice"), want)
+
     def synchronize(self):
         check(load().rtowSynchronize(self.handle), "rtowSynchronize")
 
