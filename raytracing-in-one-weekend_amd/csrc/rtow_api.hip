@@ -264,8 +264,8 @@ int planHistory(RtowContext ctx, const RtowSampleParams* p, SampleKernelArgs& a)
     if (plan.histSpillRows) {
         // the rows that do not fit LDS (32-bit stack rows of a deep tree next to a deep trace depth; a scene kept whole in LDS): 2 bytes per lane and row in HBM
         const size_t stride = (size_t)ctx->cuCount * (size_t)kBlockThreads, need = (size_t)plan.histSpillRows * stride * sizeof(unsigned short);
-        if (need > ctx->histSpillBytes) HIP_TRY(ctx, hipDeviceSynchronize(), RTOW_ERROR_LAUNCH_FAILURE);          // a batch in flight may still use the smaller area
-        RTOW_TRY(growDevice(ctx, ctx->histSpillBytes, need, {devBuf(ctx->dHistSpill, need)}));
+        if (need > ctx->dHistSpill.bytes()) HIP_TRY(ctx, hipDeviceSynchronize(), RTOW_ERROR_LAUNCH_FAILURE);      // a batch in flight may still use the smaller area
+        RTOW_TRY(growDevice(ctx, {{&ctx->dHistSpill, need}}));
         a.histSpill = ctx->dHistSpill; a.histSpillRows = plan.histSpillRows; a.histSpillStride = (uint32_t)stride;
     }
     return RTOW_SUCCESS;
@@ -323,7 +323,7 @@ int planUnits(RtowContext ctx, const RtowSampleParams* p, SampleKernelArgs& a)
     if ((uint64_t)ownedPixels * groups > 0x7fffffffull) return RTOW_ERROR_CAPACITY;
     a.groupsPerPixel = groups;
     a.totalWork = ownedPixels * groups;
-    RTOW_TRY(growDevice(ctx, ctx->unitRecordCapacity, a.totalWork, {devBuf(ctx->dUnitRecords, (size_t)a.totalWork * 64u)}));
+    RTOW_TRY(growDevice(ctx, {{&ctx->dUnitRecords, (size_t)a.totalWork * 64u}}));
     a.unitRecords = ctx->dUnitRecords;
     return RTOW_SUCCESS;
 }
@@ -348,14 +348,15 @@ int prepareTieWatch(RtowContext ctx, const RtowSampleParams* p, const RtowAccumB
     if (tie.on && tie.triangles) a.layout.exactTies = 0u;               // this launch goes through the rank-rule kernels of the kind; the fix-up launch sets the bit again
     tie.inPlace = in->color == out->color || in->normal == out->normal || in->albedo == out->albedo || in->sampleCountWeight == out->sampleCountWeight;
     if (!tie.on) return RTOW_SUCCESS;
-    if (!ctx->dTieRedo) HIP_TRY(ctx, hipMalloc(&ctx->dTieRedo, (4u + (size_t)kTieRedoCapacity) * sizeof(unsigned)), RTOW_ERROR_MEMORY_ALLOCATION);
+    RTOW_TRY(growDevice(ctx, {{&ctx->dTieRedo, (4u + (size_t)kTieRedoCapacity) * sizeof(unsigned)}}));
     const uint32_t most = (uint32_t)std::min<uint64_t>((uint64_t)ctx->scene.entityCount, listCapacity(ctx, false));
     const uint32_t entries = most > (uint32_t)kLocalHitEntries ? most - (uint32_t)kLocalHitEntries : 0u;
-    RTOW_TRY(growDevice(ctx, ctx->redoSpillEntries, entries, {devBuf(ctx->dRedoSpill, (size_t)entries * kTieRedoBlocks * kBlockThreads * sizeof(uint4))}));
+    RTOW_TRY(growDevice(ctx, {{&ctx->dRedoSpill, (size_t)entries * kTieRedoBlocks * kBlockThreads * sizeof(uint4)}}));
+    ctx->redoSpillEntries = entries;
     const size_t framePixels = (size_t)a.width * (size_t)a.height;
     const size_t words = (framePixels + 31u) / 32u;
-    RTOW_TRY(growDevice(ctx, ctx->tieBitsWords, words, {devBuf(ctx->dTieBits, words * sizeof(unsigned))}));
-    if (tie.inPlace) RTOW_TRY(growDevice(ctx, ctx->tieInputPixels, framePixels, {devBuf(ctx->dTieInputs, framePixels * 11u * sizeof(float))}));
+    RTOW_TRY(growDevice(ctx, {{&ctx->dTieBits, words * sizeof(unsigned)}}));
+    if (tie.inPlace) RTOW_TRY(growDevice(ctx, {{&ctx->dTieInputs, framePixels * 11u * sizeof(float)}}));
     return RTOW_SUCCESS;
 }
 
@@ -365,8 +366,10 @@ int refreshCameraRays(RtowContext ctx, SampleKernelArgs& a, uint32_t ownedPixels
     if (ctx->flags & RTOW_CONTEXT_NO_CAMERA_RAY_LISTS) return RTOW_SUCCESS;
     const size_t pixels = (size_t)a.width * (size_t)a.height;
     const size_t listBytes = pixels * sizeof(uint4);      // 8 x 16-bit node codes per pixel; 4 x 32-bit with wide codes
-    if (listBytes > ctx->pixCandCapacity) ctx->pixCandValid = false;
-    RTOW_TRY(growDevice(ctx, ctx->pixCandCapacity, listBytes, {devBuf(ctx->dPixCand, listBytes)}));
+    bool grew = false;
+    const int reserved = growDevice(ctx, {{&ctx->dPixCand, listBytes}}, &grew);
+    if (grew) ctx->pixCandValid = false;
+    RTOW_TRY(reserved);
     const bool same = ctx->pixCandValid && ctx->pixCandScene == ctx->sceneSerial && memcmp(&ctx->pixCandView, &a.view, sizeof(RtowView)) == 0 &&
                       ctx->pixCandW == a.width && ctx->pixCandH == a.height && ctx->pixCandOff == a.sliceOffset && ctx->pixCandDiv == a.sliceDivider &&
                       ctx->pixCandJitter == (a.subPixelJitter ? 1 : 0);
@@ -426,10 +429,11 @@ int prepareChunkOrder(RtowContext ctx, SampleKernelArgs& a, int blocks, hipStrea
     }
     order.mapped = order.want && ctx->ticketMapSide >= 1u && a.tiledPixels != 0u && !a.unitRecords;
     if (!order.want) return RTOW_SUCCESS;
-    if (a.chunkCount > ctx->chunkCapacity) ctx->orderValid = false;
-    RTOW_TRY(growDevice(ctx, ctx->chunkCapacity, a.chunkCount,
-                        {devBuf(ctx->dChunkCost, (2 * (size_t)a.chunkCount + kChunkOrderScratchWords) * sizeof(unsigned)), devBuf(ctx->dChunkOrder, a.chunkCount * sizeof(unsigned)),
-                         devBuf(ctx->dPixelCost, (size_t)a.chunkCount * 64 * sizeof(unsigned short)), devBuf(ctx->dTicketMap, (size_t)a.chunkCount * 64 * sizeof(unsigned))}));
+    bool grew = false;
+    const int reserved = growDevice(ctx, {{&ctx->dChunkCost, (2 * (size_t)a.chunkCount + kChunkOrderScratchWords) * sizeof(unsigned)}, {&ctx->dChunkOrder, a.chunkCount * sizeof(unsigned)},
+                                          {&ctx->dPixelCost, (size_t)a.chunkCount * 64 * sizeof(unsigned short)}, {&ctx->dTicketMap, (size_t)a.chunkCount * 64 * sizeof(unsigned)}}, &grew);
+    if (grew) ctx->orderValid = false;
+    RTOW_TRY(reserved);
     if (ctx->orderW != a.width || ctx->orderH != a.height || ctx->orderOff != a.sliceOffset || ctx->orderDiv != a.sliceDivider || ctx->orderGroups != a.groupsPerPixel ||
         ctx->orderMapped != order.mapped) ctx->orderValid = false;
     a.pixelCost = ctx->dPixelCost;
@@ -488,7 +492,7 @@ void measureThresholds(RtowContext ctx, SampleKernelArgs& a, int blocks, bool ha
     ctx->tuneEvents.assign((size_t)launches + 1, nullptr);
     bool ok = true;
     for (auto& e : ctx->tuneEvents) ok = ok && hipEventCreate(&e) == hipSuccess;
-    if (!ctx->dProbeSink) ok = ok && hipMalloc(&ctx->dProbeSink, 64) == hipSuccess;
+    ok = ok && ctx->dProbeSink.ensure(64) == hipSuccess;
     SampleKernelArgs probe = a;
     probe.probeOnly = kTuneProbeSamples;
     probe.pixelCost = nullptr;                           // the cost map stays the cost probe's (or the previous batch's)
@@ -538,17 +542,16 @@ int writeBatchTable(RtowContext ctx, const ChainSpec* chain, SampleKernelArgs& a
     if (a.chainCount <= 1u) return RTOW_SUCCESS;
     if (!a.chainIndependent) {
         // per-chunk hand-off counters of the chain: pixels stored so far (all batches); batch b of a chunk waits for b x its pixels
-        RTOW_TRY(growDevice(ctx, ctx->chunkDoneCapacity, a.chunkCount,
-                            {devBuf(ctx->dChunkDone, (size_t)a.chunkCount * sizeof(unsigned)), devBuf(ctx->dXcdState, sizeof(XcdState) + (size_t)kMaxXcds * a.chunkCount * sizeof(unsigned))}));
+        RTOW_TRY(growDevice(ctx, {{&ctx->dChunkDone, (size_t)a.chunkCount * sizeof(unsigned)}, {&ctx->dXcdState, sizeof(XcdState) + (size_t)kMaxXcds * a.chunkCount * sizeof(unsigned)}}));
         HIP_TRY(ctx, hipMemsetAsync(ctx->dChunkDone, 0, (size_t)a.chunkCount * sizeof(unsigned), stream), RTOW_ERROR_LAUNCH_FAILURE);
         a.chunkDone = ctx->dChunkDone;
         // chunk ownership per XCD: counters zero, list entries "not written yet" (the kernel indexes the lists with THIS launch's chunkCount)
         HIP_TRY(ctx, hipMemsetAsync(ctx->dXcdState, 0, sizeof(XcdState), stream), RTOW_ERROR_LAUNCH_FAILURE);
         HIP_TRY(ctx, hipMemsetAsync(ctx->dXcdState + sizeof(XcdState), 0xff, (size_t)kMaxXcds * a.chunkCount * sizeof(unsigned), stream), RTOW_ERROR_LAUNCH_FAILURE);
-        a.xcdState = reinterpret_cast<XcdState*>(ctx->dXcdState);
+        a.xcdState = reinterpret_cast<XcdState*>(ctx->dXcdState.get());
         a.extremaKeys = chain->extremaKeys;
     }
-    if (!ctx->dChainBatches) HIP_TRY(ctx, hipMalloc(&ctx->dChainBatches, sizeof(ChainBatch) * kMaxChain), RTOW_ERROR_MEMORY_ALLOCATION);
+    RTOW_TRY(growDevice(ctx, {{&ctx->dChainBatches, sizeof(ChainBatch) * kMaxChain}}));
     ChainBatch table[kMaxChain] = {};
     for (int b = 0; b < chain->count; b++) {
         table[b].seed = chain->seeds[b];
@@ -652,21 +655,13 @@ int enqueueListLaunch(RtowContext ctx, SampleKernelArgs& a, const ChainSpec* cha
         const uint32_t most = (uint32_t)std::min<uint64_t>((uint64_t)ctx->scene.entityCount, listCapacity(ctx, false));
         const uint32_t entries = most > (uint32_t)kLocalHitEntries ? most - (uint32_t)kLocalHitEntries : 0u;
         const uint64_t slots = (uint64_t)entries * (uint64_t)blocks;
-        RTOW_TRY(growDevice(ctx, ctx->listSpillSlots, slots, {devBuf(ctx->dListSpill, (size_t)slots * kBlockThreads * sizeof(uint4))}));
+        RTOW_TRY(growDevice(ctx, {{&ctx->dListSpill, (size_t)slots * kBlockThreads * sizeof(uint4)}}));
         a.hitSpill = entries ? ctx->dListSpill : nullptr;
         a.hitSpillEntries = entries;
         a.hitSpillStride = (uint32_t)blocks * (uint32_t)kBlockThreads;
     }   // (else buildArgs gave the scene's own area: one slice per CU, and blocks <= cuCount)
-    if (!ctx->havePixelList || list.capacity > ctx->pixelListCapacity) {
-        // grow-only, allocated on first use (hipFree waits for a launch that still reads the smaller list)
-        if (ctx->dPixelList) (void)hipFree(ctx->dPixelList);
-        if (ctx->dPixelListScratch) (void)hipFree(ctx->dPixelListScratch);
-        ctx->dPixelList = nullptr; ctx->dPixelListScratch = nullptr; ctx->havePixelList = false;
-        HIP_TRY(ctx, hipMalloc(&ctx->dPixelList, RTOW_PIXEL_LIST_BYTES(list.capacity)), RTOW_ERROR_MEMORY_ALLOCATION);
-        HIP_TRY(ctx, hipMalloc(&ctx->dPixelListScratch, (((size_t)list.capacity + 63u) / 64u + 1u) * sizeof(unsigned)), RTOW_ERROR_MEMORY_ALLOCATION);
-        ctx->pixelListCapacity = list.capacity;
-        ctx->havePixelList = true;
-    }
+    // grow-only, allocated on first use (freeing waits for a launch that still reads the smaller list); a list of capacity 0 has its four header words and a scratch word
+    RTOW_TRY(growDevice(ctx, {{&ctx->dPixelList, RTOW_PIXEL_LIST_BYTES(list.capacity)}, {&ctx->dPixelListScratch, (((size_t)list.capacity + 63u) / 64u + 1u) * sizeof(unsigned)}}));
     // the context's list, ticket counter, batch table and candidate lists are the previous batch's until it has finished (launchSample)
     if (ctx->haveBatchDone) HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->evBatchDone, 0), RTOW_ERROR_LAUNCH_FAILURE);
     HIP_TRY(ctx, launchFilterPixelList(list.words, list.capacity, ownedPixels, ctx->dPixelListScratch, ctx->dPixelList, stream), RTOW_ERROR_LAUNCH_FAILURE);
@@ -745,8 +740,10 @@ int sizeHitSpill(RtowContext ctx, uint32_t sceneKind, bool exactTies, int entity
     const uint64_t cap = listCapacity(ctx, volumes);
     if (most > cap) most = cap;
     const uint32_t entries = most > (uint64_t)kLocalHitEntries ? (uint32_t)(most - kLocalHitEntries) : 0u;
-    if (entries > ctx->hitSpillCapacity) ctx->hitSpillEntries = 0;
-    RTOW_TRY(growDevice(ctx, ctx->hitSpillCapacity, entries, {devBuf(ctx->dHitSpill, (size_t)entries * (size_t)ctx->cuCount * kBlockThreads * sizeof(uint4))}));
+    bool grew = false;
+    const int reserved = growDevice(ctx, {{&ctx->dHitSpill, (size_t)entries * (size_t)ctx->cuCount * kBlockThreads * sizeof(uint4)}}, &grew);
+    if (grew) ctx->hitSpillEntries = 0;
+    RTOW_TRY(reserved);
     ctx->hitSpillEntries = entries;
     return RTOW_SUCCESS;
 }
@@ -765,7 +762,7 @@ bool growHitList(RtowContext ctx)
     if (volumes || ctx->scene.layout.exactTies) {
         size_t freeBytes = 0, totalBytes = 0;
         if (hipMemGetInfo(&freeBytes, &totalBytes) != hipSuccess) { (void)hipGetLastError(); return false; }
-        const uint64_t held = (uint64_t)ctx->hitSpillCapacity * (uint64_t)ctx->cuCount * kBlockThreads * sizeof(uint4);
+        const uint64_t held = ctx->dHitSpill.bytes();
         const uint64_t need = (next - kLocalHitEntries) * (uint64_t)ctx->cuCount * kBlockThreads * sizeof(uint4);
         if (need > held && need > (freeBytes + held) / 4u) return false;
     }
@@ -856,8 +853,8 @@ uint8_t* mappedHost(RtowContext ctx, const void* p, size_t bytes)
 int prepareStaging(RtowContext ctx, int count, const RtowSampleParams* p, void* const* diagnostics, std::vector<void*>& devDiag)
 {
     const size_t pixels = (size_t)(int)p->size.x * (size_t)(int)p->size.y, diagBytes = pixels * (size_t)p->diagnosticsStride;
-    RTOW_TRY(growDevice(ctx, ctx->stagingPixels, pixels, {devBuf(ctx->dColor, pixels * 16), devBuf(ctx->dNormal, pixels * 12), devBuf(ctx->dAlbedo, pixels * 12), devBuf(ctx->dScw, pixels * 4)}));
-    RTOW_TRY(growDevice(ctx, ctx->stagingDiagBytes, diagnostics ? diagBytes * (size_t)count : 0, {devBuf(ctx->dDiag, diagBytes * (size_t)count)}));
+    RTOW_TRY(growDevice(ctx, {{&ctx->dColor, pixels * 16}, {&ctx->dNormal, pixels * 12}, {&ctx->dAlbedo, pixels * 12}, {&ctx->dScw, pixels * 4}}));
+    RTOW_TRY(growDevice(ctx, {{&ctx->dDiag, diagnostics ? diagBytes * (size_t)count : 0}}));
     devDiag.assign((size_t)count, nullptr);
     if (diagnostics) for (int b = 0; b < count; b++) devDiag[(size_t)b] = diagnostics[b] ? ctx->dDiag + (size_t)b * diagBytes : nullptr;
     return RTOW_SUCCESS;
@@ -1109,18 +1106,17 @@ RTOW_API int rtowCreateContext(const RtowContextOptions* options, RtowContext* o
     ok = ok && hipEventCreateWithFlags(&ctx->evBatchDone, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&ctx->evGatherDone, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&ctx->evMetricsDone, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipMalloc(&ctx->dWorkCounter, sizeof(unsigned int)) == hipSuccess;
-    ok = ok && hipMalloc(&ctx->dPartials, sizeof(MetricsPartial) * kMetricsBlocks) == hipSuccess;
+    ok = ok && ctx->dWorkCounter.ensure(sizeof(unsigned int)) == hipSuccess;
+    ok = ok && ctx->dPartials.ensure(sizeof(MetricsPartial) * kMetricsBlocks) == hipSuccess;
     // the finalize pass may be given any stream later: the table is complete before the context exists for the caller
-    ok = ok && hipMalloc(&ctx->dByteThresholds, kByteThresholdTableBytes) == hipSuccess;
+    ok = ok && ctx->dByteThresholds.ensure(kByteThresholdTableBytes) == hipSuccess;
     ok = ok && launchBuildByteThresholds(ctx->dByteThresholds, ctx->stream) == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess;
-    void* pinned = nullptr;
-    ok = ok && hipHostMalloc(&pinned, 256, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
+    ok = ok && ctx->pinned.allocate(256, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
     void* pinnedDevice = nullptr;
-    ok = ok && hipHostGetDevicePointer(&pinnedDevice, pinned, 0) == hipSuccess;
-    if (!ok) { if (pinned) (void)hipHostFree(pinned); rtowDestroyContext(ctx); return RTOW_ERROR_MEMORY_ALLOCATION; }
-    ctx->hCancel = (volatile uint32_t*)pinned;
-    ctx->hMetricsRecord = (volatile RtowMetrics*)((uint8_t*)pinned + 64);         // where the blocking metrics reduction has its record written by the device
+    ok = ok && hipHostGetDevicePointer(&pinnedDevice, ctx->pinned.get(), 0) == hipSuccess;
+    if (!ok) { rtowDestroyContext(ctx); return RTOW_ERROR_MEMORY_ALLOCATION; }
+    ctx->hCancel = (volatile uint32_t*)ctx->pinned.get();
+    ctx->hMetricsRecord = (volatile RtowMetrics*)((uint8_t*)ctx->pinned.get() + 64);        // where the blocking metrics reduction has its record written by the device
     ctx->dMetricsRecord = (RtowMetrics*)((uint8_t*)pinnedDevice + 64);
     ctx->hCancel[0] = 0u;
     ctx->hCancel[1] = 0u;
@@ -1154,47 +1150,9 @@ RTOW_API int rtowDestroyContext(RtowContext ctx)
     if (!ctx) return RTOW_ERROR_INVALID_VALUE;
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->dScene) (void)hipFree(ctx->dScene);
-    if (ctx->dEntityOfPrim) (void)hipFree(ctx->dEntityOfPrim);
-    if (ctx->dPrimOfEntity) (void)hipFree(ctx->dPrimOfEntity);
-    if (ctx->dWorkCounter) (void)hipFree(ctx->dWorkCounter);
-    if (ctx->dChunkCost) { (void)hipFree(ctx->dChunkCost); (void)hipFree(ctx->dChunkOrder); (void)hipFree(ctx->dPixelCost); (void)hipFree(ctx->dTicketMap); }
-    if (ctx->dChunkDone) (void)hipFree(ctx->dChunkDone);
-    if (ctx->dXcdState) (void)hipFree(ctx->dXcdState);
-    if (ctx->dChainBatches) (void)hipFree(ctx->dChainBatches);
-    if (ctx->dPixCand) (void)hipFree(ctx->dPixCand);
-    if (ctx->dCubemap) (void)hipFree(ctx->dCubemap);
-    if (ctx->dBlueNoise) (void)hipFree(ctx->dBlueNoise);
-    if (ctx->dStbNoise) (void)hipFree(ctx->dStbNoise);
-    if (ctx->dTexBlob) (void)hipFree(ctx->dTexBlob);
-    if (ctx->dRefTree) (void)hipFree(ctx->dRefTree);
-    if (ctx->dHitSpill) (void)hipFree(ctx->dHitSpill);
-    if (ctx->dUnitRecords) (void)hipFree(ctx->dUnitRecords);
-    if (ctx->dPartials) (void)hipFree(ctx->dPartials);
-    if (ctx->dExtremaPartials) (void)hipFree(ctx->dExtremaPartials);
-    if (ctx->dExtremaKeys) (void)hipFree(ctx->dExtremaKeys);
-    if (ctx->dByteThresholds) (void)hipFree(ctx->dByteThresholds);
     dropThresholdTuning(ctx);
-    if (ctx->dProbeSink) (void)hipFree(ctx->dProbeSink);
-    if (ctx->dTieRedo) (void)hipFree(ctx->dTieRedo);
-    if (ctx->dTieBits) (void)hipFree(ctx->dTieBits);
-    if (ctx->dTieInputs) (void)hipFree(ctx->dTieInputs);
-    if (ctx->dHistSpill) (void)hipFree(ctx->dHistSpill);
-    if (ctx->dRedoSpill) (void)hipFree(ctx->dRedoSpill);
-    if (ctx->dPixelList) (void)hipFree(ctx->dPixelList);
-    if (ctx->dPixelListScratch) (void)hipFree(ctx->dPixelListScratch);
-    if (ctx->dListSpill) (void)hipFree(ctx->dListSpill);
-    if (ctx->hCancel) (void)hipHostFree((void*)ctx->hCancel);
-    if (ctx->dColor) { (void)hipFree(ctx->dColor); (void)hipFree(ctx->dNormal); (void)hipFree(ctx->dAlbedo); (void)hipFree(ctx->dScw); }
-    if (ctx->dDiag) (void)hipFree(ctx->dDiag);
     releaseComm(ctx);
     for (const RtowContext_t::HostRange& r : ctx->hostRanges) (void)hipHostUnregister(r.base);
-    ctx->hostRanges.clear();
-    if (ctx->evStart) (void)hipEventDestroy(ctx->evStart);
-    if (ctx->evStop) (void)hipEventDestroy(ctx->evStop);
-    if (ctx->evBatchDone) (void)hipEventDestroy(ctx->evBatchDone);
-    if (ctx->evMetricsDone) (void)hipEventDestroy(ctx->evMetricsDone);
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return RTOW_SUCCESS;
 }
@@ -1214,15 +1172,15 @@ RTOW_API int rtowUploadScene(RtowContext ctx, const RtowSceneDesc* scene)
         return rc;
     }
     HIP_TRY(ctx, hipDeviceSynchronize(), RTOW_ERROR_LAUNCH_FAILURE);   // no batch (on whatever stream it was given) may still be reading the old scene
-    RTOW_TRY(growDevice(ctx, ctx->dSceneCapacity, compiled.blob.size(), {devBuf(ctx->dScene, compiled.blob.size())}));
+    RTOW_TRY(growDevice(ctx, {{&ctx->dScene, compiled.blob.size()}}));
     HIP_TRY(ctx, hipMemcpy(ctx->dScene, compiled.blob.data(), compiled.blob.size(), hipMemcpyHostToDevice), RTOW_ERROR_LAUNCH_FAILURE);
     if (!compiled.entityOfPrim.empty()) {      // all-triangle scenes: the device queries report the host's entity index, as rtowProbeNearestHit does
         const size_t n = compiled.entityOfPrim.size();
-        RTOW_TRY(growDevice(ctx, ctx->entityOfPrimCapacity, n, {devBuf(ctx->dEntityOfPrim, n * sizeof(int32_t))}));
+        RTOW_TRY(growDevice(ctx, {{&ctx->dEntityOfPrim, n * sizeof(int32_t)}}));
         HIP_TRY(ctx, hipMemcpy(ctx->dEntityOfPrim, compiled.entityOfPrim.data(), n * sizeof(int32_t), hipMemcpyHostToDevice), RTOW_ERROR_LAUNCH_FAILURE);
     }
     // ... and rtowShadeHitsDevice goes the other way, from the entity index the queries reported to the primitive: the inverse map, -1 for an entity without a primitive
-    if (ctx->dPrimOfEntity) { (void)hipFree(ctx->dPrimOfEntity); ctx->dPrimOfEntity = nullptr; }
+    ctx->dPrimOfEntity.release();
     ctx->primOfEntityCount = 0;      // (the device is idle)
     if (!compiled.entityOfPrim.empty() && compiled.entityCount > 0) {
         std::vector<int32_t> primOfEntity((size_t)compiled.entityCount, -1);
@@ -1230,12 +1188,12 @@ RTOW_API int rtowUploadScene(RtowContext ctx, const RtowSceneDesc* scene)
             const int32_t entity = compiled.entityOfPrim[prim];
             if (entity >= 0 && entity < compiled.entityCount) primOfEntity[(size_t)entity] = (int32_t)prim;
         }
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->dPrimOfEntity, primOfEntity.size() * sizeof(int32_t)), RTOW_ERROR_MEMORY_ALLOCATION);
+        RTOW_TRY(growDevice(ctx, {{&ctx->dPrimOfEntity, primOfEntity.size() * sizeof(int32_t)}}));
         HIP_TRY(ctx, hipMemcpy(ctx->dPrimOfEntity, primOfEntity.data(), primOfEntity.size() * sizeof(int32_t), hipMemcpyHostToDevice), RTOW_ERROR_LAUNCH_FAILURE);
         ctx->primOfEntityCount = compiled.entityCount;
     }
     if (!compiled.texBlob.empty()) {
-        RTOW_TRY(growDevice(ctx, ctx->texBlobCapacity, compiled.texBlob.size(), {devBuf(ctx->dTexBlob, compiled.texBlob.size())}));
+        RTOW_TRY(growDevice(ctx, {{&ctx->dTexBlob, compiled.texBlob.size()}}));
         HIP_TRY(ctx, hipMemcpy(ctx->dTexBlob, compiled.texBlob.data(), compiled.texBlob.size(), hipMemcpyHostToDevice), RTOW_ERROR_LAUNCH_FAILURE);
         compiled.texBlob.clear();
         compiled.texBlob.shrink_to_fit();                                     // the host copy is not needed again
@@ -1243,7 +1201,7 @@ RTOW_API int rtowUploadScene(RtowContext ctx, const RtowSceneDesc* scene)
     if (ctx->flags & RTOW_CONTEXT_REFERENCE_DIAGNOSTICS) {
         // the counters' walk keeps one stack entry per level of the reference tree (+1): 64 entries of scratch
         if (compiled.refTreeDepth > 62) { logf(ctx, 2, "scene", "RTOW_CONTEXT_REFERENCE_DIAGNOSTICS supports MaxBvhDepth <= 62"); return RTOW_ERROR_CAPACITY; }
-        RTOW_TRY(growDevice(ctx, ctx->refTreeCapacity, compiled.refTree.size(), {devBuf(ctx->dRefTree, compiled.refTree.size())}));
+        RTOW_TRY(growDevice(ctx, {{&ctx->dRefTree, compiled.refTree.size()}}));
         HIP_TRY(ctx, hipMemcpy(ctx->dRefTree, compiled.refTree.data(), compiled.refTree.size(), hipMemcpyHostToDevice), RTOW_ERROR_LAUNCH_FAILURE);
     }
     compiled.refTree.clear();
@@ -1320,9 +1278,7 @@ RTOW_API int rtowUploadSkyCubemap(RtowContext ctx, const RtowCubemapDesc* cubema
     HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
     if (!cubemap || !cubemap->faces) {                       // drop it: Cubemap.Sample returns default when the data pointer is null
         HIP_TRY(ctx, hipDeviceSynchronize(), RTOW_ERROR_LAUNCH_FAILURE);
-        if (ctx->dCubemap) (void)hipFree(ctx->dCubemap);
-        ctx->dCubemap = nullptr;
-        ctx->cubemapCapacity = 0;
+        ctx->dCubemap.release();
         ctx->cubemap = RtowCubemapDesc{};
         return RTOW_SUCCESS;
     }
@@ -1334,8 +1290,10 @@ RTOW_API int rtowUploadSkyCubemap(RtowContext ctx, const RtowCubemapDesc* cubema
     const size_t bytes = (size_t)6 * (size_t)cubemap->faceWidth * (size_t)cubemap->faceHeight * (size_t)cubemap->pixelStride;
     if (bytes > 0x7fffffffull) return RTOW_ERROR_CAPACITY;                                      // Cubemap.Sample's strides are int32 here as in the reference (RT/Texture.cs:146-148)
     HIP_TRY(ctx, hipDeviceSynchronize(), RTOW_ERROR_LAUNCH_FAILURE);                            // no batch may still be reading the old faces
-    if (bytes > ctx->cubemapCapacity) ctx->cubemap = RtowCubemapDesc{};
-    RTOW_TRY(growDevice(ctx, ctx->cubemapCapacity, bytes, {devBuf(ctx->dCubemap, bytes)}));
+    bool grew = false;
+    const int reserved = growDevice(ctx, {{&ctx->dCubemap, bytes}}, &grew);
+    if (grew) ctx->cubemap = RtowCubemapDesc{};
+    RTOW_TRY(reserved);
     HIP_TRY(ctx, hipMemcpy(ctx->dCubemap, cubemap->faces, bytes, hipMemcpyHostToDevice), RTOW_ERROR_LAUNCH_FAILURE);
     ctx->cubemap = *cubemap;
     ctx->cubemap.faces = nullptr;
@@ -1350,13 +1308,12 @@ RTOW_API int rtowUploadBlueNoise(RtowContext ctx, const RtowBlueNoiseDesc* noise
     std::lock_guard<std::mutex> lock(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
     HIP_TRY(ctx, hipDeviceSynchronize(), RTOW_ERROR_LAUNCH_FAILURE);
-    if (ctx->dBlueNoise) (void)hipFree(ctx->dBlueNoise);
-    ctx->dBlueNoise = nullptr;
+    ctx->dBlueNoise.release();
     ctx->blueRowStride = ctx->blueTextureCount = 0;
     if (!noise || !noise->texels) return RTOW_SUCCESS;
     if (noise->rowStride == 0 || noise->rowStride > 16384 || noise->textureCount == 0 || noise->textureCount > 4096) return RTOW_ERROR_INVALID_VALUE;
     const size_t bytes = (size_t)noise->rowStride * noise->rowStride * noise->textureCount * 8u;      // half4 texels
-    HIP_TRY(ctx, hipMalloc(&ctx->dBlueNoise, bytes), RTOW_ERROR_MEMORY_ALLOCATION);
+    RTOW_TRY(growDevice(ctx, {{&ctx->dBlueNoise, bytes}}));
     HIP_TRY(ctx, hipMemcpy(ctx->dBlueNoise, noise->texels, bytes, hipMemcpyHostToDevice), RTOW_ERROR_LAUNCH_FAILURE);
     ctx->blueRowStride = noise->rowStride;
     ctx->blueTextureCount = noise->textureCount;
@@ -1369,14 +1326,13 @@ RTOW_API int rtowUploadStbNoise(RtowContext ctx, const RtowStbNoiseDesc* noise)
     std::lock_guard<std::mutex> lock(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
     HIP_TRY(ctx, hipDeviceSynchronize(), RTOW_ERROR_LAUNCH_FAILURE);
-    if (ctx->dStbNoise) (void)hipFree(ctx->dStbNoise);
-    ctx->dStbNoise = nullptr;
+    ctx->dStbNoise.release();
     ctx->stbRowStride = ctx->stbTextureCount = 0;
     if (!noise) return RTOW_SUCCESS;
     if (!noise->scalar || !noise->vector2 || !noise->cosineUnitVector3 || !noise->unitVector2 || !noise->unitVector3) return RTOW_ERROR_INVALID_VALUE;
     if (noise->rowStride == 0 || noise->rowStride > 16384 || noise->textureCount == 0 || noise->textureCount > 4096) return RTOW_ERROR_INVALID_VALUE;
     const size_t all = (size_t)noise->rowStride * noise->rowStride * noise->textureCount;
-    HIP_TRY(ctx, hipMalloc(&ctx->dStbNoise, all * 14u), RTOW_ERROR_MEMORY_ALLOCATION);                // 1 + 3 + 4 + 3 + 3 bytes per texel
+    RTOW_TRY(growDevice(ctx, {{&ctx->dStbNoise, all * 14u}}));                                        // 1 + 3 + 4 + 3 + 3 bytes per texel
     HIP_TRY(ctx, hipMemcpy(ctx->dStbNoise, noise->scalar, all, hipMemcpyHostToDevice), RTOW_ERROR_LAUNCH_FAILURE);
     HIP_TRY(ctx, hipMemcpy(ctx->dStbNoise + all, noise->vector2, all * 3, hipMemcpyHostToDevice), RTOW_ERROR_LAUNCH_FAILURE);
     HIP_TRY(ctx, hipMemcpy(ctx->dStbNoise + all * 4, noise->cosineUnitVector3, all * 4, hipMemcpyHostToDevice), RTOW_ERROR_LAUNCH_FAILURE);
@@ -1453,13 +1409,13 @@ RTOW_API int rtowSampleBatchChainAdaptiveDevice(RtowContext ctx, int32_t count, 
     std::unique_lock<std::mutex> lock;
     hipStream_t s;
     RTOW_TRY(beginSample(ctx, lock, count, params, in, out, oneFrame, stream, &s));
-    if (!ctx->dExtremaPartials) HIP_TRY(ctx, hipMalloc(&ctx->dExtremaPartials, sizeof(RtowFloat2) * kMetricsBlocks), RTOW_ERROR_MEMORY_ALLOCATION);
+    RTOW_TRY(growDevice(ctx, {{&ctx->dExtremaPartials, sizeof(RtowFloat2) * kMetricsBlocks}}));
     const int pixels = (int)params[0].size.x * (int)params[0].size.y;
     const int lag = feed->lag;
     auto source = [&](int k) -> const RtowFloat2* { return k < lag ? (feed->extremaIn ? feed->extremaIn + k : nullptr) : feed->extremaOut + (k - lag); };
     // what a chain fuses, with the extrema free to differ - and a launch of at most `lag` batches, so lag 1 runs batch by batch
     const bool fusable = lag > 1 && canFuse(ctx, count, params, diagnostics, /*handOver*/ true, /*extremaFree*/ true);
-    if (fusable && !ctx->dExtremaKeys) HIP_TRY(ctx, hipMalloc(&ctx->dExtremaKeys, 2u * sizeof(unsigned) * kMaxChain), RTOW_ERROR_MEMORY_ALLOCATION);
+    if (fusable) RTOW_TRY(growDevice(ctx, {{&ctx->dExtremaKeys, 2u * sizeof(unsigned) * kMaxChain}}));
     for (int first = 0; first < count;) {
         int n = fusable ? std::min(count - first, std::min(lag, (int)kMaxChain)) : 1;
         // a batch without a device source reads the launch's kernarg extrema, i.e. batch `first`'s: the others must carry the same values

@@ -168,9 +168,9 @@ int copyRankRows(RtowContext ctx, const RowSet& set, float* const buffers[4], in
 int reserveStaging(RtowContext ctx, hipStream_t s, size_t sendFloats, size_t recvFloats)
 {
     if (ctx->haveGatherDone) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->evGatherDone, 0), RTOW_ERROR_LAUNCH_FAILURE);
-    if (sendFloats > ctx->gatherSendFloats || recvFloats > ctx->gatherRecvFloats) HIP_TRY(ctx, hipStreamSynchronize(s), RTOW_ERROR_LAUNCH_FAILURE);
-    RTOW_TRY(growDevice(ctx, ctx->gatherSendFloats, sendFloats, {devBuf(ctx->dGatherSend, sendFloats * 4u)}));
-    RTOW_TRY(growDevice(ctx, ctx->gatherRecvFloats, recvFloats, {devBuf(ctx->dGatherRecv, recvFloats * 4u)}));
+    if (sendFloats * 4u > ctx->dGatherSend.bytes() || recvFloats * 4u > ctx->dGatherRecv.bytes()) HIP_TRY(ctx, hipStreamSynchronize(s), RTOW_ERROR_LAUNCH_FAILURE);
+    RTOW_TRY(growDevice(ctx, {{&ctx->dGatherSend, sendFloats * 4u}}));
+    RTOW_TRY(growDevice(ctx, {{&ctx->dGatherRecv, recvFloats * 4u}}));
     return RTOW_SUCCESS;
 }
 
@@ -203,9 +203,6 @@ int gatherEnds(RtowContext ctx, hipStream_t s)
 void rtow::releaseComm(RtowContext ctx)
 {
     if (ctx->comm) { if (RcclApi* api = rccl()) (void)api->CommDestroy(ctx->comm); ctx->comm = nullptr; }
-    if (ctx->dGatherSend) (void)hipFree(ctx->dGatherSend);
-    if (ctx->dGatherRecv) (void)hipFree(ctx->dGatherRecv);
-    if (ctx->evGatherDone) (void)hipEventDestroy(ctx->evGatherDone);
 }
 
 extern "C" {

@@ -1,16 +1,16 @@
 // rtow_context.h - the context behind RtowContext and the helpers every translation unit of the C-ABI layer shares (rtow_api.hip, rtow_comm.hip):
-// logging, the error-return macros and the grow-only device buffers.  Internal: nothing here is part of include/rtow.h.
+// logging and the error-return macros.  Internal: nothing here is part of include/rtow.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
 #include <cstdio>
-#include <initializer_list>
 #include <mutex>
 #include <vector>
 
 #include "../../include/rtow.h"
 #include "rtow_bvh.h"
+#include "rtow_device_mem.h"
 #include "rtow_kernels.h"
 
 // The two tuning defaults the context's member initialisers need; the other tuning macros, and what the nine thresholds mean, are at the top of rtow_api.hip.
@@ -25,6 +25,7 @@
 #endif
 
 struct RtowContext_t {
+    template <typename T> using DeviceMem = rtow::DeviceMem<T>;   // every d* member the context allocates: it owns its block, knows its size in bytes, frees it when the context is deleted
     int device = 0;
     int cuCount = 0;
     RtowLogCallback logCb = nullptr;
@@ -40,96 +41,80 @@ struct RtowContext_t {
     // scene
     bool haveScene = false;
     rtow::CompiledScene scene;
-    uint8_t* dScene = nullptr;
-    size_t dSceneCapacity = 0;
-    int32_t* dEntityOfPrim = nullptr;     // device copy of scene.entityOfPrim for rtowTraceRaysDevice / rtowTraceViewDevice (read only while scene.entityOfPrim is not empty)
-    size_t entityOfPrimCapacity = 0;      // in entries
-    int32_t* dPrimOfEntity = nullptr;     // its inverse for rtowShadeHitsDevice: entity -> primitive, -1 for an entity without one; sized by the entity count, allocated under the same
-                                          // condition, freed at every upload and at destroy
+    DeviceMem<uint8_t> dScene;
+    DeviceMem<int32_t> dEntityOfPrim;     // device copy of scene.entityOfPrim for rtowTraceRaysDevice / rtowTraceViewDevice (read only while scene.entityOfPrim is not empty)
+    DeviceMem<int32_t> dPrimOfEntity;     // its inverse for rtowShadeHitsDevice: entity -> primitive, -1 for an entity without one; sized by the entity count, allocated under the same
+                                          // condition, released and allocated at its exact size at every upload
     int32_t primOfEntityCount = 0;        // entries of dPrimOfEntity: what rtowShadeHitsDevice bounds an entity index by, whatever an upload that failed half way left in `scene`
     uint32_t ldsSceneBytes = 0, ldsNodeCount = 0;
-    unsigned short* dHistSpill = nullptr; // path-history rows that do not fit LDS (LdsPlan.histSpillRows), [row][workgroup x 1024 + lane]
-    size_t histSpillBytes = 0;
+    DeviceMem<unsigned short> dHistSpill; // path-history rows that do not fit LDS (LdsPlan.histSpillRows), [row][workgroup x 1024 + lane]
     rtow::LdsPlan ldsPlan{};              // of launches whose variant keeps its whole path history in registers (trace depth <= 16); the others plan per launch (launchSample)
 
     // work distribution / cancellation
-    unsigned int* dWorkCounter = nullptr;
+    DeviceMem<unsigned int> dWorkCounter;
     // chunk cost map -> launch order (longest chunks first); valid for one (width, height, slice, scene) configuration
-    unsigned int* dChunkDone = nullptr;   // chained batches: pixels stored per chunk
-    uint8_t* dXcdState = nullptr;         // chained batches: XcdState + kMaxXcds lists of chunkDoneCapacity entries (which XCD owns which chunk)
-    rtow::ChainBatch* dChainBatches = nullptr;   // chained batches: per-batch seed / diagnostics table of the launch being enqueued
-    uint32_t chunkDoneCapacity = 0;
-    unsigned int *dChunkCost = nullptr, *dChunkOrder = nullptr;
-    unsigned short* dPixelCost = nullptr;
-    unsigned int* dTicketMap = nullptr;   // ticket -> owned pixel (SampleKernelArgs.ticketMap), chunkCapacity * 64 entries; re-sorted from every launch's cost map
+    DeviceMem<unsigned int> dChunkDone;   // chained batches: pixels stored per chunk (grows with dXcdState)
+    DeviceMem<uint8_t> dXcdState;         // chained batches: XcdState + kMaxXcds lists of one entry per chunk (which XCD owns which chunk)
+    DeviceMem<rtow::ChainBatch> dChainBatches;   // chained batches: per-batch seed / diagnostics table of the launch being enqueued
+    DeviceMem<unsigned int> dChunkCost, dChunkOrder;   // these four grow together (prepareChunkOrder)
+    DeviceMem<unsigned short> dPixelCost;
+    DeviceMem<unsigned int> dTicketMap;   // ticket -> owned pixel (SampleKernelArgs.ticketMap), 64 entries per chunk; re-sorted from every launch's cost map
     bool orderMapped = false;             // the cost map / order on hand were recorded under dTicketMap (else under the tiles themselves)
-    uint32_t chunkCapacity = 0;
     bool orderValid = false;
     int orderW = 0, orderH = 0, orderOff = 0, orderDiv = 0;
+    rtow::PinnedBlock pinned;             // the 256 bytes behind the next three
     volatile uint32_t* hCancel = nullptr; // pinned, device-visible: [0] cancel, [1] hit-list overflow, [2] tie-list overflow; the metrics record of rtowReduceMetricsDevice at byte 64
     volatile RtowMetrics* hMetricsRecord = nullptr;
     RtowMetrics* dMetricsRecord = nullptr;
     // RTOW_RNG_PER_SAMPLE: one 64-byte record per (owned pixel, sample group) unit
-    float* dUnitRecords = nullptr;
-    size_t unitRecordCapacity = 0;
+    DeviceMem<float> dUnitRecords;
     uint32_t orderGroups = 1;     // groups per pixel the chunk cost map was recorded with
     // RTOW_CONTEXT_REFERENCE_DIAGNOSTICS: the reference's own tree of the current scene (CompiledScene.refTree), HBM only
-    uint8_t* dRefTree = nullptr;
-    size_t refTreeCapacity = 0;
+    DeviceMem<uint8_t> dRefTree;
     // hit lists beyond the 24 entries a lane holds itself (volume scenes, exact-tie kernels): [entry][lane] columns, grow-only
-    uint4* dHitSpill = nullptr;
-    uint32_t hitSpillEntries = 0;         // of the current scene (<= hitSpillCapacity)
-    uint32_t hitSpillCapacity = 0;        // entries per lane the allocation holds
+    DeviceMem<uint4> dHitSpill;
+    uint32_t hitSpillEntries = 0;         // of the current scene (the block may hold more)
     uint32_t hitListCapacity = 0;         // RtowContextOptions.hitListCapacity (0 = default)
     uint32_t grownListCapacity = 0;       // hitListCapacity == 0 only: what the capacity has grown to after batches that met longer lists (growHitList); kept across scenes
     bool triWatchOff = false;             // this all-triangle scene ties too often for the tie watch (a watched launch marked thousands of pixels, or more than the list holds): exact-tie kernels from now on
     bool overflowGrew = false;            // the last reported overflow enlarged the capacity: the same batch, issued again, has room
     // Image-texture blob of the current scene (CompiledScene.texBlob), HBM only
-    uint8_t* dTexBlob = nullptr;
-    size_t texBlobCapacity = 0;
+    DeviceMem<uint8_t> dTexBlob;
     // noise texture sets (rtowUploadBlueNoise / rtowUploadStbNoise): device copies, `textureCount` textures back to back
-    uint8_t* dBlueNoise = nullptr;
+    DeviceMem<uint8_t> dBlueNoise;
     uint32_t blueRowStride = 0, blueTextureCount = 0;
-    uint8_t* dStbNoise = nullptr;        // scalar | vector2 | cosineUnitVector3 | unitVector2 | unitVector3 sets, in this order
+    DeviceMem<uint8_t> dStbNoise;        // scalar | vector2 | cosineUnitVector3 | unitVector2 | unitVector3 sets, in this order
     uint32_t stbRowStride = 0, stbTextureCount = 0;
     // sky cubemap (rtowUploadSkyCubemap)
-    uint8_t* dCubemap = nullptr;
-    size_t cubemapCapacity = 0;
+    DeviceMem<uint8_t> dCubemap;
     RtowCubemapDesc cubemap{};   // .faces is not kept (host pointer): dCubemap holds the copy, null when none
     // camera-ray candidate lists (primary_candidates_kernel): valid for one (scene upload, view, size, slice, jitter) configuration
-    uint2* dPixCand = nullptr;
-    size_t pixCandCapacity = 0;           // bytes
+    DeviceMem<uint2> dPixCand;
     bool pixCandValid = false;
     uint64_t sceneSerial = 0, pixCandScene = 0;
     RtowView pixCandView{};
     int pixCandW = 0, pixCandH = 0, pixCandOff = 0, pixCandDiv = 0, pixCandJitter = 0;
 
     // grow-only staging for rtowSampleBatch (host buffers) - like CudaBuffer.EnsureCapacity (OptixApi.cs:240-251)
-    float *dColor = nullptr, *dNormal = nullptr, *dAlbedo = nullptr, *dScw = nullptr;
-    uint8_t* dDiag = nullptr;
-    size_t stagingPixels = 0, stagingDiagBytes = 0;
+    DeviceMem<float> dColor, dNormal, dAlbedo, dScw;   // (grow together)
+    DeviceMem<uint8_t> dDiag;
 
-    rtow::MetricsPartial* dPartials = nullptr;
-    RtowFloat2* dExtremaPartials = nullptr;   // [kMetricsBlocks] rtowSampleBatchChainAdaptiveDevice: partials of the per-batch weight-extrema reduction
-    unsigned* dExtremaKeys = nullptr;         // [2 x kMaxChain] ... of a fused launch: every batch's (min, max) folded at store time
+    DeviceMem<rtow::MetricsPartial> dPartials;
+    DeviceMem<RtowFloat2> dExtremaPartials;   // [kMetricsBlocks] rtowSampleBatchChainAdaptiveDevice: partials of the per-batch weight-extrema reduction
+    DeviceMem<unsigned> dExtremaKeys;         // [2 x kMaxChain] ... of a fused launch: every batch's (min, max) folded at store time
 
     // nearest-hit ties of the rank-rule sphere kernels (SampleKernelArgs.tieBits / tieRedo): the bitmap the fast kernel marks, the list the fix-up launch renders, a copy
     // of the inputs of launches that accumulate in place, and the fix-up launch's own (small) hit-list spill area
-    unsigned* dTieRedo = nullptr;
-    unsigned* dTieBits = nullptr;
-    size_t tieBitsWords = 0;
-    float* dTieInputs = nullptr;          // colour | normal | albedo | weight of `tieInputPixels` pixels
-    size_t tieInputPixels = 0;
-    uint4* dRedoSpill = nullptr;
-    uint32_t redoSpillEntries = 0;
+    DeviceMem<unsigned> dTieRedo;
+    DeviceMem<unsigned> dTieBits;
+    DeviceMem<float> dTieInputs;          // colour | normal | albedo | weight of the frame's pixels
+    DeviceMem<uint4> dRedoSpill;
+    uint32_t redoSpillEntries = 0;        // entries of the current plan (prepareTieWatch; the block may hold more)
     // rtowSamplePixelsDevice: the context's own copy of the caller's list (4 + capacity words, entries beyond the frame dropped) with the filter's scan scratch, and the
     // hit-list spill area of a list launch's workgroups.  Not dTieRedo / dRedoSpill: those belong to watched launches in flight
-    unsigned* dPixelList = nullptr;
-    unsigned* dPixelListScratch = nullptr;
-    uint32_t pixelListCapacity = 0;
-    bool havePixelList = false;           // (a capacity of 0 is a valid list: the four header words)
-    uint4* dListSpill = nullptr;
-    uint64_t listSpillSlots = 0;          // entries x workgroups the area holds
+    DeviceMem<unsigned> dPixelList;       // (a capacity of 0 is a valid list: the four header words - so the block's bytes tell a list that is there from none)
+    DeviceMem<unsigned> dPixelListScratch;
+    DeviceMem<uint4> dListSpill;
 
     // RtowContextOptions: behaviour switches and development knobs (nothing is read from the environment)
     bool wideCodes = false;               // current scene: more than 65 535 entities or tree nodes (32-bit candidate / stack codes, tree read from HBM)
@@ -152,7 +137,7 @@ struct RtowContext_t {
     uint64_t tunePendingScene = 0;
     int tuneCandidates = 0, tuneBuiltin = 0;
     std::vector<hipEvent_t> tuneEvents;
-    uint32_t* dProbeSink = nullptr;       // where probes report rays beyond the hit-list capacity (not the batch's flag)
+    DeviceMem<uint32_t> dProbeSink;       // where probes report rays beyond the hit-list capacity (not the batch's flag)
     uint64_t sppSinceUpload = 0;          // samples per pixel this scene has been asked for since its upload: a measurement must be worth its probes
     uint64_t sceneSignatureNow = 0;       // of the current scene
     struct TuneCacheEntry { uint64_t signature; int winner; };
@@ -165,9 +150,8 @@ struct RtowContext_t {
     // rtowComm*: RCCL communicator of this rank (one process per GPU) and the packed-row staging of rtowGatherRowsDevice
     void* comm = nullptr;                 // ncclComm_t
     int commRank = 0, commWorld = 1;
-    float *dGatherSend = nullptr, *dGatherRecv = nullptr;
-    size_t gatherSendFloats = 0, gatherRecvFloats = 0;
-    float* dByteThresholds = nullptr;     // FinalizeTexturesJob's float -> byte step table (rtow_finalize.hip.h), built when the context is created
+    DeviceMem<float> dGatherSend, dGatherRecv;
+    DeviceMem<float> dByteThresholds;     // FinalizeTexturesJob's float -> byte step table (rtow_finalize.hip.h), built when the context is created
     hipEvent_t evGatherDone = nullptr;    // end of the last gather: the staging blocks are per context, gathers may come on different streams
     bool haveGatherDone = false;
     hipEvent_t evMetricsDone = nullptr;   // end of the last metrics reduction (the per-block partials are per context)
@@ -175,6 +159,12 @@ struct RtowContext_t {
 
     std::mutex mu;
     std::mutex sceneMu;      // guards the HOST image of the scene (scene.blob / layout / entityOfPrim, haveScene) between rtowUploadScene and rtowProbeNearestHit; taken after mu, never the other way round
+
+    ~RtowContext_t()      // rtowDestroyContext has set the device, waited for the stream and destroyed the communicator; the blocks above free themselves after this
+    {
+        for (hipEvent_t e : {evStart, evStop, evBatchDone, evGatherDone, evMetricsDone}) if (e) (void)hipEventDestroy(e);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
 };
 
 namespace rtow {
@@ -205,23 +195,14 @@ inline void logf(RtowContext ctx, int level, const char* tag, const char* fmt, .
         if (_rc != RTOW_SUCCESS) return _rc;                                                          \
     } while (0)
 
-// Grow-only device buffers of the context: when `need` exceeds `capacity` (in the caller's unit) each buffer is freed and allocated again at its own size - the
-// contents are not kept - and `capacity` becomes `need`.  Several buffers may share one capacity.  A failed allocation leaves the capacity 0, so the next call
-// allocates again.  Callers do around it what the old buffer needs first (a batch in flight may still read it) and what a new one invalidates.
-struct DeviceBuf { void** p; size_t bytes; };
-template <typename T> DeviceBuf devBuf(T*& p, size_t bytes) { return DeviceBuf{reinterpret_cast<void**>(&p), bytes}; }
-template <typename C>
-int growDevice(RtowContext ctx, C& capacity, uint64_t need, std::initializer_list<DeviceBuf> bufs)
+// DeviceBlock::ensureAll with the context's log line and error code: blocks that grow together in one call, `grew` as there
+inline int growDevice(RtowContext ctx, std::initializer_list<DeviceBlock::Need> needs, bool* grew = nullptr)
 {
-    if (need <= (uint64_t)capacity) return RTOW_SUCCESS;
-    for (const DeviceBuf& b : bufs) { if (*b.p) (void)hipFree(*b.p); *b.p = nullptr; }
-    capacity = 0;
-    for (const DeviceBuf& b : bufs) HIP_TRY(ctx, hipMalloc(b.p, b.bytes), RTOW_ERROR_MEMORY_ALLOCATION);
-    capacity = (C)need;
+    HIP_TRY(ctx, DeviceBlock::ensureAll(needs, grew), RTOW_ERROR_MEMORY_ALLOCATION);
     return RTOW_SUCCESS;
 }
 
-// rtow_comm.hip, for rtowDestroyContext: destroys the communicator, frees the packed-row staging blocks and evGatherDone
+// rtow_comm.hip, for rtowDestroyContext: destroys the communicator (before the context's packed-row staging goes)
 void releaseComm(RtowContext ctx);
 
 } // namespace rtow

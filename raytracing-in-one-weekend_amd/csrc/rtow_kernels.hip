@@ -2,6 +2,7 @@
 // node lists, chunk ordering, scene preparation and the post passes (CombineJob, FinalizeTexturesJob, ReduceMetricsJob), and the host
 // launchers of all of them.
 #include "rtow_kernels.h"
+#include "rtow_device_mem.h"
 #include "rtow_surface.hip.h"
 #include "rtow_vecmath.hip.h"
 #include "rtow_finalize.hip.h"
@@ -820,12 +821,9 @@ hipError_t runXcdCoherenceLitmus(int cuCount, hipStream_t stream, unsigned* outP
     const unsigned grid = (unsigned)(cuCount * 2 < 64 ? 64 : (cuCount * 2 > 1024 ? 1024 : cuCount * 2));
     const unsigned pairsPerXcd = grid / 2;
     const int rounds = 48;
-    unsigned *state = nullptr, *flag = nullptr, *ack = nullptr, *data = nullptr;
+    DeviceMem<unsigned> state, flag, ack, data;          // (freed on return: the stream has been waited for by then)
     const size_t pairs = (size_t)kMaxXcds * pairsPerXcd;
-    hipError_t e = hipMalloc(&state, 32 * sizeof(unsigned));
-    if (e == hipSuccess) e = hipMalloc(&flag, pairs * 32 * sizeof(unsigned));
-    if (e == hipSuccess) e = hipMalloc(&ack, pairs * 32 * sizeof(unsigned));
-    if (e == hipSuccess) e = hipMalloc(&data, pairs * 256 * sizeof(unsigned));
+    hipError_t e = DeviceBlock::ensureAll({{&state, 32 * sizeof(unsigned)}, {&flag, pairs * 32 * sizeof(unsigned)}, {&ack, pairs * 32 * sizeof(unsigned)}, {&data, pairs * 256 * sizeof(unsigned)}});
     if (e == hipSuccess) e = hipMemsetAsync(state, 0, 32 * sizeof(unsigned), stream);
     if (e == hipSuccess) e = hipMemsetAsync(flag, 0, pairs * 32 * sizeof(unsigned), stream);
     if (e == hipSuccess) e = hipMemsetAsync(ack, 0, pairs * 32 * sizeof(unsigned), stream);
@@ -837,10 +835,6 @@ hipError_t runXcdCoherenceLitmus(int cuCount, hipStream_t stream, unsigned* outP
     }
     if (e == hipSuccess) e = hipMemcpyAsync(host, state, sizeof(host), hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (state) (void)hipFree(state);
-    if (flag) (void)hipFree(flag);
-    if (ack) (void)hipFree(ack);
-    if (data) (void)hipFree(data);
     *outPairs = host[19]; *outStale = host[17]; *outTimeouts = host[18];
     return e;
 }
