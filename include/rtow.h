@@ -776,6 +776,71 @@ RTOW_API int rtowDenoiseDevice(RtowContext context, const RtowDenoiseParams* par
                                const float* inColor, const float* inNormal, const float* inAlbedo,
                                void* scratch, float* outColor, void* stream);
 
+/* ---- variance-guided denoising: per-pixel luminance moments over batches, and an a-trous filter whose colour term follows the local variance ----
+ * rtowDenoiseDevice stops at colour edges with one fixed colorSigma, tuned on a 4-spp frame: a cleaner frame is blurred as much, a noisier one hardly smoothed.
+ * The spread of the per-batch means of a pixel says how noisy that pixel is.  rtowSampleBatchGroupDevice renders up to 16 independent batches of one frame,
+ * each from zero into its own outs[k] (the sub-batches of a tiles x batches partition are the same kind of partial sums): rtowAccumulateMomentsDevice turns
+ * their colours into per-pixel moments of the luminance, and rtowDenoiseVarianceDevice is the a-trous filter above with the colour term of the spatial part of SVGF
+ * (Schied et al., HPG 2017, sections 4.2 - 4.4): the colour weight is scaled by the 3 x 3 filtered variance, and the variance is carried through the levels.
+ * Not here: temporal accumulation of the moments across a camera move (rtowReprojectAccumDevice does not carry them: a reprojected frame restarts its moments),
+ * and moments for chains that accumulate in place (a chain leaves no per-batch colours).
+ * Both added after API version 12 without changing it: a host detects the calls by their entry points (C#: EntryPointNotFoundException).
+ *
+ * rtowAccumulateMomentsDevice: moments (s1, s2, n) = (sum of l, sum of l * l, how many) of the per-batch mean luminance l, float3 per pixel.  Meant for batches of
+ * EQUAL sample count (the variance below weighs every batch alike).  Per pixel p, float32, no contraction, correctly rounded `/`:
+ *   (s1, s2, n) = inMoments[p], or (0, 0, 0) when inMoments is NULL;
+ *   for k = 0 .. count-1 in order, c = colors[k][p] (float4: rgb sums, w = successful samples): skipped unless c.w > 0 (NaN skips);
+ *     m = c.xyz / c.w per channel; l = (0.2126f * m.x + 0.7152f * m.y) + 0.0722f * m.z; skipped if l is not finite;
+ *     s1 = s1 + l; s2 = s2 + l * l; n = n + 1;
+ *   outMoments[p] = (s1, s2, n).
+ * inMoments == outMoments is allowed (in place: a host continues over the kicks of a frame); the buffers need 4-byte alignment only.  One launch; the `count`
+ * pointers travel in the kernel arguments: no allocation, no wait, so the call may be captured in a graph.
+ * Validation (RTOW_ERROR_INVALID_VALUE, nothing enqueued): a NULL context, colors, colors[k] or outMoments; pixelCount <= 0; count outside 1..16; outMoments
+ * overlapping a colour buffer, or overlapping inMoments other than exactly.
+ * Measured (profiles/r12_denoise_variance.json, HIP events on the caller's stream): count 4 / 16 at 1920 x 1080 0.030 / 0.113 ms, at 3840 x 2160 0.141 / 0.467 ms. */
+#define RTOW_MOMENTS_BYTES(pixelCount) ((size_t)(pixelCount) * (size_t)12)
+RTOW_API int rtowAccumulateMomentsDevice(RtowContext context, int32_t pixelCount, int32_t count,
+                                         const float* const* colors /* [count] host array of device float4[pixelCount]: outs[k].color */,
+                                         const float* inMoments /* device float3[pixelCount] or NULL = zeros */,
+                                         float* outMoments /* device float3[pixelCount] */, void* stream);
+
+/* rtowDenoiseVarianceDevice: RtowDenoiseParams and its ranges as rtowDenoiseDevice, but colorSigma multiplies the LOCAL standard deviation of the luminance,
+ * and the colour term has no (1 << 2k) level scaling: the filtered variance shrinks by itself.
+ * `scratch`: RTOW_DENOISE_VARIANCE_SCRATCH_BYTES(w, h) of device memory, never NULL: the colour ping-pong plane (float3) and two variance planes (float).
+ * Numeric specification (float32, in this order; no contraction, correctly rounded `/`; no exp, no pow, no sqrt):
+ *   lum(c) = (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z.
+ *   initial variance v0(p), (s1, s2, n) = moments[p]: unless n >= 2 unknown, carried as -1; else mean = s1 / n, d = s2 - s1 * mean, d = d > 0 ? d : 0,
+ *     v = d / (n * (n - 1)) (the variance of the mean); a non-finite v is unknown; with DEMODULATE_ALBEDO la = lum(albedo[p]), and la >= 2^-10 gives v = v / (la * la).
+ *     A variance v is known when v >= 0 (a NaN is unknown).
+ *   level k: taps, order, skip rules, wn, wa, centre weight, pass-through of a non-finite centre, demodulation and remodulation are exactly rtowDenoiseDevice's;
+ *     the variance plane of level k is level k-1's output (level 0: v0).
+ *     colour term: off (wc = 1, not computed) when v_p is unknown or colorSigma == 0.  Else g_p = num / den, the 3 x 3 filtered variance: q = p + (i, j),
+ *       j = -1..1 (outer), i = -1..1 (inner), weights {1/4, 1/2, 1/4} per axis, over the in-image taps with v_q known; num and den start at +0 and add
+ *       (t(i) * t(j)) * v_q and t(i) * t(j) in that order.  invC_p = 1 / ((colorSigma * colorSigma) * g_p + 2^-20) (the product of the sigmas on the host);
+ *       dl = lum(c_p) - lum(c_q) of the level's (demodulated) colours; wc = 1 / (1 + (dl * dl) * invC_p).
+ *     variance out: an unknown v_p gives -1.  A known v_p: vacc starts at +0 and adds (w * w) * v_q in tap order over the centre (w = 9/64) and every accepted tap
+ *       with v_q known (a tap with unknown v_q adds to the colour only); v_out = vacc / (wsum * wsum), and a v_out that is not >= 0 (a NaN of 0 * inf) becomes -1:
+ *       no NaN is ever stored.  A pixel that passes through keeps v_p.
+ *   outVariance (may be NULL) receives the last level's v_out, -1 where unknown, in the demodulated scale when that flag is set.
+ * Consequences: with colorSigma == 0, or with every n < 2, outColor is rtowDenoiseDevice's at colorSigma 0, bit for bit.
+ * Validation (RTOW_ERROR_INVALID_VALUE, nothing enqueued): that of rtowDenoiseDevice, and a NULL moments or scratch; outColor, outVariance or the scratch
+ * overlapping an input, moments, or each other.  Enqueued on `stream` (NULL = the context's own): the initial-variance launch and one launch per level; no
+ * allocation, no wait, so the call may be captured in a graph.
+ * Recommended (abi.DENOISE_VARIANCE_DEFAULT_*): iterations 5, normalSharpness 2, colorSigma 2, albedoSigma 0.125, DEMODULATE_ALBEDO - chosen on a grid of
+ * colorSigma {1, 1.5, 2, 3, 4, 8} x albedoSigma {0.125, 0.25, 0.5, 1} x normalSharpness {0, 2, 4, 6} (profiles/denoise_variance_timing.py --quality,
+ * profiles/r12_denoise_variance.json) on two cover-scene frames rendered as batch groups, 192 x 108, against 1024 spp (tests/test_gpu_denoise_variance.py): squared error
+ * of the denoised frame over the noisy frame's at 4 x 1 spp / 16 x 4 spp 0.479 / 0.811; rtowDenoiseDevice with its recommended set on the same frames 0.504 / 1.798
+ * (its fixed sigma makes the 64-spp frame worse).  8 of the 96 grid points keep both ratios within 0.5 / below 1; the chosen one has the smallest sum among those
+ * with normalSharpness >= 2 (sharpness 0 reaches 0.492 / 0.783 with colorSigma 1.5).  At 4 spp the gain over the plain filter is small: four batch means of one
+ * sample each give a variance estimate that is itself very noisy.
+ * Measured (the same file, HIP events on the caller's stream): 5 levels at 1920 x 1080 0.87 ms against rtowDenoiseDevice's 0.69 (1.26 x; 1.09 x .. 1.27 x over 1..8
+ * levels), at 3840 x 2160 3.40 ms against 2.72 (1.25 x). */
+#define RTOW_DENOISE_VARIANCE_SCRATCH_BYTES(w, h) ((size_t)(w) * (size_t)(h) * (size_t)20)
+RTOW_API int rtowDenoiseVarianceDevice(RtowContext context, const RtowDenoiseParams* params,
+                                       const float* inColor, const float* inNormal, const float* inAlbedo,
+                                       const float* moments /* device float3[w*h]: rtowAccumulateMomentsDevice's */,
+                                       void* scratch, float* outColor, float* outVariance /* device float[w*h] or NULL */, void* stream);
+
 /* ---- temporal reuse across a camera move: the previous view's accumulators, seen from the new view ----
  * replaces: the ZeroMemory of the four accumulation buffers in ScheduleSample(firstBatch) (UNITY/Raytracer.cs:616-626) when the reset's only cause is
  * cameraDirty (:483-489) and the world is static: instead of starting the moved camera's frame from zero, every pixel starts from the sums of the previous

@@ -325,6 +325,28 @@ def denoise_scratch_bytes(width, height):
     return int(width) * int(height) * 12
 
 
+# rtowAccumulateMomentsDevice / rtowDenoiseVarianceDevice (include/rtow.h)
+MOMENTS_MAX_BATCHES = 16                 # colour buffers one rtowAccumulateMomentsDevice call reads
+DENOISE_VARIANCE_UNKNOWN = -1.0          # outVariance where a pixel has no variance estimate
+# recommended settings of rtowDenoiseVarianceDevice: the best point of profiles/denoise_variance_timing.py's grid on tests/test_gpu_denoise_variance.py's two
+# quality frames (profiles/r12_denoise_variance.json); colorSigma multiplies the local standard deviation here
+DENOISE_VARIANCE_DEFAULT_ITERATIONS = 5
+DENOISE_VARIANCE_DEFAULT_NORMAL_SHARPNESS = 2
+DENOISE_VARIANCE_DEFAULT_COLOR_SIGMA = 2.0
+DENOISE_VARIANCE_DEFAULT_ALBEDO_SIGMA = 0.125
+DENOISE_VARIANCE_DEFAULT_FLAGS = RTOW_DENOISE_DEMODULATE_ALBEDO
+
+
+def moments_bytes(pixel_count):
+    """RTOW_MOMENTS_BYTES(pixelCount): (s1, s2, n) float3 per pixel"""
+    return int(pixel_count) * 12
+
+
+def denoise_variance_scratch_bytes(width, height):
+    """RTOW_DENOISE_VARIANCE_SCRATCH_BYTES(w, h): the ping-pong float3 colour plane and two float variance planes"""
+    return int(width) * int(height) * 20
+
+
 # every symbol include/rtow.h declares (tests/test_abi.py checks the library exports all of them)
 EXPORTED_SYMBOLS = [
     "rtowGetApiVersion", "rtowErrorString", "rtowCreateContext", "rtowDestroyContext", "rtowUploadScene",
@@ -337,4 +359,5 @@ EXPORTED_SYMBOLS = [
     "rtowDenoiseDevice", "rtowTraceRaysDevice", "rtowTraceViewDevice", "rtowReprojectAccumDevice", "rtowShadeHitsDevice",
     "rtowTraceRaysIntervalDevice", "rtowTraceOcclusionDevice", "rtowProbeNearestHitInterval", "rtowUpsampleDevice",
     "rtowBuildPixelListDevice", "rtowSamplePixelsDevice", "rtowTraceGuideRaysDevice", "rtowTraceGuideViewDevice",
+    "rtowAccumulateMomentsDevice", "rtowDenoiseVarianceDevice",
 ]

@@ -1766,6 +1766,47 @@ RTOW_API int rtowDenoiseDevice(RtowContext ctx, const RtowDenoiseParams* params,
     return RTOW_SUCCESS;
 }
 
+RTOW_API int rtowAccumulateMomentsDevice(RtowContext ctx, int32_t pixelCount, int32_t count, const float* const* colors, const float* inMoments, float* outMoments,
+                                         void* stream)
+{
+    if (!ctx || !colors || !outMoments || pixelCount <= 0 || count < 1 || count > kMomentsMaxBatches) return RTOW_ERROR_INVALID_VALUE;
+    // a lane reads its own pixel of every buffer before it writes its own moments: the only overlap that is safe is inMoments == outMoments
+    const Range out{outMoments, (size_t)pixelCount * 12};
+    for (int k = 0; k < count; ++k)
+        if (!colors[k] || overlaps(out, Range{colors[k], (size_t)pixelCount * 16})) return RTOW_ERROR_INVALID_VALUE;
+    if (inMoments != outMoments && overlaps(out, Range{inMoments, (size_t)pixelCount * 12})) return RTOW_ERROR_INVALID_VALUE;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    hipStream_t s;
+    RTOW_TRY(useDevice(ctx, stream, &s));
+    HIP_TRY(ctx, launchAccumulateMoments(pixelCount, count, colors, inMoments, outMoments, s), RTOW_ERROR_LAUNCH_FAILURE);
+    return RTOW_SUCCESS;
+}
+
+RTOW_API int rtowDenoiseVarianceDevice(RtowContext ctx, const RtowDenoiseParams* params, const float* inColor, const float* inNormal, const float* inAlbedo,
+                                       const float* moments, void* scratch, float* outColor, float* outVariance, void* stream)
+{
+    if (!ctx || !params || !inColor || !inNormal || !inAlbedo || !moments || !scratch || !outColor) return RTOW_ERROR_INVALID_VALUE;
+    const RtowDenoiseParams& p = *params;
+    if (p.width <= 0 || p.height <= 0 || (int64_t)p.width * p.height > INT32_MAX) return RTOW_ERROR_INVALID_VALUE;
+    if (p.iterations < 1 || p.iterations > 8 || p.normalSharpness < 0 || p.normalSharpness > 8) return RTOW_ERROR_INVALID_VALUE;
+    if (!(p.colorSigma >= 0.0f && p.colorSigma <= FLT_MAX) || !(p.albedoSigma >= 0.0f && p.albedoSigma <= FLT_MAX)) return RTOW_ERROR_INVALID_VALUE;   // NaN fails both
+    if ((p.flags & ~(int32_t)RTOW_DENOISE_DEMODULATE_ALBEDO) != 0 || p.reserved != 0) return RTOW_ERROR_INVALID_VALUE;
+    // the levels write outColor, outVariance and the scratch while they read the inputs and each other: no byte of a written buffer may be another buffer's
+    const size_t n = (size_t)p.width * (size_t)p.height;
+    const Range written[3] = {{outColor, n * 12}, {scratch, RTOW_DENOISE_VARIANCE_SCRATCH_BYTES(p.width, p.height)}, {outVariance, n * 4}};     // a null outVariance overlaps nothing
+    for (int i = 0; i < 3; ++i) {
+        for (const void* in : {(const void*)inColor, (const void*)inNormal, (const void*)inAlbedo, (const void*)moments})
+            if (overlaps(written[i], Range{in, n * 12})) return RTOW_ERROR_INVALID_VALUE;
+        for (int j = i + 1; j < 3; ++j)
+            if (overlaps(written[i], written[j])) return RTOW_ERROR_INVALID_VALUE;
+    }
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    hipStream_t s;
+    RTOW_TRY(useDevice(ctx, stream, &s));
+    HIP_TRY(ctx, launchDenoiseVariance(p, inColor, inNormal, inAlbedo, moments, (float*)scratch, outColor, outVariance, s), RTOW_ERROR_LAUNCH_FAILURE);
+    return RTOW_SUCCESS;
+}
+
 RTOW_API int rtowReprojectAccumDevice(RtowContext ctx, const RtowReprojectParams* params, const RtowRay* rays, const RtowHitBuffers* hits, const RtowHitBuffers* previousHits,
                                       const RtowAccumBuffers* previous, const RtowAccumBuffers* out, int32_t* outSource, void* stream)
 {

@@ -2,16 +2,13 @@
 // normal and albedo that CombineJob writes.  The numeric specification is in include/rtow.h next to RtowDenoiseParams (and DESIGN.md 5);
 // tests/denoise_reference.py restates it in numpy and the GPU tests compare the two bit for bit.
 #include "rtow_kernels.h"
+#include "rtow_denoise_taps.hip.h"
 
 namespace rtow {
 
 namespace {
 
-// float3 at a 4-byte aligned address (the buffers are tightly packed float3; a caller may pass views that start 4 bytes into an allocation)
-struct __attribute__((packed, aligned(4))) P3 { float x, y, z; };
-__device__ __forceinline__ P3 ld3(const float* p, size_t index) { return reinterpret_cast<const P3*>(p)[index]; }
-
-constexpr float kDemodMin = 0.0009765625f;      // 2^-10
+using namespace taps;      // P3 / ld3, demod / remod, b3, the guide weights: shared with rtow_denoise_variance.hip
 
 struct DenoiseLevel {
     int width, height;
@@ -23,24 +20,6 @@ struct DenoiseLevel {
     int demodIn, remodOut;      // level 0 / last level with RTOW_DENOISE_DEMODULATE_ALBEDO
     unsigned tilesX, tiles;     // 64 x 4 pixel tiles per row / in all
 };
-
-__device__ __forceinline__ bool finite3(P3 c) { return __builtin_isfinite(c.x) && __builtin_isfinite(c.y) && __builtin_isfinite(c.z); }
-__device__ __forceinline__ bool zero3(P3 n) { return n.x == 0.0f && n.y == 0.0f && n.z == 0.0f; }
-__device__ __forceinline__ float dist2(P3 a, P3 b)
-{
-    const float dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;
-    return (dx * dx + dy * dy) + dz * dz;
-}
-__device__ __forceinline__ P3 demod(P3 c, P3 a)
-{
-    return P3{a.x >= kDemodMin ? c.x / a.x : c.x, a.y >= kDemodMin ? c.y / a.y : c.y, a.z >= kDemodMin ? c.z / a.z : c.z};
-}
-__device__ __forceinline__ P3 remod(P3 r, P3 a)
-{
-    return P3{a.x >= kDemodMin ? r.x * a.x : r.x, a.y >= kDemodMin ? r.y * a.y : r.y, a.z >= kDemodMin ? r.z * a.z : r.z};
-}
-// B3 spline tap h(i), i = -2..2: exact binary fractions, so h(i) * h(j) is exact
-__device__ __forceinline__ float b3(int i) { return i == 0 ? 0.375f : (i == 1 || i == -1) ? 0.25f : 0.0625f; }
 
 // One lane per output pixel; a workgroup is a 64 x 4 tile, so every tap load of a wave reads one contiguous row segment (768 bytes of float3).
 // The guides are read from the inputs at every level.  The 25 taps stay a loop: unrolled, the compiler hoists the loads of several taps and the
@@ -85,16 +64,7 @@ __global__ void __launch_bounds__(256, 8) denoise_level_kernel(DenoiseLevel L, c
                     if (L.demodIn) cq = demod(cq, aq);
                     if (!finite3(cq)) continue;
                     const float wc = L.useColor ? 1.0f / (1.0f + dist2(cp, cq) * L.invC) : 1.0f;
-                    const P3 nq = ld3(normal, q);
-                    const bool nqZero = zero3(nq);
-                    float wn;
-                    if (npZero || nqZero) wn = (npZero && nqZero) ? 1.0f : 0.0f;
-                    else {
-                        float d = (np.x * nq.x + np.y * nq.y) + np.z * nq.z;
-                        d = d > 0.0f ? d : 0.0f;
-                        for (int e = 0; e < L.normalSharpness; ++e) d = d * d;
-                        wn = d;
-                    }
+                    const float wn = normalWeight(np, npZero, ld3(normal, q), L.normalSharpness);
                     const float wa = L.useAlbedo ? 1.0f / (1.0f + dist2(ap, aq) * L.invA) : 1.0f;
                     const float w = ((hij * wc) * wn) * wa;
                     if (!(w > 0.0f)) continue;

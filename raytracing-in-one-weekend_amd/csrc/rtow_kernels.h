@@ -393,6 +393,14 @@ hipError_t launchCombineFinalize(const RtowCombineParams& p, const float* inColo
 // rtowDenoiseDevice (rtow_denoise.hip): one launch per a-trous level on `stream`, ping-pong between scratch and outColor (params validated by the caller)
 hipError_t launchDenoise(const RtowDenoiseParams& p, const float* inColor, const float* inNormal, const float* inAlbedo, float* scratch, float* outColor,
                          hipStream_t stream);
+// rtowAccumulateMomentsDevice (rtow_denoise_variance.hip): one launch on `stream`; the `count` device pointers of the host array `colors` travel in the kernel arguments
+// (arguments validated by the caller)
+constexpr int kMomentsMaxBatches = 16;
+hipError_t launchAccumulateMoments(int pixelCount, int count, const float* const* colors, const float* inMoments, float* outMoments, hipStream_t stream);
+// rtowDenoiseVarianceDevice (rtow_denoise_variance.hip): the initial-variance launch and one launch per a-trous level on `stream`; scratch: the colour ping-pong plane
+// (float3 per pixel), then two variance planes (float per pixel); outVariance may be null (params validated by the caller)
+hipError_t launchDenoiseVariance(const RtowDenoiseParams& p, const float* inColor, const float* inNormal, const float* inAlbedo, const float* moments, float* scratch,
+                                 float* outColor, float* outVariance, hipStream_t stream);
 // rtowReprojectAccumDevice (rtow_reproject.hip): one launch on `stream` (arguments validated by the caller).  The constants of previousView the specification has the
 // host compute, in float32 (this header is compiled without contraction)
 struct ReprojectConstants { float LF, LR, LU, HR, VU; };

@@ -598,6 +598,43 @@ class DenoiseJob:
         return JobHandle(rc)
 
 
+class MomentsJob:
+    """rtowAccumulateMomentsDevice: per-pixel luminance moments (s1, s2, n) over the colour buffers of independent batches of one frame - the `outs[k]` colours of
+    sample_batch_group_device, before they are folded.  Colors: 1 .. 16 device buffers (or raw device addresses) of float4 per pixel; InputMoments: the moments so
+    far (None = zeros; may be OutputMoments itself); OutputMoments: abi.moments_bytes(PixelCount) bytes."""
+
+    def __init__(self, context, PixelCount):
+        self.context, self.PixelCount = context, PixelCount
+        self.Colors = []
+        self.InputMoments = self.OutputMoments = None
+
+    def Schedule(self, stream=None):
+        count = len(self.Colors)
+        colors = (C.c_void_p * max(count, 1))(*[_device_ptr(c) for c in self.Colors])
+        rc = load().rtowAccumulateMomentsDevice(self.context.handle, int(self.PixelCount), count, colors, _device_ptr(self.InputMoments),
+                                                _device_ptr(self.OutputMoments), stream)
+        return JobHandle(rc)
+
+
+class DenoiseVarianceJob(DenoiseJob):
+    """rtowDenoiseVarianceDevice: DenoiseJob's filter with the colour term scaled by the local variance that MomentsJob's moments give (include/rtow.h).  `Moments`:
+    float3 per pixel; `Scratch`: abi.denoise_variance_scratch_bytes(Width, Height) bytes, never None; `OutputVariance` (optional): float per pixel, the filtered
+    variance of the last level, abi.DENOISE_VARIANCE_UNKNOWN where a pixel has no estimate."""
+
+    def __init__(self, context, Width, Height, Iterations=abi.DENOISE_VARIANCE_DEFAULT_ITERATIONS, NormalSharpness=abi.DENOISE_VARIANCE_DEFAULT_NORMAL_SHARPNESS,
+                 ColorSigma=abi.DENOISE_VARIANCE_DEFAULT_COLOR_SIGMA, AlbedoSigma=abi.DENOISE_VARIANCE_DEFAULT_ALBEDO_SIGMA, Flags=abi.DENOISE_VARIANCE_DEFAULT_FLAGS,
+                 Reserved=0):
+        super().__init__(context, Width, Height, Iterations, NormalSharpness, ColorSigma, AlbedoSigma, Flags, Reserved)
+        self.Moments = self.OutputVariance = None
+
+    def Schedule(self, stream=None):
+        p = self.params()
+        rc = load().rtowDenoiseVarianceDevice(self.context.handle, C.byref(p), _device_ptr(self.InputColor), _device_ptr(self.InputNormal),
+                                              _device_ptr(self.InputAlbedo), _device_ptr(self.Moments), _device_ptr(self.Scratch),
+                                              _device_ptr(self.OutputColor), _device_ptr(self.OutputVariance), stream)
+        return JobHandle(rc)
+
+
 class ReprojectJob:
     """rtowReprojectAccumDevice: what replaces the ZeroMemory of ScheduleSample(firstBatch) (UNITY/Raytracer.cs:616-626) after a camera move over a static
     world - the previous view's accumulators gathered to the new view's pixels.  Device buffers (or raw device addresses): Rays / HitDistance / HitEntityIndex

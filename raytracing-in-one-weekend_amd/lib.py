@@ -64,6 +64,8 @@ def load():
     lib.rtowFinalizeDevice.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
     lib.rtowCombineFinalizeDevice.argtypes = [vp, C.POINTER(abi.CombineParams), vp, vp, vp, vp, vp, vp, vp]
     lib.rtowDenoiseDevice.argtypes = [vp, C.POINTER(abi.DenoiseParams), vp, vp, vp, vp, vp, vp]
+    lib.rtowAccumulateMomentsDevice.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(vp), vp, vp, vp]
+    lib.rtowDenoiseVarianceDevice.argtypes = [vp, C.POINTER(abi.DenoiseParams), vp, vp, vp, vp, vp, vp, vp, vp]
     lib.rtowTraceRaysDevice.argtypes = [vp, C.c_int32, vp, C.POINTER(abi.HitBuffers), vp]
     lib.rtowTraceViewDevice.argtypes = [vp, C.POINTER(abi.TraceViewParams), C.POINTER(abi.HitBuffers), vp, vp]
     lib.rtowTraceRaysIntervalDevice.argtypes = [vp, C.c_int32, vp, vp, C.POINTER(abi.HitBuffers), vp]
