@@ -782,8 +782,10 @@ RTOW_API int rtowDenoiseDevice(RtowContext context, const RtowDenoiseParams* par
  * each from zero into its own outs[k] (the sub-batches of a tiles x batches partition are the same kind of partial sums): rtowAccumulateMomentsDevice turns
  * their colours into per-pixel moments of the luminance, and rtowDenoiseVarianceDevice is the a-trous filter above with the colour term of the spatial part of SVGF
  * (Schied et al., HPG 2017, sections 4.2 - 4.4): the colour weight is scaled by the 3 x 3 filtered variance, and the variance is carried through the levels.
- * Not here: temporal accumulation of the moments across a camera move (rtowReprojectAccumDevice does not carry them: a reprojected frame restarts its moments),
- * and moments for chains that accumulate in place (a chain leaves no per-batch colours).
+ * Across a camera move the moments travel with the accumulators: rtowReprojectMomentsDevice (below, after rtowReprojectAccumDevice) gathers them through that call's
+ * source map, and rtowEstimateMomentsDevice gives the pixels that are left without a history - reprojection holes, and every pixel of a frame rendered as a single
+ * batch or as a chain - moments estimated from their neighbourhood.  Not here: per-batch moments for chains that accumulate in place (a chain leaves no per-batch
+ * colours; the spatial estimate is what such frames get).
  * Both added after API version 12 without changing it: a host detects the calls by their entry points (C#: EntryPointNotFoundException).
  *
  * rtowAccumulateMomentsDevice: moments (s1, s2, n) = (sum of l, sum of l * l, how many) of the per-batch mean luminance l, float3 per pixel.  Meant for batches of
@@ -887,6 +889,93 @@ RTOW_API int rtowReprojectAccumDevice(RtowContext context, const RtowReprojectPa
                                       const RtowAccumBuffers* previous, const RtowAccumBuffers* out /* device, W*H each, all four required */,
                                       int32_t* outSource /* device, W*H, or NULL: previous pixel index carried, -1 if none */,
                                       void* stream);
+
+/* ---- temporal moments: the variance estimate carried across a camera move, and filled where there is no history ----
+ * replaces: nothing the reference has; the temporal half of SVGF (Schied et al., HPG 2017, sections 4.1 - 4.2) next to rtowDenoiseVarianceDevice's spatial half.
+ * rtowReprojectAccumDevice carries the colour history to a moved camera; how noisy each pixel is was lost there: the moved frame started with n = 0 everywhere and the
+ * filter ran with its colour term off until two new batches existed.  rtowReprojectMomentsDevice carries the moments (s1, s2, n) of rtowAccumulateMomentsDevice through
+ * the source map that call writes (outSource), and rtowEstimateMomentsDevice is SVGF's spatial fallback: a pixel with fewer than minBatches batches of history takes its
+ * moments from a 7 x 7 neighbourhood of the current frame, weighted by the first-hit guides the host already has, in the same moments format - so
+ * rtowDenoiseVarianceDevice takes the result unchanged.  With inMoments == NULL every pixel is estimated: a variance for frames rendered as one batch or as a chain.
+ * The frame loop after a move: rtowTraceViewDevice, rtowReprojectAccumDevice, rtowReprojectMomentsDevice, rtowSampleBatchGroupDevice, rtowAccumulateMomentsDevice,
+ * rtowAddAccumDevice, rtowEstimateMomentsDevice (into a second moments buffer, or in place), rtowCombineDevice, rtowDenoiseVarianceDevice, rtowFinalizeDevice.
+ * Both are pure functions of their buffers (no resident scene), added after API version 12 without changing it: a host detects the calls by their entry points
+ * (C#: EntryPointNotFoundException).
+ *
+ * rtowReprojectMomentsDevice.  Moments are meant for batches of EQUAL sample count: a host keeps its batch size across the move, so that carried and new batches weigh
+ * alike.  Pixel i (float32, no contraction, correctly rounded `/`):
+ *   q = source[i].  q < 0 or q >= pixelCount: outMoments[i] = (+0, +0, +0); such a q is never used as an address.
+ *   (s1, s2, n) = previousMoments[q], valid iff all three are finite and n >= 1; an invalid triple gives (+0, +0, +0).
+ *   n > (float)maxBatches: k = (float)maxBatches / n, outMoments[i] = (s1 * k, s2 * k, (float)maxBatches).  Otherwise the three floats are copied bit for bit.
+ * The cap keeps the mean s1 / n and makes the carried estimate worth maxBatches batches, as rtowReprojectAccumDevice's maxHistory does to its sums: the batches of
+ * the new view outweigh an old history sooner.
+ * Validation (RTOW_ERROR_INVALID_VALUE, nothing enqueued): a NULL context or buffer; pixelCount <= 0; maxBatches < 1; outMoments overlapping source or
+ * previousMoments (a gather: not in place).  One launch, one lane per pixel; no allocation, no wait, so the call may be captured in a graph.  The buffers need 4-byte
+ * alignment only.
+ * Recommended: maxBatches 16 (abi.REPROJECT_MOMENTS_DEFAULT_MAX_BATCHES; the choice is described below, after rtowEstimateMomentsDevice's specification).
+ * Measured (profiles/r13_temporal_moments.json, HIP events on the caller's stream, the source map of a 2 % dolly on the cover scene): 1920 x 1080 0.012 ms,
+ * 3840 x 2160 0.036 ms. */
+RTOW_API int rtowReprojectMomentsDevice(RtowContext context, int32_t pixelCount,
+                                        const int32_t* source /* device int32[pixelCount]: rtowReprojectAccumDevice's outSource */,
+                                        const float* previousMoments /* device float3[pixelCount], the previous view's */,
+                                        int32_t maxBatches /* >= 1 */,
+                                        float* outMoments /* device float3[pixelCount] */, void* stream);
+
+typedef enum RtowEstimateMomentsFlags { RTOW_ESTIMATE_MOMENTS_MATCH_ENTITY = 1 } RtowEstimateMomentsFlags;
+typedef struct RtowEstimateMomentsParams {
+    int32_t width, height;
+    int32_t minBatches;       /* >= 1: pixels whose n is not >= this are estimated                 recommended: 8 */
+    int32_t minTaps;          /* 2..49: accepted taps (centre included) an estimate needs          recommended: 2 */
+    int32_t normalSharpness;  /* 0..8, as RtowUpsampleParams                                       recommended: 4 */
+    float   depthTolerance;   /* >= 0, finite; relative, as RtowUpsampleParams                     recommended: 0.01 */
+    int32_t flags;            /* RtowEstimateMomentsFlags                   recommended: RTOW_ESTIMATE_MOMENTS_MATCH_ENTITY */
+    int32_t reserved;         /* 0 */
+} RtowEstimateMomentsParams;  /* 32 bytes */
+/* Numeric specification (float32, in this order; no contraction, correctly rounded `/`; no sqrt, no exp, no pow).  Pixel = row * width + col.
+ *   lum(x, y, z) = (0.2126f * x + 0.7152f * y) + 0.0722f * z.
+ *   L(q): c = color[q] is valid iff c.w > 0 (NaN fails); l = lum(c.x / c.w, c.y / c.w, c.z / c.w) is valid iff finite - the per-batch rule of
+ *     rtowAccumulateMomentsDevice, on the accumulated colour.
+ *   Pixel p: (s1, s2, n) = inMoments[p], or (0, 0, 0) when inMoments is NULL.
+ *     n >= (float)minBatches (a NaN n fails, so it is estimated): outMoments[p] = the three floats bit for bit, outFilled[p] = 0 - "unchanged" below means this.
+ *     Otherwise, L(p) invalid: unchanged.
+ *     Otherwise W, S1, S2 start at +0 and taps at 0.  Taps q = p + (i, j), j = -3..3 (outer), i = -3..3 (inner); taps outside the image are skipped.
+ *       The centre tap has w = 1 and consults no guide.  Another tap is skipped if L(q) is invalid; else w = g(p, q), exactly the guide weight of rtowUpsampleDevice's
+ *       specification with both pixels' guides taken from `hits` and this struct's normalSharpness, depthTolerance and MATCH_ENTITY (the sky rule, the entity match,
+ *       fabs(t' - t) <= depthTolerance * t, max(0, n.n') squared normalSharpness times).  A tap is skipped unless w > 0 (NaN included).
+ *       Accepted taps, in tap order: W = W + w; S1 = S1 + w * l; S2 = S2 + w * (l * l); taps += 1.
+ *     taps < minTaps: unchanged.  Else a = S1 / W, b = S2 / W; both finite: outMoments[p] = (a + a, b + b, 2.0f), outFilled[p] = 1; otherwise unchanged.
+ * Consequences: the triple is the neighbourhood's weighted moments scaled to two batches, so rtowDenoiseVarianceDevice's v0 is max(0, b - a * a) up to rounding - the
+ * weighted population variance of the neighbours' luminance (n (n - 1) = 2 cancels the doubling) - and real batches a host later adds with
+ * rtowAccumulateMomentsDevice outweigh the two pseudo-batches.  inMoments == outMoments is safe by construction: the pass reads moments only at its own pixel.
+ * Validation (RTOW_ERROR_INVALID_VALUE, nothing enqueued): a NULL context, params, color, hits, outMoments or any of the three hit arrays; width or height <= 0 or
+ * width * height > INT32_MAX; minBatches < 1, minTaps outside 2..49, normalSharpness outside 0..8; a negative or non-finite depthTolerance; unknown flag bits;
+ * reserved != 0; outMoments or outFilled overlapping color or a hit array, overlapping each other, or overlapping inMoments other than outMoments == inMoments exactly.
+ * Enqueued on `stream` (NULL = the context's own): one launch, a workgroup per 64 x 4 pixel tile; a tile without a pixel to estimate reads only its moments (and writes
+ * nothing but outFilled in place), any other stages its 70 x 10 neighbourhood on chip once.  No allocation, no wait, so the call may be captured in a graph.  All arrays
+ * may start at any 4-byte aligned address, outFilled at any address.
+ * Recommended (abi.REPROJECT_MOMENTS_DEFAULT_MAX_BATCHES, abi.ESTIMATE_MOMENTS_DEFAULT_*): maxBatches 16, minBatches 8, minTaps 2, normalSharpness 4, depthTolerance
+ * 0.01, MATCH_ENTITY - the point with the smallest sum of two error ratios on a grid of maxBatches {4, 8, 16, 32, 64} x minBatches {2, 4, 8} x minTaps {2, 4, 8, 16} x
+ * normalSharpness {0, 2, 4} x depthTolerance {0.01, 0.05, 0.2} x MATCH_ENTITY on / off (profiles/temporal_moments_timing.py --quality,
+ * profiles/r13_temporal_moments.json; starting point 16 / 4 / 8 / 2 / 0.05 / on), cover scene, 192 x 108, against 1024 spp (tests/test_gpu_temporal_moments.py):
+ *   after a move (view A 16 x 4 spp with moments, a 2 % dolly, 99 % of the pixels carried, 4 x 1 spp on top): squared error of rtowDenoiseVarianceDevice with the carried
+ *     and estimated moments over the same accumulators denoised with restarted moments (the four new batches alone - what a host had before): 0.6089 (starting point
+ *     0.6156; 0.6089 .. 0.8209 over the grid).  What matters is maxBatches: 4 / 8 / 16 leave 0.78 / 0.68 / 0.61 on average, and 32 and 64 equal 16 bit for bit,
+ *     view A having 16 batches; the estimate's own parameters move the ratio by less than 0.01, since a 2 % dolly leaves under 1 % of the pixels without a history.
+ *   a single 4-spp batch, every pixel estimated (inMoments NULL): rtowDenoiseVarianceDevice on the estimated moments over rtowDenoiseDevice with its recommended set:
+ *     1.0036 (starting point 1.0276; 1.0036 .. 1.4693 over the grid).  NO grid point brings this ratio below 1: the spatial estimate gives such a frame a
+ *     variance (99.8 % of its pixels), and the variance-guided filter then equals the plain filter with its tuned fixed sigma, it does not beat it.  A measured
+ *     "no gain": the test asserts that this ratio is finite, nothing more.
+ * Measured (the same file, HIP events on the caller's stream, 1920 x 1080 / 3840 x 2160): no pixel qualifying 0.011 / 0.034 ms (rtowAccumulateMomentsDevice with count 1:
+ * 0.016 / 0.050 - the early out reads 12 bytes per pixel where that pass reads 28); the holes of the 2 % dolly qualifying (0.3 % / 0.1 % of the pixels) 0.047 / 0.091 ms; every
+ * pixel qualifying 0.110 / 0.395 ms (one level of rtowDenoiseVarianceDevice, 25 scattered taps against 49 from LDS: 0.226 / 0.796).  The same tap loop reading every tap from
+ * global memory, built from the same source and timed on the same box in the same run: every pixel 0.323 / 1.251 ms, the holes 0.082 / 0.159 ms - the LDS form is what ships. */
+RTOW_API int rtowEstimateMomentsDevice(RtowContext context, const RtowEstimateMomentsParams* params,
+                                       const float* color /* device float4[W*H]: the accumulated colour, .w = samples */,
+                                       const RtowHitBuffers* hits /* rtowTraceViewDevice of this view: distance, entityIndex, normal all required */,
+                                       const float* inMoments /* device float3[W*H], or NULL = (0, 0, 0) everywhere */,
+                                       float* outMoments /* device float3[W*H]; may be inMoments exactly */,
+                                       uint8_t* outFilled /* device, W*H bytes, or NULL: 1 where the estimate was written */,
+                                       void* stream);
 
 /* ---- from the rendered size to the displayed size: guided upsampling of a scaled-down frame ----
  * replaces: the raster blit that brings the host's scaled buffer to the screen.  resolutionScaling (UNITY/Raytracer.cs:86, two of the four scenes run at 0.5) makes

@@ -1,0 +1,224 @@
+"""Device time of rtowReprojectMomentsDevice and rtowEstimateMomentsDevice at 1920 x 1080 and 3840 x 2160 in one process on one GPU, next to
+rtowAccumulateMomentsDevice with count 1 and one level of rtowDenoiseVarianceDevice; and the parameter grid behind the recommended values of both passes.
+
+Timing: the cover scene, its camera and the camera after tests/test_gpu_temporal_moments.py's 2 % dolly; rtowTraceViewDevice at both views, rtowReprojectAccumDevice
+with its recommended values gives the source map (its holes are the pixels the estimate is for).  The gather over that map; the estimate in three states - no pixel
+qualifying (n = 8 everywhere), the reprojection holes qualifying (the gathered moments), every pixel qualifying (inMoments NULL) - out of place with outFilled; each
+call bracketed by HIP events on the stream it is enqueued on; after `--warmup` untimed calls, `--reps` timed calls per point, the median reported.  With
+`--ab-lib PATH` the three estimate states are timed again in a child process that loads the library at PATH (csrc/Makefile's A/B build with
+EXTRA=-DRTOW_ESTIMATE_TAPS_FROM_LDS=0: the same tap loop reading every tap from global memory).
+
+Quality (`--quality`): the two frames of tests/test_gpu_temporal_moments.py (MoveFrame, SingleBatchFrame) over the grid maxBatches x minBatches x minTaps x
+normalSharpness x depthTolerance x MATCH_ENTITY; per point the squared error against 1024 spp of the frame denoised with the carried and estimated moments over that
+with restarted moments (after the move), and of rtowDenoiseVarianceDevice on estimated moments over rtowDenoiseDevice (single batch; maxBatches and minBatches play
+no part there).  The chosen point has the smallest sum of the two ratios.
+
+    python profiles/temporal_moments_timing.py --quality --out profiles/r13_temporal_moments.json
+"""
+import argparse
+import ctypes as C
+import importlib
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "profiles"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+rt = importlib.import_module("raytracing-in-one-weekend_amd")
+abi = rt.abi
+from denoise_timing import frame  # noqa: E402
+from denoise_variance_timing import timed  # noqa: E402
+
+GRID_MAX_BATCHES = (4, 8, 16, 32, 64)
+GRID_MIN_BATCHES = (2, 4, 8)
+GRID_MIN_TAPS = (2, 4, 8, 16)
+GRID_NORMAL_SHARPNESS = (0, 2, 4)
+GRID_DEPTH_TOLERANCE = (0.01, 0.05, 0.2)
+GRID_FLAGS = (1, 0)
+START = (16, 4, 8, 2, 0.05, 1)
+
+
+def timing(ctx, lib, args):
+    import reproject_reference as rr
+    S = rt.scenes
+    dev = torch.device("cuda:0")
+    stream = torch.cuda.Stream(dev)
+    scene = S.cover_scene()
+    ctx.upload_scene(scene.desc())
+    rows = []
+    for w, h in ((1920, 1080), (3840, 2160)):
+        n = w * h
+        pa = S.make_params(scene, w, h, spp=1, trace_depth=8, seed=1)
+        cam = scene.camera
+        position, target = np.asarray(cam["position"], np.float64), np.asarray(cam["target"], np.float64)
+        focus = S.focus_distance(scene, np.asarray(cam["position"], np.float32), S._normalize(np.asarray(cam["target"], np.float32) - np.asarray(cam["position"], np.float32)))
+        view_b = rr.make_view(tuple(position + 0.02 * (target - position)), tuple(target), w, h, vfov=cam["vfov"], focus=focus, up=tuple(cam["up"]))
+        hits_a = ctx.trace_view(pa.view, w, h, want=("distance", "entityIndex"))
+        hits_b = ctx.trace_view(view_b, w, h, want_rays=True)
+        t = lambda x: torch.from_numpy(np.ascontiguousarray(x).view(np.float32).reshape(-1) if x.dtype != np.int32 else np.ascontiguousarray(x)).to(dev)
+        rng = np.random.default_rng(3)
+        color = np.concatenate([rng.uniform(0, 2, (n, 3)) * 4, np.full((n, 1), 4.0)], axis=1).astype(np.float32)
+        mean = rng.uniform(0.2, 2, n).astype(np.float32)
+        m8 = np.stack([8 * mean, 8 * (mean * mean + 0.05), np.full(n, 8, np.float32)], axis=1).astype(np.float32)
+        d = {"rays": t(hits_b["rays"]), "t": t(hits_b["distance"]), "e": t(hits_b["entityIndex"]), "n": t(hits_b["normal"]), "pt": t(hits_a["distance"]),
+             "pe": t(hits_a["entityIndex"]), "color": t(color), "m8": t(m8)}
+        prev = [d["color"], torch.zeros(n * 3, device=dev), torch.zeros(n * 3, device=dev), torch.zeros(n, device=dev)]
+        outs = [torch.empty(n * 4, device=dev), torch.empty(n * 3, device=dev), torch.empty(n * 3, device=dev), torch.empty(n, device=dev)]
+        src = torch.empty(n, dtype=torch.int32, device=dev)
+        carried, est = torch.empty(n * 3, device=dev), torch.empty(n * 3, device=dev)
+        filled = torch.empty(n, dtype=torch.uint8, device=dev)
+        scratch = torch.empty(abi.denoise_variance_scratch_bytes(w, h) // 4, device=dev)
+        den, var = torch.empty(n * 3, device=dev), torch.empty(n, device=dev)
+        plain = [torch.from_numpy(x.reshape(-1)).to(dev) for x in frame(w, h)]      # profiles/denoise_timing.py's frame: the yardstick level runs on what r12 timed
+        torch.cuda.synchronize()
+        s = stream.cuda_stream
+        rp = abi.ReprojectParams(w, h, pa.view, abi.REPROJECT_DEFAULT_DEPTH_TOLERANCE, abi.REPROJECT_DEFAULT_MAX_HISTORY, abi.REPROJECT_DEFAULT_FLAGS, 0)
+        hb, hp = abi.HitBuffers(d["t"].data_ptr(), d["e"].data_ptr(), None), abi.HitBuffers(d["pt"].data_ptr(), d["pe"].data_ptr(), None)
+        ab_prev, ab_out = abi.AccumBuffers(*[x.data_ptr() for x in prev]), abi.AccumBuffers(*[x.data_ptr() for x in outs])
+        rt.lib.check(lib.rtowReprojectAccumDevice(ctx.handle, C.byref(rp), d["rays"].data_ptr(), C.byref(hb), C.byref(hp), C.byref(ab_prev), C.byref(ab_out),
+                                                  src.data_ptr(), s), "rtowReprojectAccumDevice")
+
+        def gather():
+            rt.lib.check(lib.rtowReprojectMomentsDevice(ctx.handle, n, src.data_ptr(), d["m8"].data_ptr(), abi.REPROJECT_MOMENTS_DEFAULT_MAX_BATCHES, carried.data_ptr(), s),
+                         "rtowReprojectMomentsDevice")
+        gather()
+        stream.synchronize()
+        holes = float((src < 0).float().mean().item())
+        ep = abi.EstimateMomentsParams(w, h, abi.ESTIMATE_MOMENTS_DEFAULT_MIN_BATCHES, abi.ESTIMATE_MOMENTS_DEFAULT_MIN_TAPS, abi.ESTIMATE_MOMENTS_DEFAULT_NORMAL_SHARPNESS,
+                                       abi.ESTIMATE_MOMENTS_DEFAULT_DEPTH_TOLERANCE, abi.ESTIMATE_MOMENTS_DEFAULT_FLAGS, 0)
+        hits = abi.HitBuffers(d["t"].data_ptr(), d["e"].data_ptr(), d["n"].data_ptr())
+
+        def estimate(m_in):
+            def call():
+                rt.lib.check(lib.rtowEstimateMomentsDevice(ctx.handle, C.byref(ep), d["color"].data_ptr(), C.byref(hits), m_in, est.data_ptr(), filled.data_ptr(), s),
+                             "rtowEstimateMomentsDevice")
+            return call
+        one = (C.c_void_p * 1)(d["color"].data_ptr())
+        dp = abi.DenoiseParams(w, h, 1, abi.DENOISE_VARIANCE_DEFAULT_NORMAL_SHARPNESS, abi.DENOISE_VARIANCE_DEFAULT_COLOR_SIGMA, abi.DENOISE_VARIANCE_DEFAULT_ALBEDO_SIGMA,
+                               abi.DENOISE_VARIANCE_DEFAULT_FLAGS, 0)
+
+        def moments_one():
+            rt.lib.check(lib.rtowAccumulateMomentsDevice(ctx.handle, n, 1, one, carried.data_ptr(), carried.data_ptr(), s), "rtowAccumulateMomentsDevice")
+
+        def level():
+            rt.lib.check(lib.rtowDenoiseVarianceDevice(ctx.handle, C.byref(dp), plain[0].data_ptr(), plain[1].data_ptr(), plain[2].data_ptr(), d["m8"].data_ptr(),
+                                                       scratch.data_ptr(), den.data_ptr(), var.data_ptr(), s), "rtowDenoiseVarianceDevice")
+        points = [("estimate_none_qualifying", estimate(d["m8"].data_ptr())), ("estimate_holes_qualifying", estimate(carried.data_ptr())),
+                  ("estimate_all_qualifying", estimate(None))]
+        if not args.estimate_only:                                         # the moments yardstick runs after the estimates: it accumulates into `carried` in place
+            points = [("reproject_moments", gather)] + points + [("accumulate_moments_count_1", moments_one), ("denoise_variance_1_level", level)]
+        for name, call in points:
+            med, lo, hi = timed(stream, call, args.warmup, args.reps)
+            row = {"width": w, "height": h, "pass": name, "ms_median": round(med, 4), "ms_min": round(lo, 4), "ms_max": round(hi, 4), "reps": args.reps}
+            if name == "estimate_holes_qualifying":
+                stream.synchronize()
+                row["qualifying_share"], row["filled_share"] = round(holes, 4), round(float(filled.float().mean().item()), 4)
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+        del d, prev, outs, src, carried, est, filled, scratch, den, var, plain
+    return rows
+
+
+def quality(ctx):
+    import test_gpu_temporal_moments as tg
+    move = tg.MoveFrame(rt, ctx)
+    try:
+        _, den_restarted = move.restarted()
+        base = tg.mse(den_restarted, move.reference)
+        noisy = tg.mse(move.noisy, move.reference)
+        grid_move = []
+        for mb in GRID_MAX_BATCHES:
+            for minb in GRID_MIN_BATCHES:
+                for taps in GRID_MIN_TAPS:
+                    for sharp in GRID_NORMAL_SHARPNESS:
+                        for tol in GRID_DEPTH_TOLERANCE:
+                            for flags in GRID_FLAGS:
+                                _, _, filled, den = move.run(mb, (minb, taps, sharp, tol, flags))
+                                grid_move.append([mb, minb, taps, sharp, tol, flags, round(tg.mse(den, move.reference) / base, 4), round(float(filled.mean()), 4)])
+        carried = float((move.source >= 0).mean())
+    finally:
+        move.free()
+    single = tg.SingleBatchFrame(rt, ctx)
+    try:
+        plain = tg.mse(single.plain(), single.reference)
+        noisy_single = tg.mse(single.noisy, single.reference)
+        grid_single = {}
+        for taps in GRID_MIN_TAPS:
+            for sharp in GRID_NORMAL_SHARPNESS:
+                for tol in GRID_DEPTH_TOLERANCE:
+                    for flags in GRID_FLAGS:
+                        _, filled, den = single.run((abi.ESTIMATE_MOMENTS_DEFAULT_MIN_BATCHES, taps, sharp, tol, flags))
+                        grid_single[(taps, sharp, tol, flags)] = [round(tg.mse(den, single.reference) / plain, 4), round(float(filled.mean()), 4)]
+    finally:
+        single.free()
+    total = lambda p: p[6] + grid_single[tuple(p[2:6])][0]
+    best = min(grid_move, key=total)
+    at = lambda key: [p for p in grid_move if tuple(p[:6]) == key][0]
+    recommended = (abi.REPROJECT_MOMENTS_DEFAULT_MAX_BATCHES, abi.ESTIMATE_MOMENTS_DEFAULT_MIN_BATCHES, abi.ESTIMATE_MOMENTS_DEFAULT_MIN_TAPS,
+                   abi.ESTIMATE_MOMENTS_DEFAULT_NORMAL_SHARPNESS, abi.ESTIMATE_MOMENTS_DEFAULT_DEPTH_TOLERANCE, abi.ESTIMATE_MOMENTS_DEFAULT_FLAGS)
+    describe = lambda p: {"maxBatches": p[0], "minBatches": p[1], "minTaps": p[2], "normalSharpness": p[3], "depthTolerance": p[4], "flags": p[5],
+                          "ratio_after_move": p[6], "filled_share_after_move": p[7], "ratio_single_batch": grid_single[tuple(p[2:6])][0],
+                          "filled_share_single_batch": grid_single[tuple(p[2:6])][1]}
+    ratios = [p[6] for p in grid_move]
+    singles = [v[0] for v in grid_single.values()]
+    return {"protocol": "cover scene, 192 x 108.  After a move: view A 16 x 4 spp (seeds 1..16) with moments, 2 % dolly, accumulators reprojected (recommended), 4 x 1 spp "
+                        "(seeds 201..204) at B on top, against 1024 spp at B (seed 9); ratio = squared error of rtowDenoiseVarianceDevice (recommended set) with carried "
+                        "and estimated moments over the same with the moments of B's four batches alone.  Single batch: 4 spp (seed 1) against 1024 spp (seed 2); ratio = "
+                        "rtowDenoiseVarianceDevice on estimated moments over rtowDenoiseDevice (recommended set)",
+            "pixels_carried": round(carried, 4),
+            "after_move_mse": {"noisy": noisy, "denoised_with_restarted_moments": base},
+            "single_batch_mse": {"noisy": noisy_single, "plain_filter": plain},
+            "grid_after_move_columns": ["maxBatches", "minBatches", "minTaps", "normalSharpness", "depthTolerance", "flags", "ratio", "filled_share"],
+            "grid_after_move": grid_move,
+            "grid_single_batch_columns": ["minTaps", "normalSharpness", "depthTolerance", "flags", "ratio", "filled_share"],
+            "grid_single_batch": [list(k) + v for k, v in grid_single.items()],
+            "after_move_ratio_range": [min(ratios), max(ratios)], "single_batch_ratio_range": [min(singles), max(singles)],
+            "points_with_both_ratios_below_1": sum(1 for p in grid_move if p[6] < 1 and grid_single[tuple(p[2:6])][0] < 1),
+            "chosen_smallest_ratio_sum": describe(best), "starting_point": describe(at(START)), "recommended_set_in_abi": describe(at(recommended))}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--quality", action="store_true")
+    ap.add_argument("--no-timing", action="store_true")
+    ap.add_argument("--estimate-only", action="store_true", help="time the three estimate states only (what --ab-lib runs in its child process)")
+    ap.add_argument("--ab-lib", default=None, help="an A/B build of the library: its estimate timings are recorded next to the shipped library's")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    lib = rt.lib.load()
+    meta = {"what": "rtowReprojectMomentsDevice and rtowEstimateMomentsDevice next to rtowAccumulateMomentsDevice (count 1) and one level of rtowDenoiseVarianceDevice, "
+                    "HIP events on the caller's stream, median of %d after %d warm-up calls" % (args.reps, args.warmup), "device": torch.cuda.get_device_name(0),
+            "library": os.path.relpath(rt.lib.LIB_PATH, ROOT)}
+    with rt.Context(0) as ctx:
+        if not args.no_timing:
+            meta["rows"] = timing(ctx, lib, args)
+        if args.quality:
+            meta["quality"] = quality(ctx)
+            print(json.dumps({k: v for k, v in meta["quality"].items() if not k.startswith("grid_")}), flush=True)
+    if args.ab_lib and not args.no_timing:
+        env = dict(os.environ, RTOW_LIB_PATH=os.path.abspath(args.ab_lib))
+        proc = subprocess.run([sys.executable, os.path.abspath(__file__), "--estimate-only", "--reps", str(args.reps), "--warmup", str(args.warmup)], env=env,
+                              capture_output=True, text=True, timeout=300)
+        assert proc.returncode == 0, proc.stdout[-2000:] + proc.stderr[-2000:]
+        rows = [json.loads(l) for l in proc.stdout.splitlines() if l.startswith("{") and '"pass"' in l]
+        meta["ab_rows"] = {"library": os.path.relpath(os.path.abspath(args.ab_lib), ROOT), "what": "the same source built with -DRTOW_ESTIMATE_TAPS_FROM_LDS=0: every tap "
+                           "read from global memory, no LDS staging; same box, same run", "rows": rows}
+        for r in rows:
+            print(json.dumps(dict(r, library="ab")), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(meta, f, indent=None, separators=(",", ":"))
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -347,6 +347,28 @@ def denoise_variance_scratch_bytes(width, height):
     return int(width) * int(height) * 20
 
 
+# rtowReprojectMomentsDevice / rtowEstimateMomentsDevice (include/rtow.h): the moments carried across a camera move, and estimated where there is no history
+# RtowEstimateMomentsFlags
+RTOW_ESTIMATE_MOMENTS_MATCH_ENTITY = 1
+ESTIMATE_MOMENTS_MATCH_ENTITY = RTOW_ESTIMATE_MOMENTS_MATCH_ENTITY
+ESTIMATE_MOMENTS_RADIUS = 3              # the neighbourhood is 7 x 7
+ESTIMATE_MOMENTS_BATCHES = 2.0           # n of an estimated triple: the neighbourhood's weighted moments as two batches
+# recommended settings: the point profiles/temporal_moments_timing.py's grid picks on tests/test_gpu_temporal_moments.py's two quality frames
+# (profiles/r13_temporal_moments.json)
+REPROJECT_MOMENTS_DEFAULT_MAX_BATCHES = 16
+ESTIMATE_MOMENTS_DEFAULT_MIN_BATCHES = 8
+ESTIMATE_MOMENTS_DEFAULT_MIN_TAPS = 2
+ESTIMATE_MOMENTS_DEFAULT_NORMAL_SHARPNESS = 4
+ESTIMATE_MOMENTS_DEFAULT_DEPTH_TOLERANCE = 0.01
+ESTIMATE_MOMENTS_DEFAULT_FLAGS = RTOW_ESTIMATE_MOMENTS_MATCH_ENTITY
+
+
+class EstimateMomentsParams(C.Structure):
+    """RtowEstimateMomentsParams (32 bytes)"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("minBatches", C.c_int32), ("minTaps", C.c_int32), ("normalSharpness", C.c_int32),
+                ("depthTolerance", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
 # every symbol include/rtow.h declares (tests/test_abi.py checks the library exports all of them)
 EXPORTED_SYMBOLS = [
     "rtowGetApiVersion", "rtowErrorString", "rtowCreateContext", "rtowDestroyContext", "rtowUploadScene",
@@ -359,5 +381,5 @@ EXPORTED_SYMBOLS = [
     "rtowDenoiseDevice", "rtowTraceRaysDevice", "rtowTraceViewDevice", "rtowReprojectAccumDevice", "rtowShadeHitsDevice",
     "rtowTraceRaysIntervalDevice", "rtowTraceOcclusionDevice", "rtowProbeNearestHitInterval", "rtowUpsampleDevice",
     "rtowBuildPixelListDevice", "rtowSamplePixelsDevice", "rtowTraceGuideRaysDevice", "rtowTraceGuideViewDevice",
-    "rtowAccumulateMomentsDevice", "rtowDenoiseVarianceDevice",
+    "rtowAccumulateMomentsDevice", "rtowDenoiseVarianceDevice", "rtowReprojectMomentsDevice", "rtowEstimateMomentsDevice",
 ]

@@ -1839,6 +1839,46 @@ RTOW_API int rtowReprojectAccumDevice(RtowContext ctx, const RtowReprojectParams
     return RTOW_SUCCESS;
 }
 
+RTOW_API int rtowReprojectMomentsDevice(RtowContext ctx, int32_t pixelCount, const int32_t* source, const float* previousMoments, int32_t maxBatches, float* outMoments,
+                                        void* stream)
+{
+    if (!ctx || !source || !previousMoments || !outMoments || pixelCount <= 0 || maxBatches < 1) return RTOW_ERROR_INVALID_VALUE;
+    // every pixel gathers from an arbitrary pixel of the previous moments: no byte the pass writes may be one it reads
+    const Range out{outMoments, (size_t)pixelCount * 12};
+    if (overlaps(out, Range{source, (size_t)pixelCount * 4}) || overlaps(out, Range{previousMoments, (size_t)pixelCount * 12})) return RTOW_ERROR_INVALID_VALUE;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    hipStream_t s;
+    RTOW_TRY(useDevice(ctx, stream, &s));
+    HIP_TRY(ctx, launchReprojectMoments(pixelCount, source, previousMoments, maxBatches, outMoments, s), RTOW_ERROR_LAUNCH_FAILURE);
+    return RTOW_SUCCESS;
+}
+
+RTOW_API int rtowEstimateMomentsDevice(RtowContext ctx, const RtowEstimateMomentsParams* params, const float* color, const RtowHitBuffers* hits, const float* inMoments,
+                                       float* outMoments, uint8_t* outFilled, void* stream)
+{
+    if (!ctx || !params || !color || !hits || !outMoments) return RTOW_ERROR_INVALID_VALUE;
+    if (!hits->distance || !hits->entityIndex || !hits->normal) return RTOW_ERROR_INVALID_VALUE;
+    const RtowEstimateMomentsParams& p = *params;
+    if (p.width <= 0 || p.height <= 0 || (int64_t)p.width * p.height > INT32_MAX) return RTOW_ERROR_INVALID_VALUE;
+    if (p.minBatches < 1 || p.minTaps < 2 || p.minTaps > 49 || p.normalSharpness < 0 || p.normalSharpness > 8) return RTOW_ERROR_INVALID_VALUE;
+    if (!(p.depthTolerance >= 0.0f && p.depthTolerance <= FLT_MAX)) return RTOW_ERROR_INVALID_VALUE;      // NaN fails
+    if ((p.flags & ~(int32_t)RTOW_ESTIMATE_MOMENTS_MATCH_ENTITY) != 0 || p.reserved != 0) return RTOW_ERROR_INVALID_VALUE;
+    // a pixel reads the colour and the guides of its neighbourhood, the moments only at itself: the one overlap that is safe is inMoments == outMoments
+    const size_t n = (size_t)p.width * (size_t)p.height;
+    const Range written[2] = {{outMoments, n * 12}, {outFilled, n}};      // a null outFilled overlaps nothing
+    for (const Range& w : written) {
+        for (const Range& in : {Range{color, n * 16}, Range{hits->distance, n * 4}, Range{hits->entityIndex, n * 4}, Range{hits->normal, n * 12}})
+            if (overlaps(w, in)) return RTOW_ERROR_INVALID_VALUE;
+    }
+    if (overlaps(written[0], written[1]) || overlaps(written[1], Range{inMoments, n * 12})) return RTOW_ERROR_INVALID_VALUE;
+    if (inMoments != outMoments && overlaps(written[0], Range{inMoments, n * 12})) return RTOW_ERROR_INVALID_VALUE;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    hipStream_t s;
+    RTOW_TRY(useDevice(ctx, stream, &s));
+    HIP_TRY(ctx, launchEstimateMoments(p, color, *hits, inMoments, outMoments, outFilled, s), RTOW_ERROR_LAUNCH_FAILURE);
+    return RTOW_SUCCESS;
+}
+
 RTOW_API int rtowUpsampleDevice(RtowContext ctx, const RtowUpsampleParams* params, const float* srcColor, const RtowHitBuffers* srcHits, const float* srcAlbedo,
                                 const RtowHitBuffers* dstHits, const float* dstAlbedo, float* outColor, uint8_t* outStage, void* stream)
 {

@@ -411,6 +411,12 @@ inline ReprojectConstants reprojectConstants(const RtowView& v)
 }
 hipError_t launchReproject(const RtowReprojectParams& p, const ReprojectConstants& k, const RtowRay* rays, const RtowHitBuffers& hits, const RtowHitBuffers& previousHits,
                            const RtowAccumBuffers& previous, const RtowAccumBuffers& out, int32_t* outSource, hipStream_t stream);
+// rtowReprojectMomentsDevice (rtow_moments_temporal.hip): one launch on `stream`, a gather through rtowReprojectAccumDevice's source map (arguments validated by the caller)
+hipError_t launchReprojectMoments(int pixelCount, const int32_t* source, const float* previousMoments, int maxBatches, float* outMoments, hipStream_t stream);
+// rtowEstimateMomentsDevice (rtow_moments_temporal.hip): one launch on `stream`; inMoments may be null (zeros) or outMoments itself, outFilled may be null (arguments
+// validated by the caller)
+hipError_t launchEstimateMoments(const RtowEstimateMomentsParams& p, const float* color, const RtowHitBuffers& hits, const float* inMoments, float* outMoments,
+                                 uint8_t* outFilled, hipStream_t stream);
 // rtowUpsampleDevice (rtow_upsample.hip): one launch on `stream` (arguments validated by the caller); the hit sets are read in GUIDED mode only, the albedos with
 // RTOW_UPSAMPLE_DEMODULATE_ALBEDO only
 hipError_t launchUpsample(const RtowUpsampleParams& p, const float* srcColor, const RtowHitBuffers& srcHits, const float* srcAlbedo, const RtowHitBuffers& dstHits,

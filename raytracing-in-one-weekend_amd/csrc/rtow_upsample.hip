@@ -8,6 +8,7 @@
 // parameters: the POINT and BILINEAR kernels carry no guide loads, and only the DEMODULATE kernels the albedo loads and divisions.
 #include "rtow_kernels.h"
 
+#include "rtow_guide_weight.hip.h"
 #include "rtow_vecmath.hip.h"
 
 namespace rtow {
@@ -53,19 +54,19 @@ __device__ __forceinline__ void axis_position(int X, int src, int dst, int& base
     rem = N - base * (int)two;
 }
 
-// the guide weight g(p, q) of the specification; e, t, n are the dst pixel's
+// the src pixel q's guides, loaded as the guide weight asks for them
+struct SrcGuides {
+    const UpsampleArgs& A;
+    size_t q;
+    __device__ __forceinline__ int entity() const { return A.srcEntity[q]; }
+    __device__ __forceinline__ float distance() const { return A.srcDistance[q]; }
+    __device__ __forceinline__ void normal(float& x, float& y, float& z) const { const P3 n = ld3(A.srcNormal, q); x = n.x; y = n.y; z = n.z; }
+};
+
+// the guide weight g(p, q) of the specification (rtow_guide_weight.hip.h); e, t, n are the dst pixel's
 __device__ __forceinline__ float guide_weight(const UpsampleArgs& A, int e, float t, P3 n, size_t q)
 {
-    const int eq = A.srcEntity[q];
-    if (e < 0) return eq < 0 ? 1.0f : 0.0f;
-    if (eq < 0 || (A.matchEntity && eq != e)) return 0.0f;
-    const float tq = A.srcDistance[q];
-    if (!(__builtin_fabsf(tq - t) <= A.depthTolerance * t)) return 0.0f;          // NaN fails
-    const P3 nq = ld3(A.srcNormal, q);
-    float d = (n.x * nq.x + n.y * nq.y) + n.z * nq.z;
-    d = d > 0.0f ? d : 0.0f;
-    for (int k = 0; k < A.normalSharpness; ++k) d = d * d;
-    return d;
+    return guide::weight(e, t, n.x, n.y, n.z, A.matchEntity, A.depthTolerance, A.normalSharpness, SrcGuides{A, q});
 }
 
 struct Sum { float x, y, z, w; };

@@ -664,6 +664,47 @@ class ReprojectJob:
         return JobHandle(rc)
 
 
+class ReprojectMomentsJob:
+    """rtowReprojectMomentsDevice: the previous view's luminance moments (MomentsJob's) gathered to the new view's pixels through ReprojectJob's OutputSource, so that the
+    variance estimate survives a camera move as the accumulators do.  Device buffers (or raw device addresses): Source int32 per pixel, PreviousMoments and
+    OutputMoments abi.moments_bytes(PixelCount) bytes each (a gather: not in place).  MaxBatches caps the history a pixel carries; the mean s1 / n stays."""
+
+    def __init__(self, context, PixelCount, MaxBatches=abi.REPROJECT_MOMENTS_DEFAULT_MAX_BATCHES):
+        self.context, self.PixelCount, self.MaxBatches = context, PixelCount, MaxBatches
+        self.Source = self.PreviousMoments = self.OutputMoments = None
+
+    def Schedule(self, stream=None):
+        rc = load().rtowReprojectMomentsDevice(self.context.handle, int(self.PixelCount), _device_ptr(self.Source), _device_ptr(self.PreviousMoments),
+                                               int(self.MaxBatches), _device_ptr(self.OutputMoments), stream)
+        return JobHandle(rc)
+
+
+class EstimateMomentsJob:
+    """rtowEstimateMomentsDevice: moments for the pixels whose history is shorter than MinBatches batches - reprojection holes, or with InputMoments None every pixel of
+    a frame rendered as one batch or as a chain - estimated from the 7 x 7 neighbourhood of the accumulated Color (float4, .w = samples), weighted by the first-hit
+    guides HitDistance / HitEntityIndex / HitNormal of rtowTraceViewDevice for this view.  InputMoments: None = zeros, or OutputMoments itself (in place);
+    OutputMoments: abi.moments_bytes(Width * Height) bytes, what DenoiseVarianceJob takes as Moments; OutputFilled (optional): one byte per pixel, 1 where estimated."""
+
+    def __init__(self, context, Width, Height, MinBatches=abi.ESTIMATE_MOMENTS_DEFAULT_MIN_BATCHES, MinTaps=abi.ESTIMATE_MOMENTS_DEFAULT_MIN_TAPS,
+                 NormalSharpness=abi.ESTIMATE_MOMENTS_DEFAULT_NORMAL_SHARPNESS, DepthTolerance=abi.ESTIMATE_MOMENTS_DEFAULT_DEPTH_TOLERANCE,
+                 Flags=abi.ESTIMATE_MOMENTS_DEFAULT_FLAGS, Reserved=0):
+        self.context, self.Width, self.Height = context, Width, Height
+        self.MinBatches, self.MinTaps, self.NormalSharpness, self.DepthTolerance, self.Flags, self.Reserved = MinBatches, MinTaps, NormalSharpness, DepthTolerance, Flags, Reserved
+        self.Color = self.HitDistance = self.HitEntityIndex = self.HitNormal = None
+        self.InputMoments = self.OutputMoments = self.OutputFilled = None
+
+    def params(self):
+        return abi.EstimateMomentsParams(int(self.Width), int(self.Height), int(self.MinBatches), int(self.MinTaps), int(self.NormalSharpness),
+                                         float(self.DepthTolerance), int(self.Flags), int(self.Reserved))
+
+    def Schedule(self, stream=None):
+        p = self.params()
+        hits = abi.HitBuffers(_device_ptr(self.HitDistance), _device_ptr(self.HitEntityIndex), _device_ptr(self.HitNormal))
+        rc = load().rtowEstimateMomentsDevice(self.context.handle, C.byref(p), _device_ptr(self.Color), C.byref(hits), _device_ptr(self.InputMoments),
+                                              _device_ptr(self.OutputMoments), _device_ptr(self.OutputFilled), stream)
+        return JobHandle(rc)
+
+
 class PixelListJob:
     """rtowBuildPixelListDevice: the pixels of a Width x Height frame that lie in the rectangle [X0, X1) x [Y0, Y1) and in the row slice, whose Mask byte (optional) is
     not 0 and whose accumulated sample count Color[4 p + 3] (optional) is not >= MinSampleCount, as a device list in 8 x 8 tile order for rtowSamplePixelsDevice.
