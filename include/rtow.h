@@ -977,6 +977,84 @@ RTOW_API int rtowEstimateMomentsDevice(RtowContext context, const RtowEstimateMo
                                        uint8_t* outFilled /* device, W*H bytes, or NULL: 1 where the estimate was written */,
                                        void* stream);
 
+/* ---- variance-driven adaptive sampling: from the moments to the pixels that get the next batches ----
+ * replaces: SampleCountWeight (JOBS/SampleBatchJob.cs:118-126), the reference's per-sample heuristic mapped linearly to {min, max} samples, which knows nothing of the
+ * variance that was observed.  The moments (s1, s2, n) of rtowAccumulateMomentsDevice, carried and filled by the two calls above, say how noisy each pixel still is;
+ * rtowBuildPixelListDevice and rtowSamplePixelsDevice spend samples on a chosen set of pixels.  rtowNoiseMaskDevice is the link: one pass from the moments to the byte
+ * mask the list builder accepts, with a small record the host steers by - how many pixels are still above the threshold (the stop criterion) and a histogram of the
+ * error (to choose a threshold for a budget; with maxQualifying the pass does that itself).  One refinement round: rtowNoiseMaskDevice, rtowBuildPixelListDevice with
+ * the mask, rtowSamplePixelsDevice per batch from zeroed accumulators, rtowAccumulateMomentsDevice in place (an unlisted pixel has color.w == 0 and is skipped by the
+ * moments rule), rtowAddAccumDevice.  A pure function of its buffers (no resident scene), added after API version 12 without changing it: a host detects the call by its
+ * entry point (C#: EntryPointNotFoundException). */
+typedef enum RtowNoiseMaskFlags { RTOW_NOISE_MASK_ABSOLUTE = 1, RTOW_NOISE_MASK_UNKNOWN_QUALIFIES = 2 } RtowNoiseMaskFlags;
+typedef struct RtowNoiseMaskParams {
+    int32_t width, height;
+    float   errorThreshold;   /* > 0, finite: on the filtered squared error g (0.01 = a relative standard error of 10 %) */
+    float   luminanceFloor;   /* >= 0, finite; relative error only */
+    int32_t dilate;           /* 0..3: neighbours (Chebyshev distance) of a qualifying pixel are masked too */
+    int32_t maxQualifying;    /* >= 0; 0 = no budget */
+    int32_t flags;            /* RtowNoiseMaskFlags */
+    int32_t reserved;         /* 0 */
+} RtowNoiseMaskParams;        /* 32 bytes */
+typedef struct RtowNoiseStats {
+    uint32_t known, unknown, qualifying, masked;
+    float    threshold, maxError;
+    uint32_t reserved[2];     /* written 0 */
+    uint32_t histogram[64];
+} RtowNoiseStats;             /* 288 bytes */
+#define RTOW_NOISE_MASK_SCRATCH_BYTES 288
+/* Numeric specification (float32, in this order; no contraction, correctly rounded `/`; no sqrt, no log, no exp).  Pixel = row * width + col.
+ *   e(q), the pixel's own error: (s1, s2, n) = moments[q]; unknown unless all three are finite (the validity rule of rtowReprojectMomentsDevice: the clamp below would
+ *     turn a NaN sum into a variance of zero) and n >= 2.  mean = s1 / n; d = s2 - s1 * mean; d = d > 0 ? d : 0; v = d / (n * (n - 1)) - the operations of
+ *     rtowDenoiseVarianceDevice's v0.  With RTOW_NOISE_MASK_ABSOLUTE e = v; otherwise e = v / (mean * mean + F2), with F2 = luminanceFloor * luminanceFloor computed on
+ *     the host in float32.  e is unknown unless it is finite.
+ *   g(p), the filtered error: unknown if e(p) is unknown.  Otherwise the 3 x 3 tent of rtowDenoiseVarianceDevice's g_p: q = p + (i, j), j = -1..1 (outer), i = -1..1
+ *     (inner), weights t = {1/4, 1/2, 1/4} per axis, over the in-image taps whose e(q) is known; num and den start at +0, num = num + (t(i) * t(j)) * e(q),
+ *     den = den + t(i) * t(j), in that order; g = num / den.  g is unknown unless it is finite.  A pixel is "known" iff g(p) is known.
+ *   bin(g) = min(max((bits(g) >> 23) - 96, 0), 63): bin b in 1..62 holds 2^(b-31) <= g < 2^(b-30), bin 0 everything below 2^-30 (zero included), bin 63 everything
+ *     from 2^32 up.  histogram[b] counts the known pixels of bin b.
+ *   Threshold T.  maxQualifying == 0: T = errorThreshold.  Otherwise U = unknown if UNKNOWN_QUALIFIES else 0, R = maxQualifying > U ? maxQualifying - U : 0, and b* is
+ *     the smallest b in 0..63 whose tail histogram[b] + ... + histogram[63] is <= R.  No such b: T = +infinity.  Otherwise T = max(errorThreshold, L(b*)), L(0) = 0,
+ *     L(b) = 2^(b-31).
+ *   Qualifying: a known pixel iff g(p) >= T; an unknown pixel iff RTOW_NOISE_MASK_UNKNOWN_QUALIFIES is set.
+ *   outMask[p] = 1 iff some in-image q with |qx - px| <= dilate and |qy - py| <= dilate qualifies, else 0.
+ *   outError[p] = g(p), or -1 where unknown: a NaN is never stored.  stats: known + unknown = W * H; qualifying counts before dilation, masked after it;
+ *     threshold = T; maxError = the largest known g, +0 when there is none; reserved = 0.
+ * Consequences: with a budget the known qualifying pixels never exceed R, because the bins align with the L(b) - qualifying <= max(maxQualifying, U).  The budget bounds
+ * `qualifying`, not `masked`: rtowBuildPixelListDevice's words[0] still reports a list overflow.  dilate == 0 gives mask == qualifies.  Counts and bins are integers and
+ * maxError is a maximum, so two calls give identical bits.
+ * Validation (RTOW_ERROR_INVALID_VALUE, nothing enqueued): a NULL context, params, moments, outMask or scratch; width or height <= 0 or width * height > INT32_MAX;
+ * errorThreshold not > 0 or not finite; a negative or non-finite luminanceFloor; dilate outside 0..3; maxQualifying < 0; unknown flag bits; reserved != 0; any output,
+ * or the scratch, overlapping moments or another output.
+ * Enqueued on `stream` (NULL = the context's own) as a linear sequence: a clear of the scratch record, one pass (a workgroup per 64 x 4 pixel tile, its neighbourhood
+ * staged on chip once), and with a budget a pick step and a second pass.  No allocation, no wait, so the call may be captured in a graph.  moments and outError need
+ * 4-byte alignment only, outMask may start at any address; outStats is DEVICE memory (a host reads it with rtowDeviceCopy when the batch's other results are in).
+ * Recommended (abi.NOISE_MASK_DEFAULT_*): relative error, errorThreshold 0.0025, luminanceFloor 2^-4, dilate 1, maxQualifying = half the frame, UNKNOWN_QUALIFIES - the
+ * point with the smallest sum of two error ratios on a grid of errorThreshold {0.0025, 0.01, 0.04} x luminanceFloor {2^-8, 2^-6, 2^-4} x dilate {0, 1, 2} x budget
+ * {n / 8, n / 4, n / 2}, relative and ABSOLUTE (profiles/noise_mask_timing.py --quality, profiles/r14_noise_mask.json; starting point 0.01 / 2^-6 / 1 / n / 4, relative),
+ * cover scene, 192 x 108, seeds 0 / 1000 / 2000, against 1024 spp (tests/test_gpu_noise_mask.py): 8 x 2 spp as a group with moments, then 4 refinement rounds of 4
+ * list batches of 2 spp, over a uniform frame that got AT LEAST as many samples in all (rounded up to whole batches, so the comparison never favours refinement):
+ *   squared error of the luminance 0.8205 (per seed 0.854 / 0.764 / 0.843), its relative squared error err^2 / (ref^2 + 2^-12) 0.7350 (0.752 / 0.686 / 0.767); the
+ *   starting point gives 0.9002 (0.944 / 0.772 / 0.985) and 0.7836; the sum of the two ranges from 1.56 to 2.14 over the grid, and 14 of the 108 points have both
+ *   ratios below 0.95 on every seed.  What matters most is the budget (n / 2, n / 4, n / 8: 0.87 / 0.91 / 0.94 on average per ratio) and a threshold that is not too
+ *   high (0.04: 0.97); dilate 1 is ahead of 0 by 0.02 and level with 2, the floor moves the average by 0.01.
+ *   ABSOLUTE with these thresholds is a measured "no gain": at 0.01 and 0.04 no pixel of this scene qualifies after 16 spp (both ratios exactly 1), at 0.0025 a few
+ *   thousand samples are spent and the ratios are 0.99 .. 1.05 and 1.04 .. 1.09.  A host that wants the absolute kind chooses its threshold from the histogram.
+ * Measured (the same file, HIP events on the caller's stream, synthetic moments whose errors fill 15 bins, outError and outStats written, 1920 x 1080 / 3840 x 2160):
+ * no budget, dilate 0: 0.134 / 0.266 ms, dilate 3: 0.161 / 0.363 ms; with a budget (four enqueued steps), dilate 0: 0.169 / 0.338 ms, dilate 3: 0.197 / 0.433 ms; the
+ * mask alone is 0.002 - 0.007 ms less.  rtowReprojectMomentsDevice and rtowAccumulateMomentsDevice with count 1 in the same run on the same box: 0.012 / 0.036 and
+ * 0.016 / 0.049 ms.  So the pass is NOT of their order, although it moves as few bytes: about 0.1 ms of either figure is the statistics - every workgroup adds its
+ * counts, its maximum and its non-empty bins to the one record with device-wide atomics, some 20 of them on three cache lines, and the memory side takes them one after
+ * the other (0.1 ms per 1000 workgroups) - and the rest is the staging of each tile's halo through LDS.  The same source with the workgroups capped at 256 / 512 / 2048
+ * instead of 1024, same box, same run (no budget, dilate 0): 0.156 / 0.117 / 0.233 ms at 1920 x 1080, 0.538 / 0.315 / 0.356 ms at 3840 x 2160. */
+RTOW_API int rtowNoiseMaskDevice(RtowContext context, const RtowNoiseMaskParams* params,
+                                 const float* moments   /* device float3[W*H] */,
+                                 uint8_t* outMask       /* device, W*H bytes; every byte written 0 or 1 */,
+                                 float* outError        /* device float[W*H] or NULL: g, -1 where unknown */,
+                                 RtowNoiseStats* outStats /* DEVICE memory, 4-byte aligned, or NULL */,
+                                 void* scratch          /* device, RTOW_NOISE_MASK_SCRATCH_BYTES: 288 */,
+                                 void* stream);
+
 /* ---- from the rendered size to the displayed size: guided upsampling of a scaled-down frame ----
  * replaces: the raster blit that brings the host's scaled buffer to the screen.  resolutionScaling (UNITY/Raytracer.cs:86, two of the four scenes run at 0.5) makes
  * bufferSize = ceil(pixelWidth * s) x ceil(pixelHeight * s) (:478-480, :1095-1096), and the frame reaches the camera's size through a texture whose filter is

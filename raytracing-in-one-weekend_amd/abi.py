@@ -369,6 +369,48 @@ class EstimateMomentsParams(C.Structure):
                 ("depthTolerance", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
+# rtowNoiseMaskDevice (include/rtow.h): from the moments to the mask of the pixels that get the next batches
+# RtowNoiseMaskFlags
+RTOW_NOISE_MASK_ABSOLUTE = 1
+RTOW_NOISE_MASK_UNKNOWN_QUALIFIES = 2
+NOISE_MASK_ABSOLUTE, NOISE_MASK_UNKNOWN_QUALIFIES = RTOW_NOISE_MASK_ABSOLUTE, RTOW_NOISE_MASK_UNKNOWN_QUALIFIES
+NOISE_MASK_HISTOGRAM_BINS = 64           # RtowNoiseStats.histogram: one bin per binade of the filtered error g
+NOISE_MASK_MAX_DILATE = 3
+NOISE_MASK_UNKNOWN = -1.0                # outError where a pixel has no estimate
+# recommended settings: the best point of profiles/noise_mask_timing.py's grid (profiles/r14_noise_mask.json): the refined frame has 0.82 of the squared error and
+# 0.74 of the relative squared error of a uniform frame with at least as many samples (starting point 0.01 / 2^-6 / 1 / n / 4: 0.90 and 0.78)
+NOISE_MASK_DEFAULT_ERROR_THRESHOLD = 0.0025
+NOISE_MASK_DEFAULT_LUMINANCE_FLOOR = 2.0 ** -4
+NOISE_MASK_DEFAULT_DILATE = 1
+NOISE_MASK_DEFAULT_BUDGET_DIVISOR = 2    # maxQualifying = width * height // this
+NOISE_MASK_DEFAULT_FLAGS = RTOW_NOISE_MASK_UNKNOWN_QUALIFIES
+
+
+class NoiseMaskParams(C.Structure):
+    """RtowNoiseMaskParams (32 bytes)"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("errorThreshold", C.c_float), ("luminanceFloor", C.c_float), ("dilate", C.c_int32),
+                ("maxQualifying", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class NoiseStats(C.Structure):
+    """RtowNoiseStats (288 bytes): what the device leaves in outStats"""
+    _fields_ = [("known", C.c_uint32), ("unknown", C.c_uint32), ("qualifying", C.c_uint32), ("masked", C.c_uint32), ("threshold", C.c_float),
+                ("maxError", C.c_float), ("reserved", C.c_uint32 * 2), ("histogram", C.c_uint32 * NOISE_MASK_HISTOGRAM_BINS)]
+
+
+def noise_mask_scratch_bytes():
+    """RTOW_NOISE_MASK_SCRATCH_BYTES: one record"""
+    return 288
+
+
+def noise_bin_lower_bound(b):
+    """L(b): the smallest g of histogram bin b - 0 for bin 0, else 2^(b-31)"""
+    b = int(b)
+    if not 0 <= b < NOISE_MASK_HISTOGRAM_BINS:
+        raise ValueError("bin %d is not in 0..63" % b)
+    return 0.0 if b == 0 else 2.0 ** (b - 31)
+
+
 # every symbol include/rtow.h declares (tests/test_abi.py checks the library exports all of them)
 EXPORTED_SYMBOLS = [
     "rtowGetApiVersion", "rtowErrorString", "rtowCreateContext", "rtowDestroyContext", "rtowUploadScene",
@@ -382,4 +424,5 @@ EXPORTED_SYMBOLS = [
     "rtowTraceRaysIntervalDevice", "rtowTraceOcclusionDevice", "rtowProbeNearestHitInterval", "rtowUpsampleDevice",
     "rtowBuildPixelListDevice", "rtowSamplePixelsDevice", "rtowTraceGuideRaysDevice", "rtowTraceGuideViewDevice",
     "rtowAccumulateMomentsDevice", "rtowDenoiseVarianceDevice", "rtowReprojectMomentsDevice", "rtowEstimateMomentsDevice",
+    "rtowNoiseMaskDevice",
 ]

@@ -1879,7 +1879,31 @@ RTOW_API int rtowEstimateMomentsDevice(RtowContext ctx, const RtowEstimateMoment
     return RTOW_SUCCESS;
 }
 
-RTOW_API int rtowUpsampleDevice(RtowContext ctx, const RtowUpsampleParams* params, const float* srcColor, const RtowHitBuffers* srcHits, const float* srcAlbedo,
+RTOW_API int rtowNoiseMaskDevice(RtowContext ctx, const RtowNoiseMaskParams* params, const float* moments, uint8_t* outMask, float* outError, RtowNoiseStats* outStats,
+                                 void* scratch, void* stream)
+{
+    if (!ctx || !params || !moments || !outMask || !scratch) return RTOW_ERROR_INVALID_VALUE;
+    const RtowNoiseMaskParams& p = *params;
+    if (p.width <= 0 || p.height <= 0 || (int64_t)p.width * p.height > INT32_MAX) return RTOW_ERROR_INVALID_VALUE;
+    if (!(p.errorThreshold > 0.0f && p.errorThreshold <= FLT_MAX) || !(p.luminanceFloor >= 0.0f && p.luminanceFloor <= FLT_MAX)) return RTOW_ERROR_INVALID_VALUE;   // NaN fails both
+    if (p.dilate < 0 || p.dilate > 3 || p.maxQualifying < 0) return RTOW_ERROR_INVALID_VALUE;
+    if ((p.flags & ~(int32_t)(RTOW_NOISE_MASK_ABSOLUTE | RTOW_NOISE_MASK_UNKNOWN_QUALIFIES)) != 0 || p.reserved != 0) return RTOW_ERROR_INVALID_VALUE;
+    // a pixel reads the moments of its neighbourhood while other pixels are written, and the record is filled by atomics: no byte written may be another buffer's
+    const size_t n = (size_t)p.width * (size_t)p.height;
+    const Range written[4] = {{outMask, n}, {outError, n * 4}, {outStats, sizeof(RtowNoiseStats)}, {scratch, RTOW_NOISE_MASK_SCRATCH_BYTES}};      // a null output overlaps nothing
+    for (int i = 0; i < 4; ++i) {
+        if (overlaps(written[i], Range{moments, n * 12})) return RTOW_ERROR_INVALID_VALUE;
+        for (int j = i + 1; j < 4; ++j)
+            if (overlaps(written[i], written[j])) return RTOW_ERROR_INVALID_VALUE;
+    }
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    hipStream_t s;
+    RTOW_TRY(useDevice(ctx, stream, &s));
+    HIP_TRY(ctx, launchNoiseMask(p, moments, outMask, outError, outStats, scratch, s), RTOW_ERROR_LAUNCH_FAILURE);
+    return RTOW_SUCCESS;
+}
+
+RTOW_API int rtowUpsampleDevice(RtowContext ctx,const RtowUpsampleParams* params, const float* srcColor, const RtowHitBuffers* srcHits, const float* srcAlbedo,
                                 const RtowHitBuffers* dstHits, const float* dstAlbedo, float* outColor, uint8_t* outStage, void* stream)
 {
     if (!ctx || !params || !srcColor || !outColor) return RTOW_ERROR_INVALID_VALUE;

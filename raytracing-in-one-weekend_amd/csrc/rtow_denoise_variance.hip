@@ -5,6 +5,7 @@
 // tests/denoise_variance_reference.py restates it in numpy and the GPU tests compare the two bit for bit.
 #include "rtow_kernels.h"
 #include "rtow_denoise_taps.hip.h"
+#include "rtow_moments_variance.hip.h"
 
 namespace rtow {
 
@@ -49,13 +50,8 @@ __global__ void __launch_bounds__(256) initial_variance_kernel(unsigned pixels, 
 {
     for (size_t p = (size_t)blockIdx.x * 256u + threadIdx.x; p < pixels; p += (size_t)gridDim.x * 256u) {
         const P3 m = ld3(moments, p);
-        const float s1 = m.x, s2 = m.y, n = m.z;
-        float v = kVarianceUnknown;
-        if (n >= 2.0f) {
-            const float mean = s1 / n;
-            float d = s2 - s1 * mean;
-            d = d > 0.0f ? d : 0.0f;
-            const float e = d / (n * (n - 1.0f));
+        float v = kVarianceUnknown, mean, e;
+        if (mean_variance(m, mean, e)) {
             if (__builtin_isfinite(e)) {
                 v = e;
                 if (demodulate) {

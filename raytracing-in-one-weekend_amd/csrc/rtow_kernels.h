@@ -417,6 +417,10 @@ hipError_t launchReprojectMoments(int pixelCount, const int32_t* source, const f
 // validated by the caller)
 hipError_t launchEstimateMoments(const RtowEstimateMomentsParams& p, const float* color, const RtowHitBuffers& hits, const float* inMoments, float* outMoments,
                                  uint8_t* outFilled, hipStream_t stream);
+// rtowNoiseMaskDevice (rtow_noise_mask.hip): a clear of the 288-byte record `scratch`, one pass, and with a budget (maxQualifying > 0) a pick launch and a second pass,
+// all on `stream`; outError and outStats may be null (arguments validated by the caller)
+hipError_t launchNoiseMask(const RtowNoiseMaskParams& p, const float* moments, uint8_t* outMask, float* outError, RtowNoiseStats* outStats, void* scratch,
+                           hipStream_t stream);
 // rtowUpsampleDevice (rtow_upsample.hip): one launch on `stream` (arguments validated by the caller); the hit sets are read in GUIDED mode only, the albedos with
 // RTOW_UPSAMPLE_DEMODULATE_ALBEDO only
 hipError_t launchUpsample(const RtowUpsampleParams& p, const float* srcColor, const RtowHitBuffers& srcHits, const float* srcAlbedo, const RtowHitBuffers& dstHits,

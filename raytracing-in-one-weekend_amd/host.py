@@ -705,6 +705,33 @@ class EstimateMomentsJob:
         return JobHandle(rc)
 
 
+class NoiseMaskJob:
+    """rtowNoiseMaskDevice: from the luminance moments (MomentsJob's, carried by ReprojectMomentsJob, filled by EstimateMomentsJob) to the byte mask PixelListJob takes as
+    Mask - 1 where the filtered squared error of the pixel's mean (relative to mean^2 + LuminanceFloor^2 unless abi.NOISE_MASK_ABSOLUTE) is at or above ErrorThreshold,
+    or within Dilate pixels of such a pixel.  MaxQualifying > 0 raises the threshold to the histogram bin edge that keeps the qualifying pixels within that budget.
+    Device buffers (or raw device addresses): Moments abi.moments_bytes(Width * Height) bytes, OutputMask one byte per pixel, OutputError (optional) one float per
+    pixel (abi.NOISE_MASK_UNKNOWN where there is no estimate), OutputStats (optional) one abi.NoiseStats in DEVICE memory, Scratch abi.noise_mask_scratch_bytes()."""
+
+    def __init__(self, context, Width, Height, ErrorThreshold=abi.NOISE_MASK_DEFAULT_ERROR_THRESHOLD, LuminanceFloor=abi.NOISE_MASK_DEFAULT_LUMINANCE_FLOOR,
+                 Dilate=abi.NOISE_MASK_DEFAULT_DILATE, MaxQualifying=None, Flags=abi.NOISE_MASK_DEFAULT_FLAGS, Reserved=0):
+        self.context, self.Width, self.Height = context, Width, Height
+        if MaxQualifying is None:
+            MaxQualifying = int(Width) * int(Height) // abi.NOISE_MASK_DEFAULT_BUDGET_DIVISOR
+        self.ErrorThreshold, self.LuminanceFloor, self.Dilate, self.MaxQualifying, self.Flags, self.Reserved = \
+            ErrorThreshold, LuminanceFloor, Dilate, MaxQualifying, Flags, Reserved
+        self.Moments = self.OutputMask = self.OutputError = self.OutputStats = self.Scratch = None
+
+    def params(self):
+        return abi.NoiseMaskParams(int(self.Width), int(self.Height), float(self.ErrorThreshold), float(self.LuminanceFloor), int(self.Dilate),
+                                   int(self.MaxQualifying), int(self.Flags), int(self.Reserved))
+
+    def Schedule(self, stream=None):
+        p = self.params()
+        rc = load().rtowNoiseMaskDevice(self.context.handle, C.byref(p), _device_ptr(self.Moments), _device_ptr(self.OutputMask), _device_ptr(self.OutputError),
+                                        _device_ptr(self.OutputStats), _device_ptr(self.Scratch), stream)
+        return JobHandle(rc)
+
+
 class PixelListJob:
     """rtowBuildPixelListDevice: the pixels of a Width x Height frame that lie in the rectangle [X0, X1) x [Y0, Y1) and in the row slice, whose Mask byte (optional) is
     not 0 and whose accumulated sample count Color[4 p + 3] (optional) is not >= MinSampleCount, as a device list in 8 x 8 tile order for rtowSamplePixelsDevice.
@@ -738,6 +765,42 @@ def build_pixel_list(context, width, height, capacity, color=None, mask=None, mi
     job.Scratch = DeviceBuffer(context, max(4, abi.pixel_list_scratch_bytes(width, height)))
     check(job.Schedule(stream).Complete(), "rtowBuildPixelListDevice")
     return job.List, job.Scratch
+
+
+def refine_noisy_pixels(context, width, height, params_list, moments, accum, capacity=None, **mask_settings):
+    """One round of variance-driven adaptive sampling on the context's own stream, over the existing calls: NoiseMaskJob on `moments` -> build_pixel_list(mask=...) ->
+    per batch of params_list: sample_pixels_device from zeroed accumulators, rtowAccumulateMomentsDevice into `moments` in place (a pixel that is not listed has
+    color.w == 0 and is skipped by the moments rule), rtowAddAccumDevice onto `accum`.  moments: DeviceBuffer of abi.moments_bytes(width * height); accum: the frame's
+    four accumulator DeviceBuffers (color, normal, albedo, sampleCountWeight); params_list: one abi.SampleParams per batch - equal sample counts, as the moments expect,
+    and seeds the frame has not used; capacity: of the pixel list (default: every pixel); mask_settings: NoiseMaskJob's keyword arguments.
+    Returns (abi.NoiseStats as the device left it, listed: words[0] of the list - above `capacity` the list overflowed and its first `capacity` pixels were sampled)."""
+    n = int(width) * int(height)
+    capacity = n if capacity is None else int(capacity)
+    lib = load()
+    job = NoiseMaskJob(context, width, height, **mask_settings)
+    own = [DeviceBuffer(context, n), DeviceBuffer(context, C.sizeof(abi.NoiseStats)), DeviceBuffer(context, abi.noise_mask_scratch_bytes())]
+    own += [DeviceBuffer(context, n * k * 4) for k in (4, 3, 3, 1)]
+    try:
+        job.Moments, job.OutputMask, job.OutputStats, job.Scratch = moments, own[0], own[1], own[2]
+        check(job.Schedule().Complete(), "rtowNoiseMaskDevice")
+        plist, scratch = build_pixel_list(context, width, height, capacity, mask=own[0])
+        own += [plist, scratch]
+        part = own[3:7]
+        dst, src = _buffers(*[_device_ptr(b) for b in accum]), _buffers(*[b.ptr for b in part])
+        colors = (C.c_void_p * 1)(part[0].ptr)
+        for p in params_list:
+            for b in part:
+                b.zero()
+            check(sample_pixels_device(context, [p], plist, capacity, part, part), "rtowSamplePixelsDevice")
+            check(lib.rtowAccumulateMomentsDevice(context.handle, n, 1, colors, _device_ptr(moments), _device_ptr(moments), None), "rtowAccumulateMomentsDevice")
+            check(lib.rtowAddAccumDevice(context.handle, n, C.byref(dst), C.byref(src), None), "rtowAddAccumDevice")
+        context.synchronize()
+        stats = abi.NoiseStats.from_buffer_copy(own[1].download(np.uint8, (C.sizeof(abi.NoiseStats),)).tobytes())
+        listed = int(plist.download(np.uint32, (4,))[0])
+        return stats, listed
+    finally:
+        for b in own:
+            b.free()
 
 
 class UpsampleJob:
