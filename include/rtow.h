@@ -850,7 +850,8 @@ RTOW_API int rtowDenoiseVarianceDevice(RtowContext context, const RtowDenoisePar
  * rtowTraceViewDevice's outputs for the NEW view, `previousHits` those the host kept from the previous view, `previous` the accumulators of the previous view.
  * A pure function of its buffers: it needs no resident scene.  The batches of the new view then accumulate on top of `out` as on top of any accumulators.
  * Limits: what a pixel carries is what the previous view saw.  Entities with moving != 0, defocus blur (lensRadius > 0) and view-dependent shading (mirrors,
- * glass) are carried as they were seen - the host decides when to reset instead (ZeroMemory, as before).  Sampling is nearest-neighbour: one previous
+ * glass) are carried as they were seen - the host decides when to reset instead (ZeroMemory, as before), or lets rtowRectifyHistoryDevice (below) cut the
+ * history the new view's first samples refute.  Sampling is nearest-neighbour: one previous
  * pixel per new pixel, unfiltered (a bilinear variant is not part of this interface).
  * Added after API version 12 without changing it: a host detects the call by its entry point (C#: EntryPointNotFoundException). */
 typedef enum RtowReprojectFlags { RTOW_REPROJECT_MATCH_ENTITY = 1 } RtowReprojectFlags;
@@ -1054,6 +1055,101 @@ RTOW_API int rtowNoiseMaskDevice(RtowContext context, const RtowNoiseMaskParams*
                                  RtowNoiseStats* outStats /* DEVICE memory, 4-byte aligned, or NULL */,
                                  void* scratch          /* device, RTOW_NOISE_MASK_SCRATCH_BYTES: 288 */,
                                  void* stream);
+
+/* ---- carried history the new view refutes: cut it down, or drop it ----
+ * replaces: nothing the reference can do - a host's one remedy for history that has gone stale is to zero the whole frame's accumulators and start over.
+ * rtowReprojectAccumDevice and rtowReprojectMomentsDevice carry a pixel's sums to where its first hit went; what a mirror or a glass sphere SHOWS there, and what a
+ * defocused edge mixes, belongs to the old camera position.  Up to maxHistory stale samples then sit under a handful of new ones, the variance-guided filter is told the
+ * pixel is well converged, and rtowNoiseMaskDevice does not list it.  rtowRectifyHistoryDevice is the history rejection of a temporal pipeline (the variance clipping of
+ * temporal anti-aliasing; A-SVGF, Schied et al., HPG 2018) in this interface's form: after the first batches of the new view exist - rendered FROM ZERO into `fresh` - it
+ * compares each pixel's carried mean luminance with the mean and the variance of the fresh samples in the pixel's guide-weighted neighbourhood.  Inside the accepted
+ * band the history stays as it is; outside, its weight is divided by how far outside it lies (in squared band widths), and a history left with less than one sample is
+ * dropped: all zeros, the hole rtowBuildPixelListDevice (minSampleCount) and rtowEstimateMomentsDevice already treat.
+ * The frame loop after a move: rtowTraceViewDevice, rtowReprojectAccumDevice, rtowReprojectMomentsDevice, rtowSampleBatchGroupDevice of the new view (from zero),
+ * rtowRectifyHistoryDevice in place on the carried accumulators and moments, rtowAccumulateMomentsDevice in place, rtowAddAccumDevice of the fresh sums onto the rectified
+ * history, rtowEstimateMomentsDevice, rtowCombineDevice, rtowDenoiseVarianceDevice, rtowFinalizeDevice.
+ * A pure function of its buffers (no resident scene), added after API version 12 without changing it: a host detects the call by its entry point
+ * (C#: EntryPointNotFoundException). */
+typedef enum RtowRectifyFlags { RTOW_RECTIFY_MATCH_ENTITY = 1 } RtowRectifyFlags;
+typedef struct RtowRectifyParams {
+    int32_t width, height;
+    int32_t radius;            /* 1..3: (2r+1)^2 taps                                                            recommended: 1 */
+    int32_t minTaps;           /* 2..(2r+1)^2: accepted taps (centre included) a judgement needs                 recommended: 9 */
+    int32_t normalSharpness;   /* 0..8, as RtowEstimateMomentsParams                                             recommended: 4 */
+    float   depthTolerance;    /* >= 0, finite; relative, as RtowEstimateMomentsParams                           recommended: 0.01 */
+    float   sigmaScale;        /* >= 0, finite: half-width of the accepted band in neighbourhood standard deviations   recommended: 0.5 */
+    float   relativeTolerance; /* >= 0, finite: and in units of the neighbourhood mean                           recommended: 0.125 */
+    int32_t flags;             /* RtowRectifyFlags                                     recommended: RTOW_RECTIFY_MATCH_ENTITY */
+    int32_t reserved;          /* 0 */
+} RtowRectifyParams;           /* 40 bytes */
+typedef struct RtowRectifyStats { uint32_t judged, kept, cut, dropped; } RtowRectifyStats;   /* 16 bytes, DEVICE memory */
+/* Numeric specification (float32, in this order; no contraction, correctly rounded `/`; no sqrt, no exp, no pow).  Pixel = row * width + col.
+ *   lum(x, y, z) = (0.2126f * x + 0.7152f * y) + 0.0722f * z.
+ *   L(q): exactly rtowEstimateMomentsDevice's L(q), taken on `fresh`: c = fresh[q] is valid iff c.w > 0 (NaN fails); l = lum(c.x / c.w, c.y / c.w, c.z / c.w) is valid
+ *     iff finite.
+ *   History at p: h = history.color[p] is valid iff its four channels are finite and h.w >= 1; then lh = lum(h.x / h.w, h.y / h.w, h.z / h.w), which must be finite too.
+ *   Pixel p is JUDGED iff its history is valid, L(p) is valid and the neighbourhood yields a judgement.  A pixel that is not judged is UNCHANGED: its 11 accumulator
+ *     floats and its moments triple are copied bit for bit, outKeep[p] = 1.
+ *   Neighbourhood: W, S1, S2 start at +0 and taps at 0.  Taps q = p + (i, j), j = -radius..radius (outer), i = -radius..radius (inner); taps outside the image are
+ *     skipped.  The centre tap has w = 1 and consults no guide.  Another tap is skipped if L(q) is invalid; else w = g(p, q), exactly the guide weight of
+ *     rtowUpsampleDevice's specification with both pixels' guides taken from `hits` and this struct's normalSharpness, depthTolerance and MATCH_ENTITY.  A tap is skipped
+ *     unless w > 0 (NaN included).  Accepted taps, in tap order: W = W + w; S1 = S1 + w * l; S2 = S2 + w * (l * l); taps += 1.
+ *     taps < minTaps: not judged.  Else mu = S1 / W, b = S2 / W; mu or b not finite: not judged.  var = b - mu * mu; var = var > 0 ? var : 0.
+ *   Band: d = lh - mu; T = (K2 * var + R2 * (mu * mu)) + 2^-20, with K2 = sigmaScale * sigmaScale and R2 = relativeTolerance * relativeTolerance computed on the host in
+ *     float32; r = (d * d) / T.  !(r > 1) (a NaN r included): KEPT - the pixel is copied bit for bit like an unchanged one, outKeep[p] = 1.
+ *   Otherwise m = h.w / r and newW = trunc(m).
+ *     newW >= 1: CUT.  k = newW / h.w; colour x, y, z, the normal, the albedo and sampleCountWeight are written multiplied by k and color.w = newW exactly - the
+ *       maxHistory rule of rtowReprojectAccumDevice: (int)color.w stays integral.  The moments become (s1 * k, s2 * k, n * k).  outKeep[p] = k.
+ *     Else DROPPED: all 11 floats +0, the moments (+0, +0, +0), outKeep[p] = 0.
+ *   outStats: kept, cut and dropped count those pixels, judged = kept + cut + dropped.
+ * Consequences: with both tolerances large enough r never exceeds 1 and nothing changes.  A hole (all zeros: h.w < 1) stays a hole.  The pass reads history and moments
+ * only at its own pixel, so in place equals out of place bit for bit.  A cut pixel's carried mean (x * k) / newW is the old mean x / h.w up to rounding, and so is
+ * s1 / n.  After a cut n * k may be fractional: rtowDenoiseVarianceDevice reads n < 2 as unknown and rtowEstimateMomentsDevice fills n < minBatches, so a host runs the
+ * estimate after it, as it does for the holes.  The counts are integers, so two calls give identical bits.
+ * Validation (RTOW_ERROR_INVALID_VALUE, nothing enqueued): a NULL context, params, history, fresh, hits or out, a NULL member of history or out, or a NULL hit array;
+ * width or height <= 0 or width * height > INT32_MAX; radius outside 1..3, minTaps outside 2..(2 * radius + 1)^2, normalSharpness outside 0..8; a negative or non-finite
+ * depthTolerance, sigmaScale or relativeTolerance; unknown flag bits; reserved != 0; exactly one of inMoments / outMoments given; an output overlapping an input other
+ * than the exact aliases named at the arguments, or overlapping another output.
+ * Enqueued on `stream` (NULL = the context's own) as a linear sequence: with outStats a clear of its 16 bytes, then one launch, a workgroup per 64 x 4 pixel tile.  A
+ * tile without a valid history copies through (in place it writes nothing but outKeep) and reads neither `fresh` nor the guides; any other stages the neighbourhood of
+ * its tile on chip once.  No allocation, no wait, so the call may be captured in a graph.  All arrays may start at any 4-byte aligned address; outStats is DEVICE memory
+ * (a host reads it with rtowDeviceCopy when the batch's other results are in).
+ * Recommended (abi.RECTIFY_DEFAULT_*): radius 1, minTaps 9, sigmaScale 0.5, relativeTolerance 0.125, normalSharpness 4, depthTolerance 0.01, MATCH_ENTITY - a narrow band,
+ * judged only where all nine taps of the 3 x 3 neighbourhood lie on the pixel's own surface.  It is the point with the smallest sum of two ratios - (b) / (a) on the pixels
+ * whose first hit is metal or glass, (b) / (a) on the rest, each averaged over three seeds and added over two moves - on a grid of sigmaScale {0.5, 1, 2, 4} x
+ * relativeTolerance {0, 0.125, 0.25, 0.5} x radius {1, 2, 3} x minTaps {2, 4, 9}, guides as rtowEstimateMomentsDevice's (profiles/rectify_history_timing.py --quality,
+ * profiles/r15_rectify_history.json; tests/test_gpu_rectify_history.py).  Protocol: cover scene, 192 x 108, seeds 0 / 1000 / 2000; view A 16 x 4 spp with moments; a
+ * move - the 2 % dolly of the reprojection tests (99 % of the pixels carried), or an orbit of 4 degrees about the target (83 % carried); accumulators and moments
+ * reprojected with their recommended values; 4 x 1 spp of the new view from zero; against 1024 spp of the new view.  Squared luminance error of (a) carried history plus
+ * the fresh sums, (b) rectified history plus the fresh sums, (c) the fresh sums alone; 27 % of the pixels have a specular first hit (rtowShadeHitsDevice).
+ *   What the history is worth, (c) / (a): after the dolly 9.5 / 9.7 / 10.4 over all pixels and 10.4 / 10.1 / 12.3 on the specular ones; after the orbit 2.7 / 2.5 / 3.2
+ *     and 3.0 / 2.8 / 3.4.  On this scene carried history beats a restart everywhere, metal and glass included: what is stale in it is a small part of the error.
+ *   Orbit, (b) / (a): specular 0.9766 (per seed 0.980 / 0.968 / 0.982), the rest 0.9983, all 0.9901; after rtowDenoiseVarianceDevice 0.9951 / 0.9981 / 0.9970.  A gain
+ *     on all three seeds, and a small one; the test asserts the specular ratio with the spread over the seeds as its margin.
+ *   Dolly, (b) / (a): specular 0.9991 (1.003 / 0.995 / 0.999), the rest 0.9983, all 0.9986 - a measured "no gain"; after rtowDenoiseVarianceDevice the specular
+ *     pixels are WORSE, 1.075 (1.073 / 1.082 / 1.069), the rest 0.9987: 7 % of the judged pixels are cut, their moments fall below two batches, and the estimate that
+ *     replaces them serves the filter less well than the carried variance did.  The test asserts only that these ratios are finite.
+ *   Over the grid the sum of the four ratios ranges from 3.972 (this point) to 5.469, and 31 of the 144 points are below 4, which is "nothing changed".  A wider
+ *     neighbourhood or fewer required taps cut more and lose on the diffuse pixels (minTaps 2 / 4 / 9: the rest after the dolly 1.14 / 1.06 / 1.03 on average); without
+ *     the relative term a neighbourhood of equal fresh samples has no variance and everything is cut (relativeTolerance 0: 1.18 there).  The largest gain on the orbit's
+ *     specular pixels anywhere on the grid is 0.911 (sigmaScale 0.5, relativeTolerance 0), which costs 1.18 on the dolly's specular and 1.30 on its diffuse pixels.
+ *   A host whose moves are small keeps its history as it is; the pass earns its time on large moves over specular scenes, and its statistics tell a host how much of a
+ *   frame's history the new view refutes.
+ * Measured (the same file, HIP events on the caller's stream, out of place with moments, outKeep and outStats, a synthetic history of 64 samples of which three pixels in
+ * ten disagree with the fresh samples, 1920 x 1080 / 3840 x 2160): every pixel judged, radius 1 / 2 / 3: 0.117 / 0.138 / 0.169 ms and 0.320 / 0.388 / 0.527 ms; the
+ * history a 2 % dolly leaves (0.3 % / 0.15 % holes): the same within 0.005 ms; no valid history (every tile copies through): 0.043 / 0.167 ms.  rtowEstimateMomentsDevice
+ * with every pixel qualifying - the same staging, 49 taps - in the same run on the same box: 0.105 / 0.370 ms.  At radius 3 the pass takes 1.6 / 1.4 times that: it moves
+ * 152 bytes per pixel where the estimate moves 49 (the eleven accumulator floats and the moments in and out), which is also what the copy-through costs. */
+RTOW_API int rtowRectifyHistoryDevice(RtowContext context, const RtowRectifyParams* params,
+                                      const RtowAccumBuffers* history /* device, W*H each, all four: rtowReprojectAccumDevice's out */,
+                                      const float* fresh       /* device float4[W*H]: colour sums of the NEW view's batches rendered from zero, .w = samples */,
+                                      const RtowHitBuffers* hits /* rtowTraceViewDevice of the new view: distance, entityIndex, normal all required */,
+                                      const float* inMoments   /* device float3[W*H] or NULL: the carried moments (rtowReprojectMomentsDevice's) */,
+                                      const RtowAccumBuffers* out /* all four; each member may be the matching member of history exactly */,
+                                      float* outMoments        /* required iff inMoments; may be inMoments exactly */,
+                                      float* outKeep           /* device float[W*H] or NULL: the factor applied */,
+                                      RtowRectifyStats* outStats /* DEVICE memory, 4-byte aligned, or NULL */,
+                                      void* stream);
 
 /* ---- from the rendered size to the displayed size: guided upsampling of a scaled-down frame ----
  * replaces: the raster blit that brings the host's scaled buffer to the screen.  resolutionScaling (UNITY/Raytracer.cs:86, two of the four scenes run at 0.5) makes

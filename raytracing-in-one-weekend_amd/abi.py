@@ -411,6 +411,34 @@ def noise_bin_lower_bound(b):
     return 0.0 if b == 0 else 2.0 ** (b - 31)
 
 
+# rtowRectifyHistoryDevice (include/rtow.h): carried history the new view's first batches refute is cut down or dropped
+# RtowRectifyFlags
+RTOW_RECTIFY_MATCH_ENTITY = 1
+RECTIFY_MATCH_ENTITY = RTOW_RECTIFY_MATCH_ENTITY
+RECTIFY_MAX_RADIUS = 3
+# recommended settings: the point profiles/rectify_history_timing.py's grid picks on tests/test_gpu_rectify_history.py's quality frames
+# (profiles/r15_rectify_history.json): a narrow band judged only where all nine taps of a 3 x 3 neighbourhood lie on the pixel's own surface; the guides as
+# rtowEstimateMomentsDevice's.  The gain is small: 0.977 of the carried frame's squared error on the metal and glass pixels after a 4 degree orbit, none after a 2 % dolly
+RECTIFY_DEFAULT_RADIUS = 1
+RECTIFY_DEFAULT_MIN_TAPS = 9
+RECTIFY_DEFAULT_NORMAL_SHARPNESS = 4
+RECTIFY_DEFAULT_DEPTH_TOLERANCE = 0.01
+RECTIFY_DEFAULT_SIGMA_SCALE = 0.5
+RECTIFY_DEFAULT_RELATIVE_TOLERANCE = 0.125
+RECTIFY_DEFAULT_FLAGS = RTOW_RECTIFY_MATCH_ENTITY
+
+
+class RectifyParams(C.Structure):
+    """RtowRectifyParams (40 bytes)"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("radius", C.c_int32), ("minTaps", C.c_int32), ("normalSharpness", C.c_int32),
+                ("depthTolerance", C.c_float), ("sigmaScale", C.c_float), ("relativeTolerance", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RectifyStats(C.Structure):
+    """RtowRectifyStats (16 bytes): what the device leaves in outStats; judged = kept + cut + dropped"""
+    _fields_ = [("judged", C.c_uint32), ("kept", C.c_uint32), ("cut", C.c_uint32), ("dropped", C.c_uint32)]
+
+
 # every symbol include/rtow.h declares (tests/test_abi.py checks the library exports all of them)
 EXPORTED_SYMBOLS = [
     "rtowGetApiVersion", "rtowErrorString", "rtowCreateContext", "rtowDestroyContext", "rtowUploadScene",
@@ -424,5 +452,5 @@ EXPORTED_SYMBOLS = [
     "rtowTraceRaysIntervalDevice", "rtowTraceOcclusionDevice", "rtowProbeNearestHitInterval", "rtowUpsampleDevice",
     "rtowBuildPixelListDevice", "rtowSamplePixelsDevice", "rtowTraceGuideRaysDevice", "rtowTraceGuideViewDevice",
     "rtowAccumulateMomentsDevice", "rtowDenoiseVarianceDevice", "rtowReprojectMomentsDevice", "rtowEstimateMomentsDevice",
-    "rtowNoiseMaskDevice",
+    "rtowNoiseMaskDevice", "rtowRectifyHistoryDevice",
 ]

@@ -1903,6 +1903,43 @@ RTOW_API int rtowNoiseMaskDevice(RtowContext ctx, const RtowNoiseMaskParams* par
     return RTOW_SUCCESS;
 }
 
+RTOW_API int rtowRectifyHistoryDevice(RtowContext ctx, const RtowRectifyParams* params, const RtowAccumBuffers* history, const float* fresh, const RtowHitBuffers* hits,
+                                      const float* inMoments, const RtowAccumBuffers* out, float* outMoments, float* outKeep, RtowRectifyStats* outStats, void* stream)
+{
+    if (!ctx || !params || !history || !fresh || !hits || !out) return RTOW_ERROR_INVALID_VALUE;
+    if (!hits->distance || !hits->entityIndex || !hits->normal) return RTOW_ERROR_INVALID_VALUE;
+    if (!history->color || !history->normal || !history->albedo || !history->sampleCountWeight || !out->color || !out->normal || !out->albedo || !out->sampleCountWeight)
+        return RTOW_ERROR_INVALID_VALUE;
+    const RtowRectifyParams& p = *params;
+    if (p.width <= 0 || p.height <= 0 || (int64_t)p.width * p.height > INT32_MAX) return RTOW_ERROR_INVALID_VALUE;
+    if (p.radius < 1 || p.radius > 3 || p.minTaps < 2 || p.minTaps > (2 * p.radius + 1) * (2 * p.radius + 1)) return RTOW_ERROR_INVALID_VALUE;
+    if (p.normalSharpness < 0 || p.normalSharpness > 8) return RTOW_ERROR_INVALID_VALUE;
+    for (const float v : {p.depthTolerance, p.sigmaScale, p.relativeTolerance})
+        if (!(v >= 0.0f && v <= FLT_MAX)) return RTOW_ERROR_INVALID_VALUE;      // NaN fails
+    if ((p.flags & ~(int32_t)RTOW_RECTIFY_MATCH_ENTITY) != 0 || p.reserved != 0) return RTOW_ERROR_INVALID_VALUE;
+    if ((inMoments == nullptr) != (outMoments == nullptr)) return RTOW_ERROR_INVALID_VALUE;
+    // a pixel reads the fresh colour and the guides of its neighbourhood, the history and the moments only at itself, before it writes them: the overlaps that are safe
+    // are an output that IS the matching input (written[k] and same[k] below)
+    const size_t n = (size_t)p.width * (size_t)p.height;
+    const Range written[7] = {{out->color, n * 16}, {out->normal, n * 12}, {out->albedo, n * 12}, {out->sampleCountWeight, n * 4}, {outMoments, n * 12},
+                              {outKeep, n * 4}, {outStats, sizeof(RtowRectifyStats)}};      // a null output overlaps nothing
+    const Range same[5] = {{history->color, n * 16}, {history->normal, n * 12}, {history->albedo, n * 12}, {history->sampleCountWeight, n * 4}, {inMoments, n * 12}};
+    const Range read[4] = {{fresh, n * 16}, {hits->distance, n * 4}, {hits->entityIndex, n * 4}, {hits->normal, n * 12}};
+    for (int i = 0; i < 7; ++i) {
+        for (const Range& in : read)
+            if (overlaps(written[i], in)) return RTOW_ERROR_INVALID_VALUE;
+        for (int k = 0; k < 5; ++k)
+            if (!(i == k && written[i].base == same[k].base) && overlaps(written[i], same[k])) return RTOW_ERROR_INVALID_VALUE;
+        for (int j = i + 1; j < 7; ++j)
+            if (overlaps(written[i], written[j])) return RTOW_ERROR_INVALID_VALUE;
+    }
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    hipStream_t s;
+    RTOW_TRY(useDevice(ctx, stream, &s));
+    HIP_TRY(ctx, launchRectifyHistory(p, *history, fresh, *hits, inMoments, *out, outMoments, outKeep, outStats, s), RTOW_ERROR_LAUNCH_FAILURE);
+    return RTOW_SUCCESS;
+}
+
 RTOW_API int rtowUpsampleDevice(RtowContext ctx,const RtowUpsampleParams* params, const float* srcColor, const RtowHitBuffers* srcHits, const float* srcAlbedo,
                                 const RtowHitBuffers* dstHits, const float* dstAlbedo, float* outColor, uint8_t* outStage, void* stream)
 {

@@ -421,6 +421,10 @@ hipError_t launchEstimateMoments(const RtowEstimateMomentsParams& p, const float
 // all on `stream`; outError and outStats may be null (arguments validated by the caller)
 hipError_t launchNoiseMask(const RtowNoiseMaskParams& p, const float* moments, uint8_t* outMask, float* outError, RtowNoiseStats* outStats, void* scratch,
                            hipStream_t stream);
+// rtowRectifyHistoryDevice (rtow_rectify_history.hip): with outStats a clear of its 16 bytes, then one launch, on `stream`; every member of `out` may be the matching
+// member of `history`, outMoments may be inMoments (both null or neither), outKeep and outStats may be null (arguments validated by the caller)
+hipError_t launchRectifyHistory(const RtowRectifyParams& p, const RtowAccumBuffers& history, const float* fresh, const RtowHitBuffers& hits, const float* inMoments,
+                                const RtowAccumBuffers& out, float* outMoments, float* outKeep, RtowRectifyStats* outStats, hipStream_t stream);
 // rtowUpsampleDevice (rtow_upsample.hip): one launch on `stream` (arguments validated by the caller); the hit sets are read in GUIDED mode only, the albedos with
 // RTOW_UPSAMPLE_DEMODULATE_ALBEDO only
 hipError_t launchUpsample(const RtowUpsampleParams& p, const float* srcColor, const RtowHitBuffers& srcHits, const float* srcAlbedo, const RtowHitBuffers& dstHits,

@@ -732,6 +732,39 @@ class NoiseMaskJob:
         return JobHandle(rc)
 
 
+class RectifyHistoryJob:
+    """rtowRectifyHistoryDevice: carried history (ReprojectJob's four outputs, ReprojectMomentsJob's moments) that the first batches of the new view refute is scaled
+    down or dropped - a pixel whose carried mean luminance lies outside SigmaScale standard deviations plus RelativeTolerance means of the Fresh samples in its
+    (2 Radius + 1)^2 guide-weighted neighbourhood.  Device buffers (or raw device addresses): the four History* accumulators; Fresh the float4 colour sums of the new
+    view's batches rendered from zero; HitDistance / HitEntityIndex / HitNormal of rtowTraceViewDevice for the new view; InputMoments / OutputMoments both or neither;
+    each Output* may be its input (in place).  OutputKeep (optional): one float per pixel, the factor applied; OutputStats (optional): one abi.RectifyStats in DEVICE
+    memory.  Runs before MomentsJob and rtowAddAccumDevice fold the fresh batches in."""
+
+    def __init__(self, context, Width, Height, Radius=abi.RECTIFY_DEFAULT_RADIUS, MinTaps=abi.RECTIFY_DEFAULT_MIN_TAPS,
+                 NormalSharpness=abi.RECTIFY_DEFAULT_NORMAL_SHARPNESS, DepthTolerance=abi.RECTIFY_DEFAULT_DEPTH_TOLERANCE, SigmaScale=abi.RECTIFY_DEFAULT_SIGMA_SCALE,
+                 RelativeTolerance=abi.RECTIFY_DEFAULT_RELATIVE_TOLERANCE, Flags=abi.RECTIFY_DEFAULT_FLAGS, Reserved=0):
+        self.context, self.Width, self.Height = context, Width, Height
+        self.Radius, self.MinTaps, self.NormalSharpness, self.DepthTolerance = Radius, MinTaps, NormalSharpness, DepthTolerance
+        self.SigmaScale, self.RelativeTolerance, self.Flags, self.Reserved = SigmaScale, RelativeTolerance, Flags, Reserved
+        self.HistoryColor = self.HistoryNormal = self.HistoryAlbedo = self.HistorySampleCountWeight = None
+        self.Fresh = self.HitDistance = self.HitEntityIndex = self.HitNormal = self.InputMoments = None
+        self.OutputColor = self.OutputNormal = self.OutputAlbedo = self.OutputSampleCountWeight = None
+        self.OutputMoments = self.OutputKeep = self.OutputStats = None
+
+    def params(self):
+        return abi.RectifyParams(int(self.Width), int(self.Height), int(self.Radius), int(self.MinTaps), int(self.NormalSharpness), float(self.DepthTolerance),
+                                 float(self.SigmaScale), float(self.RelativeTolerance), int(self.Flags), int(self.Reserved))
+
+    def Schedule(self, stream=None):
+        p = self.params()
+        hits = abi.HitBuffers(_device_ptr(self.HitDistance), _device_ptr(self.HitEntityIndex), _device_ptr(self.HitNormal))
+        history = _buffers(*[_device_ptr(b) for b in (self.HistoryColor, self.HistoryNormal, self.HistoryAlbedo, self.HistorySampleCountWeight)])
+        out = _buffers(*[_device_ptr(b) for b in (self.OutputColor, self.OutputNormal, self.OutputAlbedo, self.OutputSampleCountWeight)])
+        rc = load().rtowRectifyHistoryDevice(self.context.handle, C.byref(p), C.byref(history), _device_ptr(self.Fresh), C.byref(hits), _device_ptr(self.InputMoments),
+                                             C.byref(out), _device_ptr(self.OutputMoments), _device_ptr(self.OutputKeep), _device_ptr(self.OutputStats), stream)
+        return JobHandle(rc)
+
+
 class PixelListJob:
     """rtowBuildPixelListDevice: the pixels of a Width x Height frame that lie in the rectangle [X0, X1) x [Y0, Y1) and in the row slice, whose Mask byte (optional) is
     not 0 and whose accumulated sample count Color[4 p + 3] (optional) is not >= MinSampleCount, as a device list in 8 x 8 tile order for rtowSamplePixelsDevice.
