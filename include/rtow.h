@@ -852,7 +852,7 @@ RTOW_API int rtowDenoiseVarianceDevice(RtowContext context, const RtowDenoisePar
  * Limits: what a pixel carries is what the previous view saw.  Entities with moving != 0, defocus blur (lensRadius > 0) and view-dependent shading (mirrors,
  * glass) are carried as they were seen - the host decides when to reset instead (ZeroMemory, as before), or lets rtowRectifyHistoryDevice (below) cut the
  * history the new view's first samples refute.  Sampling is nearest-neighbour: one previous
- * pixel per new pixel, unfiltered (a bilinear variant is not part of this interface).
+ * pixel per new pixel, unfiltered; rtowReprojectAccumBilinearDevice (below) is the four-tap variant.
  * Added after API version 12 without changing it: a host detects the call by its entry point (C#: EntryPointNotFoundException). */
 typedef enum RtowReprojectFlags { RTOW_REPROJECT_MATCH_ENTITY = 1 } RtowReprojectFlags;
 typedef struct RtowReprojectParams {
@@ -891,6 +891,61 @@ RTOW_API int rtowReprojectAccumDevice(RtowContext context, const RtowReprojectPa
                                       int32_t* outSource /* device, W*H, or NULL: previous pixel index carried, -1 if none */,
                                       void* stream);
 
+/* ---- four-tap reprojection: the previous view's accumulators (and moments) through the four previous pixels around the reprojected point ----
+ * replaces: nothing the reference has; SVGF's temporal reprojection (Schied et al., HPG 2017, section 4.1): four bilinear taps, each validated on its own, the
+ * weights renormalised over the valid ones.  rtowReprojectAccumDevice takes the one previous pixel under the reprojected point: under continuous motion the carried
+ * image is re-snapped by up to half a pixel per move, a camera that moves in duplicates one previous pixel into several new ones (correlated noise the a-trous
+ * filters cannot remove), and a pixel whose nearest previous pixel fails validation is a hole even where three valid neighbours surround the point.  This call has
+ * the same arguments (RtowReprojectParams unchanged) plus the moments: with previousMoments and outMoments given it carries the (s1, s2, n) of
+ * rtowAccumulateMomentsDevice in the same pass through the same taps, and a host needs no rtowReprojectMomentsDevice after it.
+ * A pure function of its buffers (no resident scene), added after API version 12 without changing it: a host detects the call by its entry point
+ * (C#: EntryPointNotFoundException).
+ * Numeric specification (float32, in this order; no contraction; `/` and sqrt correctly rounded; dot as in rtowReprojectAccumDevice).  Pixel i:
+ *   1., 2.       as rtowReprojectAccumDevice's, up to fx, fy and their in-frame test: the point, r, s > 0, and (fx, fy) in [0, W) x [0, H).  A pixel that fails here
+ *                carries nothing.
+ *   3. taps:     gx = fx - 0.5f, gy = fy - 0.5f; x0 = (int)floorf(gx), y0 = (int)floorf(gy) (either may be -1); ax = gx - (float)x0, ay = gy - (float)y0.
+ *                Taps k = 0..3 at (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1) with weights b_k = (1-ax)*(1-ay), ax*(1-ay), (1-ax)*ay, ax*ay.
+ *   4. validity: a tap is valid iff it is inside the image, b_k > 0, step 3 of rtowReprojectAccumDevice holds at its pixel q_k (sky rule, entity match under
+ *                RTOW_REPROJECT_MATCH_ENTITY, fabs(pt - r) <= depthTolerance * r with the same r for all four taps), and c_k = previous.color[q_k] has four finite
+ *                channels and c_k.w >= 1.  Only the colour decides: a NaN in a valid tap's normal, albedo or sampleCountWeight is blended as it stands.
+ *   5. outcome:  no valid tap: all 11 floats are +0, outSource[i] = -1.
+ *                one valid tap: step 4 of rtowReprojectAccumDevice at that q (a copy bit for bit, or scaled by k = (float)maxHistory / c.w).
+ *                two or more: B and ten sums start at +0; in tap order u_k = b_k / c_k.w, B = B + b_k, and each of the ten channels x (colour xyz, normal, albedo,
+ *                sampleCountWeight) sum_x = sum_x + u_k * x_k.  n = the smallest min(c_k.w, (float)maxHistory) over the valid taps.  Each channel is written as
+ *                (sum_x / B) * n and color.w = n: the bilinear blend of the taps' MEANS, claiming no more history than the poorest tap had; sample counts are
+ *                integral, so (int)color.w stays integral.
+ *                outSource[i] = the valid tap with the largest b_k, the first in tap order among equals.
+ *   6. moments (when given): among the valid taps a tap takes part iff its triple (s1, s2, m) = previousMoments[q_k] is finite and m >= 1.  None: (+0, +0, +0).
+ *                One: the rule of rtowReprojectMomentsDevice at that q (a copy, or scaled by (float)maxBatches / m with n = (float)maxBatches).  Several:
+ *                um_k = b_k / m_k, Bm sums b_k, S1 and S2 sum um_k * s1_k and um_k * s2_k in tap order, nm = the smallest min(m_k, (float)maxBatches); the output is
+ *                ((S1 / Bm) * nm, (S2 / Bm) * nm, nm).
+ * Consequence: every pixel rtowReprojectAccumDevice carries is carried here - the nearest pixel ((int)fx, (int)fy) is one of the four taps and its weight is at
+ * least 1/4 (for widths and heights up to 2^22) - and where that tap is the only valid one the 11 floats equal that call's bit for bit.
+ * Validation (RTOW_ERROR_INVALID_VALUE, nothing enqueued): everything rtowReprojectAccumDevice refuses; exactly one of previousMoments and outMoments NULL;
+ * maxBatches < 1 when moments are given (it is ignored otherwise); outMoments overlapping a buffer the pass gathers from (previousMoments included) or another
+ * output; any output overlapping previousMoments.
+ * Enqueued on `stream` (NULL = the context's own stream): one launch, one lane per pixel, a wave per 8 x 8 pixel tile, the taps one after another; no allocation,
+ * no wait, so the call may be captured in a graph.  The buffers need 4-byte alignment only.
+ * Recommended: RtowReprojectParams as for rtowReprojectAccumDevice, maxBatches 16 (abi.REPROJECT_MOMENTS_DEFAULT_MAX_BATCHES).
+ * Measured (profiles/r16_reproject_bilinear.json): HIP events on the caller's stream, the data of a 2 % dolly on the cover scene, in one run with what the call
+ * replaces: 1920 x 1080 0.091 ms without moments against rtowReprojectAccumDevice's 0.062 (1.47 x), 0.120 ms with moments against 0.078 for
+ * rtowReprojectAccumDevice followed by rtowReprojectMomentsDevice (1.54 x); 3840 x 2160 0.475 against 0.315 (1.51 x) and 0.565 against 0.357 (1.58 x).  64 and 54
+ * VGPRs with and without moments, no scratch, no spill, 8 waves per SIMD (tests/test_reproject_bilinear_isa.py).
+ * Quality (the same file; cover scene, 192 x 108, seeds 0 / 1000 / 2000; view A 16 x 4 spp with moments, a move, 4 x 1 spp of the new view on top, squared luminance
+ * error against 1024 spp, this call over rtowReprojectAccumDevice + rtowReprojectMomentsDevice, raw / after rtowDenoiseVarianceDevice's recommended set): 2 % dolly
+ * 0.886 / 0.973 (99.9 % of the pixels carried against 99.1 %), 4 degree orbit 0.730 / 0.764 (85.3 % against 83.0 %), a pan of half a pixel 0.559 / 0.626 (99.3 %
+ * against 96.0 %), eight successive moves of an eighth of that orbit and dolly each, reprojected from each view to the next with no sample in between, 0.354 / 0.422
+ * (90.6 % against 73.3 %).  All three seeds lie within 0.03 of these means. */
+RTOW_API int rtowReprojectAccumBilinearDevice(RtowContext context, const RtowReprojectParams* params,
+                                              const RtowRay* rays /* device, W*H: rtowTraceViewDevice's outRays of the NEW view */,
+                                              const RtowHitBuffers* hits /* of `rays`: distance and entityIndex required, normal ignored */,
+                                              const RtowHitBuffers* previousHits /* of the previous view: distance and entityIndex required */,
+                                              const RtowAccumBuffers* previous, const RtowAccumBuffers* out /* device, W*H each, all four required */,
+                                              const float* previousMoments /* device float3[W*H] or NULL */, int32_t maxBatches /* >= 1 with moments */,
+                                              float* outMoments /* device float3[W*H] or NULL */,
+                                              int32_t* outSource /* device, W*H, or NULL: the previous pixel of the heaviest valid tap, -1 if none */,
+                                              void* stream);
+
 /* ---- temporal moments: the variance estimate carried across a camera move, and filled where there is no history ----
  * replaces: nothing the reference has; the temporal half of SVGF (Schied et al., HPG 2017, sections 4.1 - 4.2) next to rtowDenoiseVarianceDevice's spatial half.
  * rtowReprojectAccumDevice carries the colour history to a moved camera; how noisy each pixel is was lost there: the moved frame started with n = 0 everywhere and the
@@ -898,7 +953,8 @@ RTOW_API int rtowReprojectAccumDevice(RtowContext context, const RtowReprojectPa
  * the source map that call writes (outSource), and rtowEstimateMomentsDevice is SVGF's spatial fallback: a pixel with fewer than minBatches batches of history takes its
  * moments from a 7 x 7 neighbourhood of the current frame, weighted by the first-hit guides the host already has, in the same moments format - so
  * rtowDenoiseVarianceDevice takes the result unchanged.  With inMoments == NULL every pixel is estimated: a variance for frames rendered as one batch or as a chain.
- * The frame loop after a move: rtowTraceViewDevice, rtowReprojectAccumDevice, rtowReprojectMomentsDevice, rtowSampleBatchGroupDevice, rtowAccumulateMomentsDevice,
+ * The frame loop after a move: rtowTraceViewDevice, rtowReprojectAccumDevice, rtowReprojectMomentsDevice (or rtowReprojectAccumBilinearDevice with moments in place
+ * of the two), rtowSampleBatchGroupDevice, rtowAccumulateMomentsDevice,
  * rtowAddAccumDevice, rtowEstimateMomentsDevice (into a second moments buffer, or in place), rtowCombineDevice, rtowDenoiseVarianceDevice, rtowFinalizeDevice.
  * Both are pure functions of their buffers (no resident scene), added after API version 12 without changing it: a host detects the calls by their entry points
  * (C#: EntryPointNotFoundException).

@@ -452,5 +452,5 @@ EXPORTED_SYMBOLS = [
     "rtowTraceRaysIntervalDevice", "rtowTraceOcclusionDevice", "rtowProbeNearestHitInterval", "rtowUpsampleDevice",
     "rtowBuildPixelListDevice", "rtowSamplePixelsDevice", "rtowTraceGuideRaysDevice", "rtowTraceGuideViewDevice",
     "rtowAccumulateMomentsDevice", "rtowDenoiseVarianceDevice", "rtowReprojectMomentsDevice", "rtowEstimateMomentsDevice",
-    "rtowNoiseMaskDevice", "rtowRectifyHistoryDevice",
+    "rtowNoiseMaskDevice", "rtowRectifyHistoryDevice", "rtowReprojectAccumBilinearDevice",
 ]

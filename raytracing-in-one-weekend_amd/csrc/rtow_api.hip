@@ -1807,8 +1807,11 @@ RTOW_API int rtowDenoiseVarianceDevice(RtowContext ctx, const RtowDenoiseParams*
     return RTOW_SUCCESS;
 }
 
-RTOW_API int rtowReprojectAccumDevice(RtowContext ctx, const RtowReprojectParams* params, const RtowRay* rays, const RtowHitBuffers* hits, const RtowHitBuffers* previousHits,
-                                      const RtowAccumBuffers* previous, const RtowAccumBuffers* out, int32_t* outSource, void* stream)
+// What rtowReprojectAccumDevice and rtowReprojectAccumBilinearDevice refuse alike; fills `k`.  outMoments and previousMoments are null for the former: a null range
+// overlaps nothing.
+static int validateReproject(RtowContext ctx, const RtowReprojectParams* params, const RtowRay* rays, const RtowHitBuffers* hits, const RtowHitBuffers* previousHits,
+                             const RtowAccumBuffers* previous, const RtowAccumBuffers* out, const float* previousMoments, float* outMoments, int32_t* outSource,
+                             ReprojectConstants* k)
 {
     if (!ctx || !params || !rays || !hits || !previousHits || !previous || !out) return RTOW_ERROR_INVALID_VALUE;
     if (!hits->distance || !hits->entityIndex || !previousHits->distance || !previousHits->entityIndex) return RTOW_ERROR_INVALID_VALUE;
@@ -1818,24 +1821,47 @@ RTOW_API int rtowReprojectAccumDevice(RtowContext ctx, const RtowReprojectParams
     if (p.width <= 0 || p.height <= 0 || (int64_t)p.width * p.height > INT32_MAX) return RTOW_ERROR_INVALID_VALUE;
     if (!(p.depthTolerance >= 0.0f && p.depthTolerance <= FLT_MAX) || p.maxHistory < 1) return RTOW_ERROR_INVALID_VALUE;      // NaN fails
     if ((p.flags & ~(int32_t)RTOW_REPROJECT_MATCH_ENTITY) != 0 || p.reserved != 0) return RTOW_ERROR_INVALID_VALUE;
-    const ReprojectConstants k = reprojectConstants(p.previousView);
-    for (const float d : {k.LF, k.HR, k.VU})
+    *k = reprojectConstants(p.previousView);
+    for (const float d : {k->LF, k->HR, k->VU})
         if (!(d != 0.0f && d >= -FLT_MAX && d <= FLT_MAX)) return RTOW_ERROR_INVALID_VALUE;      // the divisors of the projection
-    // every pixel gathers from an arbitrary pixel of the previous frame: no byte the pass writes may be one it gathers from, or another output's
+    // every pixel gathers from arbitrary pixels of the previous frame: no byte the pass writes may be one it gathers from, or another output's
     const size_t n = (size_t)p.width * (size_t)p.height;
-    const Range written[5] = {{out->color, n * 16}, {out->normal, n * 12}, {out->albedo, n * 12}, {out->sampleCountWeight, n * 4}, {outSource, n * 4}};
-    const Range gathered[6] = {{previous->color, n * 16}, {previous->normal, n * 12}, {previous->albedo, n * 12}, {previous->sampleCountWeight, n * 4},
-                               {previousHits->distance, n * 4}, {previousHits->entityIndex, n * 4}};
-    for (int i = 0; i < 5; ++i) {
+    const Range written[6] = {{out->color, n * 16}, {out->normal, n * 12}, {out->albedo, n * 12}, {out->sampleCountWeight, n * 4}, {outSource, n * 4}, {outMoments, n * 12}};
+    const Range gathered[7] = {{previous->color, n * 16}, {previous->normal, n * 12}, {previous->albedo, n * 12}, {previous->sampleCountWeight, n * 4},
+                               {previousHits->distance, n * 4}, {previousHits->entityIndex, n * 4}, {previousMoments, n * 12}};
+    for (int i = 0; i < 6; ++i) {
         for (const Range& g : gathered)
             if (overlaps(written[i], g)) return RTOW_ERROR_INVALID_VALUE;
-        for (int j = i + 1; j < 5; ++j)
+        for (int j = i + 1; j < 6; ++j)
             if (overlaps(written[i], written[j])) return RTOW_ERROR_INVALID_VALUE;
     }
+    return RTOW_SUCCESS;
+}
+
+RTOW_API int rtowReprojectAccumDevice(RtowContext ctx, const RtowReprojectParams* params, const RtowRay* rays, const RtowHitBuffers* hits, const RtowHitBuffers* previousHits,
+                                      const RtowAccumBuffers* previous, const RtowAccumBuffers* out, int32_t* outSource, void* stream)
+{
+    ReprojectConstants k;
+    RTOW_TRY(validateReproject(ctx, params, rays, hits, previousHits, previous, out, nullptr, nullptr, outSource, &k));
     std::lock_guard<std::mutex> lock(ctx->mu);
     hipStream_t s;
     RTOW_TRY(useDevice(ctx, stream, &s));
-    HIP_TRY(ctx, launchReproject(p, k, rays, *hits, *previousHits, *previous, *out, outSource, s), RTOW_ERROR_LAUNCH_FAILURE);
+    HIP_TRY(ctx, launchReproject(*params, k, rays, *hits, *previousHits, *previous, *out, outSource, s), RTOW_ERROR_LAUNCH_FAILURE);
+    return RTOW_SUCCESS;
+}
+
+RTOW_API int rtowReprojectAccumBilinearDevice(RtowContext ctx, const RtowReprojectParams* params, const RtowRay* rays, const RtowHitBuffers* hits,
+                                              const RtowHitBuffers* previousHits, const RtowAccumBuffers* previous, const RtowAccumBuffers* out,
+                                              const float* previousMoments, int32_t maxBatches, float* outMoments, int32_t* outSource, void* stream)
+{
+    if ((previousMoments == nullptr) != (outMoments == nullptr) || (outMoments && maxBatches < 1)) return RTOW_ERROR_INVALID_VALUE;
+    ReprojectConstants k;
+    RTOW_TRY(validateReproject(ctx, params, rays, hits, previousHits, previous, out, previousMoments, outMoments, outSource, &k));
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    hipStream_t s;
+    RTOW_TRY(useDevice(ctx, stream, &s));
+    HIP_TRY(ctx, launchReprojectBilinear(*params, k, rays, *hits, *previousHits, *previous, *out, previousMoments, maxBatches, outMoments, outSource, s),
+            RTOW_ERROR_LAUNCH_FAILURE);
     return RTOW_SUCCESS;
 }
 

@@ -411,6 +411,11 @@ inline ReprojectConstants reprojectConstants(const RtowView& v)
 }
 hipError_t launchReproject(const RtowReprojectParams& p, const ReprojectConstants& k, const RtowRay* rays, const RtowHitBuffers& hits, const RtowHitBuffers& previousHits,
                            const RtowAccumBuffers& previous, const RtowAccumBuffers& out, int32_t* outSource, hipStream_t stream);
+// rtowReprojectAccumBilinearDevice (rtow_reproject_bilinear.hip): one launch on `stream`, four validated taps per pixel; previousMoments and outMoments both null
+// or both given, outSource may be null (arguments validated by the caller)
+hipError_t launchReprojectBilinear(const RtowReprojectParams& p, const ReprojectConstants& k, const RtowRay* rays, const RtowHitBuffers& hits,
+                                   const RtowHitBuffers& previousHits, const RtowAccumBuffers& previous, const RtowAccumBuffers& out, const float* previousMoments,
+                                   int maxBatches, float* outMoments, int32_t* outSource, hipStream_t stream);
 // rtowReprojectMomentsDevice (rtow_moments_temporal.hip): one launch on `stream`, a gather through rtowReprojectAccumDevice's source map (arguments validated by the caller)
 hipError_t launchReprojectMoments(int pixelCount, const int32_t* source, const float* previousMoments, int maxBatches, float* outMoments, hipStream_t stream);
 // rtowEstimateMomentsDevice (rtow_moments_temporal.hip): one launch on `stream`; inMoments may be null (zeros) or outMoments itself, outFilled may be null (arguments

@@ -664,6 +664,30 @@ class ReprojectJob:
         return JobHandle(rc)
 
 
+class ReprojectBilinearJob(ReprojectJob):
+    """rtowReprojectAccumBilinearDevice: ReprojectJob through the four previous pixels around the reprojected point, each validated on its own and the bilinear
+    weights renormalised over the valid ones (SVGF's reprojection).  The fields are ReprojectJob's; with PreviousMoments and OutputMoments (both or neither,
+    abi.moments_bytes(Width * Height) bytes each) the luminance moments travel in the same pass through the same taps, capped at MaxBatches, and no
+    ReprojectMomentsJob is needed.  OutputSource (optional) receives the previous pixel of the heaviest valid tap, -1 = none."""
+
+    def __init__(self, context, Width, Height, PreviousView, DepthTolerance=abi.REPROJECT_DEFAULT_DEPTH_TOLERANCE, MaxHistory=abi.REPROJECT_DEFAULT_MAX_HISTORY,
+                 Flags=abi.REPROJECT_DEFAULT_FLAGS, Reserved=0, MaxBatches=abi.REPROJECT_MOMENTS_DEFAULT_MAX_BATCHES):
+        super().__init__(context, Width, Height, PreviousView, DepthTolerance, MaxHistory, Flags, Reserved)
+        self.MaxBatches = MaxBatches
+        self.PreviousMoments = self.OutputMoments = None
+
+    def Schedule(self, stream=None):
+        p = self.params()
+        hits = abi.HitBuffers(_device_ptr(self.HitDistance), _device_ptr(self.HitEntityIndex), None)
+        prev_hits = abi.HitBuffers(_device_ptr(self.PreviousHitDistance), _device_ptr(self.PreviousHitEntityIndex), None)
+        prev = _buffers(*[_device_ptr(b) for b in (self.PreviousColor, self.PreviousNormal, self.PreviousAlbedo, self.PreviousSampleCountWeight)])
+        out = _buffers(*[_device_ptr(b) for b in (self.OutputColor, self.OutputNormal, self.OutputAlbedo, self.OutputSampleCountWeight)])
+        rc = load().rtowReprojectAccumBilinearDevice(self.context.handle, C.byref(p), _device_ptr(self.Rays), C.byref(hits), C.byref(prev_hits), C.byref(prev),
+                                                     C.byref(out), _device_ptr(self.PreviousMoments), int(self.MaxBatches), _device_ptr(self.OutputMoments),
+                                                     _device_ptr(self.OutputSource), stream)
+        return JobHandle(rc)
+
+
 class ReprojectMomentsJob:
     """rtowReprojectMomentsDevice: the previous view's luminance moments (MomentsJob's) gathered to the new view's pixels through ReprojectJob's OutputSource, so that the
     variance estimate survives a camera move as the accumulators do.  Device buffers (or raw device addresses): Source int32 per pixel, PreviousMoments and

@@ -73,6 +73,8 @@ def load():
     lib.rtowProbeNearestHitInterval.argtypes = [vp, C.POINTER(abi.Float3), C.POINTER(abi.Float3), C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
     lib.rtowReprojectAccumDevice.argtypes = [vp, C.POINTER(abi.ReprojectParams), vp, C.POINTER(abi.HitBuffers), C.POINTER(abi.HitBuffers),
                                              C.POINTER(abi.AccumBuffers), C.POINTER(abi.AccumBuffers), vp, vp]
+    lib.rtowReprojectAccumBilinearDevice.argtypes = [vp, C.POINTER(abi.ReprojectParams), vp, C.POINTER(abi.HitBuffers), C.POINTER(abi.HitBuffers),
+                                                     C.POINTER(abi.AccumBuffers), C.POINTER(abi.AccumBuffers), vp, C.c_int32, vp, vp, vp]
     lib.rtowReprojectMomentsDevice.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp]
     lib.rtowEstimateMomentsDevice.argtypes = [vp, C.POINTER(abi.EstimateMomentsParams), vp, C.POINTER(abi.HitBuffers), vp, vp, vp, vp]
     lib.rtowNoiseMaskDevice.argtypes = [vp, C.POINTER(abi.NoiseMaskParams), vp, vp, vp, vp, vp, vp]
