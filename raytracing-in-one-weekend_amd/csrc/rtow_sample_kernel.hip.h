@@ -817,7 +817,9 @@ __device__ __forceinline__ f2 axis_distances(f2 planes, f2 oi)
     return t;
 }
 // node `idx` of the 80-byte image: the three axis blocks at the given offsets (0: (lo0 lo1 hi0 hi1)), and the children.  The reads are 8-byte aligned.
-__device__ __forceinline__ void load_node_image(const uint8_t* image, int idx, uint32_t offx, uint32_t offy, uint32_t offz, float4& px, float4& py, float4& pz, int& c0, int& c1)
+// (IMAGE: a generic pointer to the image, or its LDS address as a uint32_t - which the sign-ordered loop holds in a vector register, see there)
+template <typename IMAGE>
+__device__ __forceinline__ void load_node_image(IMAGE image, int idx, uint32_t offx, uint32_t offy, uint32_t offz, float4& px, float4& py, float4& pz, int& c0, int& c1)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     typedef __attribute__((address_space(3))) const uint8_t* LdsBytes;
@@ -830,6 +832,35 @@ __device__ __forceinline__ void load_node_image(const uint8_t* image, int idx, u
     c0 = c.x; c1 = c.y;
 #else
     (void)image; (void)idx; (void)offx; (void)offy; (void)offz; px = py = pz = make_float4(0, 0, 0, 0); c0 = c1 = -1;
+#endif
+}
+// LDS cursors of the walk (SIGNED_WALK kernels).  A lane's traversal-stack top and the end of its candidate list are carried as LDS byte addresses instead of as
+// counts: cursor = address of the lane's slot in row 0 + count * row bytes (rows are [slot][lane], 16-bit codes).  A store or a load then takes the cursor as it is (the
+// distance from the candidate rows to the stack rows is the instruction's immediate offset), a push or a pop is one add, and because a lane's offset inside a row is
+// smaller than a row, count >= k is cursor >= address of row k: a compare against a wave-uniform value, no lane base involved.  What the counts paid per visit was
+// max / add / shift-add for the pop slot and one shift-add for every other slot.
+__device__ __forceinline__ int lds_address(const void* p)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (int)(uint32_t)(uintptr_t)(__attribute__((address_space(3))) const uint8_t*)p;
+#else
+    (void)p; return 0;
+#endif
+}
+__device__ __forceinline__ int lds_code_load(int at)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (int)*(__attribute__((address_space(3))) const unsigned short*)(uint32_t)at;
+#else
+    (void)at; return 0;
+#endif
+}
+__device__ __forceinline__ void lds_code_store(int at, int code)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    *(__attribute__((address_space(3))) unsigned short*)(uint32_t)at = (unsigned short)code;
+#else
+    (void)at; (void)code;
 #endif
 }
 
@@ -881,6 +912,13 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
     const int swizzled = (tid & ~63) + ((tid & 31) << 1) + ((tid >> 5) & 1);
     Code* const cand = reinterpret_cast<Code*>(smem) + (WIDE ? tid : swizzled);                // [slot][lane] leaf candidates: the first kCandCapacity rows
     Code* const stack = cand + kCandCapacity * BT;                                             // [level][lane]: A.ldsStackRows rows, one per inner level of this scene's tree
+    // (SIGNED_WALK) the same two arrays through cursors (lds_code_load): `sp` and `nc` are then LDS addresses, laneRow0 + count * kRowBytes, in every stage;
+    // rowAt(k) <= cursor is count >= k
+    constexpr int kRowBytes = BT * (int)sizeof(Code);
+    constexpr int kStackAt = kCandCapacity * kRowBytes;                                        // from a lane's candidate row k to its stack row k
+    static_assert(!SIGNED_WALK || (!WIDE && kRowBytes == 2 * BT), "cursor compares need a lane's offset inside a row to be smaller than the row");
+    const int laneRow0 = lds_address(cand);
+    auto rowAt = [&](int k) -> int { return lds_address(smem) + k * kRowBytes; };
     HistRowsT<!ALL_LDS> histRows;
     histRows.lane = HW == 32 ? reinterpret_cast<unsigned short*>(smem + A.ldsHistOffset) + swizzled : nullptr;
     // {next, end} ticket chunk of this wave; chains: {.., needDone, chunk} = the chunk may only be handed out once chunkDone[chunk] >= needDone
@@ -1092,12 +1130,20 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
             tfar1 = vmin3(vmax(tlx.y, thx.y), vmax(tly.y, thy.y), vmax(tlz.y, thz.y));
         }
     };
+    // (SIGNED_WALK) the candidate list through its cursor: both leaf codes are written unconditionally, only the cursor is predicated (as with counts)
+    auto listLeaves = [&](int c0, int c1, bool leaf0, bool leaf1) {
+        lds_code_store(nc, ~c0);
+        nc += leaf0 ? kRowBytes : 0;
+        lds_code_store(nc, ~c1);
+        nc += leaf1 ? kRowBytes : 0;
+    };
     // a new ray segment starts: reset the traversal state
     auto startRay = [&]() {
         // rayInvDirection = rcp(ray.Direction), NaN -> +INF (JOBS/SampleBatchJob.cs:408-412).  The IEEE quotient, not v_rcp_f32: the leaf
         // children of the tree carry the reference's own entity boxes and must pass or fail the reference's own slab test (RT/HitTests.cs:9-21)
         inv = v3(RTOW_RCP_NAN_TO_INF(rd.x), RTOW_RCP_NAN_TO_INF(rd.y), RTOW_RCP_NAN_TO_INF(rd.z));
         cur = 0; sp = 0; nc = 0; prim = -1;
+        if constexpr (SIGNED_WALK) { sp = laneRow0; nc = laneRow0; }      // empty cursors
         best = __builtin_inff();
         tieAtBest = false;
         nHits = 0;
@@ -1552,14 +1598,18 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
                             const bool leaf0 = c0 < 0 && tmin0 < tfar0;                        // AxisAlignedBoundingBox.Hit on the entity's own box
                             const bool leaf1 = c1 < 0 && tmin1 < tfar1 && twoChildren;
                             if (FULL_DIAG && !refDiag) boundsHits += (leaf0 ? 1.0f : 0.0f) + (leaf1 ? 1.0f : 0.0f);
-                            cand[nc * BT] = (Code)~c0;
-                            nc += leaf0 ? 1 : 0;
-                            cand[nc * BT] = (Code)~c1;
-                            nc += leaf1 ? 1 : 0;
+                            if constexpr (SIGNED_WALK) {
+                                listLeaves(c0, c1, leaf0, leaf1);
+                            } else {
+                                cand[nc * BT] = (Code)~c0;
+                                nc += leaf0 ? 1 : 0;
+                                cand[nc * BT] = (Code)~c1;
+                                nc += leaf1 ? 1 : 0;
+                            }
                         }
                         // nodes five to eight: the exact-test stage comes back for them when these candidates are done (cur = -2 - k: node k is next)
                         if (LONG_LISTS) { if ((pcand.z & 0xffffu) != 0xffffu) cur = -6; }
-                        if (nc == 0 && cur == -1) classify(); else st = ST_TEST;
+                        if ((SIGNED_WALK ? nc < rowAt(1) : nc == 0) && cur == -1) classify(); else st = ST_TEST;
                     }
                 }
             }
@@ -1582,7 +1632,10 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
                 const float bestPrune = best * 1.000244140625f;
                 // Branch-free node visit: every LDS access of the iteration is issued up front (node, plus the stack slot a
                 // pop would need), candidate / stack slots are written unconditionally and only the counters are predicated,
-                // so the wave's EXEC mask changes only at the loop test.
+                // so the wave's EXEC mask changes only at the loop test.  What keeps it so is the FORM of the visit's tail: every value a lane keeps is one select
+                // of two operands that are already computed (nearChild, onlyChild, fromStack, pushed: named, none nested in another's arm).  Nested conditional
+                // expressions there (`both ? (swap ? c1 : c0) : ...`, `any ? next : (sp > 0 ? popped : -1)`) reached the compiler through finishVisit as control
+                // flow: two exec-mask regions and three more branches per visit in the headline kernels.  tests/test_isa_walk_loop.py reads the compiled loops.
                 // A walk hands its candidates to TEST as soon as it holds A.tune[6] of them (3; at most 7, the list holds 8 and a visit adds up to 2): the
                 // exact tests are deferred to keep the walk branch-free, but the nearest hit among the first few candidates - the walk visits near
                 // children first - prunes most of what is left of the walk, which a list filled to the brim (round 1 - 3: 7) never got to use.
@@ -1591,9 +1644,15 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
                 // (volume scenes keep every hit of a ray and prune nothing: their lists fill up as before)
                 const int candExit = VOLUMES ? kCandCapacity - 2 : (A.tune[6] < kCandCapacity - 1 ? A.tune[6] : kCandCapacity - 1) - 1;
                 if constexpr (SIGNED_WALK) {
-                    // (finishVisit = the tail of the loop in the `else` below, which is the parent's text for the variants without the walk: two copies to keep in step)
+                    // (finishVisit = the tail of the loop in the `else` below, which is the text of the variants without the walk: two copies that must compute the same -
+                    // here on cursors and in flat selects, there on counts and in the nested form; the prefetches of the wide-code kernels have no place in these)
+                    // `sp` and `nc` are LDS cursors in these kernels (lds_code_load): the loop tests and the hand-over below compare them with row addresses
+                    const int candLimit = rowAt(candExit + 1);           // nc <= candExit as a cursor: nc < candLimit
+                    // the slot a pop would read, one row under the top.  Not clamped at an empty stack: that read lands in the lane's last candidate row, the value is
+                    // dropped (fromStack), and a stack left one row under its base is not used again - the walk is over (cur = -1) and startRay resets the cursor
+                    auto popSlot = [&]() -> int { return lds_code_load(sp + (kStackAt - kRowBytes)); };
                     // the rest of a visit once the four slab distances are known: pruning, leaf test, candidate and stack stores, near child first
-                    auto finishVisit = [&](float tmin0, float tfar0, float tmin1, float tfar1, int c0, int c1, int popped, int spm1) {
+                    auto finishVisit = [&](float tmin0, float tfar0, float tmin1, float tfar1, int c0, int c1, int popped) {
                         // inner child (padded box): conservative, pruned by the nearest hit so far.  Leaf child (the reference's own entity box):
                         // AxisAlignedBoundingBox.Hit itself, tMin < tMax (RT/HitTests.cs:15-20) - pruning by `best` on top (<=, so that a tie at
                         // exactly `best` is still tested) cannot change which hit is nearest.
@@ -1601,59 +1660,53 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
                         const bool hit1 = tmin1 <= vmin(tfar1, bestPrune) && twoChildren;
                         const bool leaf0 = c0 < 0 && hit0 && tmin0 < tfar0, leaf1 = c1 < 0 && hit1 && tmin1 < tfar1;
                         if (FULL_DIAG && !refDiag) boundsHits += ((c0 < 0 ? leaf0 : hit0) ? 1.0f : 0.0f) + ((c1 < 0 ? leaf1 : hit1) ? 1.0f : 0.0f);
-                        cand[nc * BT] = (Code)~c0;
-                        nc += leaf0 ? 1 : 0;
-                        cand[nc * BT] = (Code)~c1;
-                        nc += leaf1 ? 1 : 0;
-                        if (PREFETCH_TRI) {
-                            // the listed triangle's record is on its way while the walk goes on; both leaves of one parent are neighbours in leaf order
-                            if (leaf0) prefetch_sector(sc.glob, L.triHotOffset + (uint32_t)~c0 * (uint32_t)sizeof(GpuTriHot), ldsDump);
-                            if (leaf1) prefetch_sector(sc.glob, L.triHotOffset + (uint32_t)~c1 * (uint32_t)sizeof(GpuTriHot), ldsDump);
-                        }
+                        listLeaves(c0, c1, leaf0, leaf1);
                         const bool in0 = hit0 && c0 >= 0;
                         const bool in1 = hit1 && c1 >= 0;
                         const bool both = in0 && in1;
                         const bool swap = tmin1 < tmin0;                         // near child first
-                        if (PREFETCH_FAR) {
-                            // every pushed node is visited later (nothing is dropped at the pop): ask for it now
-                            const uint32_t farNode = (uint32_t)(swap ? c0 : c1);
-                            if (both && farNode >= sc.ldsNodeCount) prefetch_sector(sc.glob, L.nodeOffset + farNode * 64u, ldsDump);
-                        }
-                        stack[sp * BT] = (Code)(swap ? c0 : c1);
-                        const int next = both ? (swap ? c1 : c0) : (in0 ? c0 : c1);
-                        const bool any = in0 || in1;
-                        cur = any ? next : (sp > 0 ? popped : -1);
-                        sp = any ? sp + (both ? 1 : 0) : spm1;
+                        lds_code_store(sp + kStackAt, swap ? c0 : c1);
+                        // flat single-level selects (see the walk's comment); `sp` is a cursor here: a push adds a row, a pop takes one off, sp >= rowAt(1) = not empty
+                        const int nearChild = swap ? c1 : c0;
+                        const int onlyChild = in0 ? c0 : c1;
+                        const int next = both ? nearChild : onlyChild;
+                        const int fromStack = sp >= rowAt(1) ? popped : -1;
+                        const bool any = in0 | in1;
+                        const int pushed = sp + (both ? kRowBytes : 0);
+                        cur = any ? next : fromStack;
+                        sp = any ? pushed : sp - kRowBytes;
                     };
                     if (signOrderedWave()) {
                         // ---- sign-ordered visit (see SIGNED_WALK): near and far planes come out of the 80-byte image by address, nothing is sorted ----
                         const uint32_t offx = near_plane_offset(inv.x), offy = near_plane_offset(inv.y), offz = near_plane_offset(inv.z);
                         const f2 oix = {ro.x, inv.x}, oiy = {ro.y, inv.y}, oiz = {ro.z, inv.z};
-                        while (budget > 0 && cur >= 0 && nc <= candExit) {
+                        // the image's LDS address in a vector register: node address = cur * 80 + image is then ONE multiply-add (with the address and the 80 both in
+                        // scalar registers the instruction can read only one of them, and every visit moved the other over first)
+                        uint32_t imageAt = (uint32_t)lds_address(ldsScene);
+                        asm volatile("" : "+v"(imageAt));
+                        while (budget > 0 && cur >= 0 && nc < candLimit) {
                             budget--;
                             STAT_ADD(3, (threadIdx.x & 63) == __builtin_ctzll(__ballot(1)) ? 1 : 0);
                             STAT_LANES(4);
                             float4 px, py, pz;
                             int c0, c1;
-                            load_node_image(ldsScene, cur, offx, offy, offz, px, py, pz, c0, c1);
-                            const int spm1 = sp > 0 ? sp - 1 : 0;
-                            const int popped = (int)stack[spm1 * BT];
+                            load_node_image(imageAt, cur, offx, offy, offz, px, py, pz, c0, c1);
+                            const int popped = popSlot();
                             // p = (near0 near1 far0 far1) of the axis
                             const f2 tnx = axis_distances(f2{px.x, px.y}, oix), tfx = axis_distances(f2{px.z, px.w}, oix);
                             const f2 tny = axis_distances(f2{py.x, py.y}, oiy), tfy = axis_distances(f2{py.z, py.w}, oiy);
                             const f2 tnz = axis_distances(f2{pz.x, pz.y}, oiz), tfz = axis_distances(f2{pz.z, pz.w}, oiz);
-                            finishVisit(vmax3(tnx.x, tny.x, vmax(tnz.x, 0.0f)), vmin3(tfx.x, tfy.x, tfz.x), vmax3(tnx.y, tny.y, vmax(tnz.y, 0.0f)), vmin3(tfx.y, tfy.y, tfz.y), c0, c1, popped, spm1);
+                            finishVisit(vmax3(tnx.x, tny.x, vmax(tnz.x, 0.0f)), vmin3(tfx.x, tfy.x, tfz.x), vmax3(tnx.y, tny.y, vmax(tnz.y, 0.0f)), vmin3(tfx.y, tfy.y, tfz.y), c0, c1, popped);
                         }
                     } else {
-                        while (budget > 0 && cur >= 0 && nc <= candExit) {
+                        while (budget > 0 && cur >= 0 && nc < candLimit) {
                             budget--;
                             STAT_ADD(3, (threadIdx.x & 63) == __builtin_ctzll(__ballot(1)) ? 1 : 0);
                             STAT_LANES(4);
                             float4 q0, q1, q2;
                             int c0, c1;
                             loadNode(cur, q0, q1, q2, c0, c1);
-                            const int spm1 = sp > 0 ? sp - 1 : 0;
-                            const int popped = (int)stack[spm1 * BT];
+                            const int popped = popSlot();
                             // q0 = (lo0.x lo1.x lo0.y lo1.y)  q1 = (lo0.z lo1.z hi0.x hi1.x)  q2 = (hi0.y hi1.y hi0.z hi1.z): pairs = (child0, child1)
                             const f2 tlx = (f2{q0.x, q0.y} - ox) * invx, thx = (f2{q1.z, q1.w} - ox) * invx;
                             const f2 tly = (f2{q0.z, q0.w} - oy) * invy, thy = (f2{q2.x, q2.y} - oy) * invy;
@@ -1662,7 +1715,7 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
                             const float tfar0 = vmin3(vmax(tlx.x, thx.x), vmax(tly.x, thy.x), vmax(tlz.x, thz.x));
                             const float tmin1 = vmax3(vmin(tlx.y, thx.y), vmin(tly.y, thy.y), vmax(vmin(tlz.y, thz.y), 0.0f));
                             const float tfar1 = vmin3(vmax(tlx.y, thx.y), vmax(tly.y, thy.y), vmax(tlz.y, thz.y));
-                            finishVisit(tmin0, tfar0, tmin1, tfar1, c0, c1, popped, spm1);
+                            finishVisit(tmin0, tfar0, tmin1, tfar1, c0, c1, popped);
                         }
                     }
                 } else {
@@ -1710,14 +1763,17 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
                             if (both && farNode >= sc.ldsNodeCount) prefetch_sector(sc.glob, L.nodeOffset + farNode * 64u, ldsDump);
                         }
                         stack[sp * BT] = (Code)(swap ? c0 : c1);
+                        // (the same values as finishVisit's flat selects, in the nested form: written inline in the loop this form compiles to selects - one basic
+                        // block in every variant, tests/test_isa_walk_loop.py - and the flat text here, though it computes the same, moved these variants' instruction
+                        // schedule and cost the 10 000-sphere and the moving-sphere configurations 0.2 - 0.3 %: HISTORY.md)
                         const int next = both ? (swap ? c1 : c0) : (in0 ? c0 : c1);
                         const bool any = in0 || in1;
                         cur = any ? next : (sp > 0 ? popped : -1);
                         sp = any ? sp + (both ? 1 : 0) : spm1;
                     }
                 }
-                if (cur < 0 || nc > candExit) {
-                    if (nc > 0) st = ST_TEST;      // exact tests pending (walk finished, or the list is full)
+                if (cur < 0 || (SIGNED_WALK ? nc >= rowAt(candExit + 1) : nc > candExit)) {
+                    if (SIGNED_WALK ? nc >= rowAt(1) : nc > 0) st = ST_TEST;      // exact tests pending (walk finished, or the list is full)
                     else classify();               // walk finished with nothing left to test
                 }
             }
@@ -1738,7 +1794,7 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
                         int k = -2 - cur;
                         cur = -1;
                         for (; k < 8; k++) {
-                            if (nc > kCandCapacity - 2) { cur = -2 - k; break; }                    // no room for two more: test what is here, then come back
+                            if (SIGNED_WALK ? nc >= rowAt(kCandCapacity - 1) : nc > kCandCapacity - 2) { cur = -2 - k; break; }                    // no room for two more: test what is here, then come back
                             const unsigned word = k < 6 ? pcand.z : pcand.w;
                             const unsigned node = (word >> (16 * (k & 1))) & 0xffffu;
                             if (node == 0xffffu) break;
@@ -1761,19 +1817,23 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
                             const bool leaf0 = c0 < 0 && tmin0 < tfar0;
                             const bool leaf1 = c1 < 0 && tmin1 < tfar1 && twoChildren;
                             if (FULL_DIAG && !refDiag) boundsHits += (leaf0 ? 1.0f : 0.0f) + (leaf1 ? 1.0f : 0.0f);
-                            cand[nc * BT] = (Code)~c0;
-                            nc += leaf0 ? 1 : 0;
-                            cand[nc * BT] = (Code)~c1;
-                            nc += leaf1 ? 1 : 0;
+                            if constexpr (SIGNED_WALK) {
+                                listLeaves(c0, c1, leaf0, leaf1);
+                            } else {
+                                cand[nc * BT] = (Code)~c0;
+                                nc += leaf0 ? 1 : 0;
+                                cand[nc * BT] = (Code)~c1;
+                                nc += leaf1 ? 1 : 0;
+                            }
                         }
                     }
                 }
                 if (FULL_DIAG && !refDiag) candidates += (float)nc;
-                while (nc > 0) {
+                while (SIGNED_WALK ? nc >= rowAt(1) : nc > 0) {
                     STAT_ADD(5, (threadIdx.x & 63) == __builtin_ctzll(__ballot(1)) ? 1 : 0);
                     STAT_LANES(6);
-                    nc--;
-                    const int i = (int)cand[nc * BT];
+                    nc -= SIGNED_WALK ? kRowBytes : 1;
+                    const int i = SIGNED_WALK ? lds_code_load(nc) : (int)cand[nc * BT];
                     if (VOLUMES) {
                         // FindHits keeps EVERY hit (:457-460) and injects an exit hit for volume hulls (Box / Sphere, :463-469)
                         const unsigned mw = *reinterpret_cast<const unsigned*>(section<ALL_LDS>(sc, L.matIndexOffset) + (uint32_t)i * 4u);
