@@ -373,7 +373,8 @@ hipError_t launchBuildChunkOrder(const unsigned short* pixelCost, unsigned* cost
 hipError_t launchInitTicketMap(unsigned* ticketMap, unsigned count, hipStream_t stream);
 // Which pixels share a wave.  Per super-tile of side x side tiles (8 x 8 pixels each; tile t = chunk t = tickets [64 t, 64 t + 64)): the super-tile's pixels sorted by the ray count the
 // last launch measured for them (pixelCost, ticket order under the map as it is), most expensive first, and dealt out to the super-tile's own chunks 64 at a time; pixelCost is
-// permuted along, so that it stays in ticket order under the NEW map.  side: 2 / 4 / 8.
+// permuted along, so that it stays in ticket order under the NEW map.  side: 2 .. kRegroupMaxSide (a partial super-tile at the right and bottom edges is sorted on its own); side 1: the tiles as they are, each tile's 64 tickets
+// most expensive first (classes[0] = levels of the tile's cost range, 0 = by the ray count itself); any other side: hipErrorInvalidValue, nothing launched.
 constexpr unsigned kRegroupMaxSide = 8;
 // classes: {0, -, -} = sort by the ray count itself; {t1, t2, t3} = by cost class (<= t1, <= t2, <= t3, beyond), pixels of a class in tile order
 hipError_t launchRegroupTickets(unsigned short* pixelCost, unsigned* ticketMap, unsigned tilesPerRow, unsigned tileRows, unsigned side, const unsigned classes[3], hipStream_t stream);
