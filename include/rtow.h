@@ -735,6 +735,83 @@ RTOW_API int rtowCombineFinalizeDevice(RtowContext context, const RtowCombinePar
                                        const float* inColor /*float4*/, const float* inNormal, const float* inAlbedo,
                                        uint8_t* outColor /*RGBA32*/, uint8_t* outNormal, uint8_t* outAlbedo, void* stream);
 
+/* Auto-exposure metering and a tone-mapped finalize.  rtowFinalizeDevice is the reference's saturate(LinearToGamma(c)) * 255: a frame lit by an HDR sky
+ * (rtowUploadSkyCubemap) or by emissive materials is white wherever radiance passes 1.  The reference carries the remedy commented out
+ * (JOBS/FinalizeTexturesJob.cs:28: ACESFitted(InputColor[index]).LinearToGamma() * 255; UTIL/Tools.cs:194-234: ACESFitted, ACESFilm).  These two calls are that line and
+ * the exposure it needs, as device passes: pure functions of their buffers, no allocation, no wait (they can be captured in a graph).  The exposure travels from the
+ * meter to the finalize through RtowExposureState in DEVICE memory; the host never reads it.  The frame loop: rtowCombineDevice, optionally a denoise or upsample
+ * pass, rtowMeterExposureDevice, rtowFinalizeToneMappedDevice, on one stream.
+ * Added after API version 12 without changing it: a host detects the calls by their entry points (C#: EntryPointNotFoundException).
+ *
+ * rtowMeterExposureDevice - a histogram of log-luminance, a trimmed mean, temporal adaptation.  Integers, and float32 in this order; no contraction, no log; the only
+ * transcendental is the deterministic exp2 of the path (det_exp2, csrc/rtow_detmath.hip.h).  min(a, b) = a < b ? a : b and max(a, b) = a > b ? a : b.
+ *   l = (0.2126f * r + 0.7152f * g) + 0.0722f * b.  A pixel is METERED iff l is finite and l >= 2^-16; everything else (NaN, inf, negatives, zeros, below 2^-16) is ignored.
+ *   bin = min((bits(l) >> 20) - 0x378, 255): eight bins per octave from 2^-16, bin 255 also takes everything from 2^16 up.
+ *   histogram[b] = the metered pixels of bin b, metered = their sum, ignored = width * height - metered.
+ *   Ranks in uint64 with floor division: lo = metered * lowPermille / 1000, hi = metered * highPermille / 1000, N = hi - lo.  Bin b owns the ranks
+ *   [cum_b, cum_b + histogram[b]) in bin order; S = sum over b of b * (the number of its ranks inside [lo, hi)).
+ *   N > 0:  Q = (S * 256 + N / 2) / N, meanLog2 = ((float)Q * 0x1p-11f - 16.0f) + 0x1p-4f (the mean bin centre in the mantissa-linear log2, exact in float32),
+ *           target = compensation - meanLog2.
+ *   N == 0: meanLog2 = +0, target = valid ? stops : 0.
+ *   targetStops = min(max(target, minStops), maxStops);  s = (valid != 0 && rate < 1) ? stops + (targetStops - stops) * rate : targetStops;
+ *   stops = min(max(s, minStops), maxStops);  exposure = det_exp2(stops);  valid becomes 1 iff N > 0 and otherwise stays as it was.
+ * Counts are integers: two calls give identical bits whatever the order of the workgroups.  Two plain launches in stream order (at most 256 workgroups with a private
+ * histogram per wave in LDS, each storing its 256 sums to its slab of `scratch`; then one workgroup that sums the slabs and resolves): no global atomics, no clear.
+ * RTOW_ERROR_INVALID_VALUE, nothing enqueued: a NULL context, params, inColor, scratch or state; width or height <= 0 or width * height > INT32_MAX; permilles outside
+ * 0 <= low <= high <= 1000; a non-finite compensation; stop limits outside -32 <= min <= max <= 32; a rate that is NaN or outside [0, 1]; flags or reserved != 0;
+ * scratch or state overlapping inColor or each other. */
+typedef struct RtowExposureParams {
+    int32_t width, height;
+    int32_t lowPermille, highPermille; /* 0 <= low <= high <= 1000: the ranks of the metered pixels that count   recommended 500 / 950 */
+    float   compensation;              /* stops, finite: log2 of the grey the trimmed mean is mapped to           recommended log2(0.18) as float32 */
+    float   minStops, maxStops;        /* -32 <= min <= max <= 32                                                recommended -8 / 8 */
+    float   rate;                      /* 0..1: share of the way to the target taken per call; 1 = at once       the host derives it from its frame time */
+    int32_t flags;                     /* 0 */
+    int32_t reserved;                  /* 0 */
+} RtowExposureParams;                  /* 40 bytes */
+
+typedef struct RtowExposureState {     /* DEVICE memory, the caller's, lives across frames; zero-filled = "no history" */
+    float    exposure;                 /* linear scale = det_exp2(stops) */
+    float    stops, targetStops, meanLog2;
+    uint32_t valid, metered, ignored, reserved;   /* reserved written 0 */
+    uint32_t histogram[256];
+} RtowExposureState;                   /* 1056 bytes */
+
+#define RTOW_EXPOSURE_SCRATCH_BYTES ((size_t)256 * 256 * 4)   /* per-workgroup partial histograms */
+
+RTOW_API int rtowMeterExposureDevice(RtowContext context, const RtowExposureParams* params,
+                                     const float* inColor /* device float3[W*H]: what finalize would take */,
+                                     void* scratch, RtowExposureState* state /* device, read and written */, void* stream);
+
+/* rtowFinalizeToneMappedDevice - rtowFinalizeDevice with an exposure and a tone curve in front of the colour's byte conversion.  float32 in this order, no contraction,
+ * correctly rounded '/':
+ *   s = params.exposure; with a state, params.exposure * (state->valid ? state->exposure : 1.0f) - read on the device when the kernel runs, never by the host.
+ *   Per channel: x = c * s, x = max(x, 0) with a NaN giving 0 (x > 0 ? x : 0), x = min(x, 65536.0f).
+ *   RTOW_TONE_CLAMP:       y = x.
+ *   RTOW_TONE_ACES_FILM    (UTIL/Tools.cs:226-234): y = (x * (2.51f * x + 0.03f)) / (x * (2.43f * x + 0.59f) + 0.14f).
+ *   RTOW_TONE_ACES_FITTED  (UTIL/Tools.cs:194-224, constants as written there): v_i = (m_i0 * x_r + m_i1 * x_g) + m_i2 * x_b with ACESInputMat,
+ *                          a = v * (v + 0.0245786f) - 0.000090537f, b = v * (0.983729f * v + 0.4329510f) + 0.238081f, w = a / b, y = the same three-term rows of
+ *                          ACESOutputMat on w.
+ *   The colour byte is rtowFinalizeDevice's conversion of y; the normal and albedo bytes are exactly rtowFinalizeDevice's.  inNormal / outNormal and inAlbedo /
+ *   outAlbedo may each be NULL as a pair: that guide is then neither read nor written.
+ * Consequence: RTOW_TONE_CLAMP with exposure 1 and no state gives rtowFinalizeDevice's bytes for every float operand (both clamps land on bytes the conversion
+ * already saturates to).
+ * RTOW_ERROR_INVALID_VALUE, nothing enqueued: a NULL context, params, inColor or outColor; a half-NULL guide pair; pixelCount <= 0; an unknown curve; an exposure that
+ * is negative or not finite; flags or reserved != 0; an output overlapping an input, the state, or another output. */
+typedef enum RtowToneCurve { RTOW_TONE_CLAMP = 0, RTOW_TONE_ACES_FITTED = 1, RTOW_TONE_ACES_FILM = 2 } RtowToneCurve;
+typedef struct RtowToneMapParams {
+    int32_t pixelCount;
+    int32_t curve;        /* RtowToneCurve */
+    float   exposure;     /* linear scale, finite, >= 0; 1 = none; multiplies the state's */
+    int32_t flags;        /* 0 */
+    int32_t reserved[2];  /* 0 */
+} RtowToneMapParams;      /* 24 bytes */
+
+RTOW_API int rtowFinalizeToneMappedDevice(RtowContext context, const RtowToneMapParams* params,
+                                          const RtowExposureState* state /* device or NULL */,
+                                          const float* inColor, const float* inNormal, const float* inAlbedo,
+                                          uint8_t* outColor, uint8_t* outNormal, uint8_t* outAlbedo, void* stream);
+
 /* replaces: OpenImageDenoiseJob / OptixDenoiseJob (JOBS/DenoiseJobs.cs:10-38, :44-119) in the reference's
  * ScheduleDenoise (UNITY/Raytracer.cs:874-949): float3 colour / normal / albedo from rtowCombineDevice in,
  * float3 colour out for rtowFinalizeDevice.  Not a neural denoiser: an edge-avoiding a-trous wavelet filter

@@ -439,6 +439,47 @@ class RectifyStats(C.Structure):
     _fields_ = [("judged", C.c_uint32), ("kept", C.c_uint32), ("cut", C.c_uint32), ("dropped", C.c_uint32)]
 
 
+# rtowMeterExposureDevice / rtowFinalizeToneMappedDevice (include/rtow.h): auto-exposure metering on the device and the finalize pass with an exposure and a tone curve
+# RtowToneCurve
+RTOW_TONE_CLAMP = 0
+RTOW_TONE_ACES_FITTED = 1
+RTOW_TONE_ACES_FILM = 2
+TONE_CLAMP, TONE_ACES_FITTED, TONE_ACES_FILM = RTOW_TONE_CLAMP, RTOW_TONE_ACES_FITTED, RTOW_TONE_ACES_FILM
+TONE_CURVES = (TONE_CLAMP, TONE_ACES_FITTED, TONE_ACES_FILM)
+TONE_DEFAULT_CURVE = TONE_ACES_FITTED          # the curve of the line the reference left commented out (JOBS/FinalizeTexturesJob.cs:28)
+TONE_DEFAULT_EXPOSURE = 1.0
+EXPOSURE_BINS = 256                            # eight per octave from 2^-16; bin 255 also takes everything from 2^16 up
+# recommended metering: the upper half of the metered pixels without the brightest 5 % (a sun, a lamp) mapped to middle grey, within eight stops either way, at once
+EXPOSURE_DEFAULT_LOW_PERMILLE = 500
+EXPOSURE_DEFAULT_HIGH_PERMILLE = 950
+EXPOSURE_DEFAULT_COMPENSATION = C.c_float(-2.4739311883324124).value      # log2(0.18) as float32: the trimmed mean lands on middle grey
+EXPOSURE_DEFAULT_MIN_STOPS = -8.0
+EXPOSURE_DEFAULT_MAX_STOPS = 8.0
+EXPOSURE_DEFAULT_RATE = 1.0
+
+
+def exposure_scratch_bytes():
+    """RTOW_EXPOSURE_SCRATCH_BYTES: a 256-bin partial histogram for each of at most 256 workgroups"""
+    return 256 * 256 * 4
+
+
+class ExposureParams(C.Structure):
+    """RtowExposureParams (40 bytes)"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("lowPermille", C.c_int32), ("highPermille", C.c_int32), ("compensation", C.c_float),
+                ("minStops", C.c_float), ("maxStops", C.c_float), ("rate", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ExposureState(C.Structure):
+    """RtowExposureState (1056 bytes): DEVICE memory of the caller's that lives across frames; zero-filled = no history"""
+    _fields_ = [("exposure", C.c_float), ("stops", C.c_float), ("targetStops", C.c_float), ("meanLog2", C.c_float), ("valid", C.c_uint32), ("metered", C.c_uint32),
+                ("ignored", C.c_uint32), ("reserved", C.c_uint32), ("histogram", C.c_uint32 * 256)]
+
+
+class ToneMapParams(C.Structure):
+    """RtowToneMapParams (24 bytes)"""
+    _fields_ = [("pixelCount", C.c_int32), ("curve", C.c_int32), ("exposure", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 # every symbol include/rtow.h declares (tests/test_abi.py checks the library exports all of them)
 EXPORTED_SYMBOLS = [
     "rtowGetApiVersion", "rtowErrorString", "rtowCreateContext", "rtowDestroyContext", "rtowUploadScene",
@@ -453,4 +494,5 @@ EXPORTED_SYMBOLS = [
     "rtowBuildPixelListDevice", "rtowSamplePixelsDevice", "rtowTraceGuideRaysDevice", "rtowTraceGuideViewDevice",
     "rtowAccumulateMomentsDevice", "rtowDenoiseVarianceDevice", "rtowReprojectMomentsDevice", "rtowEstimateMomentsDevice",
     "rtowNoiseMaskDevice", "rtowRectifyHistoryDevice", "rtowReprojectAccumBilinearDevice",
+    "rtowMeterExposureDevice", "rtowFinalizeToneMappedDevice",
 ]

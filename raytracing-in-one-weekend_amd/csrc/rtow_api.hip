@@ -2078,6 +2078,52 @@ RTOW_API int rtowCombineFinalizeDevice(RtowContext ctx, const RtowCombineParams*
     return RTOW_SUCCESS;
 }
 
+RTOW_API int rtowMeterExposureDevice(RtowContext ctx, const RtowExposureParams* params, const float* inColor, void* scratch, RtowExposureState* state, void* stream)
+{
+    if (!ctx || !params || !inColor || !scratch || !state) return RTOW_ERROR_INVALID_VALUE;
+    const RtowExposureParams& p = *params;
+    if (p.width <= 0 || p.height <= 0 || (int64_t)p.width * p.height > INT32_MAX) return RTOW_ERROR_INVALID_VALUE;
+    if (p.lowPermille < 0 || p.lowPermille > p.highPermille || p.highPermille > 1000) return RTOW_ERROR_INVALID_VALUE;
+    if (!(p.compensation >= -FLT_MAX && p.compensation <= FLT_MAX)) return RTOW_ERROR_INVALID_VALUE;      // NaN fails
+    if (!(p.minStops >= -32.0f && p.minStops <= p.maxStops && p.maxStops <= 32.0f)) return RTOW_ERROR_INVALID_VALUE;
+    if (!(p.rate >= 0.0f && p.rate <= 1.0f)) return RTOW_ERROR_INVALID_VALUE;
+    if (p.flags != 0 || p.reserved != 0) return RTOW_ERROR_INVALID_VALUE;
+    const size_t n = (size_t)p.width * (size_t)p.height;
+    const Range in{inColor, n * 12}, work{scratch, RTOW_EXPOSURE_SCRATCH_BYTES}, record{state, sizeof(RtowExposureState)};
+    if (overlaps(work, in) || overlaps(record, in) || overlaps(work, record)) return RTOW_ERROR_INVALID_VALUE;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    hipStream_t s;
+    RTOW_TRY(useDevice(ctx, stream, &s));
+    HIP_TRY(ctx, launchMeterExposure(p, inColor, scratch, state, s), RTOW_ERROR_LAUNCH_FAILURE);
+    return RTOW_SUCCESS;
+}
+
+RTOW_API int rtowFinalizeToneMappedDevice(RtowContext ctx, const RtowToneMapParams* params, const RtowExposureState* state, const float* inColor, const float* inNormal,
+                                          const float* inAlbedo, uint8_t* outColor, uint8_t* outNormal, uint8_t* outAlbedo, void* stream)
+{
+    if (!ctx || !params || !inColor || !outColor) return RTOW_ERROR_INVALID_VALUE;
+    if ((inNormal == nullptr) != (outNormal == nullptr) || (inAlbedo == nullptr) != (outAlbedo == nullptr)) return RTOW_ERROR_INVALID_VALUE;
+    const RtowToneMapParams& p = *params;
+    if (p.pixelCount <= 0) return RTOW_ERROR_INVALID_VALUE;
+    if (p.curve != RTOW_TONE_CLAMP && p.curve != RTOW_TONE_ACES_FITTED && p.curve != RTOW_TONE_ACES_FILM) return RTOW_ERROR_INVALID_VALUE;
+    if (!(p.exposure >= 0.0f && p.exposure <= FLT_MAX)) return RTOW_ERROR_INVALID_VALUE;                  // NaN fails
+    if (p.flags != 0 || p.reserved[0] != 0 || p.reserved[1] != 0) return RTOW_ERROR_INVALID_VALUE;
+    const size_t n = (size_t)p.pixelCount;
+    const Range written[3] = {{outColor, n * 4}, {outNormal, n * 4}, {outAlbedo, n * 4}};                 // a null buffer overlaps nothing
+    const Range read[4] = {{inColor, n * 12}, {inNormal, n * 12}, {inAlbedo, n * 12}, {state, sizeof(RtowExposureState)}};
+    for (int i = 0; i < 3; ++i) {
+        for (const Range& in : read)
+            if (overlaps(written[i], in)) return RTOW_ERROR_INVALID_VALUE;
+        for (int j = i + 1; j < 3; ++j)
+            if (overlaps(written[i], written[j])) return RTOW_ERROR_INVALID_VALUE;
+    }
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    hipStream_t s;
+    RTOW_TRY(useDevice(ctx, stream, &s));
+    HIP_TRY(ctx, launchFinalizeToneMapped(p, state, inColor, inNormal, inAlbedo, outColor, outNormal, outAlbedo, ctx->dByteThresholds, s), RTOW_ERROR_LAUNCH_FAILURE);
+    return RTOW_SUCCESS;
+}
+
 RTOW_API int rtowReduceMetricsDeviceAsync(RtowContext ctx, int32_t pixelCount, const void* diagnostics, int32_t diagnosticsStride, const float* color,
                                           const float* sampleCountWeight, void* stream, RtowMetrics* outMetrics)
 {

@@ -35,6 +35,8 @@ __device__ __forceinline__ unsigned to_byte_exact(float v)
 // already reached k the stretch between the two is a mixed zone, which to_byte_table hands to the exact form.  More zones than the table
 // holds: one zone covering everything (all exact, still correct).  Whether a window of kScan floats is enough is not argued, it is
 // enumerated: tests/native/finalize_parity.hip compares the two forms on all 2^32 operands.
+// (A second unit of the library that only converts - rtow_tonemap.hip - defines RTOW_FINALIZE_NO_TABLE_BUILDER: the kernel has one definition, in rtow_kernels.hip.)
+#ifndef RTOW_FINALIZE_NO_TABLE_BUILDER
 __global__ void __launch_bounds__(256) build_byte_thresholds_kernel(float* __restrict__ T)
 {
     constexpr unsigned kScan = 256u;
@@ -69,6 +71,7 @@ __global__ void __launch_bounds__(256) build_byte_thresholds_kernel(float* __res
     // more zones than the table holds: one zone covering every operand (all exact, still correct; inf itself is 255 on both paths)
     if (k == 0 && zones > (unsigned)kByteZones) { T[257] = 0.0f; T[258] = __builtin_inff(); }
 }
+#endif
 
 // T: the table above (LDS).  NaN and negative operands give 0, like the exact form (math.max(NaN, 0) is 0).
 // The conversion is written for N operands at once (a pixel's nine channels): N independent chains of estimate -> ONE paired LDS read of

@@ -390,6 +390,13 @@ hipError_t launchFinalize(int pixelCount, const float* inColor, const float* inN
 // CombineJob -> FinalizeTexturesJob in one pass (the bytes of the two kernels one after the other)
 hipError_t launchCombineFinalize(const RtowCombineParams& p, const float* inColor, const float* inNormal, const float* inAlbedo,
                                  uint8_t* outColor, uint8_t* outNormal, uint8_t* outAlbedo, const float* thresholds, hipStream_t stream);
+// rtowMeterExposureDevice (rtow_tonemap.hip): the histogram launch and the resolve launch on `stream`, no atomics on global memory, no clear; `scratch` holds
+// RTOW_EXPOSURE_SCRATCH_BYTES, `state` is read and written by the second launch (arguments validated by the caller)
+hipError_t launchMeterExposure(const RtowExposureParams& p, const float* inColor, void* scratch, RtowExposureState* state, hipStream_t stream);
+// rtowFinalizeToneMappedDevice (rtow_tonemap.hip): one launch on `stream`; `state` may be null, inNormal / outNormal and inAlbedo / outAlbedo may each be null as a
+// pair (arguments validated by the caller)
+hipError_t launchFinalizeToneMapped(const RtowToneMapParams& p, const RtowExposureState* state, const float* inColor, const float* inNormal, const float* inAlbedo,
+                                    uint8_t* outColor, uint8_t* outNormal, uint8_t* outAlbedo, const float* thresholds, hipStream_t stream);
 
 // rtowDenoiseDevice (rtow_denoise.hip): one launch per a-trous level on `stream`, ping-pong between scratch and outColor (params validated by the caller)
 hipError_t launchDenoise(const RtowDenoiseParams& p, const float* inColor, const float* inNormal, const float* inAlbedo, float* scratch, float* outColor,

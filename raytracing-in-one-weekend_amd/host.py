@@ -789,6 +789,52 @@ class RectifyHistoryJob:
         return JobHandle(rc)
 
 
+class ExposureJob:
+    """rtowMeterExposureDevice: the exposure a frame asks for, measured on the device - a 256-bin histogram of log-luminance over InputColor (the float3 colour finalize
+    would take), the mean of the bins between the LowPermille and HighPermille ranks of the metered pixels mapped to 2^Compensation, limited to MinStops .. MaxStops and
+    approached by Rate per call.  Device buffers (or raw device addresses): InputColor; Scratch of abi.exposure_scratch_bytes() bytes; State, one abi.ExposureState in
+    DEVICE memory that lives across frames (zero-filled = no history) and is what ToneMapJob reads - the host never has to."""
+
+    def __init__(self, context, Width, Height, LowPermille=abi.EXPOSURE_DEFAULT_LOW_PERMILLE, HighPermille=abi.EXPOSURE_DEFAULT_HIGH_PERMILLE,
+                 Compensation=abi.EXPOSURE_DEFAULT_COMPENSATION, MinStops=abi.EXPOSURE_DEFAULT_MIN_STOPS, MaxStops=abi.EXPOSURE_DEFAULT_MAX_STOPS,
+                 Rate=abi.EXPOSURE_DEFAULT_RATE, Flags=0, Reserved=0):
+        self.context, self.Width, self.Height = context, Width, Height
+        self.LowPermille, self.HighPermille, self.Compensation, self.MinStops, self.MaxStops = LowPermille, HighPermille, Compensation, MinStops, MaxStops
+        self.Rate, self.Flags, self.Reserved = Rate, Flags, Reserved
+        self.InputColor = self.Scratch = self.State = None
+
+    def params(self):
+        return abi.ExposureParams(int(self.Width), int(self.Height), int(self.LowPermille), int(self.HighPermille), float(self.Compensation), float(self.MinStops),
+                                  float(self.MaxStops), float(self.Rate), int(self.Flags), int(self.Reserved))
+
+    def Schedule(self, stream=None):
+        p = self.params()
+        rc = load().rtowMeterExposureDevice(self.context.handle, C.byref(p), _device_ptr(self.InputColor), _device_ptr(self.Scratch), _device_ptr(self.State), stream)
+        return JobHandle(rc)
+
+
+class ToneMapJob:
+    """rtowFinalizeToneMappedDevice: FinalizeTexturesJob with an exposure and a tone curve (abi.TONE_CLAMP / TONE_ACES_FITTED / TONE_ACES_FILM) in front of the colour's
+    byte conversion - the line the reference left commented out (JOBS/FinalizeTexturesJob.cs:28).  Device buffers (or raw device addresses).  State (optional): the
+    abi.ExposureState ExposureJob keeps in device memory, whose exposure multiplies Exposure when the kernel runs; InputNormal / OutputNormal and InputAlbedo /
+    OutputAlbedo may each stay None as a pair.  TONE_CLAMP with Exposure 1 and no State gives FinalizeTexturesJob's bytes."""
+
+    def __init__(self, context, PixelCount, Curve=abi.TONE_DEFAULT_CURVE, Exposure=abi.TONE_DEFAULT_EXPOSURE, Flags=0):
+        self.context, self.PixelCount, self.Curve, self.Exposure, self.Flags = context, PixelCount, Curve, Exposure, Flags
+        self.State = self.InputColor = self.InputNormal = self.InputAlbedo = None
+        self.OutputColor = self.OutputNormal = self.OutputAlbedo = None
+
+    def params(self):
+        return abi.ToneMapParams(int(self.PixelCount), int(self.Curve), float(self.Exposure), int(self.Flags), (C.c_int32 * 2)(0, 0))
+
+    def Schedule(self, stream=None):
+        p = self.params()
+        rc = load().rtowFinalizeToneMappedDevice(self.context.handle, C.byref(p), _device_ptr(self.State), _device_ptr(self.InputColor), _device_ptr(self.InputNormal),
+                                                 _device_ptr(self.InputAlbedo), _device_ptr(self.OutputColor), _device_ptr(self.OutputNormal),
+                                                 _device_ptr(self.OutputAlbedo), stream)
+        return JobHandle(rc)
+
+
 class PixelListJob:
     """rtowBuildPixelListDevice: the pixels of a Width x Height frame that lie in the rectangle [X0, X1) x [Y0, Y1) and in the row slice, whose Mask byte (optional) is
     not 0 and whose accumulated sample count Color[4 p + 3] (optional) is not >= MinSampleCount, as a device list in 8 x 8 tile order for rtowSamplePixelsDevice.
