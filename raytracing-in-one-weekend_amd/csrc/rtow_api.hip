@@ -2,9 +2,10 @@
 //
 // Host-side runtime of the path: context / device selection, scene compilation + upload, grow-only device staging
 // for the host-buffer entry point, kernel launch on a HIP stream with HIP-event timing, cooperative cancellation,
-// and the post passes.  There is no CPU implementation behind any entry point: without a usable HIP device
+// and the ray queries.  There is no CPU implementation behind any entry point: without a usable HIP device
 // rtowCreateContext fails with RTOW_ERROR_NO_DEVICE and nothing else can be called.  The multi-GPU entry points (rtowComm*, rtowGatherRowsDevice,
-// rtowHybridPlan, rtowExchangeAccumDevice) are in rtow_comm.hip; the context itself is rtow_context.h.
+// rtowHybridPlan, rtowExchangeAccumDevice) are in rtow_comm.hip, the post passes in rtow_api_post.hip; the context itself is rtow_context.h, and what
+// an entry point refuses before it takes its lock is rtow_validate.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -76,21 +77,6 @@ using namespace rtow;
 
 
 namespace {
-
-int validateParams(const RtowSampleParams* p)
-{
-    if (!p) return RTOW_ERROR_INVALID_VALUE;
-    const int w = (int)p->size.x, h = (int)p->size.y;
-    if (w <= 0 || h <= 0 || (long long)w * h > 0x7fffffffLL) return RTOW_ERROR_INVALID_VALUE;
-    if (p->sliceDivider < 1 || p->sliceOffset < 0 || p->sliceOffset >= p->sliceDivider) return RTOW_ERROR_INVALID_VALUE;
-    if (p->traceDepth < 1 || p->traceDepth > 64) return p->traceDepth < 1 ? RTOW_ERROR_INVALID_VALUE : RTOW_ERROR_CAPACITY;
-    if (p->noiseColor < RTOW_NOISE_WHITE || p->noiseColor > RTOW_NOISE_SPATIOTEMPORAL_BLUE) return RTOW_ERROR_INVALID_VALUE;
-    if (p->rngPolicy != RTOW_RNG_REFERENCE && p->rngPolicy != RTOW_RNG_PER_SAMPLE && p->rngPolicy != RTOW_RNG_PER_SAMPLE_XOROSHIRO) return RTOW_ERROR_INVALID_VALUE;
-    if (p->rngPolicy != RTOW_RNG_REFERENCE && p->noiseColor != RTOW_NOISE_WHITE) return RTOW_ERROR_INVALID_VALUE;   // the texture walks are per pixel by construction
-    if (p->environment.skyType < RTOW_SKY_NONE || p->environment.skyType > RTOW_SKY_CUBEMAP) return RTOW_ERROR_INVALID_VALUE;
-    if (p->diagnosticsStride != 4 && p->diagnosticsStride != 16) return RTOW_ERROR_INVALID_VALUE;
-    return RTOW_SUCCESS;
-}
 
 int ownedRows(const RtowSampleParams* p)
 {
@@ -840,15 +826,6 @@ int waitWithCancel(RtowContext ctx, const volatile uint8_t* cancel)
     return takeOverflow(ctx);
 }
 
-// device-visible address of caller memory [p, p + bytes) if it lies inside a range given to rtowRegisterHostBuffer, else null
-uint8_t* mappedHost(RtowContext ctx, const void* p, size_t bytes)
-{
-    const uint8_t* q = (const uint8_t*)p;
-    for (const RtowContext_t::HostRange& r : ctx->hostRanges)
-        if (q >= r.base && q + bytes <= r.base + r.size) return r.device + (q - r.base);
-    return nullptr;
-}
-
 // The host-buffer calls' grow-only staging: the frame's four accumulators, and one diagnostics frame per batch - devDiag[b], null for a batch without a buffer
 int prepareStaging(RtowContext ctx, int count, const RtowSampleParams* p, void* const* diagnostics, std::vector<void*>& devDiag)
 {
@@ -912,29 +889,9 @@ int enqueueBatches(RtowContext ctx, int count, const RtowSampleParams* params, c
     return rc;
 }
 
-// What the entry points do once they hold their lock: this thread on the context's device (calls come from a different worker thread each time) and the stream the work
-// goes to (null: the context's)
-int useDevice(RtowContext ctx, void* stream, hipStream_t* s)
-{
-    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
-    *s = stream ? (hipStream_t)stream : ctx->stream;
-    return RTOW_SUCCESS;
-}
-
 // primitive -> the host's entity index (all-triangle scenes number their primitives in leaf order), on the device and on the host; null: the same number
 const int32_t* entityMapDevice(RtowContext ctx) { return ctx->scene.entityOfPrim.empty() ? nullptr : ctx->dEntityOfPrim; }
 const int32_t* entityMapHost(RtowContext ctx) { return ctx->scene.entityOfPrim.empty() ? nullptr : ctx->scene.entityOfPrim.data(); }
-
-// a query has to be asked for at least one of distance / entityIndex / normal
-bool anyHitBuffer(const RtowHitBuffers& h) { return h.distance || h.entityIndex || h.normal; }
-
-// what both guide calls check of their parameters and outputs
-bool guideArgumentsValid(const RtowGuideParams* params, const RtowGuideBuffers* out)
-{
-    if (!params || !out) return false;
-    if (params->maxBounces < 0 || params->maxBounces > RTOW_GUIDE_MAX_BOUNCES || params->flags != 0 || params->reserved != 0) return false;
-    return anyHitBuffer(out->hits) || out->rays || out->throughput || out->pathDistance || out->bounces || out->end;
-}
 
 GuideScene guideScene(RtowContext ctx)
 {
@@ -945,13 +902,6 @@ GuideScene guideScene(RtowContext ctx)
     sc.texBlob = ctx->scene.texLayout.totalBytes ? ctx->dTexBlob : nullptr;
     sc.texLayout = ctx->scene.texLayout;
     return sc;
-}
-
-// the aliasing checks of the post passes: a caller's buffer, and whether two of them share a byte (a null buffer shares none)
-struct Range { const void* base; size_t bytes; };
-bool overlaps(const Range& a, const Range& b)
-{
-    return a.base && b.base && (uintptr_t)a.base < (uintptr_t)b.base + b.bytes && (uintptr_t)b.base < (uintptr_t)a.base + a.bytes;
 }
 
 // The sample entry points' common start, in this order (the same bad input gets the same code): every batch's params - validateParams, where a trace depth beyond 64
@@ -1602,7 +1552,7 @@ RTOW_API int rtowTraceViewDevice(RtowContext ctx, const RtowTraceViewParams* par
 {
     if (!ctx || !params || !hits) return RTOW_ERROR_INVALID_VALUE;
     if (!anyHitBuffer(*hits)) return RTOW_ERROR_INVALID_VALUE;
-    if (params->width <= 0 || params->height <= 0 || (int64_t)params->width * params->height > INT32_MAX || params->reserved != 0) return RTOW_ERROR_INVALID_VALUE;
+    if (!viewSizeValid(*params)) return RTOW_ERROR_INVALID_VALUE;
     std::lock_guard<std::mutex> lock(ctx->mu);
     if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
     hipStream_t s;
@@ -1640,12 +1590,8 @@ RTOW_API int rtowTraceOcclusionDevice(RtowContext ctx, int32_t count, const Rtow
 RTOW_API int rtowShadeHitsDevice(RtowContext ctx, const RtowShadeHitsParams* params, int32_t count, const RtowRay* rays, const int32_t* entityIndex,
                                  const RtowSurfaceBuffers* surface, void* stream)
 {
-    if (!ctx || !params || !rays || !entityIndex || !surface || count < 0) return RTOW_ERROR_INVALID_VALUE;
-    if (!surface->albedo && !surface->emission && !surface->texCoord && !surface->metallicGlossiness && !surface->materialIndex && !surface->materialInfo)
-        return RTOW_ERROR_INVALID_VALUE;
-    if (params->flags != 0 || params->reserved != 0) return RTOW_ERROR_INVALID_VALUE;
-    const int32_t sky = params->environment.skyType;
-    if (sky != RTOW_SKY_NONE && sky != RTOW_SKY_GRADIENT && sky != RTOW_SKY_CUBEMAP) return RTOW_ERROR_INVALID_VALUE;
+    if (!ctx) return RTOW_ERROR_INVALID_VALUE;
+    RTOW_TRY(validateShadeHits(params, count, rays, entityIndex, surface));
     std::lock_guard<std::mutex> lock(ctx->mu);
     if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
     if (count == 0) return RTOW_SUCCESS;
@@ -1681,7 +1627,7 @@ RTOW_API int rtowTraceGuideRaysDevice(RtowContext ctx, const RtowGuideParams* pa
 RTOW_API int rtowTraceGuideViewDevice(RtowContext ctx, const RtowGuideParams* params, const RtowTraceViewParams* view, const RtowGuideBuffers* out, void* stream)
 {
     if (!ctx || !view || !guideArgumentsValid(params, out)) return RTOW_ERROR_INVALID_VALUE;
-    if (view->width <= 0 || view->height <= 0 || (int64_t)view->width * view->height > INT32_MAX || view->reserved != 0) return RTOW_ERROR_INVALID_VALUE;
+    if (!viewSizeValid(*view)) return RTOW_ERROR_INVALID_VALUE;
     std::lock_guard<std::mutex> lock(ctx->mu);
     if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
     hipStream_t s;
@@ -1698,333 +1644,6 @@ RTOW_API int rtowGetLastSampleKernelMs(RtowContext ctx, float* outMs)
     HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
     HIP_TRY(ctx, hipEventSynchronize(ctx->evStop), RTOW_ERROR_LAUNCH_FAILURE);
     HIP_TRY(ctx, hipEventElapsedTime(outMs, ctx->evStart, ctx->evStop), RTOW_ERROR_LAUNCH_FAILURE);
-    return RTOW_SUCCESS;
-}
-
-RTOW_API int rtowReduceMetricsDevice(RtowContext ctx, int32_t pixelCount, const void* diagnostics, int32_t diagnosticsStride, const float* color,
-                                     const float* sampleCountWeight, void* stream, RtowMetrics* outMetrics)
-{
-    if (!ctx || !diagnostics || !color || !sampleCountWeight || !outMetrics || pixelCount <= 0) return RTOW_ERROR_INVALID_VALUE;
-    if (diagnosticsStride != 4 && diagnosticsStride != 16) return RTOW_ERROR_INVALID_VALUE;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    hipStream_t s;
-    RTOW_TRY(useDevice(ctx, stream, &s));
-    if (ctx->haveMetricsDone) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->evMetricsDone, 0), RTOW_ERROR_LAUNCH_FAILURE);      // an asynchronous reduction may still be folding the partials
-    HIP_TRY(ctx, launchReduceMetrics(pixelCount, (const uint8_t*)diagnostics, diagnosticsStride, color, sampleCountWeight, ctx->dPartials, s),
-            RTOW_ERROR_LAUNCH_FAILURE);
-    // the per-block partials are folded on the device and the 40-byte record lands in pinned host memory by the time the stream is idle: no 8 KB copy of the partials, no
-    // DMA of its own (round 4 copied and folded them on the host: 44.6 us per call at 1920 x 1080 against 18.6 us of kernels)
-    HIP_TRY(ctx, launchFoldMetrics(ctx->dPartials, ctx->dMetricsRecord, s), RTOW_ERROR_LAUNCH_FAILURE);
-    HIP_TRY(ctx, hipStreamSynchronize(s), RTOW_ERROR_LAUNCH_FAILURE);
-    memcpy(outMetrics, (const void*)ctx->hMetricsRecord, sizeof(RtowMetrics));
-    return RTOW_SUCCESS;
-}
-
-RTOW_API int rtowCombineDevice(RtowContext ctx, const RtowCombineParams* params, const float* inColor, const float* inNormal, const float* inAlbedo,
-                               float* outColor, float* outNormal, float* outAlbedo, void* stream)
-{
-    if (!ctx || !params || !inColor || !inNormal || !inAlbedo || !outColor || !outNormal || !outAlbedo) return RTOW_ERROR_INVALID_VALUE;
-    if (params->width <= 0 || params->height <= 0) return RTOW_ERROR_INVALID_VALUE;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    hipStream_t s;
-    RTOW_TRY(useDevice(ctx, stream, &s));
-    HIP_TRY(ctx, launchCombine(*params, inColor, inNormal, inAlbedo, outColor, outNormal, outAlbedo, s), RTOW_ERROR_LAUNCH_FAILURE);
-    return RTOW_SUCCESS;
-}
-
-RTOW_API int rtowFinalizeDevice(RtowContext ctx, int32_t pixelCount, const float* inColor, const float* inNormal, const float* inAlbedo,
-                                uint8_t* outColor, uint8_t* outNormal, uint8_t* outAlbedo, void* stream)
-{
-    if (!ctx || pixelCount <= 0 || !inColor || !inNormal || !inAlbedo || !outColor || !outNormal || !outAlbedo) return RTOW_ERROR_INVALID_VALUE;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    hipStream_t s;
-    RTOW_TRY(useDevice(ctx, stream, &s));
-    HIP_TRY(ctx, launchFinalize(pixelCount, inColor, inNormal, inAlbedo, outColor, outNormal, outAlbedo, ctx->dByteThresholds, s), RTOW_ERROR_LAUNCH_FAILURE);
-    return RTOW_SUCCESS;
-}
-
-RTOW_API int rtowDenoiseDevice(RtowContext ctx, const RtowDenoiseParams* params, const float* inColor, const float* inNormal, const float* inAlbedo,
-                               void* scratch, float* outColor, void* stream)
-{
-    if (!ctx || !params || !inColor || !inNormal || !inAlbedo || !outColor) return RTOW_ERROR_INVALID_VALUE;
-    const RtowDenoiseParams& p = *params;
-    if (p.width <= 0 || p.height <= 0 || (int64_t)p.width * p.height > INT32_MAX) return RTOW_ERROR_INVALID_VALUE;
-    if (p.iterations < 1 || p.iterations > 8 || p.normalSharpness < 0 || p.normalSharpness > 8) return RTOW_ERROR_INVALID_VALUE;
-    if (!(p.colorSigma >= 0.0f && p.colorSigma <= FLT_MAX) || !(p.albedoSigma >= 0.0f && p.albedoSigma <= FLT_MAX)) return RTOW_ERROR_INVALID_VALUE;   // NaN fails both
-    if ((p.flags & ~(int32_t)RTOW_DENOISE_DEMODULATE_ALBEDO) != 0 || p.reserved != 0) return RTOW_ERROR_INVALID_VALUE;
-    if (!scratch && p.iterations > 1) return RTOW_ERROR_INVALID_VALUE;
-    // the levels write outColor and scratch while they read the inputs and each other: no byte of a written buffer may be another buffer's
-    const size_t bytes = RTOW_DENOISE_SCRATCH_BYTES(p.width, p.height);      // the one length every buffer is checked with
-    const Range out{outColor, bytes}, work{scratch, bytes};
-    for (const void* in : {(const void*)inColor, (const void*)inNormal, (const void*)inAlbedo})
-        if (overlaps(out, Range{in, bytes}) || overlaps(work, Range{in, bytes})) return RTOW_ERROR_INVALID_VALUE;
-    if (overlaps(out, work)) return RTOW_ERROR_INVALID_VALUE;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    hipStream_t s;
-    RTOW_TRY(useDevice(ctx, stream, &s));
-    HIP_TRY(ctx, launchDenoise(p, inColor, inNormal, inAlbedo, (float*)scratch, outColor, s), RTOW_ERROR_LAUNCH_FAILURE);
-    return RTOW_SUCCESS;
-}
-
-RTOW_API int rtowAccumulateMomentsDevice(RtowContext ctx, int32_t pixelCount, int32_t count, const float* const* colors, const float* inMoments, float* outMoments,
-                                         void* stream)
-{
-    if (!ctx || !colors || !outMoments || pixelCount <= 0 || count < 1 || count > kMomentsMaxBatches) return RTOW_ERROR_INVALID_VALUE;
-    // a lane reads its own pixel of every buffer before it writes its own moments: the only overlap that is safe is inMoments == outMoments
-    const Range out{outMoments, (size_t)pixelCount * 12};
-    for (int k = 0; k < count; ++k)
-        if (!colors[k] || overlaps(out, Range{colors[k], (size_t)pixelCount * 16})) return RTOW_ERROR_INVALID_VALUE;
-    if (inMoments != outMoments && overlaps(out, Range{inMoments, (size_t)pixelCount * 12})) return RTOW_ERROR_INVALID_VALUE;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    hipStream_t s;
-    RTOW_TRY(useDevice(ctx, stream, &s));
-    HIP_TRY(ctx, launchAccumulateMoments(pixelCount, count, colors, inMoments, outMoments, s), RTOW_ERROR_LAUNCH_FAILURE);
-    return RTOW_SUCCESS;
-}
-
-RTOW_API int rtowDenoiseVarianceDevice(RtowContext ctx, const RtowDenoiseParams* params, const float* inColor, const float* inNormal, const float* inAlbedo,
-                                       const float* moments, void* scratch, float* outColor, float* outVariance, void* stream)
-{
-    if (!ctx || !params || !inColor || !inNormal || !inAlbedo || !moments || !scratch || !outColor) return RTOW_ERROR_INVALID_VALUE;
-    const RtowDenoiseParams& p = *params;
-    if (p.width <= 0 || p.height <= 0 || (int64_t)p.width * p.height > INT32_MAX) return RTOW_ERROR_INVALID_VALUE;
-    if (p.iterations < 1 || p.iterations > 8 || p.normalSharpness < 0 || p.normalSharpness > 8) return RTOW_ERROR_INVALID_VALUE;
-    if (!(p.colorSigma >= 0.0f && p.colorSigma <= FLT_MAX) || !(p.albedoSigma >= 0.0f && p.albedoSigma <= FLT_MAX)) return RTOW_ERROR_INVALID_VALUE;   // NaN fails both
-    if ((p.flags & ~(int32_t)RTOW_DENOISE_DEMODULATE_ALBEDO) != 0 || p.reserved != 0) return RTOW_ERROR_INVALID_VALUE;
-    // the levels write outColor, outVariance and the scratch while they read the inputs and each other: no byte of a written buffer may be another buffer's
-    const size_t n = (size_t)p.width * (size_t)p.height;
-    const Range written[3] = {{outColor, n * 12}, {scratch, RTOW_DENOISE_VARIANCE_SCRATCH_BYTES(p.width, p.height)}, {outVariance, n * 4}};     // a null outVariance overlaps nothing
-    for (int i = 0; i < 3; ++i) {
-        for (const void* in : {(const void*)inColor, (const void*)inNormal, (const void*)inAlbedo, (const void*)moments})
-            if (overlaps(written[i], Range{in, n * 12})) return RTOW_ERROR_INVALID_VALUE;
-        for (int j = i + 1; j < 3; ++j)
-            if (overlaps(written[i], written[j])) return RTOW_ERROR_INVALID_VALUE;
-    }
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    hipStream_t s;
-    RTOW_TRY(useDevice(ctx, stream, &s));
-    HIP_TRY(ctx, launchDenoiseVariance(p, inColor, inNormal, inAlbedo, moments, (float*)scratch, outColor, outVariance, s), RTOW_ERROR_LAUNCH_FAILURE);
-    return RTOW_SUCCESS;
-}
-
-// What rtowReprojectAccumDevice and rtowReprojectAccumBilinearDevice refuse alike; fills `k`.  outMoments and previousMoments are null for the former: a null range
-// overlaps nothing.
-static int validateReproject(RtowContext ctx, const RtowReprojectParams* params, const RtowRay* rays, const RtowHitBuffers* hits, const RtowHitBuffers* previousHits,
-                             const RtowAccumBuffers* previous, const RtowAccumBuffers* out, const float* previousMoments, float* outMoments, int32_t* outSource,
-                             ReprojectConstants* k)
-{
-    if (!ctx || !params || !rays || !hits || !previousHits || !previous || !out) return RTOW_ERROR_INVALID_VALUE;
-    if (!hits->distance || !hits->entityIndex || !previousHits->distance || !previousHits->entityIndex) return RTOW_ERROR_INVALID_VALUE;
-    if (!previous->color || !previous->normal || !previous->albedo || !previous->sampleCountWeight || !out->color || !out->normal || !out->albedo || !out->sampleCountWeight)
-        return RTOW_ERROR_INVALID_VALUE;
-    const RtowReprojectParams& p = *params;
-    if (p.width <= 0 || p.height <= 0 || (int64_t)p.width * p.height > INT32_MAX) return RTOW_ERROR_INVALID_VALUE;
-    if (!(p.depthTolerance >= 0.0f && p.depthTolerance <= FLT_MAX) || p.maxHistory < 1) return RTOW_ERROR_INVALID_VALUE;      // NaN fails
-    if ((p.flags & ~(int32_t)RTOW_REPROJECT_MATCH_ENTITY) != 0 || p.reserved != 0) return RTOW_ERROR_INVALID_VALUE;
-    *k = reprojectConstants(p.previousView);
-    for (const float d : {k->LF, k->HR, k->VU})
-        if (!(d != 0.0f && d >= -FLT_MAX && d <= FLT_MAX)) return RTOW_ERROR_INVALID_VALUE;      // the divisors of the projection
-    // every pixel gathers from arbitrary pixels of the previous frame: no byte the pass writes may be one it gathers from, or another output's
-    const size_t n = (size_t)p.width * (size_t)p.height;
-    const Range written[6] = {{out->color, n * 16}, {out->normal, n * 12}, {out->albedo, n * 12}, {out->sampleCountWeight, n * 4}, {outSource, n * 4}, {outMoments, n * 12}};
-    const Range gathered[7] = {{previous->color, n * 16}, {previous->normal, n * 12}, {previous->albedo, n * 12}, {previous->sampleCountWeight, n * 4},
-                               {previousHits->distance, n * 4}, {previousHits->entityIndex, n * 4}, {previousMoments, n * 12}};
-    for (int i = 0; i < 6; ++i) {
-        for (const Range& g : gathered)
-            if (overlaps(written[i], g)) return RTOW_ERROR_INVALID_VALUE;
-        for (int j = i + 1; j < 6; ++j)
-            if (overlaps(written[i], written[j])) return RTOW_ERROR_INVALID_VALUE;
-    }
-    return RTOW_SUCCESS;
-}
-
-RTOW_API int rtowReprojectAccumDevice(RtowContext ctx, const RtowReprojectParams* params, const RtowRay* rays, const RtowHitBuffers* hits, const RtowHitBuffers* previousHits,
-                                      const RtowAccumBuffers* previous, const RtowAccumBuffers* out, int32_t* outSource, void* stream)
-{
-    ReprojectConstants k;
-    RTOW_TRY(validateReproject(ctx, params, rays, hits, previousHits, previous, out, nullptr, nullptr, outSource, &k));
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    hipStream_t s;
-    RTOW_TRY(useDevice(ctx, stream, &s));
-    HIP_TRY(ctx, launchReproject(*params, k, rays, *hits, *previousHits, *previous, *out, outSource, s), RTOW_ERROR_LAUNCH_FAILURE);
-    return RTOW_SUCCESS;
-}
-
-RTOW_API int rtowReprojectAccumBilinearDevice(RtowContext ctx, const RtowReprojectParams* params, const RtowRay* rays, const RtowHitBuffers* hits,
-                                              const RtowHitBuffers* previousHits, const RtowAccumBuffers* previous, const RtowAccumBuffers* out,
-                                              const float* previousMoments, int32_t maxBatches, float* outMoments, int32_t* outSource, void* stream)
-{
-    if ((previousMoments == nullptr) != (outMoments == nullptr) || (outMoments && maxBatches < 1)) return RTOW_ERROR_INVALID_VALUE;
-    ReprojectConstants k;
-    RTOW_TRY(validateReproject(ctx, params, rays, hits, previousHits, previous, out, previousMoments, outMoments, outSource, &k));
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    hipStream_t s;
-    RTOW_TRY(useDevice(ctx, stream, &s));
-    HIP_TRY(ctx, launchReprojectBilinear(*params, k, rays, *hits, *previousHits, *previous, *out, previousMoments, maxBatches, outMoments, outSource, s),
-            RTOW_ERROR_LAUNCH_FAILURE);
-    return RTOW_SUCCESS;
-}
-
-RTOW_API int rtowReprojectMomentsDevice(RtowContext ctx, int32_t pixelCount, const int32_t* source, const float* previousMoments, int32_t maxBatches, float* outMoments,
-                                        void* stream)
-{
-    if (!ctx || !source || !previousMoments || !outMoments || pixelCount <= 0 || maxBatches < 1) return RTOW_ERROR_INVALID_VALUE;
-    // every pixel gathers from an arbitrary pixel of the previous moments: no byte the pass writes may be one it reads
-    const Range out{outMoments, (size_t)pixelCount * 12};
-    if (overlaps(out, Range{source, (size_t)pixelCount * 4}) || overlaps(out, Range{previousMoments, (size_t)pixelCount * 12})) return RTOW_ERROR_INVALID_VALUE;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    hipStream_t s;
-    RTOW_TRY(useDevice(ctx, stream, &s));
-    HIP_TRY(ctx, launchReprojectMoments(pixelCount, source, previousMoments, maxBatches, outMoments, s), RTOW_ERROR_LAUNCH_FAILURE);
-    return RTOW_SUCCESS;
-}
-
-RTOW_API int rtowEstimateMomentsDevice(RtowContext ctx, const RtowEstimateMomentsParams* params, const float* color, const RtowHitBuffers* hits, const float* inMoments,
-                                       float* outMoments, uint8_t* outFilled, void* stream)
-{
-    if (!ctx || !params || !color || !hits || !outMoments) return RTOW_ERROR_INVALID_VALUE;
-    if (!hits->distance || !hits->entityIndex || !hits->normal) return RTOW_ERROR_INVALID_VALUE;
-    const RtowEstimateMomentsParams& p = *params;
-    if (p.width <= 0 || p.height <= 0 || (int64_t)p.width * p.height > INT32_MAX) return RTOW_ERROR_INVALID_VALUE;
-    if (p.minBatches < 1 || p.minTaps < 2 || p.minTaps > 49 || p.normalSharpness < 0 || p.normalSharpness > 8) return RTOW_ERROR_INVALID_VALUE;
-    if (!(p.depthTolerance >= 0.0f && p.depthTolerance <= FLT_MAX)) return RTOW_ERROR_INVALID_VALUE;      // NaN fails
-    if ((p.flags & ~(int32_t)RTOW_ESTIMATE_MOMENTS_MATCH_ENTITY) != 0 || p.reserved != 0) return RTOW_ERROR_INVALID_VALUE;
-    // a pixel reads the colour and the guides of its neighbourhood, the moments only at itself: the one overlap that is safe is inMoments == outMoments
-    const size_t n = (size_t)p.width * (size_t)p.height;
-    const Range written[2] = {{outMoments, n * 12}, {outFilled, n}};      // a null outFilled overlaps nothing
-    for (const Range& w : written) {
-        for (const Range& in : {Range{color, n * 16}, Range{hits->distance, n * 4}, Range{hits->entityIndex, n * 4}, Range{hits->normal, n * 12}})
-            if (overlaps(w, in)) return RTOW_ERROR_INVALID_VALUE;
-    }
-    if (overlaps(written[0], written[1]) || overlaps(written[1], Range{inMoments, n * 12})) return RTOW_ERROR_INVALID_VALUE;
-    if (inMoments != outMoments && overlaps(written[0], Range{inMoments, n * 12})) return RTOW_ERROR_INVALID_VALUE;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    hipStream_t s;
-    RTOW_TRY(useDevice(ctx, stream, &s));
-    HIP_TRY(ctx, launchEstimateMoments(p, color, *hits, inMoments, outMoments, outFilled, s), RTOW_ERROR_LAUNCH_FAILURE);
-    return RTOW_SUCCESS;
-}
-
-RTOW_API int rtowNoiseMaskDevice(RtowContext ctx, const RtowNoiseMaskParams* params, const float* moments, uint8_t* outMask, float* outError, RtowNoiseStats* outStats,
-                                 void* scratch, void* stream)
-{
-    if (!ctx || !params || !moments || !outMask || !scratch) return RTOW_ERROR_INVALID_VALUE;
-    const RtowNoiseMaskParams& p = *params;
-    if (p.width <= 0 || p.height <= 0 || (int64_t)p.width * p.height > INT32_MAX) return RTOW_ERROR_INVALID_VALUE;
-    if (!(p.errorThreshold > 0.0f && p.errorThreshold <= FLT_MAX) || !(p.luminanceFloor >= 0.0f && p.luminanceFloor <= FLT_MAX)) return RTOW_ERROR_INVALID_VALUE;   // NaN fails both
-    if (p.dilate < 0 || p.dilate > 3 || p.maxQualifying < 0) return RTOW_ERROR_INVALID_VALUE;
-    if ((p.flags & ~(int32_t)(RTOW_NOISE_MASK_ABSOLUTE | RTOW_NOISE_MASK_UNKNOWN_QUALIFIES)) != 0 || p.reserved != 0) return RTOW_ERROR_INVALID_VALUE;
-    // a pixel reads the moments of its neighbourhood while other pixels are written, and the record is filled by atomics: no byte written may be another buffer's
-    const size_t n = (size_t)p.width * (size_t)p.height;
-    const Range written[4] = {{outMask, n}, {outError, n * 4}, {outStats, sizeof(RtowNoiseStats)}, {scratch, RTOW_NOISE_MASK_SCRATCH_BYTES}};      // a null output overlaps nothing
-    for (int i = 0; i < 4; ++i) {
-        if (overlaps(written[i], Range{moments, n * 12})) return RTOW_ERROR_INVALID_VALUE;
-        for (int j = i + 1; j < 4; ++j)
-            if (overlaps(written[i], written[j])) return RTOW_ERROR_INVALID_VALUE;
-    }
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    hipStream_t s;
-    RTOW_TRY(useDevice(ctx, stream, &s));
-    HIP_TRY(ctx, launchNoiseMask(p, moments, outMask, outError, outStats, scratch, s), RTOW_ERROR_LAUNCH_FAILURE);
-    return RTOW_SUCCESS;
-}
-
-RTOW_API int rtowRectifyHistoryDevice(RtowContext ctx, const RtowRectifyParams* params, const RtowAccumBuffers* history, const float* fresh, const RtowHitBuffers* hits,
-                                      const float* inMoments, const RtowAccumBuffers* out, float* outMoments, float* outKeep, RtowRectifyStats* outStats, void* stream)
-{
-    if (!ctx || !params || !history || !fresh || !hits || !out) return RTOW_ERROR_INVALID_VALUE;
-    if (!hits->distance || !hits->entityIndex || !hits->normal) return RTOW_ERROR_INVALID_VALUE;
-    if (!history->color || !history->normal || !history->albedo || !history->sampleCountWeight || !out->color || !out->normal || !out->albedo || !out->sampleCountWeight)
-        return RTOW_ERROR_INVALID_VALUE;
-    const RtowRectifyParams& p = *params;
-    if (p.width <= 0 || p.height <= 0 || (int64_t)p.width * p.height > INT32_MAX) return RTOW_ERROR_INVALID_VALUE;
-    if (p.radius < 1 || p.radius > 3 || p.minTaps < 2 || p.minTaps > (2 * p.radius + 1) * (2 * p.radius + 1)) return RTOW_ERROR_INVALID_VALUE;
-    if (p.normalSharpness < 0 || p.normalSharpness > 8) return RTOW_ERROR_INVALID_VALUE;
-    for (const float v : {p.depthTolerance, p.sigmaScale, p.relativeTolerance})
-        if (!(v >= 0.0f && v <= FLT_MAX)) return RTOW_ERROR_INVALID_VALUE;      // NaN fails
-    if ((p.flags & ~(int32_t)RTOW_RECTIFY_MATCH_ENTITY) != 0 || p.reserved != 0) return RTOW_ERROR_INVALID_VALUE;
-    if ((inMoments == nullptr) != (outMoments == nullptr)) return RTOW_ERROR_INVALID_VALUE;
-    // a pixel reads the fresh colour and the guides of its neighbourhood, the history and the moments only at itself, before it writes them: the overlaps that are safe
-    // are an output that IS the matching input (written[k] and same[k] below)
-    const size_t n = (size_t)p.width * (size_t)p.height;
-    const Range written[7] = {{out->color, n * 16}, {out->normal, n * 12}, {out->albedo, n * 12}, {out->sampleCountWeight, n * 4}, {outMoments, n * 12},
-                              {outKeep, n * 4}, {outStats, sizeof(RtowRectifyStats)}};      // a null output overlaps nothing
-    const Range same[5] = {{history->color, n * 16}, {history->normal, n * 12}, {history->albedo, n * 12}, {history->sampleCountWeight, n * 4}, {inMoments, n * 12}};
-    const Range read[4] = {{fresh, n * 16}, {hits->distance, n * 4}, {hits->entityIndex, n * 4}, {hits->normal, n * 12}};
-    for (int i = 0; i < 7; ++i) {
-        for (const Range& in : read)
-            if (overlaps(written[i], in)) return RTOW_ERROR_INVALID_VALUE;
-        for (int k = 0; k < 5; ++k)
-            if (!(i == k && written[i].base == same[k].base) && overlaps(written[i], same[k])) return RTOW_ERROR_INVALID_VALUE;
-        for (int j = i + 1; j < 7; ++j)
-            if (overlaps(written[i], written[j])) return RTOW_ERROR_INVALID_VALUE;
-    }
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    hipStream_t s;
-    RTOW_TRY(useDevice(ctx, stream, &s));
-    HIP_TRY(ctx, launchRectifyHistory(p, *history, fresh, *hits, inMoments, *out, outMoments, outKeep, outStats, s), RTOW_ERROR_LAUNCH_FAILURE);
-    return RTOW_SUCCESS;
-}
-
-RTOW_API int rtowUpsampleDevice(RtowContext ctx,const RtowUpsampleParams* params, const float* srcColor, const RtowHitBuffers* srcHits, const float* srcAlbedo,
-                                const RtowHitBuffers* dstHits, const float* dstAlbedo, float* outColor, uint8_t* outStage, void* stream)
-{
-    if (!ctx || !params || !srcColor || !outColor) return RTOW_ERROR_INVALID_VALUE;
-    const RtowUpsampleParams& p = *params;
-    for (const int32_t size : {p.srcWidth, p.srcHeight, p.dstWidth, p.dstHeight})
-        if (size < 1 || size > 16384) return RTOW_ERROR_INVALID_VALUE;
-    if (p.mode != RTOW_UPSAMPLE_POINT && p.mode != RTOW_UPSAMPLE_BILINEAR && p.mode != RTOW_UPSAMPLE_GUIDED) return RTOW_ERROR_INVALID_VALUE;
-    if (p.normalSharpness < 0 || p.normalSharpness > 8 || !(p.depthTolerance >= 0.0f && p.depthTolerance <= FLT_MAX)) return RTOW_ERROR_INVALID_VALUE;      // NaN fails
-    if ((p.flags & ~(int32_t)(RTOW_UPSAMPLE_MATCH_ENTITY | RTOW_UPSAMPLE_DEMODULATE_ALBEDO)) != 0 || p.reserved != 0) return RTOW_ERROR_INVALID_VALUE;
-    const bool guided = p.mode == RTOW_UPSAMPLE_GUIDED, demod = (p.flags & RTOW_UPSAMPLE_DEMODULATE_ALBEDO) != 0;
-    if (p.mode == RTOW_UPSAMPLE_POINT && p.flags != 0) return RTOW_ERROR_INVALID_VALUE;
-    if (!guided && (p.flags & RTOW_UPSAMPLE_MATCH_ENTITY) != 0) return RTOW_ERROR_INVALID_VALUE;
-    if (guided) {
-        if (!srcHits || !dstHits) return RTOW_ERROR_INVALID_VALUE;
-        if (!srcHits->distance || !srcHits->entityIndex || !srcHits->normal || !dstHits->distance || !dstHits->entityIndex || !dstHits->normal) return RTOW_ERROR_INVALID_VALUE;
-    }
-    if (demod && (!srcAlbedo || !dstAlbedo)) return RTOW_ERROR_INVALID_VALUE;
-    // a dst pixel reads src pixels and dst guides of other lanes' neighbourhoods: no byte the pass writes may be one the mode reads, or the other output's
-    const size_t ns = (size_t)p.srcWidth * (size_t)p.srcHeight, nd = (size_t)p.dstWidth * (size_t)p.dstHeight;
-    const Range written[2] = {{outColor, nd * 12}, {outStage, nd}};
-    Range read[9] = {{srcColor, ns * 12}};
-    int reads = 1;
-    if (guided) {
-        read[reads++] = {srcHits->distance, ns * 4}; read[reads++] = {srcHits->entityIndex, ns * 4}; read[reads++] = {srcHits->normal, ns * 12};
-        read[reads++] = {dstHits->distance, nd * 4}; read[reads++] = {dstHits->entityIndex, nd * 4}; read[reads++] = {dstHits->normal, nd * 12};
-    }
-    if (demod) { read[reads++] = {srcAlbedo, ns * 12}; read[reads++] = {dstAlbedo, nd * 12}; }
-    for (const Range& w : written)
-        for (int i = 0; i < reads; ++i)
-            if (overlaps(w, read[i])) return RTOW_ERROR_INVALID_VALUE;
-    if (overlaps(written[0], written[1])) return RTOW_ERROR_INVALID_VALUE;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    hipStream_t s;
-    RTOW_TRY(useDevice(ctx, stream, &s));
-    const RtowHitBuffers none{};
-    HIP_TRY(ctx, launchUpsample(p, srcColor, guided ? *srcHits : none, srcAlbedo, guided ? *dstHits : none, dstAlbedo, outColor, outStage, s), RTOW_ERROR_LAUNCH_FAILURE);
-    return RTOW_SUCCESS;
-}
-
-RTOW_API int rtowBuildPixelListDevice(RtowContext ctx, const RtowPixelListParams* params, const float* color, const uint8_t* mask, void* scratch, const RtowPixelList* list,
-                                      void* stream)
-{
-    if (!ctx || !params || !list || !list->words || !scratch) return RTOW_ERROR_INVALID_VALUE;
-    const RtowPixelListParams& p = *params;
-    if (p.width <= 0 || p.height <= 0 || (int64_t)p.width * p.height > RTOW_PIXEL_LIST_MAX_PIXELS) return RTOW_ERROR_INVALID_VALUE;
-    if (p.sliceDivider < 1 || p.sliceOffset < 0 || p.sliceOffset >= p.sliceDivider) return RTOW_ERROR_INVALID_VALUE;
-    if (color && !(p.minSampleCount >= 0.0f)) return RTOW_ERROR_INVALID_VALUE;                                  // NaN fails
-    if (p.flags != 0 || p.reserved != 0) return RTOW_ERROR_INVALID_VALUE;
-    // the launches write the list and the scratch while they read the inputs and each other
-    const size_t n = (size_t)p.width * (size_t)p.height;
-    const Range words{list->words, RTOW_PIXEL_LIST_BYTES(list->capacity)}, work{scratch, RTOW_PIXEL_LIST_SCRATCH_BYTES(p.width, p.height)};
-    for (const Range& in : {Range{color, n * 16}, Range{mask, n}})
-        if (overlaps(words, in) || overlaps(work, in)) return RTOW_ERROR_INVALID_VALUE;
-    if (overlaps(words, work)) return RTOW_ERROR_INVALID_VALUE;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    hipStream_t s;
-    RTOW_TRY(useDevice(ctx, stream, &s));
-    HIP_TRY(ctx, launchBuildPixelList(p, color, mask, (unsigned*)scratch, list->words, list->capacity, s), RTOW_ERROR_LAUNCH_FAILURE);
     return RTOW_SUCCESS;
 }
 
@@ -2050,103 +1669,6 @@ RTOW_API int rtowSamplePixelsDevice(RtowContext ctx, int32_t count, const RtowSa
         if (params[b].rngPolicy != RTOW_RNG_REFERENCE) return RTOW_ERROR_UNSUPPORTED;
     const ListSpec spec{list->words, list->capacity};
     return enqueueBatches(ctx, count, params, in, out, diagnostics, false, canFuse(ctx, count, params, diagnostics, /*handOver*/ false, false), s, cancel, &spec);
-}
-
-RTOW_API int rtowAddAccumDevice(RtowContext ctx, int32_t pixelCount, const RtowAccumBuffers* dst, const RtowAccumBuffers* src, void* stream)
-{
-    if (!ctx || !dst || !src || pixelCount <= 0) return RTOW_ERROR_INVALID_VALUE;
-    if (!dst->color || !dst->normal || !dst->albedo || !dst->sampleCountWeight || !src->color || !src->normal || !src->albedo || !src->sampleCountWeight)
-        return RTOW_ERROR_INVALID_VALUE;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    hipStream_t s;
-    RTOW_TRY(useDevice(ctx, stream, &s));
-    float* const d[4] = {dst->color, dst->normal, dst->albedo, dst->sampleCountWeight};
-    const float* const q[4] = {src->color, src->normal, src->albedo, src->sampleCountWeight};
-    HIP_TRY(ctx, launchAddAccum((size_t)pixelCount, d, q, s), RTOW_ERROR_LAUNCH_FAILURE);      // one launch for the four buffers
-    return RTOW_SUCCESS;
-}
-
-RTOW_API int rtowCombineFinalizeDevice(RtowContext ctx, const RtowCombineParams* params, const float* inColor, const float* inNormal, const float* inAlbedo,
-                                       uint8_t* outColor, uint8_t* outNormal, uint8_t* outAlbedo, void* stream)
-{
-    if (!ctx || !params || !inColor || !inNormal || !inAlbedo || !outColor || !outNormal || !outAlbedo) return RTOW_ERROR_INVALID_VALUE;
-    if (params->width <= 0 || params->height <= 0) return RTOW_ERROR_INVALID_VALUE;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    hipStream_t s;
-    RTOW_TRY(useDevice(ctx, stream, &s));
-    HIP_TRY(ctx, launchCombineFinalize(*params, inColor, inNormal, inAlbedo, outColor, outNormal, outAlbedo, ctx->dByteThresholds, s), RTOW_ERROR_LAUNCH_FAILURE);
-    return RTOW_SUCCESS;
-}
-
-RTOW_API int rtowMeterExposureDevice(RtowContext ctx, const RtowExposureParams* params, const float* inColor, void* scratch, RtowExposureState* state, void* stream)
-{
-    if (!ctx || !params || !inColor || !scratch || !state) return RTOW_ERROR_INVALID_VALUE;
-    const RtowExposureParams& p = *params;
-    if (p.width <= 0 || p.height <= 0 || (int64_t)p.width * p.height > INT32_MAX) return RTOW_ERROR_INVALID_VALUE;
-    if (p.lowPermille < 0 || p.lowPermille > p.highPermille || p.highPermille > 1000) return RTOW_ERROR_INVALID_VALUE;
-    if (!(p.compensation >= -FLT_MAX && p.compensation <= FLT_MAX)) return RTOW_ERROR_INVALID_VALUE;      // NaN fails
-    if (!(p.minStops >= -32.0f && p.minStops <= p.maxStops && p.maxStops <= 32.0f)) return RTOW_ERROR_INVALID_VALUE;
-    if (!(p.rate >= 0.0f && p.rate <= 1.0f)) return RTOW_ERROR_INVALID_VALUE;
-    if (p.flags != 0 || p.reserved != 0) return RTOW_ERROR_INVALID_VALUE;
-    const size_t n = (size_t)p.width * (size_t)p.height;
-    const Range in{inColor, n * 12}, work{scratch, RTOW_EXPOSURE_SCRATCH_BYTES}, record{state, sizeof(RtowExposureState)};
-    if (overlaps(work, in) || overlaps(record, in) || overlaps(work, record)) return RTOW_ERROR_INVALID_VALUE;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    hipStream_t s;
-    RTOW_TRY(useDevice(ctx, stream, &s));
-    HIP_TRY(ctx, launchMeterExposure(p, inColor, scratch, state, s), RTOW_ERROR_LAUNCH_FAILURE);
-    return RTOW_SUCCESS;
-}
-
-RTOW_API int rtowFinalizeToneMappedDevice(RtowContext ctx, const RtowToneMapParams* params, const RtowExposureState* state, const float* inColor, const float* inNormal,
-                                          const float* inAlbedo, uint8_t* outColor, uint8_t* outNormal, uint8_t* outAlbedo, void* stream)
-{
-    if (!ctx || !params || !inColor || !outColor) return RTOW_ERROR_INVALID_VALUE;
-    if ((inNormal == nullptr) != (outNormal == nullptr) || (inAlbedo == nullptr) != (outAlbedo == nullptr)) return RTOW_ERROR_INVALID_VALUE;
-    const RtowToneMapParams& p = *params;
-    if (p.pixelCount <= 0) return RTOW_ERROR_INVALID_VALUE;
-    if (p.curve != RTOW_TONE_CLAMP && p.curve != RTOW_TONE_ACES_FITTED && p.curve != RTOW_TONE_ACES_FILM) return RTOW_ERROR_INVALID_VALUE;
-    if (!(p.exposure >= 0.0f && p.exposure <= FLT_MAX)) return RTOW_ERROR_INVALID_VALUE;                  // NaN fails
-    if (p.flags != 0 || p.reserved[0] != 0 || p.reserved[1] != 0) return RTOW_ERROR_INVALID_VALUE;
-    const size_t n = (size_t)p.pixelCount;
-    const Range written[3] = {{outColor, n * 4}, {outNormal, n * 4}, {outAlbedo, n * 4}};                 // a null buffer overlaps nothing
-    const Range read[4] = {{inColor, n * 12}, {inNormal, n * 12}, {inAlbedo, n * 12}, {state, sizeof(RtowExposureState)}};
-    for (int i = 0; i < 3; ++i) {
-        for (const Range& in : read)
-            if (overlaps(written[i], in)) return RTOW_ERROR_INVALID_VALUE;
-        for (int j = i + 1; j < 3; ++j)
-            if (overlaps(written[i], written[j])) return RTOW_ERROR_INVALID_VALUE;
-    }
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    hipStream_t s;
-    RTOW_TRY(useDevice(ctx, stream, &s));
-    HIP_TRY(ctx, launchFinalizeToneMapped(p, state, inColor, inNormal, inAlbedo, outColor, outNormal, outAlbedo, ctx->dByteThresholds, s), RTOW_ERROR_LAUNCH_FAILURE);
-    return RTOW_SUCCESS;
-}
-
-RTOW_API int rtowReduceMetricsDeviceAsync(RtowContext ctx, int32_t pixelCount, const void* diagnostics, int32_t diagnosticsStride, const float* color,
-                                          const float* sampleCountWeight, void* stream, RtowMetrics* outMetrics)
-{
-    if (!ctx || !diagnostics || !color || !sampleCountWeight || !outMetrics || pixelCount <= 0) return RTOW_ERROR_INVALID_VALUE;
-    if (diagnosticsStride != 4 && diagnosticsStride != 16) return RTOW_ERROR_INVALID_VALUE;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    hipStream_t s;
-    RTOW_TRY(useDevice(ctx, stream, &s));
-    // where the record goes: memory registered with rtowRegisterHostBuffer (the device writes it over PCIe), else a device pointer (any HIP allocation)
-    RtowMetrics* target = (RtowMetrics*)mappedHost(ctx, outMetrics, sizeof(RtowMetrics));
-    if (!target) {
-        hipPointerAttribute_t attr{};
-        if (hipPointerGetAttributes(&attr, outMetrics) != hipSuccess) { (void)hipGetLastError(); return RTOW_ERROR_INVALID_VALUE; }   // plain pageable host memory: the device cannot write it
-        if (attr.type != hipMemoryTypeDevice && attr.type != hipMemoryTypeHost && attr.type != hipMemoryTypeManaged) return RTOW_ERROR_INVALID_VALUE;
-        target = attr.type == hipMemoryTypeHost && attr.devicePointer ? (RtowMetrics*)attr.devicePointer : outMetrics;
-    }
-    // the partials are one block per context: this reduction starts after the previous one's fold has read them
-    if (ctx->haveMetricsDone) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->evMetricsDone, 0), RTOW_ERROR_LAUNCH_FAILURE);
-    HIP_TRY(ctx, launchReduceMetrics(pixelCount, (const uint8_t*)diagnostics, diagnosticsStride, color, sampleCountWeight, ctx->dPartials, s), RTOW_ERROR_LAUNCH_FAILURE);
-    HIP_TRY(ctx, launchFoldMetrics(ctx->dPartials, target, s), RTOW_ERROR_LAUNCH_FAILURE);
-    HIP_TRY(ctx, hipEventRecord(ctx->evMetricsDone, s), RTOW_ERROR_LAUNCH_FAILURE);
-    ctx->haveMetricsDone = true;
-    return RTOW_SUCCESS;
 }
 
 RTOW_API int rtowDeviceAlloc(RtowContext ctx, size_t sizeInBytes, void** outPointer)

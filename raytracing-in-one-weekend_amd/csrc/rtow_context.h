@@ -1,5 +1,5 @@
-// rtow_context.h - the context behind RtowContext and the helpers every translation unit of the C-ABI layer shares (rtow_api.hip, rtow_comm.hip):
-// logging and the error-return macros.  Internal: nothing here is part of include/rtow.h.
+// rtow_context.h - the context behind RtowContext and the helpers every translation unit of the C-ABI layer shares (rtow_api.hip, rtow_api_post.hip, rtow_comm.hip):
+// logging, the error-return macros and what an entry point does once it holds its lock.  Internal: nothing here is part of include/rtow.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -200,6 +200,24 @@ inline int growDevice(RtowContext ctx, std::initializer_list<DeviceBlock::Need> 
 {
     HIP_TRY(ctx, DeviceBlock::ensureAll(needs, grew), RTOW_ERROR_MEMORY_ALLOCATION);
     return RTOW_SUCCESS;
+}
+
+// What the entry points do once they hold their lock: this thread on the context's device (calls come from a different worker thread each time) and the stream the work
+// goes to (null: the context's)
+inline int useDevice(RtowContext ctx, void* stream, hipStream_t* s)
+{
+    HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
+    *s = stream ? (hipStream_t)stream : ctx->stream;
+    return RTOW_SUCCESS;
+}
+
+// device-visible address of caller memory [p, p + bytes) if it lies inside a range given to rtowRegisterHostBuffer, else null
+inline uint8_t* mappedHost(RtowContext ctx, const void* p, size_t bytes)
+{
+    const uint8_t* q = (const uint8_t*)p;
+    for (const RtowContext_t::HostRange& r : ctx->hostRanges)
+        if (q >= r.base && q + bytes <= r.base + r.size) return r.device + (q - r.base);
+    return nullptr;
 }
 
 // rtow_comm.hip, for rtowDestroyContext: destroys the communicator (before the context's packed-row staging goes)

@@ -1,4 +1,4 @@
-// rtow_kernels.h - launch interface between the C-ABI layer (rtow_api.hip, rtow_comm.hip) and the gfx950 kernels (rtow_kernels.hip).
+// rtow_kernels.h - launch interface between the C-ABI layer (rtow_api.hip, rtow_api_post.hip, rtow_comm.hip) and the gfx950 kernels (rtow_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -6,6 +6,7 @@
 #include "../../include/rtow.h"
 #include "rtow_bvh.h"
 #include "rtow_scene.h"
+#include "rtow_validate.h"
 
 namespace rtow {
 
@@ -402,21 +403,14 @@ hipError_t launchFinalizeToneMapped(const RtowToneMapParams& p, const RtowExposu
 hipError_t launchDenoise(const RtowDenoiseParams& p, const float* inColor, const float* inNormal, const float* inAlbedo, float* scratch, float* outColor,
                          hipStream_t stream);
 // rtowAccumulateMomentsDevice (rtow_denoise_variance.hip): one launch on `stream`; the `count` device pointers of the host array `colors` travel in the kernel arguments
-// (arguments validated by the caller)
-constexpr int kMomentsMaxBatches = 16;
+// (arguments validated by the caller; at most kMomentsMaxBatches of them: rtow_validate.h)
 hipError_t launchAccumulateMoments(int pixelCount, int count, const float* const* colors, const float* inMoments, float* outMoments, hipStream_t stream);
 // rtowDenoiseVarianceDevice (rtow_denoise_variance.hip): the initial-variance launch and one launch per a-trous level on `stream`; scratch: the colour ping-pong plane
 // (float3 per pixel), then two variance planes (float per pixel); outVariance may be null (params validated by the caller)
 hipError_t launchDenoiseVariance(const RtowDenoiseParams& p, const float* inColor, const float* inNormal, const float* inAlbedo, const float* moments, float* scratch,
                                  float* outColor, float* outVariance, hipStream_t stream);
-// rtowReprojectAccumDevice (rtow_reproject.hip): one launch on `stream` (arguments validated by the caller).  The constants of previousView the specification has the
-// host compute, in float32 (this header is compiled without contraction)
-struct ReprojectConstants { float LF, LR, LU, HR, VU; };
-inline ReprojectConstants reprojectConstants(const RtowView& v)
-{
-    const auto dot = [](const RtowFloat3& a, const RtowFloat3& b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; };
-    return ReprojectConstants{dot(v.lowerLeftCorner, v.forward), dot(v.lowerLeftCorner, v.right), dot(v.lowerLeftCorner, v.up), dot(v.horizontal, v.right), dot(v.vertical, v.up)};
-}
+// rtowReprojectAccumDevice (rtow_reproject.hip): one launch on `stream` (arguments validated by the caller, which also computes the constants `k` of previousView:
+// rtow_validate.h)
 hipError_t launchReproject(const RtowReprojectParams& p, const ReprojectConstants& k, const RtowRay* rays, const RtowHitBuffers& hits, const RtowHitBuffers& previousHits,
                            const RtowAccumBuffers& previous, const RtowAccumBuffers& out, int32_t* outSource, hipStream_t stream);
 // rtowReprojectAccumBilinearDevice (rtow_reproject_bilinear.hip): one launch on `stream`, four validated taps per pixel; previousMoments and outMoments both null

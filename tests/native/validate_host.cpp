@@ -1,0 +1,200 @@
+// Stand-alone host program (tests/test_validate.py builds it with -fsanitize=address,undefined together with csrc/rtow_validate.cpp): every validator once with good
+// arguments and once with each extreme - INT32_MIN / INT32_MAX sizes, radius and minTaps at their type limits, a list capacity of UINT32_MAX, buffers within a few
+// bytes of UINTPTR_MAX.  The sanitizers decide: no signed overflow, no read of a fake address.  Prints "ok"; what base + bytes does at the top of the address space goes
+// to stderr.
+#include <climits>
+#include <cstdio>
+#include <cstdlib>
+#include <initializer_list>
+
+#include "../../raytracing-in-one-weekend_amd/csrc/rtow_validate.h"
+
+using namespace rtow;
+
+#define CHECK(cond)                                                          \
+    do {                                                                     \
+        if (!(cond)) { fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #cond); return 1; } \
+    } while (0)
+
+template <typename T> static T* at(uintptr_t address) { return reinterpret_cast<T*>(address); }
+static const int32_t kLimits[] = {INT32_MIN, INT32_MAX};
+static constexpr int OK = RTOW_SUCCESS, BAD = RTOW_ERROR_INVALID_VALUE;
+static constexpr uintptr_t M = 0x10000000;      // between the fake buffers
+
+int main()
+{
+    float* const f[20] = {at<float>(1 * M), at<float>(2 * M), at<float>(3 * M), at<float>(4 * M), at<float>(5 * M), at<float>(6 * M), at<float>(7 * M), at<float>(8 * M),
+                          at<float>(9 * M), at<float>(10 * M), at<float>(11 * M), at<float>(12 * M), at<float>(13 * M), at<float>(14 * M), at<float>(15 * M),
+                          at<float>(16 * M), at<float>(17 * M), at<float>(18 * M), at<float>(19 * M), at<float>(20 * M)};
+    uint8_t* const b[4] = {at<uint8_t>(21 * M), at<uint8_t>(22 * M), at<uint8_t>(23 * M), at<uint8_t>(24 * M)};
+    int32_t* const i32[3] = {at<int32_t>(25 * M), at<int32_t>(26 * M), at<int32_t>(27 * M)};
+    void* const scratch = at<void>(28 * M);
+    const RtowHitBuffers hits{f[10], i32[0], f[11]}, previousHits{f[12], i32[1], f[13]};
+    const RtowAccumBuffers in{f[0], f[1], f[2], f[3]}, out{f[4], f[5], f[6], f[7]};
+
+    // sample params
+    RtowSampleParams sp{};
+    sp.size = {96.0f, 54.0f}; sp.sliceDivider = 1; sp.traceDepth = 8; sp.diagnosticsStride = 4; sp.environment.skyType = RTOW_SKY_GRADIENT;
+    CHECK(validateParams(&sp) == OK);
+    for (const int32_t v : kLimits) {
+        RtowSampleParams q = sp; q.traceDepth = v; CHECK(validateParams(&q) == (v < 0 ? BAD : (int)RTOW_ERROR_CAPACITY));
+        q = sp; q.sliceDivider = v; q.sliceOffset = v; CHECK(validateParams(&q) == BAD);
+        q = sp; q.sliceOffset = v; CHECK(validateParams(&q) == BAD);
+        q = sp; q.diagnosticsStride = v; CHECK(validateParams(&q) == BAD);
+    }
+    sp.size = {46341.0f, 46341.0f}; CHECK(validateParams(&sp) == BAD);
+
+    // view size, guides, shade
+    RtowTraceViewParams tv{}; tv.width = 8; tv.height = 8;
+    CHECK(viewSizeValid(tv));
+    for (const int32_t v : kLimits) {
+        RtowTraceViewParams q = tv; q.width = v; CHECK(!viewSizeValid(q));      // INT32_MAX x 8 is beyond INT32_MAX pixels
+        q.height = v; CHECK(!viewSizeValid(q));
+        q.height = 1; CHECK(viewSizeValid(q) == (v > 0));
+    }
+    RtowGuideParams gp{8, 0, 0};
+    RtowGuideBuffers gb{}; gb.end = b[0];
+    CHECK(guideArgumentsValid(&gp, &gb));
+    for (const int32_t v : kLimits) { RtowGuideParams q = gp; q.maxBounces = v; CHECK(!guideArgumentsValid(&q, &gb)); }
+    RtowShadeHitsParams sh{}; sh.environment.skyType = RTOW_SKY_NONE;
+    RtowSurfaceBuffers sb{}; sb.albedo = f[0];
+    CHECK(validateShadeHits(&sh, 16, at<RtowRay>(29 * M), i32[0], &sb) == OK);
+    CHECK(validateShadeHits(&sh, INT32_MAX, at<RtowRay>(29 * M), i32[0], &sb) == OK && validateShadeHits(&sh, INT32_MIN, at<RtowRay>(29 * M), i32[0], &sb) == BAD);
+
+    // counts
+    RtowMetrics* const metrics = at<RtowMetrics>(30 * M);
+    CHECK(validateReduceMetrics(64, scratch, 4, f[0], f[1], metrics) == OK);
+    CHECK(validateReduceMetrics(INT32_MAX, scratch, 16, f[0], f[1], metrics) == OK && validateReduceMetrics(INT32_MIN, scratch, 4, f[0], f[1], metrics) == BAD);
+    CHECK(validateReduceMetrics(64, scratch, INT32_MAX, f[0], f[1], metrics) == BAD && validateReduceMetrics(64, scratch, INT32_MIN, f[0], f[1], metrics) == BAD);
+    RtowCombineParams cp{}; cp.width = 8; cp.height = 8;
+    CHECK(validateCombine(&cp, f[0], f[1], f[2], f[4], f[5], f[6]) == OK);
+    cp.width = INT32_MAX; cp.height = INT32_MAX; CHECK(validateCombine(&cp, f[0], f[1], f[2], f[4], f[5], f[6]) == OK);      // no bound on the product today
+    cp.width = INT32_MIN; CHECK(validateCombine(&cp, f[0], f[1], f[2], f[4], f[5], f[6]) == BAD);
+    CHECK(validateFinalize(INT32_MAX, f[0], f[1], f[2], b[0], b[1], b[2]) == OK && validateFinalize(INT32_MIN, f[0], f[1], f[2], b[0], b[1], b[2]) == BAD);
+    CHECK(validateAddAccum(INT32_MAX, &out, &in) == OK && validateAddAccum(INT32_MIN, &out, &in) == BAD);
+
+    // the denoisers
+    RtowDenoiseParams dp{8, 8, 3, 4, 0.5f, 0.5f, RTOW_DENOISE_DEMODULATE_ALBEDO, 0};
+    CHECK(validateDenoise(&dp, f[0], f[1], f[2], scratch, f[4]) == OK);
+    CHECK(validateDenoiseVariance(&dp, f[0], f[1], f[2], f[3], scratch, f[4], f[5]) == OK);
+    for (const int32_t v : kLimits) {
+        for (int32_t RtowDenoiseParams::*m : {&RtowDenoiseParams::width, &RtowDenoiseParams::height, &RtowDenoiseParams::iterations, &RtowDenoiseParams::normalSharpness,
+                                              &RtowDenoiseParams::flags, &RtowDenoiseParams::reserved}) {
+            RtowDenoiseParams q = dp; q.*m = v;
+            CHECK(validateDenoise(&q, f[0], f[1], f[2], scratch, f[4]) == BAD && validateDenoiseVariance(&q, f[0], f[1], f[2], f[3], scratch, f[4], f[5]) == BAD);
+        }
+        RtowDenoiseParams q = dp; q.width = v; q.height = 1;       // INT32_MAX pixels: the byte counts are computed in size_t
+        CHECK(validateDenoise(&q, f[0], f[1], f[2], scratch, f[4]) == BAD && validateDenoiseVariance(&q, f[0], f[1], f[2], f[3], scratch, f[4], f[5]) == BAD);   // ... and far beyond the 256 MB between the fakes
+    }
+    const float* colors[kMomentsMaxBatches];
+    for (int k = 0; k < kMomentsMaxBatches; ++k) colors[k] = f[k];
+    CHECK(validateAccumulateMoments(64, kMomentsMaxBatches, colors, f[17], f[17]) == OK);
+    for (const int32_t v : kLimits) {
+        CHECK(validateAccumulateMoments(64, v, colors, nullptr, f[17]) == BAD);
+        CHECK(validateAccumulateMoments(v, 1, colors, nullptr, at<float>(UINTPTR_MAX / 2)) == (v > 0 ? OK : BAD));
+    }
+
+    // reprojection
+    RtowReprojectParams rp{};
+    rp.width = 8; rp.height = 8; rp.depthTolerance = 0.01f; rp.maxHistory = 64; rp.flags = RTOW_REPROJECT_MATCH_ENTITY;
+    rp.previousView.lowerLeftCorner = {-1.0f, -1.0f, 1.0f}; rp.previousView.forward = {0.0f, 0.0f, 1.0f}; rp.previousView.right = {1.0f, 0.0f, 0.0f};
+    rp.previousView.up = {0.0f, 1.0f, 0.0f}; rp.previousView.horizontal = {2.0f, 0.0f, 0.0f}; rp.previousView.vertical = {0.0f, 2.0f, 0.0f};
+    ReprojectConstants k{};
+    const RtowRay* const rays = at<RtowRay>(29 * M);
+    CHECK(validateReproject(&rp, rays, &hits, &previousHits, &in, &out, nullptr, nullptr, i32[2], &k) == OK && k.LF == 1.0f && k.HR == 2.0f && k.VU == 2.0f);
+    CHECK(validateReprojectBilinear(&rp, rays, &hits, &previousHits, &in, &out, f[14], 16, f[15], i32[2], &k) == OK);
+    for (const int32_t v : kLimits) {
+        for (int32_t RtowReprojectParams::*m : {&RtowReprojectParams::width, &RtowReprojectParams::height, &RtowReprojectParams::flags, &RtowReprojectParams::reserved}) {
+            RtowReprojectParams q = rp; q.*m = v;
+            CHECK(validateReproject(&q, rays, &hits, &previousHits, &in, &out, nullptr, nullptr, i32[2], &k) == BAD);
+        }
+        RtowReprojectParams q = rp; q.maxHistory = v;
+        CHECK(validateReproject(&q, rays, &hits, &previousHits, &in, &out, nullptr, nullptr, i32[2], &k) == (v > 0 ? OK : BAD));
+        CHECK(validateReprojectBilinear(&rp, rays, &hits, &previousHits, &in, &out, f[14], v, f[15], i32[2], &k) == (v > 0 ? OK : BAD));
+        CHECK(validateReprojectMoments(64, i32[0], f[14], v, f[15]) == (v > 0 ? OK : BAD));
+        CHECK(validateReprojectMoments(v, i32[0], at<float>(UINTPTR_MAX / 4), 16, at<float>(UINTPTR_MAX / 2)) == (v > 0 ? OK : BAD));
+    }
+    rp.previousView.forward = {FLT_MAX, FLT_MAX, FLT_MAX};       // LF overflows to -inf: refused, no trap
+    CHECK(validateReproject(&rp, rays, &hits, &previousHits, &in, &out, nullptr, nullptr, i32[2], &k) == BAD);
+
+    // moments, mask, rectify
+    RtowEstimateMomentsParams ep{8, 8, 4, 8, 2, 0.05f, RTOW_ESTIMATE_MOMENTS_MATCH_ENTITY, 0};
+    CHECK(validateEstimateMoments(&ep, f[0], &hits, f[14], f[14], b[0]) == OK);
+    RtowNoiseMaskParams np{8, 8, 0.0025f, 0.0625f, 1, 0, RTOW_NOISE_MASK_UNKNOWN_QUALIFIES, 0};
+    RtowNoiseStats* const noiseStats = at<RtowNoiseStats>(31 * M);
+    CHECK(validateNoiseMask(&np, f[0], b[0], f[1], noiseStats, scratch) == OK);
+    RtowRectifyParams rectify{8, 8, 2, 4, 2, 0.05f, 1.0f, 0.125f, RTOW_RECTIFY_MATCH_ENTITY, 0};
+    RtowRectifyStats* const rectifyStats = at<RtowRectifyStats>(32 * M);
+    CHECK(validateRectifyHistory(&rectify, &in, f[8], &hits, f[14], &in, f[14], f[16], rectifyStats) == OK);       // every output its input
+    for (const int32_t v : kLimits) {
+        for (int32_t RtowEstimateMomentsParams::*m : {&RtowEstimateMomentsParams::width, &RtowEstimateMomentsParams::height, &RtowEstimateMomentsParams::minTaps,
+                                                      &RtowEstimateMomentsParams::normalSharpness, &RtowEstimateMomentsParams::flags, &RtowEstimateMomentsParams::reserved}) {
+            RtowEstimateMomentsParams q = ep; q.*m = v;
+            CHECK(validateEstimateMoments(&q, f[0], &hits, f[14], f[15], b[0]) == BAD);
+        }
+        RtowEstimateMomentsParams q = ep; q.minBatches = v;
+        CHECK(validateEstimateMoments(&q, f[0], &hits, f[14], f[15], b[0]) == (v > 0 ? OK : BAD));
+        for (int32_t RtowNoiseMaskParams::*m : {&RtowNoiseMaskParams::width, &RtowNoiseMaskParams::height, &RtowNoiseMaskParams::dilate, &RtowNoiseMaskParams::flags,
+                                                &RtowNoiseMaskParams::reserved}) {
+            RtowNoiseMaskParams r = np; r.*m = v;
+            CHECK(validateNoiseMask(&r, f[0], b[0], f[1], noiseStats, scratch) == BAD);
+        }
+        RtowNoiseMaskParams r = np; r.maxQualifying = v;
+        CHECK(validateNoiseMask(&r, f[0], b[0], f[1], noiseStats, scratch) == (v > 0 ? OK : BAD));
+        for (int32_t RtowRectifyParams::*m : {&RtowRectifyParams::width, &RtowRectifyParams::height, &RtowRectifyParams::radius, &RtowRectifyParams::minTaps,
+                                              &RtowRectifyParams::normalSharpness, &RtowRectifyParams::flags, &RtowRectifyParams::reserved}) {
+            RtowRectifyParams s = rectify; s.*m = v;       // radius INT32_MAX: (2 * radius + 1)^2 is never evaluated
+            CHECK(validateRectifyHistory(&s, &in, f[8], &hits, f[14], &out, f[15], f[16], rectifyStats) == BAD);
+        }
+    }
+
+    // upsample, pixel list, exposure, tone map
+    RtowUpsampleParams up{8, 4, 16, 8, RTOW_UPSAMPLE_GUIDED, 4, 0.05f, RTOW_UPSAMPLE_MATCH_ENTITY | RTOW_UPSAMPLE_DEMODULATE_ALBEDO, 0};
+    const RtowHitBuffers dstHits{f[12], i32[1], f[13]};
+    CHECK(validateUpsample(&up, f[0], &hits, f[1], &dstHits, f[2], f[4], b[0]) == OK);
+    for (const int32_t v : kLimits)
+        for (int32_t RtowUpsampleParams::*m : {&RtowUpsampleParams::srcWidth, &RtowUpsampleParams::srcHeight, &RtowUpsampleParams::dstWidth, &RtowUpsampleParams::dstHeight,
+                                               &RtowUpsampleParams::mode, &RtowUpsampleParams::normalSharpness, &RtowUpsampleParams::flags, &RtowUpsampleParams::reserved}) {
+            RtowUpsampleParams q = up; q.*m = v;
+            CHECK(validateUpsample(&q, f[0], &hits, f[1], &dstHits, f[2], f[4], b[0]) == BAD);
+        }
+    RtowPixelListParams lp{16, 8, 0, 0, 16, 8, 0, 1, 1.0f, 0, 0};
+    RtowPixelList list{at<uint32_t>(33 * M), 32};
+    CHECK(validateBuildPixelList(&lp, f[0], b[0], scratch, &list) == OK);
+    list.capacity = UINT32_MAX;                                  // 16 GB + 12 bytes of list: it reaches over every fake above it, and only those
+    CHECK(validateBuildPixelList(&lp, f[0], b[0], scratch, &list) == OK);
+    CHECK(validateBuildPixelList(&lp, f[0], b[0], at<void>(34 * M), &list) == BAD);
+    list.capacity = 32;
+    for (const int32_t v : kLimits)
+        for (int32_t RtowPixelListParams::*m : {&RtowPixelListParams::width, &RtowPixelListParams::height, &RtowPixelListParams::sliceOffset, &RtowPixelListParams::flags,
+                                                &RtowPixelListParams::reserved}) {
+            RtowPixelListParams q = lp; q.*m = v;
+            CHECK(validateBuildPixelList(&q, f[0], b[0], scratch, &list) == BAD);
+        }
+    RtowExposureParams xp{8, 8, 500, 950, -2.5f, -8.0f, 8.0f, 1.0f, 0, 0};
+    RtowExposureState* const state = at<RtowExposureState>(35 * M);
+    CHECK(validateMeterExposure(&xp, f[0], scratch, state) == OK);
+    for (const int32_t v : kLimits)
+        for (int32_t RtowExposureParams::*m : {&RtowExposureParams::width, &RtowExposureParams::height, &RtowExposureParams::lowPermille, &RtowExposureParams::highPermille,
+                                               &RtowExposureParams::flags, &RtowExposureParams::reserved}) {
+            RtowExposureParams q = xp; q.*m = v;
+            CHECK(validateMeterExposure(&q, f[0], scratch, state) == BAD);
+        }
+    RtowToneMapParams tp{64, RTOW_TONE_ACES_FITTED, 1.0f, 0, {0, 0}};
+    CHECK(validateFinalizeToneMapped(&tp, state, f[0], f[1], f[2], b[0], b[1], b[2]) == OK);
+    tp.pixelCount = INT32_MAX;                                   // 24 GB of colour from f[0]: over f[1], which is read too, and under no output
+    CHECK(validateFinalizeToneMapped(&tp, nullptr, f[0], nullptr, nullptr, b[0], nullptr, nullptr) == BAD);      // ... but over b[0]
+    CHECK(validateFinalizeToneMapped(&tp, nullptr, at<float>(UINTPTR_MAX / 2), nullptr, nullptr, b[0], nullptr, nullptr) == OK);
+    tp.pixelCount = INT32_MIN; CHECK(validateFinalizeToneMapped(&tp, state, f[0], f[1], f[2], b[0], b[1], b[2]) == BAD);
+    tp.pixelCount = 64; tp.curve = INT32_MAX; CHECK(validateFinalizeToneMapped(&tp, state, f[0], f[1], f[2], b[0], b[1], b[2]) == BAD);
+
+    // the top of the address space: base + bytes is computed in uintptr_t and wraps.  Pairs of 64-byte ranges, the later one ending at 2^64:
+    const Range low{at<void>(UINTPTR_MAX - 127), 64}, high{at<void>(UINTPTR_MAX - 63), 64};        // abut, the later one ends exactly at 2^64: its end wraps to 0
+    const Range a{at<void>(UINTPTR_MAX - 67), 64}, c{at<void>(UINTPTR_MAX - 63), 64};              // share 60 bytes
+    CHECK(overlaps(low, Range{at<void>(UINTPTR_MAX - 100), 8}));                                   // nothing wraps: decided as anywhere else
+    fprintf(stderr, "ranges ending at 2^64: abutting -> %d (0 is right), sharing 60 bytes -> %d (1 would be right)\n", (int)overlaps(low, high), (int)overlaps(a, c));
+    const Range written[] = {a}, read[] = {c};
+    fprintf(stderr, "aliasingOk on the pair sharing 60 bytes -> %d (0 would be right)\n", (int)aliasingOk(written, 1, read, 1));
+    puts("ok");
+    return 0;
+}

@@ -1,0 +1,424 @@
+"""CPU: the argument checks of the C ABI (csrc/rtow_validate.h) decided without a device.
+
+Every entry point refuses a null context first, so a test that calls the library without a GPU sees RTOW_ERROR_INVALID_VALUE whatever else it passes.  The checks
+themselves are pure functions of a few structs and addresses; tests/native/validate_shim.cpp exports them, and here each validator is held to: a good call succeeds
+(optional buffers given and null), every single-field refusal of the pass's test_*_abi.py / test_gpu_*.py lists is refused, every written buffer against every read
+buffer and every other written buffer is refused when it shares the last byte and accepted when it abuts (sizes from rt.abi, not from the validator), the documented
+in-place forms are accepted exactly at equal bases, aliasingOk agrees with a restatement of its three rules, and reprojectConstants is the float32 expression."""
+import ctypes as C
+import os
+import random
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "raytracing-in-one-weekend_amd", "csrc")
+NAN, INF = float("nan"), float("inf")
+STEP = 0x10000000           # between the fake buffers: far more than the largest of them
+F4, F3, F1, I4, U1 = 16, 12, C.sizeof(C.c_float), C.sizeof(C.c_int32), 1      # float4 / float3 / float / int32 / byte per pixel
+BIG, WIDE = (65536, 65536), (65536, 32768)      # as an index: both sizes at once, beyond INT32_MAX pixels
+
+SIGNATURES = {           # p: an address or a struct by reference, i: int32
+    "shim_params": "p", "shim_view_size": "p", "shim_guide_arguments": "pp", "shim_shade_hits": "pippp", "shim_reduce_metrics": "ipippp", "shim_combine": "ppppppp",
+    "shim_finalize": "ipppppp", "shim_add_accum": "ipp", "shim_denoise": "pppppp", "shim_accumulate_moments": "iippp", "shim_denoise_variance": "pppppppp",
+    "shim_reproject": "pppppppp", "shim_reproject_bilinear": "pppppppipp", "shim_reproject_moments": "ippip", "shim_estimate_moments": "pppppp",
+    "shim_noise_mask": "pppppp", "shim_rectify_history": "ppppppppp", "shim_upsample": "pppppppp", "shim_build_pixel_list": "ppppp", "shim_meter_exposure": "pppp",
+    "shim_finalize_tone_mapped": "pppppppp", "shim_aliasing_ok": "ppiii", "shim_reproject_constants": "pp",
+}
+
+
+@pytest.fixture(scope="module")
+def shim():
+    out_dir = os.path.join(ROOT, "tests", "build")
+    os.makedirs(out_dir, exist_ok=True)
+    src, so = os.path.join(ROOT, "tests", "native", "validate_shim.cpp"), os.path.join(out_dir, "libvalidate_shim.so")
+    deps = [src, os.path.join(CSRC, "rtow_validate.cpp"), os.path.join(CSRC, "rtow_validate.h"), os.path.join(ROOT, "include", "rtow.h")]
+    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
+        subprocess.run(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wextra", "-fPIC", "-shared", src, deps[1], "-o", so],
+                       check=True, capture_output=True)
+    lib = C.CDLL(so)
+    for name, sig in SIGNATURES.items():
+        getattr(lib, name).argtypes = [C.c_void_p if k == "p" else C.c_int32 for k in sig]
+        getattr(lib, name).restype = C.c_int
+    lib.shim_overlaps.argtypes = [C.c_uint64] * 4
+    return lib
+
+
+def ref(x):
+    return C.byref(x) if x is not None else None
+
+
+class Pass:
+    """One validator: `call(values, ptr)` runs it with the parameter values (the struct's fields, or the scalar arguments) and the addresses of `ptr` (name -> address or
+    None; "params" and the names of `structs` -> given or not).  sizes: bytes of every buffer for the good values."""
+
+    def __init__(self, call, values, sizes, written, read, same=(), nullable=(), structs=(), refused=(), refused_ptr=(), good_ptr=(), good_values=()):
+        self.call, self.values, self.sizes, self.written, self.read, self.same = call, list(values), sizes, list(written), list(read), dict(same)
+        self.nullable, self.structs, self.refused, self.refused_ptr, self.good_ptr, self.good_values = set(nullable), ["params"] + list(structs), refused, refused_ptr, good_ptr, good_values
+        self.base = {name: STEP * (k + 1) for k, name in enumerate(sizes)}
+
+    def run(self, values=None, **over):
+        ptr = {**self.base, **{s: True for s in self.structs}, **over}
+        return self.call(list(self.values if values is None else values), ptr)
+
+    def edited(self, index, value):
+        v = list(self.values)
+        if isinstance(index, tuple):
+            v[0], v[1] = index
+        else:
+            v[index] = value
+        return v
+
+
+def _passes(rt, shim):
+    a = rt.abi
+    n = 8 * 8
+    view = rt.scenes.make_view(rt.scenes.cover_scene(), 8, 8)
+    P = {}
+
+    dn = a.denoise_scratch_bytes(8, 8)
+    P["denoise"] = Pass(
+        lambda v, p: shim.shim_denoise(ref(a.DenoiseParams(*v)) if p["params"] else None, p["c"], p["n"], p["a"], p["scratch"], p["out"]),
+        [8, 8, 3, 4, 0.5, 0.5, 1, 0], {"c": dn, "n": dn, "a": dn, "scratch": dn, "out": dn}, ["out", "scratch"], ["c", "n", "a"],
+        refused=[(0, 0), (1, 0), (0, -1), (BIG, 0), (WIDE, 0), (2, 0), (2, 9), (3, -1), (3, 9), (4, -0.5), (4, -1.0), (4, NAN), (4, INF), (5, -1e-30), (5, NAN), (5, INF), (6, 2), (6, 3), (6, -1), (7, 1), (7, -7)],
+        refused_ptr=[{"params": None}, {"c": None}, {"n": None}, {"a": None}, {"out": None}, {"scratch": None}],
+        good_values=[([8, 8, 1, 4, 0.5, 0.5, 1, 0], {"scratch": None}), ([8, 8, 8, 0, 0.0, 0.0, 0, 0], {}), ([8, 8, 8, 8, 3e38, 3e38, 1, 0], {})])
+
+    P["denoise_variance"] = Pass(
+        lambda v, p: shim.shim_denoise_variance(ref(a.DenoiseParams(*v)) if p["params"] else None, p["c"], p["n"], p["a"], p["m"], p["scratch"], p["out"], p["var"]),
+        [8, 8, 3, 4, 4.0, 0.5, 1, 0], {"c": n * F3, "n": n * F3, "a": n * F3, "m": a.moments_bytes(n), "scratch": a.denoise_variance_scratch_bytes(8, 8), "out": n * F3, "var": n * F1},
+        ["out", "scratch", "var"], ["c", "n", "a", "m"], nullable=["var"],
+        refused=[(0, 0), (1, 0), (0, -1), (BIG, 0), (WIDE, 0), (2, 0), (2, 9), (3, -1), (3, 9), (4, -0.5), (4, NAN), (5, -1e-30), (5, INF), (6, 3), (6, -1), (7, 1), (7, -7)],
+        refused_ptr=[{"params": None}, {"c": None}, {"n": None}, {"a": None}, {"m": None}, {"scratch": None}, {"out": None}])
+
+    def accumulate(v, p):
+        colors = None if not p["colors"] else (C.c_void_p * max(v[1], 1))(*[p["c%d" % k] for k in range(min(max(v[1], 0), 3))])
+        return shim.shim_accumulate_moments(v[0], v[1], colors, p["in"], p["out"])
+    P["accumulate_moments"] = Pass(
+        accumulate, [n, 3], {"c0": n * F4, "c1": n * F4, "c2": n * F4, "in": a.moments_bytes(n), "out": a.moments_bytes(n)}, ["out"], ["c0", "c1", "c2"], same={"out": "in"},
+        nullable=["in"], structs=["colors"], refused=[(0, 0), (0, -1), (1, 0), (1, -1)], refused_ptr=[{"colors": None}, {"out": None}, {"c1": None}], good_values=[([n, 1], {})])
+
+    hit2 = lambda p, t, e: a.HitBuffers(p[t], p[e], None)
+    rp_sizes = {"rays": n * C.sizeof(a.Ray), "t": n * F1, "e": n * I4, "pt": n * F1, "pe": n * I4, "pc": n * F4, "pn": n * F3, "pa": n * F3, "ps": n * F1,
+                "oc": n * F4, "on": n * F3, "oa": n * F3, "os": n * F1, "src": n * I4}
+    rp_args = lambda v, p: (ref(a.ReprojectParams(*v)) if p["params"] else None, p["rays"], ref(hit2(p, "t", "e")) if p["hits"] else None,
+                            ref(hit2(p, "pt", "pe")) if p["prev_hits"] else None, ref(a.AccumBuffers(p["pc"], p["pn"], p["pa"], p["ps"])) if p["prev"] else None,
+                            ref(a.AccumBuffers(p["oc"], p["on"], p["oa"], p["os"])) if p["out"] else None)
+    rp_refused = [(0, 0), (1, 0), (0, -1), (1, -1), (BIG, 0), (WIDE, 0), (3, -0.01), (3, NAN), (3, INF), (4, 0), (4, -3), (5, 2), (5, 3), (5, -1), (6, 1)]
+    rp_null = [{k: None} for k in ("params", "rays", "hits", "prev_hits", "prev", "out", "t", "e", "pt", "pe", "pc", "pn", "pa", "ps", "oc", "on", "oa", "os")]
+    P["reproject"] = Pass(lambda v, p: shim.shim_reproject(*rp_args(v, p), p["src"], None), [8, 8, view, 0.01, 64, 1, 0], rp_sizes,
+                          ["oc", "on", "oa", "os", "src"], ["pc", "pn", "pa", "ps", "pt", "pe"], nullable=["src"], structs=["hits", "prev_hits", "prev", "out"],
+                          refused=rp_refused, refused_ptr=rp_null)
+    P["reproject_bilinear"] = Pass(
+        lambda v, p: shim.shim_reproject_bilinear(*rp_args(v[:7], p), p["pm"], v[7], p["om"], p["src"]), [8, 8, view, 0.01, 64, 1, 0, 16],
+        {**rp_sizes, "pm": a.moments_bytes(n), "om": a.moments_bytes(n)}, ["oc", "on", "oa", "os", "src", "om"], ["pc", "pn", "pa", "ps", "pt", "pe", "pm"], nullable=["src"],
+        structs=["hits", "prev_hits", "prev", "out"], refused=rp_refused + [(7, 0), (7, -1)], refused_ptr=rp_null + [{"pm": None}, {"om": None}],      # half of the pair
+        good_ptr=[{"pm": None, "om": None}], good_values=[([8, 8, view, 0.01, 64, 1, 0, 0], {"pm": None, "om": None})])
+
+    P["reproject_moments"] = Pass(lambda v, p: shim.shim_reproject_moments(v[0], p["src"], p["prev"], v[1], p["out"]), [n, 16],
+                                  {"src": n * I4, "prev": a.moments_bytes(n), "out": a.moments_bytes(n)}, ["out"], ["src", "prev"],
+                                  refused=[(0, 0), (0, -5), (1, 0), (1, -1)], refused_ptr=[{"src": None}, {"prev": None}, {"out": None}])
+
+    hit3 = lambda p, t, e, nn: a.HitBuffers(p[t], p[e], p[nn])
+    P["estimate_moments"] = Pass(
+        lambda v, p: shim.shim_estimate_moments(ref(a.EstimateMomentsParams(*v)) if p["params"] else None, p["color"], ref(hit3(p, "t", "e", "n")) if p["hits"] else None,
+                                                p["in"], p["out"], p["fill"]),
+        [8, 8, 4, 8, 2, 0.05, 1, 0], {"color": n * F4, "t": n * F1, "e": n * I4, "n": n * F3, "in": a.moments_bytes(n), "out": a.moments_bytes(n), "fill": n * U1},
+        ["out", "fill"], ["color", "t", "e", "n"], same={"out": "in"}, nullable=["in", "fill"], structs=["hits"],
+        refused=[(0, 0), (0, -1), (1, 0), (BIG, 0), (WIDE, 0), (2, 0), (2, -3), (3, 1), (3, 50), (3, 0), (4, -1), (4, 9), (5, -0.01), (5, NAN), (5, INF), (6, 2), (6, 3), (6, -1), (7, 1)],
+        refused_ptr=[{k: None} for k in ("params", "color", "hits", "t", "e", "n", "out")], good_ptr=[{"in": None, "fill": None}])
+
+    P["noise_mask"] = Pass(
+        lambda v, p: shim.shim_noise_mask(ref(a.NoiseMaskParams(*v)) if p["params"] else None, p["m"], p["mask"], p["err"], p["stats"], p["scratch"]),
+        [8, 8, 0.0025, 0.0625, 1, 0, 2, 0], {"m": a.moments_bytes(n), "mask": n * U1, "err": n * F1, "stats": C.sizeof(a.NoiseStats), "scratch": a.noise_mask_scratch_bytes()},
+        ["mask", "err", "stats", "scratch"], ["m"], nullable=["err", "stats"],
+        refused=[(0, 0), (0, -1), (1, 0), (1, -7), (BIG, 0), (WIDE, 0), (2, 0.0), (2, -0.01), (2, NAN), (2, INF), (3, -0.5), (3, NAN), (3, INF), (4, -1), (4, 4), (5, -1), (6, 4), (6, 7), (6, -1), (7, 1)],
+        refused_ptr=[{k: None} for k in ("params", "m", "mask", "scratch")], good_values=[([8, 8, 1e-30, 0.0, 3, 32, 3, 0], {}), ([8, 8, 0.0025, 0.0625, 0, 0, 0, 0], {})])
+
+    P["rectify_history"] = Pass(
+        lambda v, p: shim.shim_rectify_history(ref(a.RectifyParams(*v)) if p["params"] else None, ref(a.AccumBuffers(p["hc"], p["hn"], p["ha"], p["hs"])) if p["history"] else None,
+                                               p["fresh"], ref(hit3(p, "t", "e", "n")) if p["hits"] else None, p["m_in"],
+                                               ref(a.AccumBuffers(p["oc"], p["on"], p["oa"], p["os"])) if p["out"] else None, p["m_out"], p["keep"], p["stats"]),
+        [8, 8, 2, 4, 2, 0.05, 1.0, 0.125, 1, 0],
+        {"hc": n * F4, "hn": n * F3, "ha": n * F3, "hs": n * F1, "fresh": n * F4, "t": n * F1, "e": n * I4, "n": n * F3, "m_in": a.moments_bytes(n),
+         "oc": n * F4, "on": n * F3, "oa": n * F3, "os": n * F1, "m_out": a.moments_bytes(n), "keep": n * F1, "stats": C.sizeof(a.RectifyStats)},
+        ["oc", "on", "oa", "os", "m_out", "keep", "stats"], ["fresh", "t", "e", "n"], same={"oc": "hc", "on": "hn", "oa": "ha", "os": "hs", "m_out": "m_in"},
+        nullable=["keep", "stats"], structs=["history", "hits", "out"],
+        refused=[(0, 0), (0, -1), (1, 0), (1, -1), (BIG, 0), (WIDE, 0), (2, 0), (2, 4), (2, -1), (3, 1), (3, 26), (3, 0), (4, 9), (4, -1), (5, -1.0), (5, -0.01), (5, NAN), (5, INF),
+                 (6, -1.0), (6, NAN), (6, INF), (7, -0.5), (7, NAN), (7, INF), (8, 2), (8, 3), (8, -1), (9, 1)],
+        refused_ptr=[{k: None} for k in ("params", "history", "out", "hits", "fresh", "hn", "os", "n", "t", "e", "m_in", "m_out")],      # m_in / m_out: exactly one of the two
+        good_ptr=[{"m_in": None, "m_out": None}], good_values=[([8, 8, 3, 49, 8, 0.0, 0.0, 0.0, 0, 0], {}), ([8, 8, 1, 9, 0, 0.05, 1.0, 0.125, 1, 0], {})])
+
+    ns, nd = 8 * 4, 16 * 8
+    G, M, D = a.RTOW_UPSAMPLE_GUIDED, a.RTOW_UPSAMPLE_MATCH_ENTITY, a.RTOW_UPSAMPLE_DEMODULATE_ALBEDO
+    P["upsample"] = Pass(
+        lambda v, p: shim.shim_upsample(ref(a.UpsampleParams(*v)) if p["params"] else None, p["c"], ref(hit3(p, "st", "se", "sn")) if p["src_hits"] else None, p["sa"],
+                                        ref(hit3(p, "dt", "de", "dn")) if p["dst_hits"] else None, p["da"], p["out"], p["stage"]),
+        [8, 4, 16, 8, G, 4, 0.05, M | D, 0],
+        {"c": ns * F3, "st": ns * F1, "se": ns * I4, "sn": ns * F3, "sa": ns * F3, "dt": nd * F1, "de": nd * I4, "dn": nd * F3, "da": nd * F3, "out": nd * F3, "stage": nd * U1},
+        ["out", "stage"], ["c", "st", "se", "sn", "sa", "dt", "de", "dn", "da"], nullable=["stage"], structs=["src_hits", "dst_hits"],
+        refused=[(0, 0), (1, 0), (2, 0), (3, 0), (0, -1), (3, -7), (0, 16385), (1, 16385), (2, 16385), (3, 16385), (2, 1 << 30), (4, 3), (4, -1), (5, -1), (5, 9), (6, -0.01), (6, NAN),
+                 (6, INF), (6, -INF), (7, 4), (7, 8 | M), (7, -1), (8, 1), (8, -1), (4, a.RTOW_UPSAMPLE_POINT), (4, a.RTOW_UPSAMPLE_BILINEAR)],      # the last two: M | D outside GUIDED
+        refused_ptr=[{k: None} for k in ("params", "c", "st", "se", "sn", "sa", "dt", "de", "dn", "da", "out", "src_hits", "dst_hits")],
+        good_values=[([8, 4, 16, 8, a.RTOW_UPSAMPLE_POINT, 4, 0.05, 0, 0], {k: None for k in ("st", "se", "sn", "sa", "dt", "de", "dn", "da", "stage", "src_hits", "dst_hits")}),
+                     ([8, 4, 16, 8, a.RTOW_UPSAMPLE_BILINEAR, 0, 0.0, D, 0], {"src_hits": None, "dst_hits": None}), ([8, 4, 16, 8, G, 8, 3e38, 0, 0], {"sa": None, "da": None})])
+
+    cap = 32
+    P["build_pixel_list"] = Pass(
+        lambda v, p: shim.shim_build_pixel_list(ref(a.PixelListParams(*v)) if p["params"] else None, p["color"], p["mask"], p["scratch"],
+                                                ref(a.PixelList(p["words"], cap)) if p["list"] else None),
+        [16, 8, 0, 0, 16, 8, 0, 1, 1.0, 0, 0], {"color": 16 * 8 * F4, "mask": 16 * 8 * U1, "scratch": a.pixel_list_scratch_bytes(16, 8), "words": a.pixel_list_bytes(cap)},
+        ["words", "scratch"], ["color", "mask"], nullable=["color", "mask"], structs=["list"],
+        refused=[(0, 0), (1, 0), (0, -3), (1, -1), (BIG, 0), (((1 << 27) + 1, 1), 0), ((1 << 14, (1 << 13) + 1), 0), (6, -1), (6, 1), (7, 0), (7, -1), (8, NAN), (8, -1.0), (8, -1e-30),
+                 (8, -INF), (9, 1), (9, -1), (10, 1), (10, -2)],
+        refused_ptr=[{k: None} for k in ("params", "list", "words", "scratch")], good_ptr=[{"color": None, "mask": None}],
+        good_values=[([16, 8, 0, 0, 16, 8, 2, 3, 0.0, 0, 0], {}), ([1 << 14, 1 << 13, 0, 0, 16, 8, 0, 1, 1.0, 0, 0], {"color": None, "mask": None}), ([16, 8, 0, 0, 16, 8, 0, 1, NAN, 0, 0], {"color": None})])      # the count is read only with a colour buffer
+
+    P["meter_exposure"] = Pass(
+        lambda v, p: shim.shim_meter_exposure(ref(a.ExposureParams(*v)) if p["params"] else None, p["color"], p["scratch"], p["state"]),
+        [8, 8, 500, 950, -2.5, -8.0, 8.0, 1.0, 0, 0], {"color": n * F3, "scratch": a.exposure_scratch_bytes(), "state": C.sizeof(a.ExposureState)}, ["scratch", "state"], ["color"],
+        refused=[(0, 0), (1, -1), (BIG, 0), (2, -1), (2, 951), (3, 1001), (4, NAN), (4, INF), (4, -INF), (5, -32.5), (5, 8.5), (6, 32.5), (5, NAN), (6, NAN), (7, NAN), (7, -0.25),
+                 (7, 1.25), (8, 1), (9, 1)],
+        refused_ptr=[{k: None} for k in ("params", "color", "scratch", "state")], good_values=[([8, 8, 0, 1000, 3e38, -32.0, 32.0, 0.0, 0, 0], {})])
+
+    tone = lambda v: a.ToneMapParams(v[0], v[1], v[2], v[3], (C.c_int32 * 2)(v[4], v[5]))
+    P["finalize_tone_mapped"] = Pass(
+        lambda v, p: shim.shim_finalize_tone_mapped(ref(tone(v)) if p["params"] else None, p["state"], p["ic"], p["in"], p["ia"], p["oc"], p["on"], p["oa"]),
+        [n, 1, 1.0, 0, 0, 0], {"state": C.sizeof(a.ExposureState), "ic": n * F3, "in": n * F3, "ia": n * F3, "oc": n * 4 * U1, "on": n * 4 * U1, "oa": n * 4 * U1},
+        ["oc", "on", "oa"], ["ic", "in", "ia", "state"], nullable=["state"],
+        refused=[(0, 0), (0, -1), (1, 3), (1, -1), (2, -0.5), (2, NAN), (2, INF), (3, 1), (4, 1), (5, 1)],
+        refused_ptr=[{"params": None}, {"ic": None}, {"oc": None}, {"in": None}, {"on": None}, {"ia": None}, {"oa": None}],      # the last four: half a guide pair
+        good_ptr=[{"in": None, "on": None}, {"ia": None, "oa": None}, {"in": None, "on": None, "ia": None, "oa": None, "state": None}],
+        good_values=[([n, 0, 0.0, 0, 0, 0], {}), ([n, 2, 3e38, 0, 0, 0], {})])
+
+    # no aliasing rule today: pointers and sizes only
+    P["reduce_metrics"] = Pass(lambda v, p: shim.shim_reduce_metrics(v[0], p["diag"], v[1], p["color"], p["scw"], p["out"]), [n, 4],
+                               {"diag": n * 4, "color": n * F4, "scw": n * F1, "out": C.sizeof(a.Metrics)}, [], [],
+                               refused=[(0, 0), (0, -1), (1, 0), (1, 8), (1, -4)], refused_ptr=[{k: None} for k in ("diag", "color", "scw", "out")], good_values=[([n, 16], {})])
+    six = {"ic": n * F4, "in": n * F3, "ia": n * F3, "oc": n * F3, "on": n * F3, "oa": n * F3}
+    P["combine"] = Pass(lambda v, p: shim.shim_combine(ref(a.CombineParams(*v)) if p["params"] else None, p["ic"], p["in"], p["ia"], p["oc"], p["on"], p["oa"]), [8, 8, 0, 0], six, [], [],
+                        refused=[(0, 0), (1, 0), (0, -1), (1, -1)], refused_ptr=[{k: None} for k in ("params",) + tuple(six)])
+    P["finalize"] = Pass(lambda v, p: shim.shim_finalize(v[0], p["ic"], p["in"], p["ia"], p["oc"], p["on"], p["oa"]), [n], six, [], [],
+                         refused=[(0, 0), (0, -1)], refused_ptr=[{k: None} for k in six])
+    P["add_accum"] = Pass(lambda v, p: shim.shim_add_accum(v[0], ref(a.AccumBuffers(p["dc"], p["dn"], p["da"], p["ds"])) if p["dst"] else None,
+                                                          ref(a.AccumBuffers(p["sc"], p["sn"], p["sa"], p["ss"])) if p["src"] else None), [n],
+                          {"dc": n * F4, "dn": n * F3, "da": n * F3, "ds": n * F1, "sc": n * F4, "sn": n * F3, "sa": n * F3, "ss": n * F1}, [], [], structs=["dst", "src"],
+                          refused=[(0, 0), (0, -1)], refused_ptr=[{k: None} for k in ("dst", "src", "dc", "dn", "da", "ds", "sc", "sn", "sa", "ss")])
+    return P
+
+
+PASSES = ["denoise", "denoise_variance", "accumulate_moments", "reproject", "reproject_bilinear", "reproject_moments", "estimate_moments", "noise_mask", "rectify_history",
+          "upsample", "build_pixel_list", "meter_exposure", "finalize_tone_mapped", "reduce_metrics", "combine", "finalize", "add_accum"]
+
+
+@pytest.fixture(scope="module")
+def passes(rt, shim):
+    table = _passes(rt, shim)
+    assert sorted(table) == sorted(PASSES)
+    return table
+
+
+@pytest.mark.parametrize("name", PASSES)
+def test_good_calls_succeed_and_single_refusals_are_refused(rt, passes, name):
+    p = passes[name]
+    ok, bad = rt.abi.RTOW_SUCCESS, rt.abi.RTOW_ERROR_INVALID_VALUE
+    assert p.run() == ok
+    for k in p.nullable:                                   # every optional buffer absent on its own, unless it is half of a pair (good_ptr has the pair)
+        if {k: None} not in p.refused_ptr:
+            assert p.run(**{k: None}) == ok, k
+    for over in p.good_ptr:
+        assert p.run(**over) == ok, over
+    for values, over in p.good_values:
+        assert p.run(values, **over) == ok, (values, over)
+    for index, value in p.refused:
+        assert p.run(p.edited(index, value)) == bad, (index, value)
+    for over in p.refused_ptr:
+        assert p.run(**over) == bad, over
+
+
+@pytest.mark.parametrize("name", [k for k in PASSES if k not in ("reduce_metrics", "combine", "finalize", "add_accum")])
+def test_aliasing_is_decided_at_the_byte(rt, passes, name):
+    """Every written buffer against every buffer the pass reads (the in-place inputs included) and every other written buffer: sharing exactly one byte is refused, in
+    either order, and abutting is accepted."""
+    p = passes[name]
+    ok, bad = rt.abi.RTOW_SUCCESS, rt.abi.RTOW_ERROR_INVALID_VALUE
+    pairs = 0
+    for w in p.written:
+        for o in p.read + list(p.same.values()) + [x for x in p.written if x != w]:
+            wb, ob, at = p.sizes[w], p.sizes[o], p.base[o]
+            assert p.run(**{w: at + ob - 1}) == bad, (w, "on the last byte of", o)
+            assert p.run(**{w: at + ob}) == ok, (w, "behind", o)
+            assert p.run(**{w: at - wb + 1}) == bad, (w, "ends on the first byte of", o)
+            assert p.run(**{w: at - wb}) == ok, (w, "before", o)
+            if p.same.get(w) != o:
+                assert p.run(**{w: at}) == bad, (w, "is", o)
+            pairs += 1
+    assert pairs == len(p.written) * (len(p.read) + len(p.same) + len(p.written) - 1)
+
+
+@pytest.mark.parametrize("name", ["accumulate_moments", "estimate_moments", "rectify_history"])
+def test_documented_in_place_forms_are_accepted_at_equal_bases_only(rt, passes, name):
+    p = passes[name]
+    ok, bad = rt.abi.RTOW_SUCCESS, rt.abi.RTOW_ERROR_INVALID_VALUE
+    assert p.run(**{w: p.base[s] for w, s in p.same.items()}) == ok            # all of them at once
+    for w, s in p.same.items():
+        assert p.run(**{w: p.base[s]}) == ok, (w, s)
+        assert p.run(**{w: p.base[s] + 4}) == bad and p.run(**{w: p.base[s] - 4}) == bad, (w, s, "shifted by 4 bytes")
+        assert p.run(**{s: p.base[w] + 4}) == bad, (s, w, "the input shifted instead")
+        for other in set(p.same.values()) - {s}:
+            assert p.run(**{w: p.base[other]}) == bad, (w, "is a different input:", other)
+    if name == "estimate_moments":                                             # in place, with outFilled inside the moments
+        assert p.run(**{"out": p.base["in"], "fill": p.base["in"] + 4}) == bad
+
+
+def _rules(written, read, same):
+    """The three rules, restated: ranges are (base, bytes), a null base overlaps nothing"""
+    hit = lambda x, y: bool(x[0] and y[0] and x[0] < y[0] + y[1] and y[0] < x[0] + x[1])
+    for i, w in enumerate(written):
+        if any(hit(w, r) for r in read):
+            return False
+        if any(hit(w, v) for j, v in enumerate(written) if j != i):
+            return False
+        if any(hit(w, s) and not (i == k and w[0] == s[0]) for k, s in enumerate(same)):
+            return False
+    return True
+
+
+def test_aliasing_rule_against_a_restatement(shim):
+    rng = random.Random(20)
+    verdicts = []
+    for _ in range(400):
+        sizes = [rng.randint(0, 7), rng.randint(0, 7), rng.randint(0, 5)]
+        span = rng.choice((256, 1024, 4096))             # the smaller, the more collisions
+        table = [[(0 if rng.random() < 0.15 else 0x1000 + rng.randrange(span), rng.choice((1, 4, 12, 16, 48))) for _ in range(k)] for k in sizes]
+        for k in range(min(sizes[0], sizes[2])):         # some outputs ARE their input, some nearly
+            roll = rng.random()
+            if roll < 0.5:
+                table[2][k] = (table[0][k][0] + (0 if roll < 0.35 else 4), table[2][k][1])
+        flat = table[0] + table[1] + table[2]
+        base, size = (C.c_uint64 * max(len(flat), 1))(*[b for b, _ in flat]), (C.c_uint64 * max(len(flat), 1))(*[s for _, s in flat])
+        got = shim.shim_aliasing_ok(base, size, *sizes)
+        assert got == int(_rules(*table)), table
+        verdicts.append(got)
+    assert 100 <= sum(verdicts) <= 300, sum(verdicts)    # both verdicts in at least a quarter of the tables
+    assert shim.shim_overlaps(0, 16, 0, 16) == 0 and shim.shim_overlaps(16, 16, 31, 1) == 1 and shim.shim_overlaps(16, 16, 32, 1) == 0
+
+
+def test_reproject_constants_are_the_float32_expression(rt, shim, passes):
+    f = np.float32
+    vec = lambda v: np.array([v.x, v.y, v.z], f)
+    dot = lambda p, q: f(f(f(p[0] * q[0]) + f(p[1] * q[1])) + f(p[2] * q[2]))
+    views = [rt.scenes.make_view(rt.scenes.cover_scene(), 1920, 1080)]
+    rng = np.random.default_rng(3)
+    for scale in (1.0, 1e-3):
+        v = rt.abi.View()
+        for name in ("origin", "lowerLeftCorner", "horizontal", "vertical", "forward", "up", "right"):
+            setattr(v, name, rt.abi.Float3(*[float(x) for x in (rng.standard_normal(3) * scale).astype(f)]))
+        views.append(v)
+    for v in views:
+        want = np.array([dot(vec(v.lowerLeftCorner), vec(v.forward)), dot(vec(v.lowerLeftCorner), vec(v.right)), dot(vec(v.lowerLeftCorner), vec(v.up)),
+                         dot(vec(v.horizontal), vec(v.right)), dot(vec(v.vertical), vec(v.up))], f)
+        got = (C.c_float * 5)()
+        shim.shim_reproject_constants(C.byref(v), got)
+        assert np.array_equal(np.array(got[:], f).view(np.uint32), want.view(np.uint32)), (list(got), want)
+        p = passes["reproject"]                            # the validator leaves the same five numbers
+        values = list(p.values)
+        values[2] = v
+        ptr = {**p.base, **{s: True for s in p.structs}}
+        a = rt.abi
+        hits, prev_hits = a.HitBuffers(ptr["t"], ptr["e"], None), a.HitBuffers(ptr["pt"], ptr["pe"], None)
+        prev, out = a.AccumBuffers(ptr["pc"], ptr["pn"], ptr["pa"], ptr["ps"]), a.AccumBuffers(ptr["oc"], ptr["on"], ptr["oa"], ptr["os"])
+        filled = (C.c_float * 5)()
+        assert shim.shim_reproject(C.byref(a.ReprojectParams(*values)), ptr["rays"], C.byref(hits), C.byref(prev_hits), C.byref(prev), C.byref(out), ptr["src"], filled) == a.RTOW_SUCCESS
+        assert np.array_equal(np.array(filled[:], f).view(np.uint32), want.view(np.uint32))
+
+
+@pytest.mark.parametrize("name", ["reproject", "reproject_bilinear"])
+def test_a_zero_divisor_of_the_projection_is_refused(rt, passes, name):
+    """LF = lowerLeftCorner . forward, HR = horizontal . right, VU = vertical . up: each zero (and not finite) in turn"""
+    p = passes[name]
+    a = rt.abi
+    good = p.values[2]
+    zero = a.Float3(0.0, 0.0, 0.0)
+    for fields in (("forward",), ("horizontal",), ("vertical",)):
+        for value in (zero, a.Float3(INF, INF, INF), a.Float3(NAN, 0.0, 0.0)):
+            v = a.View.from_buffer_copy(good)
+            for name_ in fields:
+                setattr(v, name_, value)
+            assert p.run(p.edited(2, v)) == a.RTOW_ERROR_INVALID_VALUE, (fields, value.x)
+    v = a.View.from_buffer_copy(good)                          # LR and LU are no divisors: a corner straight ahead is accepted
+    v.lowerLeftCorner = a.Float3(good.forward.x, good.forward.y, good.forward.z)
+    assert p.run(p.edited(2, v)) == a.RTOW_SUCCESS
+
+
+def test_sample_params_and_query_arguments(rt, shim):
+    a = rt.abi
+    ok, bad = a.RTOW_SUCCESS, a.RTOW_ERROR_INVALID_VALUE
+    scene = rt.scenes.cover_scene()
+
+    def params(**over):
+        p = rt.scenes.make_params(scene, 96, 54, spp=4, trace_depth=8)
+        for k, v in over.items():
+            setattr(p, k, v)
+        return shim.shim_params(C.byref(p))
+    assert params() == ok and params(traceDepth=64) == ok and params(traceDepth=1) == ok and params(diagnosticsStride=16) == ok and params(sliceDivider=3, sliceOffset=2) == ok
+    assert shim.shim_params(None) == bad
+    assert params(traceDepth=0) == bad and params(traceDepth=-1) == bad
+    assert params(traceDepth=65) == a.RTOW_ERROR_CAPACITY and params(traceDepth=1 << 20) == a.RTOW_ERROR_CAPACITY
+    assert params(traceDepth=65, diagnosticsStride=8) == a.RTOW_ERROR_CAPACITY and params(traceDepth=65, sliceDivider=0) == bad          # the order of the checks
+    for over in ({"size": a.Float2(0.0, 54.0)}, {"size": a.Float2(96.0, -1.0)}, {"size": a.Float2(65536.0, 65536.0)}, {"sliceDivider": 0}, {"sliceOffset": -1}, {"sliceOffset": 1},
+                 {"noiseColor": -1}, {"noiseColor": 3}, {"rngPolicy": 3}, {"rngPolicy": -1}, {"rngPolicy": 1, "noiseColor": 1}, {"diagnosticsStride": 8}, {"diagnosticsStride": 0}):
+        assert params(**over) == bad, over
+    env = a.Environment(4, a.Float3(0, 0, 0), a.Float3(0, 0, 0))
+    assert params(environment=env) == bad
+
+    view = rt.scenes.make_view(scene, 8, 8)
+    size = lambda w, h, reserved=0: shim.shim_view_size(C.byref(a.TraceViewParams(w, h, view, 0.0, reserved)))
+    assert size(8, 8) == 1 and size(46340, 46340) == 1 and size(1, 1) == 1
+    assert size(0, 8) == 0 and size(8, -1) == 0 and size(65536, 65536) == 0 and size(65536, 32768) == 0 and size(8, 8, 1) == 0
+
+    fake = [STEP * k for k in range(1, 9)]
+    guide = lambda bounces=8, flags=0, reserved=0, outs=None, params=True, out=True: shim.shim_guide_arguments(
+        C.byref(a.GuideParams(bounces, flags, reserved)) if params else None, C.byref(a.guide_buffers(outs if outs is not None else {"distance": fake[0], "end": fake[1]})) if out else None)
+    assert guide() == 1 and guide(0) == 1 and guide(a.GUIDE_MAX_BOUNCES) == 1
+    for only in a.GUIDE_OUTPUTS:
+        assert guide(outs={only: fake[2]}) == 1, only
+    assert guide(-1) == 0 and guide(a.GUIDE_MAX_BOUNCES + 1) == 0 and guide(flags=1) == 0 and guide(reserved=1) == 0 and guide(outs={}) == 0
+    assert guide(params=False) == 0 and guide(out=False) == 0
+
+    def shade(count=16, sky=1, flags=0, reserved=0, rays=fake[0], entity=fake[1], outs=(fake[2], None, None, None, None, None), params=True, surface=True):
+        p = a.ShadeHitsParams(a.Environment(sky, a.Float3(0, 0, 0), a.Float3(0, 0, 0)), flags, reserved)
+        return shim.shim_shade_hits(C.byref(p) if params else None, count, rays, entity, C.byref(a.SurfaceBuffers(*outs)) if surface else None)
+    assert shade() == ok and shade(count=0) == ok and shade(sky=0) == ok and shade(sky=2) == ok
+    for k in range(6):
+        assert shade(outs=tuple(fake[3] if j == k else None for j in range(6))) == ok
+    assert shade(count=-1) == bad and shade(sky=3) == bad and shade(sky=-1) == bad and shade(flags=1) == bad and shade(reserved=1) == bad
+    assert shade(rays=None) == bad and shade(entity=None) == bad and shade(outs=(None,) * 6) == bad and shade(params=False) == bad and shade(surface=False) == bad
+
+
+def test_accumulate_moments_takes_up_to_the_batch_limit(rt, shim):
+    a = rt.abi
+    n = 64
+    assert shim.shim_moments_max_batches() == a.MOMENTS_MAX_BATCHES
+    colors = (C.c_void_p * (a.MOMENTS_MAX_BATCHES + 1))(*[STEP * (k + 1) for k in range(a.MOMENTS_MAX_BATCHES + 1)])
+    out = STEP * 32
+    assert shim.shim_accumulate_moments(n, a.MOMENTS_MAX_BATCHES, colors, None, out) == a.RTOW_SUCCESS
+    assert shim.shim_accumulate_moments(n, a.MOMENTS_MAX_BATCHES + 1, colors, None, out) == a.RTOW_ERROR_INVALID_VALUE
+    for k in range(a.MOMENTS_MAX_BATCHES):                    # the output on the last byte of any of the sixteen, and behind it
+        assert shim.shim_accumulate_moments(n, a.MOMENTS_MAX_BATCHES, colors, None, colors[k] + n * F4 - 1) == a.RTOW_ERROR_INVALID_VALUE, k
+        assert shim.shim_accumulate_moments(n, a.MOMENTS_MAX_BATCHES, colors, None, colors[k] + n * F4) == a.RTOW_SUCCESS, k
+
+
+def test_validate_host_program_runs_clean_under_sanitizers(tmp_path):
+    """tests/native/validate_host.cpp: every validator once good and once with each extreme - INT32_MIN / INT32_MAX sizes, radius and minTaps at their type limits, a list
+    capacity of UINT32_MAX, a base within a few bytes of UINTPTR_MAX - under the address and undefined-behaviour sanitizers (a stand-alone program: nothing is loaded
+    into Python)."""
+    exe = str(tmp_path / "validate_host")
+    build = subprocess.run(["g++", "-std=c++17", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                            os.path.join(ROOT, "tests", "native", "validate_host.cpp"), os.path.join(CSRC, "rtow_validate.cpp"), "-o", exe],
+                           capture_output=True, text=True, timeout=300)
+    assert build.returncode == 0, build.stdout + build.stderr
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert run.returncode == 0 and run.stdout.strip().splitlines()[-1] == "ok", run.stdout + run.stderr
