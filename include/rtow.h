@@ -692,7 +692,9 @@ RTOW_API int rtowTraceGuideViewDevice(RtowContext context, const RtowGuideParams
  * stream the kernel was launched on (the RecordTimeJob 0/1 bracket, JOBS/UtilJobs.cs:77-86). Synchronises on the end event. */
 RTOW_API int rtowGetLastSampleKernelMs(RtowContext context, float* outMs);
 
-/* replaces: ReduceMetricsJob.Execute (JOBS/ReduceMetricsJob.cs:22-45). Device buffers in, host scalars out. */
+/* replaces: ReduceMetricsJob.Execute (JOBS/ReduceMetricsJob.cs:22-45). Device buffers in, host scalars out.
+ * Domain: every RayCount and every color.w is finite with a magnitude below 2^31 - `(int)` of anything else is undefined in the reference's C# and C++ and saturates
+ * on the device, so the record is unspecified there (sampleCountWeight may hold anything: a NaN weight is skipped, +inf counts). */
 typedef struct RtowMetrics {
     int32_t totalRayCount;              /* sum of (int)RayCount */
     int32_t totalSamples;               /* sum of (int)color.w */
@@ -713,7 +715,10 @@ RTOW_API int rtowReduceMetricsDeviceAsync(RtowContext context, int32_t pixelCoun
                                           int32_t diagnosticsStride, const float* color, const float* sampleCountWeight,
                                           void* stream, RtowMetrics* outMetrics);
 
-/* replaces: CombineJob.Execute (JOBS/CombineJob.cs:29-71): sum -> mean, interlace look-around, NaN handling. */
+/* replaces: CombineJob.Execute (JOBS/CombineJob.cs:29-71): sum -> mean, interlace look-around, NaN handling.
+ * Domain: color.w is finite with a magnitude below 2^31 (`(int) color.w` is undefined beyond that in the reference and saturates on the device); r, g, b, the normals and
+ * the albedos may hold anything.  RTOW_ERROR_INVALID_VALUE, nothing enqueued: a NULL pointer, width or height <= 0, width * height > INT32_MAX (the product is taken in
+ * 64 bits) - for rtowCombineFinalizeDevice alike. */
 typedef struct RtowCombineParams {
     int32_t width, height;          /* CombineJob.Size */
     int32_t debugMode;              /* CombineJob.DebugMode */

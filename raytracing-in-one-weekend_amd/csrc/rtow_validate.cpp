@@ -78,7 +78,7 @@ int validateCombine(const RtowCombineParams* params, const float* inColor, const
                     const void* outAlbedo)
 {
     if (!params || !inColor || !inNormal || !inAlbedo || !outColor || !outNormal || !outAlbedo) return kBad;
-    if (params->width <= 0 || params->height <= 0) return kBad;
+    if (!frameSizeValid(params->width, params->height)) return kBad;      // the kernels index pixels in int: width * height beyond INT32_MAX would wrap to an empty launch
     return RTOW_SUCCESS;
 }
 

@@ -68,7 +68,8 @@ int main()
     CHECK(validateReduceMetrics(64, scratch, INT32_MAX, f[0], f[1], metrics) == BAD && validateReduceMetrics(64, scratch, INT32_MIN, f[0], f[1], metrics) == BAD);
     RtowCombineParams cp{}; cp.width = 8; cp.height = 8;
     CHECK(validateCombine(&cp, f[0], f[1], f[2], f[4], f[5], f[6]) == OK);
-    cp.width = INT32_MAX; cp.height = INT32_MAX; CHECK(validateCombine(&cp, f[0], f[1], f[2], f[4], f[5], f[6]) == OK);      // no bound on the product today
+    cp.width = INT32_MAX; cp.height = INT32_MAX; CHECK(validateCombine(&cp, f[0], f[1], f[2], f[4], f[5], f[6]) == BAD);     // the product is taken in 64 bits: beyond INT32_MAX pixels
+    cp.height = 1; CHECK(validateCombine(&cp, f[0], f[1], f[2], f[4], f[5], f[6]) == OK);
     cp.width = INT32_MIN; CHECK(validateCombine(&cp, f[0], f[1], f[2], f[4], f[5], f[6]) == BAD);
     CHECK(validateFinalize(INT32_MAX, f[0], f[1], f[2], b[0], b[1], b[2]) == OK && validateFinalize(INT32_MIN, f[0], f[1], f[2], b[0], b[1], b[2]) == BAD);
     CHECK(validateAddAccum(INT32_MAX, &out, &in) == OK && validateAddAccum(INT32_MIN, &out, &in) == BAD);

@@ -199,7 +199,8 @@ def _passes(rt, shim):
                                refused=[(0, 0), (0, -1), (1, 0), (1, 8), (1, -4)], refused_ptr=[{k: None} for k in ("diag", "color", "scw", "out")], good_values=[([n, 16], {})])
     six = {"ic": n * F4, "in": n * F3, "ia": n * F3, "oc": n * F3, "on": n * F3, "oa": n * F3}
     P["combine"] = Pass(lambda v, p: shim.shim_combine(ref(a.CombineParams(*v)) if p["params"] else None, p["ic"], p["in"], p["ia"], p["oc"], p["on"], p["oa"]), [8, 8, 0, 0], six, [], [],
-                        refused=[(0, 0), (1, 0), (0, -1), (1, -1)], refused_ptr=[{k: None} for k in ("params",) + tuple(six)])
+                        refused=[(0, 0), (1, 0), (0, -1), (1, -1), (BIG, 0), (WIDE, 0), ((46341, 46341), 0)], refused_ptr=[{k: None} for k in ("params",) + tuple(six)],
+                        good_values=[([46340, 46340, 0, 0], {}), ([1, 0x7fffffff, 1, 1], {})])      # the largest square and the largest count the int index holds
     P["finalize"] = Pass(lambda v, p: shim.shim_finalize(v[0], p["ic"], p["in"], p["ia"], p["oc"], p["on"], p["oa"]), [n], six, [], [],
                          refused=[(0, 0), (0, -1)], refused_ptr=[{k: None} for k in six])
     P["add_accum"] = Pass(lambda v, p: shim.shim_add_accum(v[0], ref(a.AccumBuffers(p["dc"], p["dn"], p["da"], p["ds"])) if p["dst"] else None,
