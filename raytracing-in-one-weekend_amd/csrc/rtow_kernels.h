@@ -54,6 +54,11 @@ __host__ __device__ inline void node_image(const uint32_t n[16], uint32_t o[20])
     }
     o[18] = n[12]; o[19] = n[13];
 }
+// Child words as the kernels with the sign-ordered walk read them (signed_walk_variant, rtow_sample_kernel.hip.h): a leaf child ~prim becomes 0x80000000 | prim, so that
+// its low 16 bits ARE the candidate code the visit stores (no inversion per visit) and its sign still says "leaf"; an inner child (>= 0) stays the node index it is.
+// The blob and node_image keep ~prim: the re-encoding happens where such a kernel takes a node in - once per node while it stages the image, or per load of a 64-byte node.
+__host__ __device__ inline uint32_t leaf_code_ready(uint32_t child) { return child ^ ((uint32_t)((int32_t)child >> 31) & 0x7fffffffu); }
+__host__ __device__ inline void node_image_leaf_codes(uint32_t o[20]) { o[18] = leaf_code_ready(o[18]); o[19] = leaf_code_ready(o[19]); }
 // What the sign-ordered walk assumes of a tree: lo <= hi in every plane pair of every child (no NaN either).  True of every tree the scene compiler builds from finite
 // entities - the one-entity scene's placeholder second child (lo = +FLT_MAX, hi = -FLT_MAX) is masked in the kernel and exempt here; a scene that fails keeps 64-byte nodes.
 inline bool node_planes_ordered(const GpuNode* nodes, uint32_t nodeCount, bool twoChildren)

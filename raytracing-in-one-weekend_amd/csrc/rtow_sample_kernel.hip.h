@@ -855,6 +855,15 @@ __device__ __forceinline__ int lds_code_load(int at)
     (void)at; return 0;
 #endif
 }
+// ... sign-extended: 0xffff reads back as -1 (the walk's pop, whose empty-stack slot holds that sentinel)
+__device__ __forceinline__ int lds_code_load_signed(int at)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (int)*(__attribute__((address_space(3))) const short*)(uint32_t)at;
+#else
+    (void)at; return 0;
+#endif
+}
 __device__ __forceinline__ void lds_code_store(int at, int code)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -917,8 +926,16 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
     constexpr int kRowBytes = BT * (int)sizeof(Code);
     constexpr int kStackAt = kCandCapacity * kRowBytes;                                        // from a lane's candidate row k to its stack row k
     static_assert(!SIGNED_WALK || (!WIDE && kRowBytes == 2 * BT), "cursor compares need a lane's offset inside a row to be smaller than the row");
+    // (SIGNED_WALK) the last candidate row holds no candidate: it is the row directly under the stack, which a pop from an EMPTY stack reads (popSlot), and every lane keeps
+    // 0xffff there - read back sign-extended that is -1, "walk over", with no compare or select in the visit.  Stack codes are node indices of a scene that is whole in
+    // LDS: far below 32 768 (kLdsBytesMax / sizeof(GpuNode) nodes at most; launchVariant refuses anything else), so a real code never reads back negative.
+    constexpr int kPopSentinelRow __attribute__((unused)) = kCandCapacity - 1;
+    static_assert(!SIGNED_WALK || (size_t)kLdsBytesMax / sizeof(GpuNode) <= 32768u, "stack codes are read back as signed 16-bit values");
     const int laneRow0 = lds_address(cand);
     auto rowAt = [&](int k) -> int { return lds_address(smem) + k * kRowBytes; };
+    // the sentinel: the lane's own slot, written once, nothing below stores into this row.  (Written HERE, ahead of the staging: the same store in front of the main loop
+    // left the HW 8 kernel a 36-byte private segment of dead spill slots - tests/test_isa_guards.py)
+    if constexpr (SIGNED_WALK) lds_code_store(laneRow0 + kPopSentinelRow * kRowBytes, 0xffff);
     HistRowsT<!ALL_LDS> histRows;
     histRows.lane = HW == 32 ? reinterpret_cast<unsigned short*>(smem + A.ldsHistOffset) + swizzled : nullptr;
     // {next, end} ticket chunk of this wave; chains: {.., needDone, chunk} = the chunk may only be handed out once chunkDone[chunk] >= needDone
@@ -947,6 +964,7 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
         for (uint32_t i = (uint32_t)tid; i < nodes; i += BT) {
             uint4 in[4] = {src[4u * i], src[4u * i + 1u], src[4u * i + 2u], src[4u * i + 3u]}, out[5];
             node_image(reinterpret_cast<const uint32_t*>(in), reinterpret_cast<uint32_t*>(out));
+            node_image_leaf_codes(reinterpret_cast<uint32_t*>(out));      // leaf children ready to store (listLeaves)
             for (int k = 0; k < 5; k++) img[5u * i + (uint32_t)k] = out[k];
         }
         uint4* dst = reinterpret_cast<uint4*>(ldsScene + imageGrowth);
@@ -1101,6 +1119,8 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
             q0 = make_float4(px.x, px.y, py.x, py.y); q1 = make_float4(pz.x, pz.y, px.z, px.w); q2 = make_float4(py.z, py.w, pz.z, pz.w);
         } else {
             load_node<ALL_LDS, SPLIT_NODES>(sc, L, idx, q0, q1, q2, c0, c1);
+            // a launch without the image (RTOW_CONTEXT_NODE_IMAGE_64, or a scene that fits with 64-byte nodes only): the same leaf codes as the image's, per load - not the hot path
+            if (SIGNED_WALK) { c0 = (int)leaf_code_ready((uint32_t)c0); c1 = (int)leaf_code_ready((uint32_t)c1); }
         }
     };
     // slab distances of both children of a node, for the camera-ray lists - the walk's own expressions: sign-ordered (ordered = signOrderedWave() of this list) or generic
@@ -1130,11 +1150,13 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
             tfar1 = vmin3(vmax(tlx.y, thx.y), vmax(tly.y, thy.y), vmax(tlz.y, thz.y));
         }
     };
-    // (SIGNED_WALK) the candidate list through its cursor: both leaf codes are written unconditionally, only the cursor is predicated (as with counts)
+    // (SIGNED_WALK) the candidate list through its cursor: both leaf codes are written unconditionally, only the cursor is predicated (as with counts).  The children
+    // arrive as leaf_code_ready made them (rtow_kernels.h): the low 16 bits of a leaf child are its primitive, stored as they are.  A caller has fewer than kCandCapacity - 2
+    // candidates listed when it calls, so the two stores reach row kCandCapacity - 2 at most: the last row is the walk's empty-stack sentinel (kPopSentinelRow)
     auto listLeaves = [&](int c0, int c1, bool leaf0, bool leaf1) {
-        lds_code_store(nc, ~c0);
+        lds_code_store(nc, c0);
         nc += leaf0 ? kRowBytes : 0;
-        lds_code_store(nc, ~c1);
+        lds_code_store(nc, c1);
         nc += leaf1 ? kRowBytes : 0;
     };
     // a new ray segment starts: reset the traversal state
@@ -1579,6 +1601,8 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
                             const unsigned node = WIDE ? (k == 0 ? pcand.x : k == 1 ? pcand.y : k == 2 ? pcand.z : pcand.w)
                                                        : ((k < 2 ? pcand.x >> (16 * k) : pcand.y >> (16 * (k - 2))) & 0xffffu);
                             if (node == (WIDE ? 0xffffffffu : 0xffffu)) break;
+                            // (SIGNED_WALK) the list's last row is the walk's sentinel: a fourth node that finds six candidates listed waits for the exact-test stage, as nodes five to eight do
+                            if constexpr (SIGNED_WALK) { if (k == 3 && nc >= rowAt(kCandCapacity - 2)) { cur = -2 - k; break; } }
                             float tmin0, tfar0, tmin1, tfar1;
                             int c0, c1;
                             if constexpr (SIGNED_WALK) {
@@ -1608,7 +1632,7 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
                             }
                         }
                         // nodes five to eight: the exact-test stage comes back for them when these candidates are done (cur = -2 - k: node k is next)
-                        if (LONG_LISTS) { if ((pcand.z & 0xffffu) != 0xffffu) cur = -6; }
+                        if (LONG_LISTS) { if ((!SIGNED_WALK || cur == -1) && (pcand.z & 0xffffu) != 0xffffu) cur = -6; }      // (a fourth node that waits comes first: the stage goes on from it)
                         if ((SIGNED_WALK ? nc < rowAt(1) : nc == 0) && cur == -1) classify(); else st = ST_TEST;
                     }
                 }
@@ -1633,32 +1657,50 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
                 // Branch-free node visit: every LDS access of the iteration is issued up front (node, plus the stack slot a
                 // pop would need), candidate / stack slots are written unconditionally and only the counters are predicated,
                 // so the wave's EXEC mask changes only at the loop test.  What keeps it so is the FORM of the visit's tail: every value a lane keeps is one select
-                // of two operands that are already computed (nearChild, onlyChild, fromStack, pushed: named, none nested in another's arm).  Nested conditional
+                // of two operands that are already computed (nearChild, onlyChild, popped, pushed: named, none nested in another's arm).  Nested conditional
                 // expressions there (`both ? (swap ? c1 : c0) : ...`, `any ? next : (sp > 0 ? popped : -1)`) reached the compiler through finishVisit as control
                 // flow: two exec-mask regions and three more branches per visit in the headline kernels.  tests/test_isa_walk_loop.py reads the compiled loops.
-                // A walk hands its candidates to TEST as soon as it holds A.tune[6] of them (3; at most 7, the list holds 8 and a visit adds up to 2): the
+                // A walk hands its candidates to TEST as soon as it holds A.tune[6] of them (3; at most 7, the list holds 8 and a visit adds up to 2 - at most 6 in the
+                // kernels with the sign-ordered walk, whose last candidate row is the empty-stack sentinel: the sweep below puts 7 no better than 3): the
                 // exact tests are deferred to keep the walk branch-free, but the nearest hit among the first few candidates - the walk visits near
                 // children first - prunes most of what is left of the walk, which a list filled to the brim (round 1 - 3: 7) never got to use.
                 // 1 / 2 / 3 / 4 / 7 candidates: cover 9.18 / 8.87 / 9.52 / 9.41 / 9.18 Gsamples/s, 10 000 spheres 7.37 / 7.42 / 7.85 / 7.64 / 7.37,
                 // 250 k-triangle mesh 1.84 / 1.90 / 1.98 / 1.96 / 1.84 (gpurun_out/r03bb; "1" = the 7 of before in that run's encoding)
                 // (volume scenes keep every hit of a ray and prune nothing: their lists fill up as before)
-                const int candExit = VOLUMES ? kCandCapacity - 2 : (A.tune[6] < kCandCapacity - 1 ? A.tune[6] : kCandCapacity - 1) - 1;
+                constexpr int kHandOverMost = SIGNED_WALK ? kCandCapacity - 2 : kCandCapacity - 1;
+                const int candExit = VOLUMES ? kCandCapacity - 2 : (A.tune[6] < kHandOverMost ? A.tune[6] : kHandOverMost) - 1;
                 if constexpr (SIGNED_WALK) {
                     // (finishVisit = the tail of the loop in the `else` below, which is the text of the variants without the walk: two copies that must compute the same -
                     // here on cursors and in flat selects, there on counts and in the nested form; the prefetches of the wide-code kernels have no place in these)
                     // `sp` and `nc` are LDS cursors in these kernels (lds_code_load): the loop tests and the hand-over below compare them with row addresses
                     const int candLimit = rowAt(candExit + 1);           // nc <= candExit as a cursor: nc < candLimit
-                    // the slot a pop would read, one row under the top.  Not clamped at an empty stack: that read lands in the lane's last candidate row, the value is
-                    // dropped (fromStack), and a stack left one row under its base is not used again - the walk is over (cur = -1) and startRay resets the cursor
-                    auto popSlot = [&]() -> int { return lds_code_load(sp + (kStackAt - kRowBytes)); };
+                    // the slot a pop would read, one row under the top, sign-extended.  Not clamped at an empty stack: that read lands in the lane's last candidate row, which
+                    // holds the sentinel 0xffff (kPopSentinelRow) - the pop of an empty stack IS -1 - and a stack left one row under its base is not used again: the walk
+                    // is over (cur = -1) and startRay resets the cursor
+                    auto popSlot = [&]() -> int { return lds_code_load_signed(sp + (kStackAt - kRowBytes)); };
                     // the rest of a visit once the four slab distances are known: pruning, leaf test, candidate and stack stores, near child first
-                    auto finishVisit = [&](float tmin0, float tfar0, float tmin1, float tfar1, int c0, int c1, int popped) {
+                    // (ordered: std::true_type in the sign-ordered loop, whose distances cannot be NaN)
+                    auto finishVisit = [&](auto ordered, float tmin0, float tfar0, float tmin1, float tfar1, int c0, int c1, int popped) {
                         // inner child (padded box): conservative, pruned by the nearest hit so far.  Leaf child (the reference's own entity box):
                         // AxisAlignedBoundingBox.Hit itself, tMin < tMax (RT/HitTests.cs:15-20) - pruning by `best` on top (<=, so that a tie at
                         // exactly `best` is still tested) cannot change which hit is nearest.
-                        const bool hit0 = tmin0 <= vmin(tfar0, bestPrune);
-                        const bool hit1 = tmin1 <= vmin(tfar1, bestPrune) && twoChildren;
-                        const bool leaf0 = c0 < 0 && hit0 && tmin0 < tfar0, leaf1 = c1 < 0 && hit1 && tmin1 < tfar1;
+                        // Sign-ordered loop: ONE test for both kinds of child, tmin <= bestPrune && tmin < tfar - two compares, no min.  For a leaf that is the test above
+                        // as it stands (tmin < tfar implies tmin <= tfar).  For an inner child it is stricter than tmin <= tfar and loses no candidate: a stored child box
+                        // encloses the stored boxes of its own children (tests/test_scene_compiler.py), (plane - o) * inv is monotone in the plane for a finite origin and a
+                        // finite non-zero inv, and max3 / min3 are monotone, so tmin_inner <= tmin_leaf < tfar_leaf <= tfar_inner for every leaf below it that passes its
+                        // own test - every ancestor of a passing leaf passes the strict test too.  What it skips are inner boxes the ray meets with tmin == tfar (an edge,
+                        // a corner): no leaf in them can pass.  The order of the visits (swap) is untouched.  The generic loop keeps tmin <= min(tfar, bestPrune): its rays
+                        // are the ones whose products can be NaN, and the argument needs the monotone products.
+                        bool hit0, hit1, leaf0, leaf1;
+                        if constexpr (decltype(ordered)::value) {
+                            hit0 = tmin0 <= bestPrune && tmin0 < tfar0;
+                            hit1 = tmin1 <= bestPrune && tmin1 < tfar1 && twoChildren;
+                            leaf0 = c0 < 0 && hit0; leaf1 = c1 < 0 && hit1;
+                        } else {
+                            hit0 = tmin0 <= vmin(tfar0, bestPrune);
+                            hit1 = tmin1 <= vmin(tfar1, bestPrune) && twoChildren;
+                            leaf0 = c0 < 0 && hit0 && tmin0 < tfar0; leaf1 = c1 < 0 && hit1 && tmin1 < tfar1;
+                        }
                         if (FULL_DIAG && !refDiag) boundsHits += ((c0 < 0 ? leaf0 : hit0) ? 1.0f : 0.0f) + ((c1 < 0 ? leaf1 : hit1) ? 1.0f : 0.0f);
                         listLeaves(c0, c1, leaf0, leaf1);
                         const bool in0 = hit0 && c0 >= 0;
@@ -1666,14 +1708,14 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
                         const bool both = in0 && in1;
                         const bool swap = tmin1 < tmin0;                         // near child first
                         lds_code_store(sp + kStackAt, swap ? c0 : c1);
-                        // flat single-level selects (see the walk's comment); `sp` is a cursor here: a push adds a row, a pop takes one off, sp >= rowAt(1) = not empty
+                        // flat single-level selects (see the walk's comment); `sp` is a cursor here: a push adds a row, a pop takes one off; an empty stack pops
+                        // the sentinel -1 by itself (popSlot)
                         const int nearChild = swap ? c1 : c0;
                         const int onlyChild = in0 ? c0 : c1;
                         const int next = both ? nearChild : onlyChild;
-                        const int fromStack = sp >= rowAt(1) ? popped : -1;
                         const bool any = in0 | in1;
                         const int pushed = sp + (both ? kRowBytes : 0);
-                        cur = any ? next : fromStack;
+                        cur = any ? next : popped;
                         sp = any ? pushed : sp - kRowBytes;
                     };
                     if (signOrderedWave()) {
@@ -1696,7 +1738,7 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
                             const f2 tnx = axis_distances(f2{px.x, px.y}, oix), tfx = axis_distances(f2{px.z, px.w}, oix);
                             const f2 tny = axis_distances(f2{py.x, py.y}, oiy), tfy = axis_distances(f2{py.z, py.w}, oiy);
                             const f2 tnz = axis_distances(f2{pz.x, pz.y}, oiz), tfz = axis_distances(f2{pz.z, pz.w}, oiz);
-                            finishVisit(vmax3(tnx.x, tny.x, vmax(tnz.x, 0.0f)), vmin3(tfx.x, tfy.x, tfz.x), vmax3(tnx.y, tny.y, vmax(tnz.y, 0.0f)), vmin3(tfx.y, tfy.y, tfz.y), c0, c1, popped);
+                            finishVisit(std::true_type{}, vmax3(tnx.x, tny.x, vmax(tnz.x, 0.0f)), vmin3(tfx.x, tfy.x, tfz.x), vmax3(tnx.y, tny.y, vmax(tnz.y, 0.0f)), vmin3(tfx.y, tfy.y, tfz.y), c0, c1, popped);
                         }
                     } else {
                         while (budget > 0 && cur >= 0 && nc < candLimit) {
@@ -1715,7 +1757,7 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
                             const float tfar0 = vmin3(vmax(tlx.x, thx.x), vmax(tly.x, thy.x), vmax(tlz.x, thz.x));
                             const float tmin1 = vmax3(vmin(tlx.y, thx.y), vmin(tly.y, thy.y), vmax(vmin(tlz.y, thz.y), 0.0f));
                             const float tfar1 = vmin3(vmax(tlx.y, thx.y), vmax(tly.y, thy.y), vmax(tlz.y, thz.y));
-                            finishVisit(tmin0, tfar0, tmin1, tfar1, c0, c1, popped);
+                            finishVisit(std::false_type{}, tmin0, tfar0, tmin1, tfar1, c0, c1, popped);
                         }
                     }
                 } else {
@@ -1794,8 +1836,8 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
                         int k = -2 - cur;
                         cur = -1;
                         for (; k < 8; k++) {
-                            if (SIGNED_WALK ? nc >= rowAt(kCandCapacity - 1) : nc > kCandCapacity - 2) { cur = -2 - k; break; }                    // no room for two more: test what is here, then come back
-                            const unsigned word = k < 6 ? pcand.z : pcand.w;
+                            if (SIGNED_WALK ? nc >= rowAt(kCandCapacity - 2) : nc > kCandCapacity - 2) { cur = -2 - k; break; }                    // no room for two more (SIGNED_WALK: under the sentinel row): test what is here, then come back
+                            const unsigned word = SIGNED_WALK && k < 4 ? pcand.y : k < 6 ? pcand.z : pcand.w;      // (SIGNED_WALK: k = 3, the fourth node, can have been left to this stage)
                             const unsigned node = (word >> (16 * (k & 1))) & 0xffffu;
                             if (node == 0xffffu) break;
                             float tmin0, tfar0, tmin1, tfar1;
@@ -2341,7 +2383,12 @@ hipError_t launchVariant(const SampleKernelArgs& args, int numBlocks, hipStream_
     // travSlice, so THEIR launches always get a slice of this launcher's making (travSliceForImage): the bit is set exactly when the LDS below is sized for the image and is
     // clear otherwise, whatever the arguments came in with; the other variants read travSlice as a plain count and get the arguments as they are
     constexpr bool SIGNED_WALK = signed_walk_variant<ALL_LDS, KIND, HW, DIAG, NOISE, PER_SAMPLE, GEO>();
-    const bool imageGranted = SIGNED_WALK && args.ldsNodeImageBytes != 0u && args.ldsNodeImageBytes == args.layout.nodeCount * (kNodeImageBytes - (uint32_t)sizeof(GpuNode));
+    // These variants also read their traversal stack back as SIGNED 16-bit codes (the empty-stack sentinel, see kPopSentinelRow): every node index must be below 32 768.
+    // A scene that is whole in LDS has a few thousand nodes at most; the grant says so, and a launch that is not such a scene is refused, not walked wrongly.
+    constexpr uint32_t kSignedCodeNodes = 32768u;
+    if (SIGNED_WALK && args.layout.nodeCount > kSignedCodeNodes) return hipErrorInvalidValue;
+    const bool imageGranted = SIGNED_WALK && args.ldsNodeImageBytes != 0u && args.layout.nodeCount <= kSignedCodeNodes &&
+                              args.ldsNodeImageBytes == args.layout.nodeCount * (kNodeImageBytes - (uint32_t)sizeof(GpuNode));
     SampleKernelArgs ownSlice;
     const SampleKernelArgs* launchArgs = &args;
     if (SIGNED_WALK) {
