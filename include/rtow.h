@@ -1426,6 +1426,70 @@ RTOW_API int rtowSamplePixelsDevice(RtowContext context, int32_t count, const Rt
                                     const RtowAccumBuffers* in, const RtowAccumBuffers* out,
                                     void* const* diagnostics /* [count] or NULL */, void* stream, const volatile uint8_t* cancel);
 
+/* ---- one sample of a pixel, segment by segment ----
+ * replaces: the PATH_DEBUGGING block of SampleBatchJob (JOBS/SampleBatchJob.cs:53-55 DebugCoordinates / DebugPaths, :96-101 the clear, :140-142 sample 0 only,
+ * :304-307 a surface segment {From = ray.Origin, To = rec.Point}, :344-347 the sky segment {From, To = ray.Direction * 99999}; drawn by UNITY/Raytracer.Editor.cs:129-139).
+ * The reference records sample 0 of one pixel; this call records one sample of every pixel of a device list, with what the path met at every depth.
+ * Take list entry i (positions 0 .. min(words[0], capacity) - 1, read as rtowSamplePixelsDevice reads a list - here in place, no copy) and call its pixel p.  The call
+ * replays what rtowSampleBatchDevice(batch, in, ...) does at p under RTOW_RNG_REFERENCE: the pixel's generator (:91), the sample count N from inColor[p].w and
+ * inSampleCountWeight[p] (:118-126, the extrema from the parameter block), then samples 0 .. N - 1 in order on that one random stream, every draw in the sample
+ * kernel's order.  ONE sample k* is reported:
+ *   RTOW_PATH_SELECT_INDEX      k* = params->sampleIndex (0: the reference's).  k* >= N: flags bit 1, segmentCount 0, sampleCount N, zero segments.
+ *   RTOW_PATH_SELECT_BRIGHTEST  the sample of 0 .. N - 1 that ranks first: a sample whose colour has a NaN channel above all others; then the larger
+ *                               lum(c) = (0.2126f * c.r + 0.7152f * c.g) + 0.0722f * c.b (a failed sample: +0); among equals the lowest k.  N == 0: flags bit 1.
+ *                               (A first pass over all N samples, then the winner once more: N + 1 samples per pixel.)
+ * Summary: color / normal / albedo = sampleColor / sampleNormal / sampleAlbedo as Sample leaves them (a failed sample: colour 0 and its fallback AOVs); randomEvents =
+ * randomEventsLocalAcc; time = the camera ray's Ray.Time as drawn (rtowTraceRaysDevice takes (from, time, direction) of a segment as it stands); luminance =
+ * lum(color); segmentCount = the rays traced = the sample's RayCount contribution (traceDepth for a failed sample).
+ * Segments: segment d of slot i, at segments[i * traceDepth + d], is depth d for d < segmentCount; the others of a reported slot are 96 zero bytes
+ * (DebugPaths[i] = default).  Slots at or beyond min(words[0], capacity) are not written, and nothing else is written anywhere.  The nearest hit of a segment is one
+ * ray of rtowTraceRaysDevice, bit for bit (ties at the bit-identical nearest distance as that call settles them).  The colour is the fold tail -> head, c = c * a + e
+ * per channel in two roundings, started from the sky colour as the sample kernel starts it.
+ * segments == NULL: only summaries.  The lanes' emission / attenuation stacks then live in a block the CONTEXT owns (capacity * traceDepth * 24 bytes, grow-only):
+ * this one form may allocate on its first use and whenever it needs more, and is then not capturable; with `segments` the call allocates nothing, waits for nothing
+ * and is one launch on `stream` (NULL = the context's own stream), so a graph can capture it.  summaries / segments may start at any 4-byte aligned address.
+ * An entry >= W * H is never used as an address: its slot reports flags bit 2, `pixel` = the entry, everything else 0.
+ * Not a sample batch: rtowGetLastSampleKernelMs, the batch status, the cost map, threshold tuning and hit-list growth are left alone.  Ordered against
+ * rtowUploadScene like the trace calls.
+ * RTOW_ERROR_UNSUPPORTED (nothing enqueued, no output touched): a scene with a ProbabilisticVolume material (its branch needs every hit of a ray);
+ * batch->rngPolicy != RTOW_RNG_REFERENCE.
+ * RTOW_ERROR_INVALID_VALUE: everything rtowSampleBatchDevice refuses in `batch` (a trace depth beyond 64: RTOW_ERROR_CAPACITY); slice fields other than 0 / 1;
+ * W * H > 2^27; a NULL context, batch, params, list, list->words, inColor, inSampleCountWeight or summaries; an unknown select; sampleIndex < 0, or != 0 under
+ * BRIGHTEST; non-zero flags or reserved; summaries or segments overlapping each other, the list or either input, or reaching beyond the address range (sizes are
+ * taken in 64 bits: capacity * traceDepth * 96).  RTOW_ERROR_NO_SCENE before rtowUploadScene.  capacity == 0 succeeds and launches nothing.
+ * Measured (profiles/r18_record_paths.json; MI355X, cover scene, 1920 x 1080, every pixel listed, traceDepth 8, jitter on, HIP events on the caller's stream):
+ * INDEX with one sample 1.21 ms with segments (1.6 GB of slots, most of them zeroed) and 0.81 ms without; BRIGHTEST over 16 samples 12.3 ms; in the same run
+ * rtowSampleBatchDevice 0.63 ms at 1 spp and 3.66 ms at 16 spp, rtowTraceGuideViewDevice(maxBounces 8) 0.11 ms.  Nine kernels (three scene bases x three noise
+ * sources): 114 - 164 VGPRs, 3 - 4 waves per SIMD, no scratch, no spilled register; 26 KB of LDS per 256-lane workgroup (the walk's stack).
+ * Added after API version 12 without changing it: a host detects the call by its entry point. */
+typedef enum RtowPathSelect { RTOW_PATH_SELECT_INDEX = 0, RTOW_PATH_SELECT_BRIGHTEST = 1 } RtowPathSelect;
+typedef enum RtowPathEvent  { RTOW_PATH_SKY = 0, RTOW_PATH_LAMBERT = 1, RTOW_PATH_METAL = 2, RTOW_PATH_GLOSSY = 3,
+                              RTOW_PATH_REFRACT = 4, RTOW_PATH_REFLECT = 5 } RtowPathEvent;
+typedef struct RtowPathSegment {          /* 96 bytes */
+    RtowFloat3 from;        float    distance;     /* ray.Origin; rec.Distance, +INFINITY for the sky segment              */
+    RtowFloat3 direction;   int32_t  entityIndex;  /* ray.Direction as traced; index into RtowSceneDesc.entities, -1 sky   */
+    RtowFloat3 to;          uint32_t info;         /* rec.Point; sky: direction * 99999.0f per component (:346)            */
+    RtowFloat3 normal;      float    randomEvents; /* rec.Normal ((0,0,0) sky); rng.RandomEvents of this depth BEFORE /2^depth */
+    RtowFloat3 attenuation; float    pad0;         /* what :330 / :362 push; +0 pads                                        */
+    RtowFloat3 emission;    float    pad1;         /* what :311 / :361 push (sky colour on the sky segment)                 */
+} RtowPathSegment;
+/* info: bits 0..15 material index (0xFFFF sky), bits 16..18 RtowPathEvent, bit 19 Material.IsPerfectSpecular.  Events: GLOSSY = the untinted glossy branch
+ * (RT/Material.cs:91-96), METAL = the rough-metal branch, LAMBERT = the diffuse branch, REFRACT / REFLECT = the dielectric's (total internal reflection: REFLECT) */
+typedef struct RtowPathSummary {           /* 68 bytes */
+    int32_t pixel, sampleIndex, sampleCount, segmentCount;
+    uint32_t flags; float time, luminance, randomEvents;
+    RtowFloat3 color, normal, albedo;
+} RtowPathSummary;
+/* flags: bit 0 the sample succeeded (Sample returned true), bit 1 no such sample, bit 2 the list entry was >= W*H */
+typedef struct RtowRecordPathsParams { int32_t select; int32_t sampleIndex; int32_t flags /* 0 */; int32_t reserved /* 0 */; } RtowRecordPathsParams;
+
+RTOW_API int rtowRecordPathsDevice(RtowContext context, const RtowSampleParams* batch, const RtowRecordPathsParams* params,
+                                   const RtowPixelList* list,
+                                   const float* inColor /* device float4[W*H] */, const float* inSampleCountWeight /* device float[W*H] */,
+                                   RtowPathSummary* summaries /* device, list->capacity */,
+                                   RtowPathSegment* segments  /* device, list->capacity * batch->traceDepth, or NULL */,
+                                   void* stream);
+
 /* dst += src for the four accumulation buffers (device pointers, `pixelCount` elements each).  The reference accumulates
  * successive batches by feeding a batch's outputs to the next one as inputs (UNITY/Raytracer.cs:798-802); when batches run
  * CONCURRENTLY on several GPUs (each from zeroed accumulators, its own Seed) their partial sums are folded with this, in

@@ -272,6 +272,45 @@ def pixel_list_scratch_bytes(width, height):
     return ((int(width) + 7) // 8) * ((int(height) + 7) // 8) * 4
 
 
+# rtowRecordPathsDevice (include/rtow.h): one sample of every listed pixel, segment by segment
+PATH_SELECT_INDEX, PATH_SELECT_BRIGHTEST = 0, 1                                                      # RtowPathSelect
+PATH_SKY, PATH_LAMBERT, PATH_METAL, PATH_GLOSSY, PATH_REFRACT, PATH_REFLECT = 0, 1, 2, 3, 4, 5      # RtowPathEvent
+PATH_EVENTS = (PATH_SKY, PATH_LAMBERT, PATH_METAL, PATH_GLOSSY, PATH_REFRACT, PATH_REFLECT)
+# RtowPathSegment.info
+PATH_INFO_MATERIAL_MASK = 0xFFFF          # 0xFFFF: the sky segment
+PATH_INFO_EVENT_SHIFT, PATH_INFO_EVENT_MASK = 16, 7
+PATH_INFO_PERFECT_SPECULAR = 1 << 19
+# RtowPathSummary.flags
+PATH_FLAG_SUCCEEDED, PATH_FLAG_NO_SUCH_SAMPLE, PATH_FLAG_NOT_A_PIXEL = 1, 2, 4
+PATH_SKY_REACH = 99999.0                  # a sky segment's `to` is direction * this (JOBS/SampleBatchJob.cs:346)
+
+
+class PathSegment(C.Structure):
+    """RtowPathSegment (96 bytes): depth d of the recorded sample."""
+    _fields_ = [("origin", Float3), ("distance", C.c_float), ("direction", Float3), ("entityIndex", C.c_int32), ("to", Float3), ("info", C.c_uint32),
+                ("normal", Float3), ("randomEvents", C.c_float), ("attenuation", Float3), ("pad0", C.c_float), ("emission", Float3), ("pad1", C.c_float)]
+
+
+# (the C member `from` is a Python keyword: the mirrors call it "origin", the numpy types keep the C name)
+PATH_SEGMENT_DTYPE = [("from", "<f4", (3,)), ("distance", "<f4"), ("direction", "<f4", (3,)), ("entityIndex", "<i4"), ("to", "<f4", (3,)), ("info", "<u4"),
+                      ("normal", "<f4", (3,)), ("randomEvents", "<f4"), ("attenuation", "<f4", (3,)), ("pad0", "<f4"), ("emission", "<f4", (3,)), ("pad1", "<f4")]
+
+
+class PathSummary(C.Structure):
+    """RtowPathSummary (68 bytes): the recorded sample of one list entry."""
+    _fields_ = [("pixel", C.c_int32), ("sampleIndex", C.c_int32), ("sampleCount", C.c_int32), ("segmentCount", C.c_int32), ("flags", C.c_uint32),
+                ("time", C.c_float), ("luminance", C.c_float), ("randomEvents", C.c_float), ("color", Float3), ("normal", Float3), ("albedo", Float3)]
+
+
+PATH_SUMMARY_DTYPE = [("pixel", "<i4"), ("sampleIndex", "<i4"), ("sampleCount", "<i4"), ("segmentCount", "<i4"), ("flags", "<u4"), ("time", "<f4"),
+                      ("luminance", "<f4"), ("randomEvents", "<f4"), ("color", "<f4", (3,)), ("normal", "<f4", (3,)), ("albedo", "<f4", (3,))]
+
+
+class RecordPathsParams(C.Structure):
+    """RtowRecordPathsParams (16 bytes): select (PATH_SELECT_*), sampleIndex (0 under BRIGHTEST); flags and reserved are 0."""
+    _fields_ = [("select", C.c_int32), ("sampleIndex", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
 class SurfaceBuffers(C.Structure):
     """RtowSurfaceBuffers (48 bytes): device pointers, any may be NULL (not written), not all six."""
     _fields_ = [("albedo", C.c_void_p), ("emission", C.c_void_p), ("texCoord", C.c_void_p), ("metallicGlossiness", C.c_void_p),
@@ -494,5 +533,5 @@ EXPORTED_SYMBOLS = [
     "rtowBuildPixelListDevice", "rtowSamplePixelsDevice", "rtowTraceGuideRaysDevice", "rtowTraceGuideViewDevice",
     "rtowAccumulateMomentsDevice", "rtowDenoiseVarianceDevice", "rtowReprojectMomentsDevice", "rtowEstimateMomentsDevice",
     "rtowNoiseMaskDevice", "rtowRectifyHistoryDevice", "rtowReprojectAccumBilinearDevice",
-    "rtowMeterExposureDevice", "rtowFinalizeToneMappedDevice",
+    "rtowMeterExposureDevice", "rtowFinalizeToneMappedDevice", "rtowRecordPathsDevice",
 ]

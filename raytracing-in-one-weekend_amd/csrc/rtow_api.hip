@@ -1636,6 +1636,30 @@ RTOW_API int rtowTraceGuideViewDevice(RtowContext ctx, const RtowGuideParams* pa
     return RTOW_SUCCESS;
 }
 
+RTOW_API int rtowRecordPathsDevice(RtowContext ctx, const RtowSampleParams* batch, const RtowRecordPathsParams* params, const RtowPixelList* list, const float* inColor,
+                                   const float* inSampleCountWeight, RtowPathSummary* summaries, RtowPathSegment* segments, void* stream)
+{
+    if (!ctx) return RTOW_ERROR_INVALID_VALUE;
+    RTOW_TRY(validateRecordPaths(batch, params, list, inColor, inSampleCountWeight, summaries, segments));
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
+    const uint32_t kind = ctx->scene.layout.sceneKind;
+    if (kind == SCENE_KIND_VOLUMES || kind == SCENE_KIND_VOLUMES_TEXTURED) return RTOW_ERROR_UNSUPPORTED;      // the volume branch needs every hit of a ray
+    // the batch planner's arguments for these params - scene, textures, cubemap, the noise set (RTOW_ERROR_INVALID_VALUE: not uploaded) - and nothing of a batch's state:
+    // no event, no counter, no cost map, no threshold probe, no hit-list spill
+    SampleKernelArgs a{};
+    const RtowAccumBuffers in{const_cast<float*>(inColor), nullptr, nullptr, const_cast<float*>(inSampleCountWeight)}, out{};
+    RTOW_TRY(buildArgs(ctx, batch, &in, &out, nullptr, false, nullptr, nullptr, a));
+    if (list->capacity == 0u) return RTOW_SUCCESS;
+    hipStream_t s;
+    RTOW_TRY(useDevice(ctx, stream, &s));
+    // without `segments` the lanes' stacks live in the context's block: grow-only, allocated here on first use (freeing the smaller block waits for a launch that uses it)
+    if (!segments) RTOW_TRY(growDevice(ctx, {{&ctx->dPathStack, (size_t)list->capacity * (size_t)batch->traceDepth * 24u}}));
+    HIP_TRY(ctx, launchRecordPaths(a, entityMapDevice(ctx), *params, list->words, list->capacity, summaries, segments, segments ? nullptr : ctx->dPathStack.get(), s),
+            RTOW_ERROR_LAUNCH_FAILURE);
+    return RTOW_SUCCESS;
+}
+
 RTOW_API int rtowGetLastSampleKernelMs(RtowContext ctx, float* outMs)
 {
     if (!ctx || !outMs) return RTOW_ERROR_INVALID_VALUE;

@@ -115,6 +115,8 @@ struct RtowContext_t {
     DeviceMem<unsigned> dPixelList;       // (a capacity of 0 is a valid list: the four header words - so the block's bytes tell a list that is there from none)
     DeviceMem<unsigned> dPixelListScratch;
     DeviceMem<uint4> dListSpill;
+    // rtowRecordPathsDevice without `segments`: the lanes' emission / attenuation stacks (capacity x traceDepth x 24 bytes), allocated on first use
+    DeviceMem<float> dPathStack;
 
     // RtowContextOptions: behaviour switches and development knobs (nothing is read from the environment)
     bool wideCodes = false;               // current scene: more than 65 535 entities or tree nodes (32-bit candidate / stack codes, tree read from HBM)

@@ -500,6 +500,12 @@ struct GuideScene {
 hipError_t launchTraceGuideRays(const GuideScene& scene, int32_t maxBounces, int64_t count, const RtowRay* rays, const RtowGuideBuffers& out, hipStream_t stream);
 hipError_t launchTraceGuideView(const GuideScene& scene, int32_t maxBounces, const RtowTraceViewParams& p, const RtowGuideBuffers& out, hipStream_t stream);
 
+// rtowRecordPathsDevice (rtow_record_paths.hip): one launch on `stream`, one lane per entry of the caller's list, read in place (arguments validated by the caller).
+// batch: what buildArgs fills for a batch of the call's params (scene, textures, cubemap, noise textures, view, counts; of the accumulators inColor and inScw alone are
+// read); entityOfPrim as for launchTraceRays; segments may be null - stackRows then holds capacity x traceDepth x 24 bytes of device memory for the lanes' stacks
+hipError_t launchRecordPaths(const SampleKernelArgs& batch, const int32_t* entityOfPrim, const RtowRecordPathsParams& params, const uint32_t* words, uint32_t capacity,
+                             RtowPathSummary* summaries, RtowPathSegment* segments, float* stackRows, hipStream_t stream);
+
 // same-XCD hand-over litmus of the chained launches (rtow_kernels.hip): pairs of workgroups that ran on one XCD, stale dwords seen, waits that timed out
 hipError_t runXcdCoherenceLitmus(int cuCount, hipStream_t stream, unsigned* outPairs, unsigned* outStale, unsigned* outTimeouts);
 

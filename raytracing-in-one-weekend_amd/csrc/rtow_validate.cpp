@@ -66,6 +66,30 @@ int validateShadeHits(const RtowShadeHitsParams* params, int32_t count, const Rt
     return RTOW_SUCCESS;
 }
 
+int validateRecordPaths(const RtowSampleParams* batch, const RtowRecordPathsParams* params, const RtowPixelList* list, const float* inColor,
+                        const float* inSampleCountWeight, const RtowPathSummary* summaries, const RtowPathSegment* segments)
+{
+    if (!batch || !params || !list || !list->words || !inColor || !inSampleCountWeight || !summaries) return kBad;
+    const int v = validateParams(batch);
+    if (v != RTOW_SUCCESS) return v;
+    if (batch->sliceOffset != 0 || batch->sliceDivider != 1) return kBad;                                     // the list alone says which pixels
+    const uint64_t n = (uint64_t)(int)batch->size.x * (uint64_t)(int)batch->size.y;
+    if (n > (uint64_t)RTOW_PIXEL_LIST_MAX_PIXELS) return kBad;
+    if (params->select != RTOW_PATH_SELECT_INDEX && params->select != RTOW_PATH_SELECT_BRIGHTEST) return kBad;
+    if (params->sampleIndex < 0 || (params->select == RTOW_PATH_SELECT_BRIGHTEST && params->sampleIndex != 0)) return kBad;
+    if (params->flags != 0 || params->reserved != 0) return kBad;
+    if (batch->rngPolicy != RTOW_RNG_REFERENCE) return RTOW_ERROR_UNSUPPORTED;
+    // capacity <= 2^32 - 1 and traceDepth <= 64: the products fit 64 bits; what does not fit behind its base address is refused, not wrapped
+    const uint64_t capacity = list->capacity;
+    const uint64_t summaryBytes = capacity * sizeof(RtowPathSummary), segmentBytes = capacity * (uint64_t)batch->traceDepth * sizeof(RtowPathSegment);
+    if (summaryBytes > UINTPTR_MAX - (uintptr_t)summaries) return kBad;
+    if (segments && segmentBytes > UINTPTR_MAX - (uintptr_t)segments) return kBad;
+    // every lane writes its own slots while others read the list and the accumulators
+    const Range written[] = {{summaries, (size_t)summaryBytes}, {segments, (size_t)segmentBytes}};                 // segments may be null
+    const Range read[] = {{list->words, RTOW_PIXEL_LIST_BYTES(list->capacity)}, {inColor, (size_t)n * 16}, {inSampleCountWeight, (size_t)n * 4}};
+    return aliasingOk(written, countOf(written), read, countOf(read)) ? RTOW_SUCCESS : kBad;
+}
+
 int validateReduceMetrics(int32_t pixelCount, const void* diagnostics, int32_t diagnosticsStride, const float* color, const float* sampleCountWeight,
                           const RtowMetrics* outMetrics)
 {

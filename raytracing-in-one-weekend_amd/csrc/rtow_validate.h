@@ -54,6 +54,9 @@ int validateParams(const RtowSampleParams* p);
 bool viewSizeValid(const RtowTraceViewParams& v);
 bool guideArgumentsValid(const RtowGuideParams* params, const RtowGuideBuffers* out);
 int validateShadeHits(const RtowShadeHitsParams* params, int32_t count, const RtowRay* rays, const int32_t* entityIndex, const RtowSurfaceBuffers* surface);
+// rtowRecordPathsDevice (RTOW_ERROR_UNSUPPORTED: a policy other than the reference stream; the sizes of the outputs are taken in 64 bits)
+int validateRecordPaths(const RtowSampleParams* batch, const RtowRecordPathsParams* params, const RtowPixelList* list, const float* inColor,
+                        const float* inSampleCountWeight, const RtowPathSummary* summaries, const RtowPathSegment* segments);
 // the post passes
 int validateReduceMetrics(int32_t pixelCount, const void* diagnostics, int32_t diagnosticsStride, const float* color, const float* sampleCountWeight,
                           const RtowMetrics* outMetrics);      // both forms: pointers, count and stride

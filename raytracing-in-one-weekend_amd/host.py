@@ -350,6 +350,62 @@ class Context:
         return self._trace_guide(int(width) * int(height),
                                  lambda out: check(load().rtowTraceGuideViewDevice(self.handle, C.byref(p), C.byref(v), C.byref(out), stream), "rtowTraceGuideViewDevice"), want)
 
+    def record_paths(self, params, pixels_or_list, in_color=None, in_scw=None, select=abi.PATH_SELECT_INDEX, sample_index=0, want_segments=True, stream=None):
+        """rtowRecordPathsDevice: one sample of every listed pixel, replayed as rtowSampleBatchDevice(params, ...) runs it there, with its segments.
+        pixels_or_list: frame pixel indices (row * W + col), or (pixel_list, capacity) with a DeviceBuffer / device address of 4 + capacity uint32 words.
+        in_color (W*H, 4) / in_scw (W*H,): the accumulators the batch reads - float32 arrays or DeviceBuffers; None: zeros.
+        select: abi.PATH_SELECT_INDEX (sample `sample_index`) or abi.PATH_SELECT_BRIGHTEST.
+        Returns (summaries, segments): numpy arrays of abi.PATH_SUMMARY_DTYPE, shape (n,), and of abi.PATH_SEGMENT_DTYPE, shape (n, traceDepth) - None without
+        want_segments - for the n = min(words[0], capacity) entries of the list."""
+        n_pixels = int(params.size.x) * int(params.size.y)
+        depth = int(params.traceDepth)
+        own = []
+        try:
+            if isinstance(pixels_or_list, tuple):
+                words, capacity = pixels_or_list
+                words = words.ptr if isinstance(words, DeviceBuffer) else words
+                capacity = int(capacity)
+                head = np.empty(1, np.uint32)
+                check(load().rtowDeviceCopy(self.handle, words, head.ctypes.data, 4, abi.MEMCPY_DEVICE_TO_HOST), "rtowDeviceCopy")
+                count = min(int(head[0]), capacity)
+            else:
+                pixels = np.ascontiguousarray(pixels_or_list, dtype=np.uint32).reshape(-1)
+                count = capacity = int(pixels.size)
+                own.append(DeviceBuffer(self, abi.pixel_list_bytes(capacity)).upload(np.concatenate([np.array([count, 0, 0, 0], np.uint32), pixels])))
+                words = own[-1].ptr
+
+            def device(a, width):
+                if isinstance(a, DeviceBuffer):
+                    return a.ptr
+                own.append(DeviceBuffer(self, n_pixels * width * 4))
+                if a is None:
+                    own[-1].zero()
+                else:
+                    own[-1].upload(np.ascontiguousarray(a, dtype=np.float32).reshape(n_pixels, width))
+                return own[-1].ptr
+
+            color, scw = device(in_color, 4), device(in_scw, 1)
+            s_type, g_type = np.dtype(abi.PATH_SUMMARY_DTYPE), np.dtype(abi.PATH_SEGMENT_DTYPE)
+            summaries = DeviceBuffer(self, max(1, capacity) * s_type.itemsize).zero()
+            own.append(summaries)
+            segments = None
+            if want_segments:
+                segments = DeviceBuffer(self, max(1, capacity * depth) * g_type.itemsize).zero()
+                own.append(segments)
+            p = abi.RecordPathsParams(int(select), int(sample_index), 0, 0)
+            lst = abi.PixelList(words, capacity)
+            check(load().rtowRecordPathsDevice(self.handle, C.byref(params), C.byref(p), C.byref(lst), color, scw, summaries.handle,
+                                               segments.handle if segments else None, stream), "rtowRecordPathsDevice")
+            self.synchronize()
+            out_s = summaries.download(s_type, (capacity,))[:count] if capacity else np.zeros(0, s_type)
+            out_g = None
+            if want_segments:
+                out_g = segments.download(g_type, (capacity, depth))[:count] if capacity else np.zeros((0, depth), g_type)
+            return out_s, out_g
+        finally:
+            for b in own:
+                b.free()
+
     def synchronize(self):
         check(load().rtowSynchronize(self.handle), "rtowSynchronize")
 

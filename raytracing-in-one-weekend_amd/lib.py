@@ -84,6 +84,7 @@ def load():
     lib.rtowUpsampleDevice.argtypes = [vp, C.POINTER(abi.UpsampleParams), vp, C.POINTER(abi.HitBuffers), vp, C.POINTER(abi.HitBuffers), vp, vp, vp, vp]
     lib.rtowBuildPixelListDevice.argtypes = [vp, C.POINTER(abi.PixelListParams), vp, vp, vp, C.POINTER(abi.PixelList), vp]
     lib.rtowSamplePixelsDevice.argtypes = [vp, C.c_int32, C.POINTER(abi.SampleParams), C.POINTER(abi.PixelList), AB, AB, C.POINTER(vp), vp, vp]
+    lib.rtowRecordPathsDevice.argtypes = [vp, C.POINTER(abi.SampleParams), C.POINTER(abi.RecordPathsParams), C.POINTER(abi.PixelList), vp, vp, vp, vp, vp]
     lib.rtowTraceGuideRaysDevice.argtypes = [vp, C.POINTER(abi.GuideParams), C.c_int32, vp, C.POINTER(abi.GuideBuffers), vp]
     lib.rtowTraceGuideViewDevice.argtypes = [vp, C.POINTER(abi.GuideParams), C.POINTER(abi.TraceViewParams), C.POINTER(abi.GuideBuffers), vp]
     lib.rtowShadeHitsDevice.argtypes = [vp, C.POINTER(abi.ShadeHitsParams), C.c_int32, vp, vp, C.POINTER(abi.SurfaceBuffers), vp]
