@@ -1,7 +1,7 @@
 // rtow_albedo.hip.h - Albedo.SampleColor(rec.TexCoords) of a named primitive for a given ray: the one evaluation behind rtowShadeHitsDevice's albedo (rtow_shade.hip) and the
 // tint of a surface that rtowTraceGuide*Device follows (rtow_guides.hip).  The material's folded constant, or - for a material with an Image texture - the texel at the
 // triangle's UV, found by the triangle's own test once more (tMin 0) as the HIT stage of the textured sample kernels does for the winner.
-// Also the checked forms of texture_color / texture_scalar the shade pass evaluates the other three textures with.
+// Also the checked forms of texture_color / texture_scalar the shade pass evaluates the other three textures with, and prim_material (rtow_guides.hip, rtow_record_paths.hip).
 #pragma once
 #include "rtow_hit_tests.hip.h"
 #include "rtow_surface.hip.h"
@@ -27,6 +27,18 @@ __device__ __forceinline__ float scalar_checked(const TexRefs& tex, const GpuTex
 
 // GpuImage records in a texture blob (0: no blob)
 inline uint32_t image_count(const TexLayout& T) { return T.totalBytes ? (T.pixelOffset - T.imageOffset) / (uint32_t)sizeof(GpuImage) : 0u; }
+
+// The material of a primitive the walk found, as the HIT stage finds it: the primitive's matIndex word (rtow_scene.h), the material's number and the address of its
+// 64-byte record.  (rtow_shade.hip, whose primitive is the caller's, checks the number before it forms the address; with this helper its kernels compile to other code.)
+struct PrimMaterial { unsigned word, index; const uint8_t* record; };
+__device__ __forceinline__ PrimMaterial prim_material(const SceneRefs& sc, const SceneLayout& L, int prim)
+{
+    PrimMaterial m;
+    m.word = *reinterpret_cast<const unsigned*>(section<false>(sc, L.matIndexOffset) + (uint32_t)prim * 4u);
+    m.index = m.word & 0xffffu;
+    m.record = section<false>(sc, L.materialOffset) + m.index * 64u;
+    return m;
+}
 
 // HitRecord.TexCoords of primitive `prim` (mi: its matIndex word) for the ray: the named triangle's own test once more (tMin 0), as HIT does for the winner; every other
 // entity type, and a ray that does not meet the triangle, leaves (0, 0)

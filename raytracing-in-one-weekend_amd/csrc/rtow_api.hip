@@ -2,9 +2,10 @@
 //
 // Host-side runtime of the path: context / device selection, scene compilation + upload, grow-only device staging
 // for the host-buffer entry point, kernel launch on a HIP stream with HIP-event timing, cooperative cancellation,
-// and the ray queries.  There is no CPU implementation behind any entry point: without a usable HIP device
+// and rtowRecordPathsDevice, the one query the batch planner feeds.  There is no CPU implementation behind any entry point: without a usable HIP device
 // rtowCreateContext fails with RTOW_ERROR_NO_DEVICE and nothing else can be called.  The multi-GPU entry points (rtowComm*, rtowGatherRowsDevice,
-// rtowHybridPlan, rtowExchangeAccumDevice) are in rtow_comm.hip, the post passes in rtow_api_post.hip; the context itself is rtow_context.h, and what
+// rtowHybridPlan, rtowExchangeAccumDevice) are in rtow_comm.hip, the post passes in rtow_api_post.hip, the probes, the trace, shade and guide calls in
+// rtow_api_query.hip; the context itself - and queryScene, the resident scene as a query launch gets it - is rtow_context.h, and what
 // an entry point refuses before it takes its lock is rtow_validate.h.
 #include <hip/hip_runtime.h>
 
@@ -889,21 +890,6 @@ int enqueueBatches(RtowContext ctx, int count, const RtowSampleParams* params, c
     return rc;
 }
 
-// primitive -> the host's entity index (all-triangle scenes number their primitives in leaf order), on the device and on the host; null: the same number
-const int32_t* entityMapDevice(RtowContext ctx) { return ctx->scene.entityOfPrim.empty() ? nullptr : ctx->dEntityOfPrim; }
-const int32_t* entityMapHost(RtowContext ctx) { return ctx->scene.entityOfPrim.empty() ? nullptr : ctx->scene.entityOfPrim.data(); }
-
-GuideScene guideScene(RtowContext ctx)
-{
-    GuideScene sc{};
-    sc.blob = ctx->dScene;
-    sc.layout = ctx->scene.layout;
-    sc.entityOfPrim = entityMapDevice(ctx);
-    sc.texBlob = ctx->scene.texLayout.totalBytes ? ctx->dTexBlob : nullptr;
-    sc.texLayout = ctx->scene.texLayout;
-    return sc;
-}
-
 // The sample entry points' common start, in this order (the same bad input gets the same code): every batch's params - validateParams, where a trace depth beyond 64
 // is RTOW_ERROR_CAPACITY - each followed by the call's own per-batch check; the four input buffers and, unless `out` is null (groups check theirs per batch), the four
 // output buffers; then the lock, the scene, the device (calls come from a different worker thread each time), the stream (null: the context's) and a clear cancel word.
@@ -1504,138 +1490,6 @@ RTOW_API int rtowUnregisterHostBuffer(RtowContext ctx, void* pointer)
     return RTOW_ERROR_INVALID_VALUE;
 }
 
-RTOW_API int rtowProbeNearestHit(RtowContext ctx, const RtowFloat3* origin, const RtowFloat3* direction, float time, float* distance, int32_t* entityIndex)
-{
-    if (!ctx || !origin || !direction) return RTOW_ERROR_INVALID_VALUE;
-    // the host image of the scene has a lock of its own (held here and while rtowUploadScene swaps the image in): the blocking entry points hold ctx->mu for a whole
-    // batch, and a probe from another thread must not wait for them
-    std::lock_guard<std::mutex> lock(ctx->sceneMu);
-    if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
-    const float o[3] = {origin->x, origin->y, origin->z}, d[3] = {direction->x, direction->y, direction->z};
-    float t = 0.0f;
-    int prim = -1;
-    (void)probeNearestHitHost(ctx->scene.blob.data(), ctx->scene.layout, entityMapHost(ctx), o, d, time, &t, &prim);      // no device work: batches in flight are neither waited for nor disturbed
-    if (distance) *distance = t;
-    if (entityIndex) *entityIndex = prim;
-    return RTOW_SUCCESS;
-}
-
-RTOW_API int rtowProbeNearestHitInterval(RtowContext ctx, const RtowFloat3* origin, const RtowFloat3* direction, float time, float tMin, float tMax, float* distance,
-                                         int32_t* entityIndex)
-{
-    if (!ctx || !origin || !direction) return RTOW_ERROR_INVALID_VALUE;
-    std::lock_guard<std::mutex> lock(ctx->sceneMu);          // the probe's own lock, as rtowProbeNearestHit
-    if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
-    const float o[3] = {origin->x, origin->y, origin->z}, d[3] = {direction->x, direction->y, direction->z};
-    float t = 0.0f;
-    int prim = -1;
-    (void)probeIntervalHost(ctx->scene.blob.data(), ctx->scene.layout, entityMapHost(ctx), o, d, time, tMin, tMax, false, &t, &prim);
-    if (distance) *distance = t;
-    if (entityIndex) *entityIndex = prim;
-    return RTOW_SUCCESS;
-}
-
-RTOW_API int rtowTraceRaysDevice(RtowContext ctx, int32_t count, const RtowRay* rays, const RtowHitBuffers* hits, void* stream)
-{
-    if (!ctx || !rays || !hits || count < 0) return RTOW_ERROR_INVALID_VALUE;
-    if (!anyHitBuffer(*hits)) return RTOW_ERROR_INVALID_VALUE;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
-    if (count == 0) return RTOW_SUCCESS;
-    hipStream_t s;
-    RTOW_TRY(useDevice(ctx, stream, &s));
-    HIP_TRY(ctx, launchTraceRays(ctx->dScene, ctx->scene.layout, entityMapDevice(ctx), count, rays, *hits, s), RTOW_ERROR_LAUNCH_FAILURE);
-    return RTOW_SUCCESS;
-}
-
-RTOW_API int rtowTraceViewDevice(RtowContext ctx, const RtowTraceViewParams* params, const RtowHitBuffers* hits, RtowRay* outRays, void* stream)
-{
-    if (!ctx || !params || !hits) return RTOW_ERROR_INVALID_VALUE;
-    if (!anyHitBuffer(*hits)) return RTOW_ERROR_INVALID_VALUE;
-    if (!viewSizeValid(*params)) return RTOW_ERROR_INVALID_VALUE;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
-    hipStream_t s;
-    RTOW_TRY(useDevice(ctx, stream, &s));
-    HIP_TRY(ctx, launchTraceView(ctx->dScene, ctx->scene.layout, entityMapDevice(ctx), *params, *hits, outRays, s), RTOW_ERROR_LAUNCH_FAILURE);
-    return RTOW_SUCCESS;
-}
-
-RTOW_API int rtowTraceRaysIntervalDevice(RtowContext ctx, int32_t count, const RtowRay* rays, const RtowRayInterval* intervals, const RtowHitBuffers* hits, void* stream)
-{
-    if (!ctx || !rays || !hits || count < 0) return RTOW_ERROR_INVALID_VALUE;
-    if (!anyHitBuffer(*hits)) return RTOW_ERROR_INVALID_VALUE;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
-    if (count == 0) return RTOW_SUCCESS;
-    hipStream_t s;
-    RTOW_TRY(useDevice(ctx, stream, &s));
-    HIP_TRY(ctx, launchTraceRaysInterval(ctx->dScene, ctx->scene.layout, entityMapDevice(ctx), count, rays, intervals, *hits, s),
-            RTOW_ERROR_LAUNCH_FAILURE);
-    return RTOW_SUCCESS;
-}
-
-RTOW_API int rtowTraceOcclusionDevice(RtowContext ctx, int32_t count, const RtowRay* rays, const RtowRayInterval* intervals, uint8_t* occluded, void* stream)
-{
-    if (!ctx || !rays || !occluded || count < 0) return RTOW_ERROR_INVALID_VALUE;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
-    if (count == 0) return RTOW_SUCCESS;
-    hipStream_t s;
-    RTOW_TRY(useDevice(ctx, stream, &s));
-    HIP_TRY(ctx, launchTraceOcclusion(ctx->dScene, ctx->scene.layout, count, rays, intervals, occluded, s), RTOW_ERROR_LAUNCH_FAILURE);
-    return RTOW_SUCCESS;
-}
-
-RTOW_API int rtowShadeHitsDevice(RtowContext ctx, const RtowShadeHitsParams* params, int32_t count, const RtowRay* rays, const int32_t* entityIndex,
-                                 const RtowSurfaceBuffers* surface, void* stream)
-{
-    if (!ctx) return RTOW_ERROR_INVALID_VALUE;
-    RTOW_TRY(validateShadeHits(params, count, rays, entityIndex, surface));
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
-    if (count == 0) return RTOW_SUCCESS;
-    const bool mapped = !ctx->scene.entityOfPrim.empty();
-    if (mapped && !ctx->dPrimOfEntity) return RTOW_ERROR_INTERNAL;      // (an upload that failed half way: the old scene's description, no map)
-    hipStream_t s;
-    RTOW_TRY(useDevice(ctx, stream, &s));
-    ShadeScene sc{};
-    sc.blob = ctx->dScene;
-    sc.layout = ctx->scene.layout;
-    sc.primOfEntity = mapped ? ctx->dPrimOfEntity : nullptr;
-    sc.entityCount = mapped ? std::min(ctx->scene.entityCount, ctx->primOfEntityCount) : ctx->scene.entityCount;      // never beyond the map on the device
-    sc.texBlob = ctx->scene.texLayout.totalBytes ? ctx->dTexBlob : nullptr;
-    sc.texLayout = ctx->scene.texLayout;
-    sc.cubemapData = ctx->dCubemap;
-    sc.cubemap = ctx->cubemap;
-    HIP_TRY(ctx, launchShadeHits(sc, params->environment, count, rays, entityIndex, *surface, s), RTOW_ERROR_LAUNCH_FAILURE);
-    return RTOW_SUCCESS;
-}
-
-RTOW_API int rtowTraceGuideRaysDevice(RtowContext ctx, const RtowGuideParams* params, int32_t count, const RtowRay* rays, const RtowGuideBuffers* out, void* stream)
-{
-    if (!ctx || !rays || count < 0 || !guideArgumentsValid(params, out)) return RTOW_ERROR_INVALID_VALUE;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
-    if (count == 0) return RTOW_SUCCESS;
-    hipStream_t s;
-    RTOW_TRY(useDevice(ctx, stream, &s));
-    HIP_TRY(ctx, launchTraceGuideRays(guideScene(ctx), params->maxBounces, count, rays, *out, s), RTOW_ERROR_LAUNCH_FAILURE);
-    return RTOW_SUCCESS;
-}
-
-RTOW_API int rtowTraceGuideViewDevice(RtowContext ctx, const RtowGuideParams* params, const RtowTraceViewParams* view, const RtowGuideBuffers* out, void* stream)
-{
-    if (!ctx || !view || !guideArgumentsValid(params, out)) return RTOW_ERROR_INVALID_VALUE;
-    if (!viewSizeValid(*view)) return RTOW_ERROR_INVALID_VALUE;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
-    hipStream_t s;
-    RTOW_TRY(useDevice(ctx, stream, &s));
-    HIP_TRY(ctx, launchTraceGuideView(guideScene(ctx), params->maxBounces, *view, *out, s), RTOW_ERROR_LAUNCH_FAILURE);
-    return RTOW_SUCCESS;
-}
-
 RTOW_API int rtowRecordPathsDevice(RtowContext ctx, const RtowSampleParams* batch, const RtowRecordPathsParams* params, const RtowPixelList* list, const float* inColor,
                                    const float* inSampleCountWeight, RtowPathSummary* summaries, RtowPathSegment* segments, void* stream)
 {
@@ -1655,7 +1509,7 @@ RTOW_API int rtowRecordPathsDevice(RtowContext ctx, const RtowSampleParams* batc
     RTOW_TRY(useDevice(ctx, stream, &s));
     // without `segments` the lanes' stacks live in the context's block: grow-only, allocated here on first use (freeing the smaller block waits for a launch that uses it)
     if (!segments) RTOW_TRY(growDevice(ctx, {{&ctx->dPathStack, (size_t)list->capacity * (size_t)batch->traceDepth * 24u}}));
-    HIP_TRY(ctx, launchRecordPaths(a, entityMapDevice(ctx), *params, list->words, list->capacity, summaries, segments, segments ? nullptr : ctx->dPathStack.get(), s),
+    HIP_TRY(ctx, launchRecordPaths(a, queryScene(ctx), *params, list->words, list->capacity, summaries, segments, segments ? nullptr : ctx->dPathStack.get(), s),
             RTOW_ERROR_LAUNCH_FAILURE);
     return RTOW_SUCCESS;
 }

@@ -1,8 +1,9 @@
-// rtow_context.h - the context behind RtowContext and the helpers every translation unit of the C-ABI layer shares (rtow_api.hip, rtow_api_post.hip, rtow_comm.hip):
-// logging, the error-return macros and what an entry point does once it holds its lock.  Internal: nothing here is part of include/rtow.h.
+// rtow_context.h - the context behind RtowContext and the helpers every translation unit of the C-ABI layer shares (rtow_api.hip, rtow_api_query.hip, rtow_api_post.hip,
+// rtow_comm.hip): logging, the error-return macros, what an entry point does once it holds its lock and the resident scene as a query launch gets it (queryScene).  Internal: nothing here is part of include/rtow.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <mutex>
@@ -211,6 +212,28 @@ inline int useDevice(RtowContext ctx, void* stream, hipStream_t* s)
     HIP_TRY(ctx, hipSetDevice(ctx->device), RTOW_ERROR_NO_DEVICE);
     *s = stream ? (hipStream_t)stream : ctx->stream;
     return RTOW_SUCCESS;
+}
+
+// primitive -> the host's entity index (all-triangle scenes number their primitives in leaf order), on the device and on the host; null: the same number
+inline const int32_t* entityMapDevice(const RtowContext_t* ctx) { return ctx->scene.entityOfPrim.empty() ? nullptr : ctx->dEntityOfPrim.get(); }
+inline const int32_t* entityMapHost(const RtowContext_t* ctx) { return ctx->scene.entityOfPrim.empty() ? nullptr : ctx->scene.entityOfPrim.data(); }
+
+// The resident scene for a query launch (QueryScene, rtow_kernels.h); the caller holds ctx->mu.  The two rules every query shares are here: a scene without an Image
+// texture has no texture blob, and an entity index is never bounded beyond the inverse map that is on the device
+inline QueryScene queryScene(const RtowContext_t* ctx)
+{
+    const bool mapped = !ctx->scene.entityOfPrim.empty();
+    QueryScene q{};
+    q.binding.blob = ctx->dScene;
+    q.binding.entityOfPrim = entityMapDevice(ctx);
+    q.binding.layout = ctx->scene.layout;
+    q.tex.blob = ctx->scene.texLayout.totalBytes ? ctx->dTexBlob.get() : nullptr;
+    q.tex.layout = ctx->scene.texLayout;
+    q.primOfEntity = mapped ? ctx->dPrimOfEntity.get() : nullptr;
+    q.entityCount = mapped ? std::min(ctx->scene.entityCount, ctx->primOfEntityCount) : ctx->scene.entityCount;
+    q.cubemapData = ctx->dCubemap;
+    q.cubemap = ctx->cubemap;
+    return q;
 }
 
 // device-visible address of caller memory [p, p + bytes) if it lies inside a range given to rtowRegisterHostBuffer, else null

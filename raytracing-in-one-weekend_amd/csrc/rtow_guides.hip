@@ -22,9 +22,7 @@ namespace rtow {
 namespace {
 
 struct GuideArgs {
-    const uint8_t* blob;            // device image of the scene
-    const int32_t* entityOfPrim;    // primitive -> the host's entity index, or null (the same number)
-    SceneLayout layout;
+    SceneBinding scene;             // device image of the scene, entity map, layout (rtow_kernels.h)
     TexRefs tex;
     uint32_t imageCount;            // GpuImage records in the texture blob
     int32_t maxBounces;
@@ -66,12 +64,12 @@ __global__ void __launch_bounds__(kTraceBlock) guide_kernel(GuideArgs A)
         if (i >= A.count) return;
         index = (size_t)i;
         const Ray8 r = reinterpret_cast<const Ray8*>(A.rays)[index];      // read before anything is written: A.rays may be A.outRays
-        ro = v3(r.ox, r.oy, r.oz);
+        ro = v3(r.ox, r.oy, r.oz);      // (not load_ray: with it the compiler orders two moves of this kernel differently)
         time = r.time;
         rd = v3(r.dx, r.dy, r.dz);
     }
-    const SceneLayout& L = A.layout;
-    const SceneRefs sc = global_scene(A.blob);
+    const SceneLayout& L = A.scene.layout;
+    const SceneRefs sc = global_scene(A.scene.blob);
     LdsStack stack;
     stack.col = stackRows + threadIdx.x;
 
@@ -83,15 +81,14 @@ __global__ void __launch_bounds__(kTraceBlock) guide_kernel(GuideArgs A)
         // ---- 1. nearest hit: one ray of rtowTraceRaysDevice ----
         float rtime;
         stack.sp = 0;
-        (void)walk<BASE, WALK_OPEN>(A.blob, L, ro, rd, time, 0.0f, 0.0f, stack, t, prim, rtime);      // (the launcher refuses a tree deeper than the stack: push cannot fail)
+        (void)walk<BASE, WALK_OPEN>(A.scene.blob, L, ro, rd, time, 0.0f, 0.0f, stack, t, prim, rtime);      // (the launcher refuses a tree deeper than the stack: push cannot fail)
         N = v3(0, 0, 0);
         if (prim < 0) { end = GUIDE_END_SKY; break; }
 
         // ---- 2. hit record (HIT of the sample kernel) ----
         D = D + t;
-        const unsigned mi = *reinterpret_cast<const unsigned*>(section<false>(sc, L.matIndexOffset) + (uint32_t)prim * 4u);
-        const unsigned matIdx = mi & 0xffffu;
-        const uint8_t* mp = section<false>(sc, L.materialOffset) + matIdx * 64u;
+        const PrimMaterial pm = prim_material(sc, L, prim);
+        const uint8_t* mp = pm.record;
         const float4 m2 = *reinterpret_cast<const float4*>(mp + 32);  // glossiness parameter flags roughness
         const unsigned flags = __float_as_uint(m2.z);
         const bool specular = (flags & MAT_FLAG_PERFECT_SPECULAR) != 0;
@@ -104,8 +101,8 @@ __global__ void __launch_bounds__(kTraceBlock) guide_kernel(GuideArgs A)
         const float4 m0 = *reinterpret_cast<const float4*>(mp);       // albedo.xyz emission.x
         const float4 m1 = *reinterpret_cast<const float4*>(mp + 16);  // emission.yz type metallic
         float2 uv = make_float2(0, 0);
-        if (textures_evaluated<BASE>(A.tex, flags)) uv = hit_tex_coord<BASE>(sc, L, prim, mi, ro, rd);
-        V3 tint = material_albedo<BASE>(A.tex, A.imageCount, matIdx, v3(m0.x, m0.y, m0.z), flags, uv);
+        if (textures_evaluated<BASE>(A.tex, flags)) uv = hit_tex_coord<BASE>(sc, L, prim, pm.word, ro, rd);
+        V3 tint = material_albedo<BASE>(A.tex, A.imageCount, pm.index, v3(m0.x, m0.y, m0.z), flags, uv);
         V3 sdir;
         if (__float_as_int(m1.z) == RTOW_MATERIAL_STANDARD) {
             sdir = reflect(rd, N);                                     // the metal branch; the untinted glossy branch (reflectionChance) is left out
@@ -152,18 +149,15 @@ __global__ void __launch_bounds__(kTraceBlock) guide_kernel(GuideArgs A)
 template <bool VIEW>
 hipError_t launch(const GuideArgs& A, unsigned long long blocks, hipStream_t stream)
 {
-    return launch_query(A.layout, blocks, [&](auto base, dim3 grid, dim3 block) { hipLaunchKernelGGL((guide_kernel<decltype(base)::value, VIEW>), grid, block, 0, stream, A); });
+    return launch_query(A.scene.layout, blocks, [&](auto base, dim3 grid, dim3 block) { hipLaunchKernelGGL((guide_kernel<decltype(base)::value, VIEW>), grid, block, 0, stream, A); });
 }
 
-GuideArgs guide_args(const GuideScene& scene, int32_t maxBounces, const RtowGuideBuffers& out)
+GuideArgs guide_args(const QueryScene& scene, int32_t maxBounces, const RtowGuideBuffers& out)
 {
     GuideArgs A{};
-    A.blob = scene.blob;
-    A.entityOfPrim = scene.entityOfPrim;
-    A.layout = scene.layout;
-    A.tex.blob = scene.texBlob;
-    A.tex.layout = scene.texLayout;
-    A.imageCount = image_count(scene.texLayout);
+    A.scene = scene.binding;
+    A.tex = scene.tex;
+    A.imageCount = image_count(scene.tex.layout);
     A.maxBounces = maxBounces;
     A.hits = out.hits;
     A.outRays = out.rays;
@@ -176,7 +170,7 @@ GuideArgs guide_args(const GuideScene& scene, int32_t maxBounces, const RtowGuid
 
 }  // namespace
 
-hipError_t launchTraceGuideRays(const GuideScene& scene, int32_t maxBounces, int64_t count, const RtowRay* rays, const RtowGuideBuffers& out, hipStream_t stream)
+hipError_t launchTraceGuideRays(const QueryScene& scene, int32_t maxBounces, int64_t count, const RtowRay* rays, const RtowGuideBuffers& out, hipStream_t stream)
 {
     GuideArgs A = guide_args(scene, maxBounces, out);
     A.rays = rays;
@@ -184,7 +178,7 @@ hipError_t launchTraceGuideRays(const GuideScene& scene, int32_t maxBounces, int
     return launch<false>(A, ((unsigned long long)count + kTraceBlock - 1) / kTraceBlock, stream);
 }
 
-hipError_t launchTraceGuideView(const GuideScene& scene, int32_t maxBounces, const RtowTraceViewParams& p, const RtowGuideBuffers& out, hipStream_t stream)
+hipError_t launchTraceGuideView(const QueryScene& scene, int32_t maxBounces, const RtowTraceViewParams& p, const RtowGuideBuffers& out, hipStream_t stream)
 {
     GuideArgs A = guide_args(scene, maxBounces, out);
     return launch<true>(A, set_view(A, p), stream);

@@ -1,4 +1,4 @@
-// rtow_kernels.h - launch interface between the C-ABI layer (rtow_api.hip, rtow_api_post.hip, rtow_comm.hip) and the gfx950 kernels (rtow_kernels.hip).
+// rtow_kernels.h - launch interface between the C-ABI layer (rtow_api.hip, rtow_api_query.hip, rtow_api_post.hip, rtow_comm.hip) and the gfx950 kernels (rtow_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -458,52 +458,49 @@ bool probeNearestHitHost(const uint8_t* blob, const SceneLayout& L, const int32_
 bool probeIntervalHost(const uint8_t* blob, const SceneLayout& L, const int32_t* entityOfPrim, const float origin[3], const float direction[3], float time, float tMin, float tMax,
                        bool any, float* distance, int* entity);
 
-// rtowTraceRaysDevice / rtowTraceViewDevice (rtow_trace.hip): one launch on `stream`, one lane per ray, through the DEVICE image of the scene (arguments validated by the caller);
-// entityOfPrim: the device copy of CompiledScene.entityOfPrim, or null
-hipError_t launchTraceRays(const uint8_t* blob, const SceneLayout& layout, const int32_t* entityOfPrim, int64_t count, const RtowRay* rays, const RtowHitBuffers& hits,
-                           hipStream_t stream);
-hipError_t launchTraceView(const uint8_t* blob, const SceneLayout& layout, const int32_t* entityOfPrim, const RtowTraceViewParams& p, const RtowHitBuffers& hits,
-                           RtowRay* outRays, hipStream_t stream);
-
-// rtowTraceRaysIntervalDevice / rtowTraceOcclusionDevice (rtow_trace_interval.hip): one launch on `stream`, one lane per ray, as launchTraceRays; intervals: device, or null
-// = (0, +inf) for every ray; occluded: one byte per ray
-hipError_t launchTraceRaysInterval(const uint8_t* blob, const SceneLayout& layout, const int32_t* entityOfPrim, int64_t count, const RtowRay* rays,
-                                   const RtowRayInterval* intervals, const RtowHitBuffers& hits, hipStream_t stream);
-hipError_t launchTraceOcclusion(const uint8_t* blob, const SceneLayout& layout, int64_t count, const RtowRay* rays, const RtowRayInterval* intervals, uint8_t* occluded,
-                                hipStream_t stream);
-
-// rtowShadeHitsDevice (rtow_shade.hip): one launch on `stream`, one lane per element (arguments validated by the caller).  What the pass reads of the context, all device
-// memory but the descriptor: primOfEntity = the inverse of CompiledScene.entityOfPrim (-1: no primitive), or null (the same number); texBlob may be null (no Image texture),
-// cubemapData too (no cubemap: black)
-struct ShadeScene {
+// The resident scene as the device queries read it.  SceneBinding is what their kernels take by value - the first member of the argument structs of rtow_trace.hip,
+// rtow_trace_interval.hip and rtow_guides.hip, read there and by the helpers of rtow_trace_lanes.hip.h - all device memory: blob = the device image of the scene,
+// entityOfPrim = the device copy of CompiledScene.entityOfPrim (primitive -> the host's entity index), or null (the same number)
+struct SceneBinding {
     const uint8_t* blob;
+    const int32_t* entityOfPrim;
     SceneLayout layout;
+};
+static_assert(sizeof(SceneBinding) == 16 + sizeof(SceneLayout) && sizeof(SceneBinding) % 8 == 0, "two pointers and the layout without padding: the member behind it starts where the layout ends");
+// ... and QueryScene everything a query launch reads of the context (queryScene, rtow_context.h, fills it under the context's lock): tex.blob is null when the scene has
+// no Image texture; primOfEntity = the inverse of entityOfPrim (-1: no primitive), or null (the same number), entityCount what an entity index is bounded by;
+// cubemapData may be null (no cubemap: black)
+struct QueryScene {
+    SceneBinding binding;
+    TexRefs tex;
     const int32_t* primOfEntity;
     int32_t entityCount;
-    const uint8_t* texBlob;
-    TexLayout texLayout;
     const uint8_t* cubemapData;
     RtowCubemapDesc cubemap;
 };
-hipError_t launchShadeHits(const ShadeScene& scene, const RtowEnvironment& environment, int32_t count, const RtowRay* rays, const int32_t* entityIndex,
+
+// rtowTraceRaysDevice / rtowTraceViewDevice (rtow_trace.hip): one launch on `stream`, one lane per ray, through the DEVICE image of the scene (arguments validated by the caller)
+hipError_t launchTraceRays(const QueryScene& scene, int64_t count, const RtowRay* rays, const RtowHitBuffers& hits, hipStream_t stream);
+hipError_t launchTraceView(const QueryScene& scene, const RtowTraceViewParams& p, const RtowHitBuffers& hits, RtowRay* outRays, hipStream_t stream);
+
+// rtowTraceRaysIntervalDevice / rtowTraceOcclusionDevice (rtow_trace_interval.hip): one launch on `stream`, one lane per ray, as launchTraceRays; intervals: device, or null
+// = (0, +inf) for every ray; occluded: one byte per ray
+hipError_t launchTraceRaysInterval(const QueryScene& scene, int64_t count, const RtowRay* rays, const RtowRayInterval* intervals, const RtowHitBuffers& hits, hipStream_t stream);
+hipError_t launchTraceOcclusion(const QueryScene& scene, int64_t count, const RtowRay* rays, const RtowRayInterval* intervals, uint8_t* occluded, hipStream_t stream);
+
+// rtowShadeHitsDevice (rtow_shade.hip): one launch on `stream`, one lane per element (arguments validated by the caller)
+hipError_t launchShadeHits(const QueryScene& scene, const RtowEnvironment& environment, int32_t count, const RtowRay* rays, const int32_t* entityIndex,
                            const RtowSurfaceBuffers& surface, hipStream_t stream);
 
 // rtowTraceGuideRaysDevice / rtowTraceGuideViewDevice (rtow_guides.hip): one launch on `stream`, one lane per ray, as launchTraceRays / launchTraceView (arguments validated
-// by the caller).  What the pass reads of the context, all device memory: entityOfPrim as for launchTraceRays; texBlob may be null (no Image texture)
-struct GuideScene {
-    const uint8_t* blob;
-    SceneLayout layout;
-    const int32_t* entityOfPrim;
-    const uint8_t* texBlob;
-    TexLayout texLayout;
-};
-hipError_t launchTraceGuideRays(const GuideScene& scene, int32_t maxBounces, int64_t count, const RtowRay* rays, const RtowGuideBuffers& out, hipStream_t stream);
-hipError_t launchTraceGuideView(const GuideScene& scene, int32_t maxBounces, const RtowTraceViewParams& p, const RtowGuideBuffers& out, hipStream_t stream);
+// by the caller)
+hipError_t launchTraceGuideRays(const QueryScene& scene, int32_t maxBounces, int64_t count, const RtowRay* rays, const RtowGuideBuffers& out, hipStream_t stream);
+hipError_t launchTraceGuideView(const QueryScene& scene, int32_t maxBounces, const RtowTraceViewParams& p, const RtowGuideBuffers& out, hipStream_t stream);
 
 // rtowRecordPathsDevice (rtow_record_paths.hip): one launch on `stream`, one lane per entry of the caller's list, read in place (arguments validated by the caller).
 // batch: what buildArgs fills for a batch of the call's params (scene, textures, cubemap, noise textures, view, counts; of the accumulators inColor and inScw alone are
-// read); entityOfPrim as for launchTraceRays; segments may be null - stackRows then holds capacity x traceDepth x 24 bytes of device memory for the lanes' stacks
-hipError_t launchRecordPaths(const SampleKernelArgs& batch, const int32_t* entityOfPrim, const RtowRecordPathsParams& params, const uint32_t* words, uint32_t capacity,
+// read); of `scene` the entity map and the texture blob; segments may be null - stackRows then holds capacity x traceDepth x 24 bytes of device memory for the lanes' stacks
+hipError_t launchRecordPaths(const SampleKernelArgs& batch, const QueryScene& scene, const RtowRecordPathsParams& params, const uint32_t* words, uint32_t capacity,
                              RtowPathSummary* summaries, RtowPathSegment* segments, float* stackRows, hipStream_t stream);
 
 // same-XCD hand-over litmus of the chained launches (rtow_kernels.hip): pairs of workgroups that ran on one XCD, stale dwords seen, waits that timed out

@@ -112,16 +112,8 @@ __device__ __forceinline__ SampleResult run_sample(const RecordArgs& A, const No
 
         if (prim < 0) {
             // ---- sky (:341-374), then fold tail -> head (:384-396): SKY of the sample kernel ----
-            V3 sky = v3(0, 0, 0);
             const SampleKernelArgs& ES = cold_args(A).S;
-            const RtowEnvironment& ENV = ES.environment;
-            if (ENV.skyType == RTOW_SKY_GRADIENT) {
-                const float s = 0.5f * (rd.y + 1);
-                const V3 b = v3(ENV.skyBottomColor), tp = v3(ENV.skyTopColor);
-                sky = v3(b.x + s * (tp.x - b.x), b.y + s * (tp.y - b.y), b.z + s * (tp.z - b.z));
-            } else if (ENV.skyType == RTOW_SKY_CUBEMAP) {
-                sky = cubemap_sample(ES.cubemap, rd);
-            }
+            const V3 sky = sky_color(ES.environment, ES.cubemap, rd);
             if (!firstNonSpecular) { R.albedo = sky; R.normal = neg(rd); }
             if (seg) {
                 RtowPathSegment s;
@@ -144,12 +136,11 @@ __device__ __forceinline__ SampleResult run_sample(const RecordArgs& A, const No
         }
 
         // ---- surface hit: Entity.Hit record + Material.Scatter: HIT of the sample kernel ----
-        const unsigned mi = *reinterpret_cast<const unsigned*>(section<false>(sc, L.matIndexOffset) + (uint32_t)prim * 4u);
-        const unsigned matIdx = mi & 0xffffu;
-        const unsigned cls = (mi >> 16) & 3u;
+        const PrimMaterial pm = prim_material(sc, L, prim);
+        const unsigned matIdx = pm.index, cls = (pm.word >> 16) & 3u;
         const V3 P = v3(ro.x + t * rd.x, ro.y + t * rd.y, ro.z + t * rd.z);           // ray.GetPoint(distance)
         const V3 N = hit_normal<BASE>(sc, L, prim, ro, rd, rtime, 0.0f, t);
-        const uint8_t* mp = section<false>(sc, L.materialOffset) + matIdx * 64u;
+        const uint8_t* mp = pm.record;
         const float4 m0 = *reinterpret_cast<const float4*>(mp);       // albedo.xyz emission.x
         const float4 m1 = *reinterpret_cast<const float4*>(mp + 16);  // emission.yz type metallic
         float4 m2 = *reinterpret_cast<const float4*>(mp + 32);        // glossiness parameter flags roughness
@@ -161,7 +152,7 @@ __device__ __forceinline__ SampleResult run_sample(const RecordArgs& A, const No
         const TexRefs& tex = TA.S.tex;
         if (textures_evaluated<BASE>(tex, __float_as_uint(m2.z))) {
             // Material.Scatter / Emit evaluate the four textures at rec.TexCoords, and everything derived from metallic / glossiness follows per hit
-            const float2 hitUv = hit_tex_coord<BASE>(sc, L, prim, mi, ro, rd);
+            const float2 hitUv = hit_tex_coord<BASE>(sc, L, prim, pm.word, ro, rd);
             const GpuTexMaterial& tm = tex_material(tex, matIdx);
             reflectance = color_checked(tex, tm.albedo, hitUv, TA.imageCount);
             emission = color_checked(tex, tm.emission, hitUv, TA.imageCount);
@@ -387,16 +378,16 @@ hipError_t launch(const RecordArgs& A, unsigned long long blocks, hipStream_t st
 
 }  // namespace
 
-hipError_t launchRecordPaths(const SampleKernelArgs& batch, const int32_t* entityOfPrim, const RtowRecordPathsParams& params, const uint32_t* words, uint32_t capacity,
+hipError_t launchRecordPaths(const SampleKernelArgs& batch, const QueryScene& scene, const RtowRecordPathsParams& params, const uint32_t* words, uint32_t capacity,
                              RtowPathSummary* summaries, RtowPathSegment* segments, float* stackRows, hipStream_t stream)
 {
     if (capacity == 0u) return hipSuccess;
     if (!segments && !stackRows) return hipErrorInvalidValue;
     RecordArgs A{};
     A.S = batch;
-    if (!batch.tex.layout.totalBytes) A.S.tex.blob = nullptr;
-    A.entityOfPrim = entityOfPrim;
-    A.imageCount = image_count(batch.tex.layout);
+    A.S.tex = scene.tex;      // (a batch's own launch is handed the blob whatever the scene; the queries' is null without an Image texture)
+    A.entityOfPrim = scene.binding.entityOfPrim;
+    A.imageCount = image_count(scene.tex.layout);
     A.words = words;
     A.capacity = capacity;
     A.select = params.select;

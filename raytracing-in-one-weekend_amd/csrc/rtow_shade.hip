@@ -6,7 +6,7 @@
 // the cursor, a material to match on in rtowReprojectAccumDevice's host.  include/rtow.h holds the numeric specification.
 //
 // Every value is computed by the sample kernel's own helpers (rtow_hit_tests.hip.h: general_hit's texCoord as the HIT stage of the textured kernels asks for it;
-// rtow_surface.hip.h: texture_color / texture_scalar, cubemap_sample; the SKY stage's gradient expression), so the pass cannot drift from what a sample batch shades with.
+// rtow_surface.hip.h: texture_color / texture_scalar, cubemap_sample; sky_color, the SKY stage's expressions), so the pass cannot drift from what a sample batch shades with.
 // The albedo comes through rtow_albedo.hip.h, which rtow_guides.hip tints the surfaces it follows with: one evaluation for both.
 //
 // Launch shape: a plain grid of 256-lane workgroups, one lane per element, no LDS, no barrier; a lane without an element leaves at once.  The scene comes
@@ -68,7 +68,7 @@ __global__ void __launch_bounds__(kShadeBlock) shade_kernel(ShadeArgs A)
     uint32_t materialInfo = 0xffffffffu;
     if (prim >= 0) {
         uv = hit_tex_coord<BASE>(sc, L, prim, mi, ro, rd);
-        const uint8_t* mp = section<false>(sc, L.materialOffset) + matIdx * 64u;
+        const uint8_t* mp = section<false>(sc, L.materialOffset) + matIdx * 64u;      // (not prim_material: the number is checked before it is part of an address)
         const float4 m0 = *reinterpret_cast<const float4*>(mp);       // albedo.xyz emission.x
         const float4 m1 = *reinterpret_cast<const float4*>(mp + 16);  // emission.yz type metallic
         const float4 m2 = *reinterpret_cast<const float4*>(mp + 32);  // glossiness parameter flags roughness
@@ -85,15 +85,7 @@ __global__ void __launch_bounds__(kShadeBlock) shade_kernel(ShadeArgs A)
         materialIndex = (int32_t)matIdx;
         materialInfo = (__float_as_uint(m1.z) & 0xffu) | ((flags & MAT_FLAG_PERFECT_SPECULAR) ? 0x100u : 0u);
     } else {
-        // sampleAlbedo = hitSkyColor (JOBS/SampleBatchJob.cs:349-370): the SKY stage's expressions on the direction as stored
-        const RtowEnvironment& ENV = A.environment;
-        if (ENV.skyType == RTOW_SKY_GRADIENT) {
-            const float s = 0.5f * (rd.y + 1);
-            const V3 b = v3(ENV.skyBottomColor), tp = v3(ENV.skyTopColor);
-            albedo = v3(b.x + s * (tp.x - b.x), b.y + s * (tp.y - b.y), b.z + s * (tp.z - b.z));
-        } else if (ENV.skyType == RTOW_SKY_CUBEMAP) {
-            albedo = cubemap_sample(A.cubemap, rd);
-        }
+        albedo = sky_color(A.environment, A.cubemap, rd);      // sampleAlbedo = hitSkyColor: the SKY stage's expressions on the direction as stored
     }
 
     if (A.out.albedo) { float* o = A.out.albedo + index * 3u; o[0] = albedo.x; o[1] = albedo.y; o[2] = albedo.z; }
@@ -106,15 +98,14 @@ __global__ void __launch_bounds__(kShadeBlock) shade_kernel(ShadeArgs A)
 
 }  // namespace
 
-hipError_t launchShadeHits(const ShadeScene& scene, const RtowEnvironment& environment, int32_t count, const RtowRay* rays, const int32_t* entityIndex,
+hipError_t launchShadeHits(const QueryScene& scene, const RtowEnvironment& environment, int32_t count, const RtowRay* rays, const int32_t* entityIndex,
                            const RtowSurfaceBuffers& surface, hipStream_t stream)
 {
     if (count <= 0) return hipSuccess;
     ShadeArgs A{};
-    A.sceneBlob = scene.blob;
-    A.layout = scene.layout;
-    A.tex.blob = scene.texBlob;
-    A.tex.layout = scene.texLayout;
+    A.sceneBlob = scene.binding.blob;
+    A.layout = scene.binding.layout;
+    A.tex = scene.tex;
     A.cubemap = cubemapRefs(scene.cubemap, scene.cubemapData);
     A.environment = environment;
     A.primOfEntity = scene.primOfEntity;
@@ -123,10 +114,10 @@ hipError_t launchShadeHits(const ShadeScene& scene, const RtowEnvironment& envir
     A.out = surface;
     A.count = count;
     A.entityCount = scene.entityCount;
-    A.imageCount = image_count(scene.texLayout);
+    A.imageCount = image_count(scene.tex.layout);
     const dim3 grid((unsigned)(((long long)count + kShadeBlock - 1) / kShadeBlock)), block(kShadeBlock);
-    if (scene.layout.sceneKind == SCENE_KIND_SPHERES) hipLaunchKernelGGL((shade_kernel<SCENE_KIND_SPHERES>), grid, block, 0, stream, A);
-    else if (scene.layout.sceneKind == SCENE_KIND_SPHERES_MOTION) hipLaunchKernelGGL((shade_kernel<SCENE_KIND_SPHERES_MOTION>), grid, block, 0, stream, A);
+    if (scene.binding.layout.sceneKind == SCENE_KIND_SPHERES) hipLaunchKernelGGL((shade_kernel<SCENE_KIND_SPHERES>), grid, block, 0, stream, A);
+    else if (scene.binding.layout.sceneKind == SCENE_KIND_SPHERES_MOTION) hipLaunchKernelGGL((shade_kernel<SCENE_KIND_SPHERES_MOTION>), grid, block, 0, stream, A);
     else hipLaunchKernelGGL((shade_kernel<SCENE_KIND_GENERAL>), grid, block, 0, stream, A);
     return hipGetLastError();
 }

@@ -65,6 +65,19 @@ __device__ __forceinline__ V3 cubemap_sample(const CubemapRefs& A, V3 d)
     return v3(half_bits_to_float(hp[0]), half_bits_to_float(hp[1]), half_bits_to_float(hp[2]));
 }
 
+// hitSkyColor (JOBS/SampleBatchJob.cs:349-370) of direction rd, the SKY stage's expressions for the query units (rtow_shade.hip, rtow_record_paths.hip; the sample
+// kernel keeps its own): the gradient between the two sky colours or the cubemap's texel; any other sky type is black
+__device__ __forceinline__ V3 sky_color(const RtowEnvironment& ENV, const CubemapRefs& cubemap, V3 rd)
+{
+    if (ENV.skyType == RTOW_SKY_GRADIENT) {
+        const float s = 0.5f * (rd.y + 1);
+        const V3 b = v3(ENV.skyBottomColor), tp = v3(ENV.skyTopColor);
+        return v3(b.x + s * (tp.x - b.x), b.y + s * (tp.y - b.y), b.z + s * (tp.z - b.z));
+    }
+    if (ENV.skyType == RTOW_SKY_CUBEMAP) return cubemap_sample(cubemap, rd);
+    return v3(0, 0, 0);
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // Texture.SampleColor / SampleScalar (RT/Texture.cs:51-138) for the per-hit evaluation of textured materials.  Image: the texel
 // (int2)(uv * ImageSize) - clamped into the image, where the reference would read out of bounds - as bytes / 255 * MainColor.

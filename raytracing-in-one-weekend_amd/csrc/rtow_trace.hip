@@ -20,9 +20,7 @@ namespace rtow {
 namespace {
 
 struct TraceArgs {
-    const uint8_t* blob;            // device image of the scene
-    const int32_t* entityOfPrim;    // primitive -> the host's entity index, or null (the same number)
-    SceneLayout layout;
+    SceneBinding scene;             // device image of the scene, entity map, layout (rtow_kernels.h)
     RtowHitBuffers hits;
     // ray form
     const RtowRay* rays;
@@ -57,48 +55,39 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(TraceArgs A)
         const long long i = (long long)blockIdx.x * kTraceBlock + threadIdx.x;
         if (i >= A.count) return;
         index = (size_t)i;
-        const Ray8 r = reinterpret_cast<const Ray8*>(A.rays)[index];
-        ro = v3(r.ox, r.oy, r.oz);
-        time = r.time;
-        rd = v3(r.dx, r.dy, r.dz);
+        load_ray(A.rays, index, ro, rd, time);
     }
     LdsStack stack;
     stack.col = stackRows + threadIdx.x;
     stack.sp = 0;
     float t, rtime;
     int prim;
-    (void)walk<BASE, WALK_OPEN>(A.blob, A.layout, ro, rd, time, 0.0f, 0.0f, stack, t, prim, rtime);      // (the launcher refuses a tree deeper than the stack: push cannot fail)
+    (void)walk<BASE, WALK_OPEN>(A.scene.blob, A.scene.layout, ro, rd, time, 0.0f, 0.0f, stack, t, prim, rtime);      // (the launcher refuses a tree deeper than the stack: push cannot fail)
     store_hit<BASE>(A, index, ro, rd, rtime, 0.0f, t, prim);
 }
 
 template <bool VIEW>
 hipError_t launch(const TraceArgs& A, unsigned long long blocks, hipStream_t stream)
 {
-    return launch_query(A.layout, blocks, [&](auto base, dim3 grid, dim3 block) { hipLaunchKernelGGL((trace_kernel<decltype(base)::value, VIEW>), grid, block, 0, stream, A); });
+    return launch_query(A.scene.layout, blocks, [&](auto base, dim3 grid, dim3 block) { hipLaunchKernelGGL((trace_kernel<decltype(base)::value, VIEW>), grid, block, 0, stream, A); });
 }
 
 }  // namespace
 
-hipError_t launchTraceRays(const uint8_t* blob, const SceneLayout& layout, const int32_t* entityOfPrim, int64_t count, const RtowRay* rays, const RtowHitBuffers& hits,
-                           hipStream_t stream)
+hipError_t launchTraceRays(const QueryScene& scene, int64_t count, const RtowRay* rays, const RtowHitBuffers& hits, hipStream_t stream)
 {
     TraceArgs A{};
-    A.blob = blob;
-    A.entityOfPrim = entityOfPrim;
-    A.layout = layout;
+    A.scene = scene.binding;
     A.hits = hits;
     A.rays = rays;
     A.count = count;
     return launch<false>(A, ((unsigned long long)count + kTraceBlock - 1) / kTraceBlock, stream);
 }
 
-hipError_t launchTraceView(const uint8_t* blob, const SceneLayout& layout, const int32_t* entityOfPrim, const RtowTraceViewParams& p, const RtowHitBuffers& hits,
-                           RtowRay* outRays, hipStream_t stream)
+hipError_t launchTraceView(const QueryScene& scene, const RtowTraceViewParams& p, const RtowHitBuffers& hits, RtowRay* outRays, hipStream_t stream)
 {
     TraceArgs A{};
-    A.blob = blob;
-    A.entityOfPrim = entityOfPrim;
-    A.layout = layout;
+    A.scene = scene.binding;
     A.hits = hits;
     A.outRays = outRays;
     return launch<true>(A, set_view(A, p), stream);

@@ -19,9 +19,7 @@ struct __attribute__((packed, aligned(4))) Interval2 { float tMin, tMax; };
 static_assert(sizeof(Interval2) == sizeof(RtowRayInterval), "RtowRayInterval is two floats");
 
 struct IntervalArgs {
-    const uint8_t* blob;            // device image of the scene
-    const int32_t* entityOfPrim;    // primitive -> the host's entity index, or null (the same number)
-    SceneLayout layout;
+    SceneBinding scene;             // device image of the scene, entity map, layout (rtow_kernels.h)
     const RtowRay* rays;
     const RtowRayInterval* intervals;   // null: (0, +inf) for every ray
     long long count;
@@ -36,21 +34,22 @@ __global__ void __launch_bounds__(kTraceBlock) interval_kernel(IntervalArgs A)
     const long long i = (long long)blockIdx.x * kTraceBlock + threadIdx.x;
     if (i >= A.count) return;
     const size_t index = (size_t)i;
-    const Ray8 r = reinterpret_cast<const Ray8*>(A.rays)[index];
-    const V3 ro = v3(r.ox, r.oy, r.oz), rd = v3(r.dx, r.dy, r.dz);
+    V3 ro, rd;
+    float time;
+    load_ray(A.rays, index, ro, rd, time);
     float tMin = 0.0f, tMax = __builtin_inff();
     if (A.intervals) {
         const Interval2 iv = reinterpret_cast<const Interval2*>(A.intervals)[index];
         tMin = iv.tMin;
         tMax = iv.tMax;
     }
-    float t = __builtin_inff(), rtime = r.time;
+    float t = __builtin_inff(), rtime = time;
     int prim = -1;
     if (interval_is_traced(tMin, tMax)) {
         LdsStack stack;
         stack.col = stackRows + threadIdx.x;
         stack.sp = 0;
-        (void)walk<BASE, ANY ? WALK_ANY : WALK_NEAREST>(A.blob, A.layout, ro, rd, r.time, tMin, tMax, stack, t, prim, rtime);      // (the launcher refuses a tree deeper than the stack: push cannot fail)
+        (void)walk<BASE, ANY ? WALK_ANY : WALK_NEAREST>(A.scene.blob, A.scene.layout, ro, rd, time, tMin, tMax, stack, t, prim, rtime);      // (the launcher refuses a tree deeper than the stack: push cannot fail)
     }
     if (ANY) {
         A.occluded[index] = prim >= 0 ? 1 : 0;
@@ -62,19 +61,16 @@ __global__ void __launch_bounds__(kTraceBlock) interval_kernel(IntervalArgs A)
 template <bool ANY>
 hipError_t launch(const IntervalArgs& A, hipStream_t stream)
 {
-    return launch_query(A.layout, ((unsigned long long)A.count + kTraceBlock - 1) / kTraceBlock,
+    return launch_query(A.scene.layout, ((unsigned long long)A.count + kTraceBlock - 1) / kTraceBlock,
                         [&](auto base, dim3 grid, dim3 block) { hipLaunchKernelGGL((interval_kernel<decltype(base)::value, ANY>), grid, block, 0, stream, A); });
 }
 
 }  // namespace
 
-hipError_t launchTraceRaysInterval(const uint8_t* blob, const SceneLayout& layout, const int32_t* entityOfPrim, int64_t count, const RtowRay* rays,
-                                   const RtowRayInterval* intervals, const RtowHitBuffers& hits, hipStream_t stream)
+hipError_t launchTraceRaysInterval(const QueryScene& scene, int64_t count, const RtowRay* rays, const RtowRayInterval* intervals, const RtowHitBuffers& hits, hipStream_t stream)
 {
     IntervalArgs A{};
-    A.blob = blob;
-    A.entityOfPrim = entityOfPrim;
-    A.layout = layout;
+    A.scene = scene.binding;
     A.rays = rays;
     A.intervals = intervals;
     A.count = count;
@@ -82,12 +78,10 @@ hipError_t launchTraceRaysInterval(const uint8_t* blob, const SceneLayout& layou
     return launch<false>(A, stream);
 }
 
-hipError_t launchTraceOcclusion(const uint8_t* blob, const SceneLayout& layout, int64_t count, const RtowRay* rays, const RtowRayInterval* intervals, uint8_t* occluded,
-                                hipStream_t stream)
+hipError_t launchTraceOcclusion(const QueryScene& scene, int64_t count, const RtowRay* rays, const RtowRayInterval* intervals, uint8_t* occluded, hipStream_t stream)
 {
     IntervalArgs A{};
-    A.blob = blob;
-    A.layout = layout;
+    A.scene = scene.binding;      // (the entity map travels along unread: the occlusion form stores no entity)
     A.rays = rays;
     A.intervals = intervals;
     A.count = count;

@@ -1,5 +1,5 @@
-// rtow_trace_lanes.hip.h - what one lane of a device ray query needs besides the walk: its column of the workgroup's LDS stack, the camera ray of its pixel (view forms), the
-// winner's world-space normal and the store of its result - and the launcher's part that does not depend on the kernel.  Shared by rtow_trace.hip (rtowTraceRaysDevice /
+// rtow_trace_lanes.hip.h - what one lane of a device ray query needs besides the walk: its column of the workgroup's LDS stack, its ray of the caller's array (load_ray) or the camera
+// ray of its pixel (view forms), the winner's world-space normal and the store of its result - and the launcher's part that does not depend on the kernel.  Shared by rtow_trace.hip (rtowTraceRaysDevice /
 // rtowTraceViewDevice), rtow_trace_interval.hip (rtowTraceRaysIntervalDevice / rtowTraceOcclusionDevice) and rtow_guides.hip (rtowTraceGuideRaysDevice /
 // rtowTraceGuideViewDevice): one launch shape, DESIGN.md 4.2.
 #pragma once
@@ -28,6 +28,15 @@ struct LdsStack {
     __device__ __forceinline__ int pop() { sp--; return col[sp * kTraceBlock]; }
     __device__ __forceinline__ bool empty() const { return sp == 0; }
 };
+
+// Ray `index` of a caller's array: origin, direction and Ray.Time
+__device__ __forceinline__ void load_ray(const RtowRay* rays, size_t index, V3& ro, V3& rd, float& time)
+{
+    const Ray8 r = reinterpret_cast<const Ray8*>(rays)[index];
+    ro = v3(r.ox, r.oy, r.oz);
+    time = r.time;
+    rd = v3(r.dx, r.dy, r.dz);
+}
 
 // The camera ray of pixel (cx, cy): REGEN of the sample kernel (JOBS/SampleBatchJob.cs:134, RT/View.cs:38-47) with the jitter at the pixel centre and no lens offset
 __device__ __forceinline__ V3 view_direction(const RtowView& VW, int cx, int cy, float frameX, float frameY)
@@ -94,13 +103,13 @@ __device__ __forceinline__ V3 hit_normal(const SceneRefs& sc, const SceneLayout&
     return normalize(nLocal);
 }
 
-// A lane's result into the caller's buffers A.hits: the distance and the host's entity index (A.entityOfPrim: primitive -> entity, or null for the same number) of the hit
-// the walk found; a miss stores +inf and -1.  Args: the kernel's argument struct.
+// A lane's result into the caller's buffers A.hits: the distance and the host's entity index (A.scene.entityOfPrim: primitive -> entity, or null for the same number) of the
+// hit the walk found; a miss stores +inf and -1.  Args: the kernel's argument struct, whose member `scene` is the launch's SceneBinding (rtow_kernels.h).
 template <typename Args>
 __device__ __forceinline__ void store_hit_place(const Args& A, size_t index, float t, int prim)
 {
     if (A.hits.distance) A.hits.distance[index] = t;
-    if (A.hits.entityIndex) A.hits.entityIndex[index] = prim >= 0 && A.entityOfPrim ? A.entityOfPrim[prim] : prim;
+    if (A.hits.entityIndex) A.hits.entityIndex[index] = prim >= 0 && A.scene.entityOfPrim ? A.scene.entityOfPrim[prim] : prim;
 }
 // ... and its normal, for a caller who asked for it (A.hits.normal is not null)
 template <typename Args>
@@ -110,7 +119,7 @@ __device__ __forceinline__ void store_hit_normal(const Args& A, size_t index, V3
     o[0] = n.x; o[1] = n.y; o[2] = n.z;
 }
 
-// The whole result of a query lane: the hit the walk found in A.blob / A.layout under `tMin` (0 for the open form), the normal derived only where the caller asks for
+// The whole result of a query lane: the hit the walk found in A.scene under `tMin` (0 for the open form), the normal derived only where the caller asks for
 // it; a miss stores +inf, -1 and a zero normal
 template <int BASE, typename Args>
 __device__ __forceinline__ void store_hit(const Args& A, size_t index, V3 ro, V3 rd, float rtime, float tMin, float t, int prim)
@@ -118,7 +127,7 @@ __device__ __forceinline__ void store_hit(const Args& A, size_t index, V3 ro, V3
     store_hit_place(A, index, t, prim);
     if (A.hits.normal) {
         V3 n = v3(0, 0, 0);
-        if (prim >= 0) n = hit_normal<BASE>(global_scene(A.blob), A.layout, prim, ro, rd, rtime, tMin, t);
+        if (prim >= 0) n = hit_normal<BASE>(global_scene(A.scene.blob), A.scene.layout, prim, ro, rd, rtime, tMin, t);
         store_hit_normal(A, index, n);
     }
 }

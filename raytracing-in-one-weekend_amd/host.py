@@ -62,6 +62,14 @@ class DeviceBuffer:
         return self.handle.value
 
 
+def _ray_array(rays):
+    """`rays` as the ray queries take them - an array of abi.RAY_DTYPE, or (n, 8) float32: origin, time, direction, pad - contiguous, and how many: (array, count)"""
+    a = np.ascontiguousarray(rays)
+    if a.dtype != np.dtype(abi.RAY_DTYPE):
+        a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 8)
+    return a, int(a.shape[0])
+
+
 class Context:
     """RtowContext: one per GPU (one process per GPU in multi-GPU runs)."""
 
@@ -201,10 +209,7 @@ class Context:
     def trace_rays(self, rays, want=("distance", "entityIndex", "normal"), stream=None):
         """rtowTraceRaysDevice on host data: `rays` is an array of abi.RAY_DTYPE (or (n, 8) float32: origin, time, direction, pad).
         Returns {"distance": (n,) float32, "entityIndex": (n,) int32, "normal": (n, 3) float32} for the names in `want`."""
-        a = np.ascontiguousarray(rays)
-        if a.dtype != np.dtype(abi.RAY_DTYPE):
-            a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 8)
-        count = int(a.shape[0])
+        a, count = _ray_array(rays)
         dev = DeviceBuffer(self, max(1, count) * C.sizeof(abi.Ray))
         try:
             if count:
@@ -231,10 +236,7 @@ class Context:
 
     def _upload_rays_intervals(self, rays, intervals):
         """Device copies of `rays` (as for trace_rays) and of `intervals` (abi.RAY_INTERVAL_DTYPE or (n, 2) float32; None: no buffer): (count, rays, intervals or None)"""
-        a = np.ascontiguousarray(rays)
-        if a.dtype != np.dtype(abi.RAY_DTYPE):
-            a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 8)
-        count = int(a.shape[0])
+        a, count = _ray_array(rays)
         iv = None
         if intervals is not None:
             iv = np.ascontiguousarray(intervals)
@@ -280,10 +282,7 @@ class Context:
         abi.Environment (None: RTOW_SKY_NONE, a miss's albedo is black).  Returns {"albedo": (n, 3) float32, "emission": (n, 3), "texCoord": (n, 2),
         "metallicGlossiness": (n, 2), "materialIndex": (n,) int32, "materialInfo": (n,) uint32} for the names in `outputs`.  Runs on the context's own stream and waits for it
         (ShadeHitsJob is the form for device buffers on a caller's stream)."""
-        a = np.ascontiguousarray(rays)
-        if a.dtype != np.dtype(abi.RAY_DTYPE):
-            a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 8)
-        count = int(a.shape[0])
+        a, count = _ray_array(rays)
         ent = np.ascontiguousarray(entity_index, dtype=np.int32).reshape(-1)
         if ent.shape[0] != count:
             raise ValueError("entity_index must hold one int32 per ray")
@@ -329,10 +328,7 @@ class Context:
         """rtowTraceGuideRaysDevice on host data: every ray followed through mirrors and glass to the first surface that is not perfectly specular (or the sky, or
         `max_bounces` surfaces).  `rays` as for trace_rays.  Returns, for the names in `want`, trace_rays' arrays for the LAST segment plus "rays" (that segment's rays,
         abi.RAY_DTYPE: with "entityIndex" the input of shade_hits), "throughput" (n, 3), "pathDistance" (n,), "bounces" (n,) int32 and "end" (n,) uint8 (abi.GUIDE_END_*)."""
-        a = np.ascontiguousarray(rays)
-        if a.dtype != np.dtype(abi.RAY_DTYPE):
-            a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 8)
-        count = int(a.shape[0])
+        a, count = _ray_array(rays)
         p = abi.GuideParams(int(max_bounces), 0, 0)
         dev = DeviceBuffer(self, max(1, count) * C.sizeof(abi.Ray))
         try:
