@@ -11,7 +11,9 @@
 // reciprocal the IEEE quotient?" does not depend on the exponents while no intermediate leaves the normal range (every step scales exactly
 // by powers of two), so it is enumerated over MANTISSAS: all 2^23 x 2^23 pairs, 34 s of an MI355X, no mismatch
 // (tests/native/exactdiv_parity.hip).  exact_div3 uses it where three numerators share one divisor (a sphere's normal, RT/HitTests.cs:56);
-// a single division gains nothing once the range guard is paid for and stays the compiler's.
+// a single division gains nothing once the range guard is paid for and stays the compiler's - unless its reciprocal is shared: the exact sphere tests of one TEST
+// run all divide by the run's dot(rd, rd), whose reciprocal and range test are formed once per run (sphere_hit_shared_rcp, rtow_hit_tests.hip.h; the whole function
+// against sphere_hit: tests/native/sphere_quotient_parity.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

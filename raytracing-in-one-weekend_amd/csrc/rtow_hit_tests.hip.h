@@ -124,6 +124,50 @@ __host__ __device__ __forceinline__ bool sphere_hit(V3 oc, V3 d, float a, float 
     return false;
 }
 
+// The quotient of sphere_hit for a run of tests that share the ray (TEST of the sphere kernels): the divisor a = dot(d, d) is the run's, so its correctly rounded
+// reciprocal ya = RN(1 / a) and the range test aOk (exact_div3's bOk: positive, biased exponent in [96, 159]) are formed once per run and a candidate pays three instructions
+// for t = n / a instead of the IEEE expansion (exact_div_step, enumerated over every mantissa pair by tests/native/exactdiv_parity.hip).
+//  * One quotient a candidate.  sphere_hit's decision tree on sphere_hit's operands, with the root picked before the division: n0 > 0 takes the first root, anything
+//    else the second (n1 >= n0, so a positive n0 has a positive n1 behind it).  Only a first root whose quotient fails `t < inf && t > 0` goes on to the second one,
+//    as there - a cold region: the quotient of a positive numerator fails only by overflow, underflow to zero or a degenerate a.
+//  * The quotient from the reciprocal where exact_div3's ranges hold: a in [2^-31, 2^33) and n in [2^-63, 2^65) (the numerators' range of exact_div3, positive only).
+//    Then the quotient lies in (2^-96, 2^96): positive, finite and normal, so `t < inf && t > 0` holds and is not evaluated.  Anything else takes n / a and both tests.
+// n0 and n1 as sphere_hit forms them; tests/native/sphere_quotient_parity.hip compares the two functions bit for bit.
+__device__ __forceinline__ bool sphere_root_quotient(float n0, float n1, float a, float ya, bool aOk, float& tOut)
+{
+    const bool first = n0 > 0;
+    const float n = first ? n0 : n1;
+    // Straight-line for the lanes in range: the short quotient is formed for every lane (on other operands it is a value nobody reads) and ONE rare region redoes
+    // the lanes with a positive numerator outside the ranges.  bits(n) in [0x20000000, 0x60000000) says positive AND biased exponent in [64, 191] in one unsigned
+    // compare; `&`, not `&&`: a scalar AND of two lane masks, no region for the second test.  tOut is written without a hit too (that same unread value, or the
+    // quotient that failed its tests): callers read it behind the returned flag only, as they do sphere_hit's.
+    bool hit = RTOW_EXACT_DIV3 && (aOk & ((__float_as_uint(n) - 0x20000000u) < 0x40000000u));
+    float t = exact_div_step(n, a, ya);
+    if (__builtin_expect(n > 0 && !hit, 0)) {
+        t = n / a;
+        hit = t < __builtin_inff() && t > 0;
+        if (!hit && first && n1 > 0) {
+            t = n1 / a;
+            hit = t < __builtin_inff() && t > 0;
+        }
+    }
+    tOut = t;
+    return hit;
+}
+
+// sphere_hit with the run's reciprocal: the same operands, the same result for every operand (device only: the host probe keeps sphere_hit)
+__device__ __forceinline__ bool sphere_hit_shared_rcp(V3 oc, V3 d, float a, float ya, bool aOk, float radius, float& tOut)
+{
+    const float b = dot(oc, d);
+    const float c = dot(oc, oc) - radius * radius;
+    const float disc = b * b - a * c;
+    if (disc > 0) {
+        const float sq = RTOW_SQRT(disc);
+        return sphere_root_quotient(-b - sq, -b + sq, a, ya, aOk, tOut);
+    }
+    return false;
+}
+
 // the same test with an arbitrary tMin (strict: t > tMin), RT/HitTests.cs:40,49
 __host__ __device__ __forceinline__ bool sphere_hit_tmin(V3 oc, V3 d, float a, float radius, float tMin, float& tOut)
 {

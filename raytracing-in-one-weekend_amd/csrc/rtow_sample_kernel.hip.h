@@ -1826,6 +1826,11 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
             // ================= exact sphere tests: FindHits (JOBS/SampleBatchJob.cs:450-475) =================
             if (st == ST_TEST) {
                 const float a = dot(rd, rd);
+                // the sphere kinds take every quotient of this run from a's reciprocal (sphere_hit_shared_rcp): the divisor's range test and RN(1 / a), once per run.
+                // (exact_div3's bOk without its mask: a sum of squares has no sign bit, and a negative divisor, which the short form would not refuse, fails this one too)
+                // (the other kinds read neither)
+                const bool aOk = VOLUMES || GENERAL ? false : (__float_as_uint(a) - 0x30000000u) < 0x20000000u;
+                const float ya = VOLUMES || GENERAL ? 0.0f : RTOW_RCP(a);
                 for (;;) {
                 if (LONG_LISTS) {
                     if (cur <= -2) {
@@ -1927,7 +1932,7 @@ __global__ void __launch_bounds__(geo_block_threads(GEO)) sample_batch_kernel(co
                     } else {
                         V3 c; float r, t;
                         sphere_at<ALL_LDS, HAS_MOTION>(sc, L, i, rtime, c, r);
-                        if (sphere_hit(sub(ro, c), rd, a, r, t) && t <= best) {
+                        if (sphere_hit_shared_rcp(sub(ro, c), rd, a, ya, aOk, r, t) && t <= best) {
                             // same tie rule as above (duplicate or exactly tangent spheres)
                             const unsigned* rank = reinterpret_cast<const unsigned*>(section<ALL_LDS>(sc, L.rankOffset));
                             if (EXACT_TIES) tieAtBest = !(t < best) && prim >= 0;                    // t == best here
