@@ -317,6 +317,10 @@ typedef enum RtowContextFlags {
                                                     * (UNITY/BvhNodeData.cs:122-213, JOBS/SampleBatchJob.cs:427-440, UNITY/Raytracer.cs:54-64) - instead of the
                                                     * library's own tree.  Costs a second, unpruned walk per ray in such batches */
     RTOW_CONTEXT_NO_CAMERA_RAY_LISTS = 1u << 3,    /* development: walk the tree for camera rays too */
+    RTOW_CONTEXT_UNPRUNED_CAMERA_RAY_LISTS = 1u << 9, /* development: keep on a pixel's camera-ray list every tree node whose leaf boxes its beam meets.  By default (sphere
+                                                    * scenes) a node is left out when no camera ray of the pixel can hit or see any of its spheres; launches that write
+                                                    * 16-byte diagnostic records keep the whole lists anyway, so BoundsHitCount / CandidateCount do not depend on it.
+                                                    * Same results either way (rtowGetCameraRayListStats shows the lists) */
     RTOW_CONTEXT_NO_CHUNK_ORDER = 1u << 4,         /* development: hand out pixel chunks in row order, not most-expensive-first */
     RTOW_CONTEXT_FORCE_WIDE_CODES = 1u << 5,       /* development: run the scene through the kernels with 32-bit candidate / stack codes (every scene kind has them)
                                                     * (what scenes beyond 65 535 entities or tree nodes use; the tree is then read from HBM) */
@@ -388,6 +392,17 @@ RTOW_API int rtowDestroyContext(RtowContext context);
  * Copies the description, builds the native BVH, uploads the flat GPU layout. Called only when the world changes. */
 RTOW_API int rtowUploadScene(RtowContext context, const RtowSceneDesc* scene);
 RTOW_API int rtowGetSceneInfo(RtowContext context, RtowSceneInfo* outInfo);
+
+/* Development: the camera-ray node lists the context holds right now - one list per owned pixel of the last sample launch's (scene, view, size, slice, jitter), built
+ * once and reused until one of them changes.  Counted on demand by a small reduction on the device (never on the batch path); waits for that launch. */
+typedef struct RtowCameraRayListStats {
+    uint64_t pixelsWithEntries[9];  /* [k]: owned pixels whose list names k tree nodes (k = 0: every camera ray of the pixel goes straight to the sky) */
+    uint64_t pixelsWithoutList;     /* owned pixels whose camera rays walk the tree (more nodes than a list holds, or a degenerate view) */
+    uint64_t ownedPixels;           /* the sum of the ten counters */
+    int32_t pruned;                 /* 1: built with pruning; 0: whole lists (16-byte diagnostic records, or RTOW_CONTEXT_UNPRUNED_CAMERA_RAY_LISTS) */
+    int32_t valid;                  /* 0: the context holds no lists (no sample launch since the upload, or RTOW_CONTEXT_NO_CAMERA_RAY_LISTS): everything else is zero */
+} RtowCameraRayListStats;
+RTOW_API int rtowGetCameraRayListStats(RtowContext context, RtowCameraRayListStats* outStats);
 
 /* replaces: `new Cubemap(skyCubemap)` when the environment is built (UNITY/Raytracer.cs, RT/Texture.cs:150-169): copies the six
  * faces to the device; sample batches whose environment.skyType is RTOW_SKY_CUBEMAP then evaluate Cubemap.Sample(ray.Direction)

@@ -141,6 +141,7 @@ LogCallback = C.CFUNCTYPE(None, C.c_int32, C.c_char_p, C.c_char_p, C.c_void_p)
 # RtowContextFlags
 CONTEXT_EXACT_TIES_ALWAYS, CONTEXT_EXACT_TIES_NEVER, CONTEXT_REFERENCE_DIAGNOSTICS, CONTEXT_NO_CAMERA_RAY_LISTS, CONTEXT_NO_CHUNK_ORDER, CONTEXT_FORCE_WIDE_CODES, CONTEXT_NO_THRESHOLD_TUNING, CONTEXT_NO_CHAIN_FUSION = 1, 2, 4, 8, 16, 32, 64, 128
 CONTEXT_NODE_IMAGE_64 = 256   # development: 64-byte tree nodes in LDS where the sphere kernels would walk the 80-byte image
+CONTEXT_UNPRUNED_CAMERA_RAY_LISTS = 512   # development: camera-ray lists keep every node whose leaf boxes the pixel's beam meets
 # RtowGatherMask
 GATHER_COLOR, GATHER_NORMAL, GATHER_ALBEDO, GATHER_SAMPLE_COUNT_WEIGHT, GATHER_ALL, GATHER_NO_BATCH_WAIT, GATHER_LOOPBACK = 1, 2, 4, 8, 15, 16, 32
 
@@ -519,6 +520,11 @@ class ToneMapParams(C.Structure):
     _fields_ = [("pixelCount", C.c_int32), ("curve", C.c_int32), ("exposure", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class CameraRayListStats(C.Structure):
+    """RtowCameraRayListStats (96 bytes)"""
+    _fields_ = [("pixelsWithEntries", C.c_uint64 * 9), ("pixelsWithoutList", C.c_uint64), ("ownedPixels", C.c_uint64), ("pruned", C.c_int32), ("valid", C.c_int32)]
+
+
 # every symbol include/rtow.h declares (tests/test_abi.py checks the library exports all of them)
 EXPORTED_SYMBOLS = [
     "rtowGetApiVersion", "rtowErrorString", "rtowCreateContext", "rtowDestroyContext", "rtowUploadScene",
@@ -533,5 +539,5 @@ EXPORTED_SYMBOLS = [
     "rtowBuildPixelListDevice", "rtowSamplePixelsDevice", "rtowTraceGuideRaysDevice", "rtowTraceGuideViewDevice",
     "rtowAccumulateMomentsDevice", "rtowDenoiseVarianceDevice", "rtowReprojectMomentsDevice", "rtowEstimateMomentsDevice",
     "rtowNoiseMaskDevice", "rtowRectifyHistoryDevice", "rtowReprojectAccumBilinearDevice",
-    "rtowMeterExposureDevice", "rtowFinalizeToneMappedDevice", "rtowRecordPathsDevice",
+    "rtowMeterExposureDevice", "rtowFinalizeToneMappedDevice", "rtowRecordPathsDevice", "rtowGetCameraRayListStats",
 ]

@@ -357,18 +357,23 @@ int refreshCameraRays(RtowContext ctx, SampleKernelArgs& a, uint32_t ownedPixels
     const int reserved = growDevice(ctx, {{&ctx->dPixCand, listBytes}}, &grew);
     if (grew) ctx->pixCandValid = false;
     RTOW_TRY(reserved);
+    // Pruned lists (rtow_camera_lists.hip.h) leave out what no camera ray of the pixel can hit or see: the frame is the same, but BoundsHitCount / CandidateCount
+    // are not - so a launch that writes the 16-byte records keeps the whole lists, and the lists are rebuilt when a context goes from one record size to the other
+    const bool prune = !(ctx->flags & RTOW_CONTEXT_UNPRUNED_CAMERA_RAY_LISTS) && !(a.diagnostics && a.diagnosticsStride >= 16);
     const bool same = ctx->pixCandValid && ctx->pixCandScene == ctx->sceneSerial && memcmp(&ctx->pixCandView, &a.view, sizeof(RtowView)) == 0 &&
                       ctx->pixCandW == a.width && ctx->pixCandH == a.height && ctx->pixCandOff == a.sliceOffset && ctx->pixCandDiv == a.sliceDivider &&
-                      ctx->pixCandJitter == (a.subPixelJitter ? 1 : 0);
+                      ctx->pixCandJitter == (a.subPixelJitter ? 1 : 0) && ctx->pixCandPruned == prune;
     if (!same) {
         SampleKernelArgs perPixel = a;                       // the lists are per pixel whatever the work units are
         perPixel.totalWork = ownedPixels;
-        HIP_TRY(ctx, launchPrimaryCandidates(perPixel, ctx->dPixCand, stream), RTOW_ERROR_LAUNCH_FAILURE);
+        HIP_TRY(ctx, launchPrimaryCandidates(perPixel, ctx->dPixCand, prune, stream), RTOW_ERROR_LAUNCH_FAILURE);
         ctx->pixCandValid = true;
         ctx->pixCandScene = ctx->sceneSerial;
         ctx->pixCandView = a.view;
         ctx->pixCandW = a.width; ctx->pixCandH = a.height; ctx->pixCandOff = a.sliceOffset; ctx->pixCandDiv = a.sliceDivider;
         ctx->pixCandJitter = a.subPixelJitter ? 1 : 0;
+        ctx->pixCandPruned = prune;
+        ctx->pixCandOwned = ownedPixels;
     }
     a.pixelCandidates = ctx->dPixCand;
     return RTOW_SUCCESS;
@@ -1303,6 +1308,31 @@ RTOW_API int rtowGetSceneInfo(RtowContext ctx, RtowSceneInfo* info)
     info->thresholdSet = ctx->tunedScene == ctx->sceneSerial ? ctx->tunedCandidate : -1;
     for (int k = 0; k < 9; k++) info->schedulerTune[k] = ctx->tune[k];
     info->schedulerTune[7] = ctx->schedulerKnob;
+    return RTOW_SUCCESS;
+}
+
+// What the camera-ray lists the context holds look like: a reduction over them on demand, behind the batch that last used them; blocks until it is done
+RTOW_API int rtowGetCameraRayListStats(RtowContext ctx, RtowCameraRayListStats* stats)
+{
+    if (!ctx || !stats) return RTOW_ERROR_INVALID_VALUE;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    memset(stats, 0, sizeof(*stats));
+    if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
+    if (!ctx->pixCandValid || ctx->pixCandScene != ctx->sceneSerial || !ctx->dPixCand) return RTOW_SUCCESS;      // no lists: valid = 0
+    hipStream_t s;
+    RTOW_TRY(useDevice(ctx, nullptr, &s));
+    RTOW_TRY(growDevice(ctx, {{&ctx->dPixCandStats, 10 * sizeof(unsigned long long)}}));
+    if (ctx->haveBatchDone) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->evBatchDone, 0), RTOW_ERROR_LAUNCH_FAILURE);
+    HIP_TRY(ctx, launchCameraListStats(ctx->dPixCand, ctx->pixCandOwned, ctx->pixCandW, ctx->pixCandOff, ctx->pixCandDiv, ctx->wideCodes, ctx->dPixCandStats, s),
+            RTOW_ERROR_LAUNCH_FAILURE);
+    unsigned long long counts[10];
+    HIP_TRY(ctx, hipMemcpyAsync(counts, ctx->dPixCandStats, sizeof(counts), hipMemcpyDeviceToHost, s), RTOW_ERROR_LAUNCH_FAILURE);
+    HIP_TRY(ctx, hipStreamSynchronize(s), RTOW_ERROR_LAUNCH_FAILURE);
+    for (int k = 0; k < 9; k++) stats->pixelsWithEntries[k] = counts[k];
+    stats->pixelsWithoutList = counts[9];
+    stats->ownedPixels = ctx->pixCandOwned;
+    stats->pruned = ctx->pixCandPruned ? 1 : 0;
+    stats->valid = 1;
     return RTOW_SUCCESS;
 }
 

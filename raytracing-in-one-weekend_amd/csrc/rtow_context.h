@@ -95,6 +95,9 @@ struct RtowContext_t {
     uint64_t sceneSerial = 0, pixCandScene = 0;
     RtowView pixCandView{};
     int pixCandW = 0, pixCandH = 0, pixCandOff = 0, pixCandDiv = 0, pixCandJitter = 0;
+    bool pixCandPruned = false;           // ... built with pruning (launches that write 16-byte diagnostic records, and RTOW_CONTEXT_UNPRUNED_CAMERA_RAY_LISTS, keep whole lists)
+    uint32_t pixCandOwned = 0;            // owned pixels the lists were built for
+    DeviceMem<unsigned long long> dPixCandStats;   // rtowGetCameraRayListStats: ten counters, allocated on first use
 
     // grow-only staging for rtowSampleBatch (host buffers) - like CudaBuffer.EnsureCapacity (OptixApi.cs:240-251)
     DeviceMem<float> dColor, dNormal, dAlbedo, dScw;   // (grow together)

@@ -372,7 +372,10 @@ hipError_t launchSampleTrianglesTextured(const SampleKernelArgs& args, int numBl
 hipError_t launchSampleTrianglesTexturedTies(const SampleKernelArgs& args, int numBlocks, hipStream_t stream, bool allLds);
 hipError_t launchSampleBatch(const SampleKernelArgs& args, int numBlocks, hipStream_t stream);
 hipError_t launchPrepareMaterials(uint8_t* blob, const SceneLayout& layout, hipStream_t stream); // derived material constants, on device
-hipError_t launchPrimaryCandidates(const SampleKernelArgs& args, uint2* out, hipStream_t stream);
+// prune: leave out what no camera ray of the pixel can hit or see (rtow_camera_lists.hip.h; sphere kinds only - other kinds keep their lists either way)
+hipError_t launchPrimaryCandidates(const SampleKernelArgs& args, uint2* out, bool prune, hipStream_t stream);
+// rtowGetCameraRayListStats: counts[0 .. 8] = owned pixels with that many list entries, counts[9] = without a list; counts: 10 words of device memory, cleared here
+hipError_t launchCameraListStats(const uint2* lists, unsigned ownedPixels, int width, int sliceOffset, int sliceDivider, bool wide, unsigned long long* counts, hipStream_t stream);
 hipError_t launchFoldUnitRecords(const SampleKernelArgs& args, hipStream_t stream);
 hipError_t launchBuildChunkOrder(const unsigned short* pixelCost, unsigned* cost, unsigned chunkCount, unsigned* order, int byMax, hipStream_t stream);
 // ticketMap[t] = t for t < count (the tiles themselves)

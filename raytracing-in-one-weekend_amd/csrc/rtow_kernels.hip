@@ -7,6 +7,7 @@
 #include "rtow_vecmath.hip.h"
 #include "rtow_finalize.hip.h"
 #include "rtow_schedule.hip.h"
+#include "rtow_camera_lists.hip.h"
 
 namespace rtow {
 
@@ -88,7 +89,7 @@ __global__ void __launch_bounds__(256) fold_unit_records_kernel(SampleKernelArgs
 // delta(B) = R + (far + R) * (chordPix + chordLens) on every side - tested with a slab test, tMin = 0.  chordPix is exact at the
 // pixel's corners (a cone cut by the image plane is convex).  Lists longer than 4 fall back to the normal walk (kNoPrimaryList).
 // ------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) primary_candidates_kernel(SampleKernelArgs A, uint2* __restrict__ out)
+__global__ void __launch_bounds__(256) primary_candidates_kernel(SampleKernelArgs A, uint2* __restrict__ out, int prune)
 {
     const unsigned ticket = blockIdx.x * blockDim.x + threadIdx.x;
     if (ticket >= A.totalWork) return;
@@ -134,36 +135,89 @@ __global__ void __launch_bounds__(256) primary_candidates_kernel(SampleKernelArg
         return !(tn > tf);                                                      // NaN (cannot happen with finite inv) would count as a hit
     };
 
+    // Pruning (rtow_camera_lists.hip.h: the two rules, their margins and what they rest on).  A leaf child found in the beam is left out when no ray of the pixel can be
+    // reported as hitting its sphere (a), or when a static sphere that every ray of the pixel is certain to be reported as hitting lies wholly in front of it (b); a node is
+    // listed only if one of its leaf children in the beam stays.  Sphere kinds only (scenes with volumes keep every hit of a ray; general, triangle and textured kinds are left
+    // as they are), static spheres only: a moving sphere is never dropped and never covers.  The rounding allowance of the exact test is the header's E = 2^-19 (|oc|^2 + r^2),
+    // derived there from the text of sphere_hit.  Rule (b) needs the covering spheres first, so the beam is walked twice: once for the smallest tA, once for the list.
+    const CameraBeam beam = camera_beam(o.x, o.y, o.z, dc.x, dc.y, dc.z, R, spread, gmin, ok);
+    const bool pruning = prune != 0 && L.sceneKind <= SCENE_KIND_SPHERES_MOTION && beam.prunable;
+    const GpuSphere* spheres = reinterpret_cast<const GpuSphere*>(A.sceneBlob + L.sphereOffset);
+    const GpuMotion* motion = L.hasMotion ? reinterpret_cast<const GpuMotion*>(A.sceneBlob + L.motionOffset) : nullptr;
+    bool covered = false;
+    double tCover = 0.0;
+
     const unsigned none = A.wideCodes ? 0xffffffffu : 0xffffu;
     const int capacity = (A.wideCodes || L.sceneKind > SCENE_KIND_SPHERES_MOTION) ? 4 : 8;      // what one uint4 per pixel holds - and what the scene kind's kernels keep of it (sphere kinds: all eight)
     unsigned list[8] = {none, none, none, none, none, none, none, none};
     int count = 0;
     int stack[RTOW_STACK_CAPACITY + 1];
-    int sp = 0, cur = 0;
     const GpuNode* nodes = reinterpret_cast<const GpuNode*>(A.sceneBlob + L.nodeOffset);
-    while (ok && cur >= 0) {
-        const int node = cur;
-        const GpuNode n = nodes[node];
-        cur = -1;
-        bool leafChildInBeam = false;
-        for (int side = 0; side < 2; side++) {
-            if (side == 1 && L.sphereCount < 2) break;                          // single-entity scene: the second child is a placeholder
-            const int child = side ? n.child1 : n.child0;
-            if (!beamHitsBox(n.lox[side], n.loy[side], n.loz[side], n.hix[side], n.hiy[side], n.hiz[side])) continue;
-            if (child < 0) leafChildInBeam = true;
-            else if (cur < 0) cur = child;
-            else if (sp <= RTOW_STACK_CAPACITY) stack[sp++] = child;
-            else ok = false;
+    for (int pass = pruning ? 0 : 1; pass < 2; pass++) {
+        int sp = 0, cur = 0;
+        while (ok && cur >= 0) {
+            const int node = cur;
+            const GpuNode n = nodes[node];
+            cur = -1;
+            bool leafChildStays = false;
+            for (int side = 0; side < 2; side++) {
+                if (side == 1 && L.sphereCount < 2) break;                          // single-entity scene: the second child is a placeholder
+                const int child = side ? n.child1 : n.child0;
+                if (!beamHitsBox(n.lox[side], n.loy[side], n.loz[side], n.hix[side], n.hiy[side], n.hiz[side])) continue;
+                if (child < 0) {
+                    if (!pruning) { leafChildStays = true; continue; }
+                    const int prim = ~child;
+                    if (motion && motion[prim].moving != 0) { leafChildStays = true; continue; }
+                    const GpuSphere s = spheres[prim];
+                    if (pass == 0) {
+                        double t;
+                        if (camera_sphere_covers(beam, s.cx, s.cy, s.cz, s.radius, t)) { tCover = covered ? (t < tCover ? t : tCover) : t; covered = true; }
+                    } else if (!camera_sphere_unreachable(beam, s.cx, s.cy, s.cz, s.radius) && !(covered && camera_sphere_hidden(beam, s.cx, s.cy, s.cz, s.radius, tCover))) {
+                        leafChildStays = true;
+                    }
+                }
+                else if (cur < 0) cur = child;
+                else if (sp <= RTOW_STACK_CAPACITY) stack[sp++] = child;
+                else ok = false;
+            }
+            if (leafChildStays && pass == 1) {                                      // the NODE goes on the list: its leaf boxes are re-tested per ray
+                if (count == capacity) ok = false;
+                for (int k = 0; k < 8; k++) if (k == count) list[k] = (unsigned)node;
+                count++;
+            }
+            if (cur < 0 && sp > 0) cur = stack[--sp];
         }
-        if (leafChildInBeam) {                                                  // the NODE goes on the list: its leaf boxes are re-tested per ray
-            if (count == capacity) ok = false;
-            for (int k = 0; k < 8; k++) if (k == count) list[k] = (unsigned)node;
-            count++;
-        }
-        if (cur < 0 && sp > 0) cur = stack[--sp];
     }
     if (A.wideCodes) reinterpret_cast<uint4*>(out)[pix] = ok ? make_uint4(list[0], list[1], list[2], list[3]) : make_uint4(0xffffffffu, 0u, 0u, 0u);   // first slot empty, second not: no list
     else reinterpret_cast<uint4*>(out)[pix] = ok ? make_uint4(list[0] | (list[1] << 16), list[2] | (list[3] << 16), list[4] | (list[5] << 16), list[6] | (list[7] << 16)) : make_uint4(kNoPrimaryList, 0u, 0u, 0u);
+}
+
+// What the lists in `lists` look like (rtowGetCameraRayListStats): counts[k] = owned pixels whose list has k entries (k = 0 .. 8), counts[9] = owned pixels without a
+// list (they walk the tree).  counts is zeroed by the launcher; never on the batch path.
+__global__ void __launch_bounds__(256) camera_list_stats_kernel(const uint4* __restrict__ lists, unsigned ownedPixels, int width, int sliceOffset, int sliceDivider, int wide,
+                                                                unsigned long long* __restrict__ counts)
+{
+    __shared__ unsigned local[10];
+    if (threadIdx.x < 10) local[threadIdx.x] = 0u;
+    __syncthreads();
+    for (unsigned t = blockIdx.x * blockDim.x + threadIdx.x; t < ownedPixels; t += gridDim.x * blockDim.x) {
+        const unsigned ownedRow = t / (unsigned)width, cx = t - ownedRow * (unsigned)width;
+        const size_t pix = (size_t)(sliceOffset + (int)ownedRow * sliceDivider) * (size_t)width + cx;
+        const uint4 l = lists[pix];
+        unsigned k;
+        if (wide) {
+            const unsigned e[4] = {l.x, l.y, l.z, l.w};
+            if (l.x == 0xffffffffu && l.y != 0xffffffffu) k = 9u;
+            else for (k = 0; k < 4u && e[k] != 0xffffffffu; k++) {}
+        } else {
+            const unsigned e[4] = {l.x, l.y, l.z, l.w};
+            if (l.x == kNoPrimaryList) k = 9u;
+            else for (k = 0; k < 8u && ((e[k >> 1] >> (16u * (k & 1u))) & 0xffffu) != 0xffffu; k++) {}
+        }
+        atomicAdd(&local[k], 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x < 10 && local[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)local[threadIdx.x]);
 }
 
 // Derived per-entity transform data for SCENE_KIND_GENERAL, on the device: InverseTransform = inverse(OriginTransform)
@@ -725,9 +779,19 @@ hipError_t launchFoldUnitRecords(const SampleKernelArgs& args, hipStream_t strea
     return hipGetLastError();
 }
 
-hipError_t launchPrimaryCandidates(const SampleKernelArgs& args, uint2* out, hipStream_t stream)
+hipError_t launchPrimaryCandidates(const SampleKernelArgs& args, uint2* out, bool prune, hipStream_t stream)
 {
-    hipLaunchKernelGGL(primary_candidates_kernel, dim3((args.totalWork + 255u) / 256u), dim3(256), 0, stream, args, out);
+    hipLaunchKernelGGL(primary_candidates_kernel, dim3((args.totalWork + 255u) / 256u), dim3(256), 0, stream, args, out, prune ? 1 : 0);
+    return hipGetLastError();
+}
+
+hipError_t launchCameraListStats(const uint2* lists, unsigned ownedPixels, int width, int sliceOffset, int sliceDivider, bool wide, unsigned long long* counts, hipStream_t stream)
+{
+    hipError_t e = hipMemsetAsync(counts, 0, 10 * sizeof(unsigned long long), stream);
+    if (e != hipSuccess || ownedPixels == 0u) return e;
+    const unsigned blocks = (ownedPixels + 255u) / 256u;
+    hipLaunchKernelGGL(camera_list_stats_kernel, dim3(blocks < 1024u ? blocks : 1024u), dim3(256), 0, stream, reinterpret_cast<const uint4*>(lists), ownedPixels, width,
+                       sliceOffset, sliceDivider, wide ? 1 : 0, counts);
     return hipGetLastError();
 }
 

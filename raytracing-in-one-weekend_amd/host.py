@@ -181,6 +181,13 @@ class Context:
         check(load().rtowGetSceneInfo(self.handle, C.byref(info)), "rtowGetSceneInfo")
         return info
 
+    def camera_ray_list_stats(self):
+        """rtowGetCameraRayListStats as a dict: entries[k] = owned pixels whose camera-ray list names k nodes, no_list, owned, pruned, valid."""
+        st = abi.CameraRayListStats()
+        check(load().rtowGetCameraRayListStats(self.handle, C.byref(st)), "rtowGetCameraRayListStats")
+        return {"entries": [int(x) for x in st.pixelsWithEntries], "no_list": int(st.pixelsWithoutList), "owned": int(st.ownedPixels),
+                "pruned": bool(st.pruned), "valid": bool(st.valid)}
+
     def hit_world(self, origin, direction, time=0.0):
         """Raytracer.HitWorld (UNITY/Raytracer.cs:1353; the auto-focus probe of ScheduleSample, :608-609) through rtowProbeNearestHit:
         (hit, distance, entity index) - `if hit: focusDistance = distance`."""

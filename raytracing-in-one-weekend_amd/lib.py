@@ -51,6 +51,7 @@ def load():
     lib.rtowUploadBlueNoise.argtypes = [vp, C.POINTER(abi.BlueNoiseDesc)]
     lib.rtowUploadStbNoise.argtypes = [vp, C.POINTER(abi.StbNoiseDesc)]
     lib.rtowGetSceneInfo.argtypes = [vp, C.POINTER(abi.SceneInfo)]
+    lib.rtowGetCameraRayListStats.argtypes = [vp, C.POINTER(abi.CameraRayListStats)]
     lib.rtowSampleBatch.argtypes = [vp, C.POINTER(abi.SampleParams), AB, AB, vp, vp]
     lib.rtowSampleBatchDevice.argtypes = [vp, C.POINTER(abi.SampleParams), AB, AB, vp, vp, vp]
     lib.rtowSampleBatchChainDevice.argtypes = [vp, C.c_int32, C.POINTER(abi.SampleParams), AB, AB, C.POINTER(vp), vp, vp]
