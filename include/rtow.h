@@ -267,6 +267,7 @@ typedef struct RtowEnvironment {
 
 typedef struct RtowSampleParams {
     RtowFloat2 size;                /* SampleBatchJob.Size (float2; coordinates use (int)Size.x, :64-67) */
+                                    /* each component finite and in [1, 2^31), else RTOW_ERROR_INVALID_VALUE; the fraction is honoured: u = (x + jitter) / Size.x, and the float's bits are in the key of the camera-ray lists */
     int32_t sliceOffset;            /* :26  rows with (row % sliceDivider) != sliceOffset are skipped (:69-70) */
     int32_t sliceDivider;           /* :27  (>= 1) */
     uint32_t seed;                  /* :28 */

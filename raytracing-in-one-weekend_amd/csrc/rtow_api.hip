@@ -360,8 +360,12 @@ int refreshCameraRays(RtowContext ctx, SampleKernelArgs& a, uint32_t ownedPixels
     // Pruned lists (rtow_camera_lists.hip.h) leave out what no camera ray of the pixel can hit or see: the frame is the same, but BoundsHitCount / CandidateCount
     // are not - so a launch that writes the 16-byte records keeps the whole lists, and the lists are rebuilt when a context goes from one record size to the other
     const bool prune = !(ctx->flags & RTOW_CONTEXT_UNPRUNED_CAMERA_RAY_LISTS) && !(a.diagnostics && a.diagnosticsStride >= 16);
+    // a pixel's beam spans cx / Size.x .. (cx + 1) / Size.x of the view: the fraction of Size moves every beam, so the key holds the float's bits beside the integer frame
+    uint32_t sizeBits[2];
+    memcpy(&sizeBits[0], &a.sizeX, sizeof(uint32_t)); memcpy(&sizeBits[1], &a.sizeY, sizeof(uint32_t));
     const bool same = ctx->pixCandValid && ctx->pixCandScene == ctx->sceneSerial && memcmp(&ctx->pixCandView, &a.view, sizeof(RtowView)) == 0 &&
-                      ctx->pixCandW == a.width && ctx->pixCandH == a.height && ctx->pixCandOff == a.sliceOffset && ctx->pixCandDiv == a.sliceDivider &&
+                      ctx->pixCandW == a.width && ctx->pixCandH == a.height && ctx->pixCandSizeBits[0] == sizeBits[0] && ctx->pixCandSizeBits[1] == sizeBits[1] &&
+                      ctx->pixCandOff == a.sliceOffset && ctx->pixCandDiv == a.sliceDivider &&
                       ctx->pixCandJitter == (a.subPixelJitter ? 1 : 0) && ctx->pixCandPruned == prune;
     if (!same) {
         SampleKernelArgs perPixel = a;                       // the lists are per pixel whatever the work units are
@@ -371,6 +375,7 @@ int refreshCameraRays(RtowContext ctx, SampleKernelArgs& a, uint32_t ownedPixels
         ctx->pixCandScene = ctx->sceneSerial;
         ctx->pixCandView = a.view;
         ctx->pixCandW = a.width; ctx->pixCandH = a.height; ctx->pixCandOff = a.sliceOffset; ctx->pixCandDiv = a.sliceDivider;
+        ctx->pixCandSizeBits[0] = sizeBits[0]; ctx->pixCandSizeBits[1] = sizeBits[1];
         ctx->pixCandJitter = a.subPixelJitter ? 1 : 0;
         ctx->pixCandPruned = prune;
         ctx->pixCandOwned = ownedPixels;

@@ -89,12 +89,14 @@ struct RtowContext_t {
     // sky cubemap (rtowUploadSkyCubemap)
     DeviceMem<uint8_t> dCubemap;
     RtowCubemapDesc cubemap{};   // .faces is not kept (host pointer): dCubemap holds the copy, null when none
-    // camera-ray candidate lists (primary_candidates_kernel): valid for one (scene upload, view, size, slice, jitter) configuration
+    // camera-ray candidate lists (primary_candidates_kernel): valid for one (scene upload, view, size - the integer frame and the float Size the beams divide by -,
+    // slice, jitter, pruning) configuration
     DeviceMem<uint2> dPixCand;
     bool pixCandValid = false;
     uint64_t sceneSerial = 0, pixCandScene = 0;
     RtowView pixCandView{};
     int pixCandW = 0, pixCandH = 0, pixCandOff = 0, pixCandDiv = 0, pixCandJitter = 0;
+    uint32_t pixCandSizeBits[2] = {0u, 0u};   // the bits of SampleKernelArgs.sizeX / sizeY: compared as bits, so that a NaN Size rebuilds every time rather than never
     bool pixCandPruned = false;           // ... built with pruning (launches that write 16-byte diagnostic records, and RTOW_CONTEXT_UNPRUNED_CAMERA_RAY_LISTS, keep whole lists)
     uint32_t pixCandOwned = 0;            // owned pixels the lists were built for
     DeviceMem<unsigned long long> dPixCandStats;   // rtowGetCameraRayListStats: ten counters, allocated on first use

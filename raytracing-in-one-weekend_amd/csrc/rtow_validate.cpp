@@ -35,6 +35,9 @@ bool denoiseParamsValid(const RtowDenoiseParams& p)
 int validateParams(const RtowSampleParams* p)
 {
     if (!p) return RTOW_ERROR_INVALID_VALUE;
+    // Size is a float2 whose fraction is honoured; the frame is (int) Size.  NaN, an infinity, anything below 1 or from 2^31 on is refused before the cast sees it
+    for (const float s : {p->size.x, p->size.y})
+        if (!(s >= 1.0f && s < 2147483648.0f)) return RTOW_ERROR_INVALID_VALUE;
     const int w = (int)p->size.x, h = (int)p->size.y;
     if (w <= 0 || h <= 0 || (long long)w * h > 0x7fffffffLL) return RTOW_ERROR_INVALID_VALUE;
     if (p->sliceDivider < 1 || p->sliceOffset < 0 || p->sliceOffset >= p->sliceDivider) return RTOW_ERROR_INVALID_VALUE;

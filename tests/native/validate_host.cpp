@@ -1,8 +1,9 @@
-// Stand-alone host program (tests/test_validate.py builds it with -fsanitize=address,undefined together with csrc/rtow_validate.cpp): every validator once with good
+// Stand-alone host program (tests/test_validate.py builds it with -fsanitize=address,undefined,float-cast-overflow together with csrc/rtow_validate.cpp): every validator once with good
 // arguments and once with each extreme - INT32_MIN / INT32_MAX sizes, radius and minTaps at their type limits, a list capacity of UINT32_MAX, buffers within a few
 // bytes of UINTPTR_MAX.  The sanitizers decide: no signed overflow, no read of a fake address.  Prints "ok"; what base + bytes does at the top of the address space goes
 // to stderr.
 #include <climits>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <initializer_list>
@@ -43,6 +44,15 @@ int main()
         q = sp; q.diagnosticsStride = v; CHECK(validateParams(&q) == BAD);
     }
     sp.size = {46341.0f, 46341.0f}; CHECK(validateParams(&sp) == BAD);
+    // Size is a float: what no int holds is refused before any cast (-fsanitize=float-cast-overflow watches the cast), a fraction is part of the contract
+    for (const float v : {NAN, INFINITY, -INFINITY, 3e9f, -3e9f, 2147483648.0f, 0.5f}) {
+        RtowSampleParams q = sp; q.size = {v, 54.0f}; CHECK(validateParams(&q) == BAD);
+        q.size = {96.0f, v}; CHECK(validateParams(&q) == BAD);
+        q.size = {v, v}; CHECK(validateParams(&q) == BAD);
+    }
+    sp.size = {96.9f, 54.0f}; CHECK(validateParams(&sp) == OK);
+    sp.size = {96.0f, 54.9f}; CHECK(validateParams(&sp) == OK);
+    sp.size = {96.9f, 54.9f}; CHECK(validateParams(&sp) == OK);
 
     // view size, guides, shade
     RtowTraceViewParams tv{}; tv.width = 8; tv.height = 8;

@@ -414,10 +414,10 @@ def test_accumulate_moments_takes_up_to_the_batch_limit(rt, shim):
 
 def test_validate_host_program_runs_clean_under_sanitizers(tmp_path):
     """tests/native/validate_host.cpp: every validator once good and once with each extreme - INT32_MIN / INT32_MAX sizes, radius and minTaps at their type limits, a list
-    capacity of UINT32_MAX, a base within a few bytes of UINTPTR_MAX - under the address and undefined-behaviour sanitizers (a stand-alone program: nothing is loaded
-    into Python)."""
+    capacity of UINT32_MAX, a base within a few bytes of UINTPTR_MAX, a sample Size that is NaN, infinite, below 1 or beyond INT32_MAX - under the address and
+    undefined-behaviour sanitizers and -fsanitize=float-cast-overflow, which `undefined` does not include (a stand-alone program: nothing is loaded into Python)."""
     exe = str(tmp_path / "validate_host")
-    build = subprocess.run(["g++", "-std=c++17", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+    build = subprocess.run(["g++", "-std=c++17", "-g", "-ffp-contract=off", "-fsanitize=address,undefined,float-cast-overflow", "-fno-sanitize-recover=all",
                             os.path.join(ROOT, "tests", "native", "validate_host.cpp"), os.path.join(CSRC, "rtow_validate.cpp"), "-o", exe],
                            capture_output=True, text=True, timeout=300)
     assert build.returncode == 0, build.stdout + build.stderr
