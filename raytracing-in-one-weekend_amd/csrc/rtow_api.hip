@@ -5,8 +5,8 @@
 // and rtowRecordPathsDevice, the one query the batch planner feeds.  There is no CPU implementation behind any entry point: without a usable HIP device
 // rtowCreateContext fails with RTOW_ERROR_NO_DEVICE and nothing else can be called.  The multi-GPU entry points (rtowComm*, rtowGatherRowsDevice,
 // rtowHybridPlan, rtowExchangeAccumDevice) are in rtow_comm.hip, the post passes in rtow_api_post.hip, the probes, the trace, shade and guide calls in
-// rtow_api_query.hip; the context itself - and queryScene, the resident scene as a query launch gets it - is rtow_context.h, and what
-// an entry point refuses before it takes its lock is rtow_validate.h.
+// rtow_api_query.hip; the context itself - and queryScene, the resident scene as a query launch gets it - is rtow_context.h, what
+// an entry point refuses before it takes its lock is rtow_validate.h, and what the caches a context keeps between launches are valid for is rtow_launch_cache.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -92,12 +92,22 @@ int ownedRows(const RtowSampleParams* p)
 // extrema / extremaKeys (optional, chains only): per batch where it reads SampleCountWeightExtrema (null = p's), and the [2 x count] keys its stores fold the batch's extrema into
 struct ChainSpec { int count; const uint32_t* seeds; void* const* diags; const RtowAccumBuffers* outs; const RtowFloat2* const* extrema = nullptr; unsigned* extremaKeys = nullptr; };
 
-// per-scene threshold measurement (launchSample): forget a measurement in flight (new scene, context going away)
+// per-scene threshold measurement (launchSample): forget the scene's measurement, in flight or settled (new scene, context going away; a measurement that ends settles after it)
 void dropThresholdTuning(RtowContext ctx)
 {
-    for (auto& e : ctx->tuneEvents) if (e) (void)hipEventDestroy(e);
-    ctx->tuneEvents.clear();
-    ctx->tunePending = false;
+    RtowContext_t::ThresholdTuning& t = ctx->tuning;
+    for (auto& e : t.events) if (e) (void)hipEventDestroy(e);
+    t.events.clear();
+    t.state = t.Unmeasured;
+    t.winner = -1;
+}
+
+// ... and settle it: `winner`'s thresholds (-1: the kernel kind's built-in ones) run until the next upload, nothing is measured again
+void settleThresholdTuning(RtowContext ctx, int winner)
+{
+    dropThresholdTuning(ctx);
+    ctx->tuning.state = ctx->tuning.Settled;
+    ctx->tuning.winner = winner;
 }
 
 // Which scenes get the same thresholds without being measured again: a host that re-uploads on every scene edit (sceneSerial moves) keeps what was
@@ -111,10 +121,11 @@ uint64_t sceneSignature(const CompiledScene& sc, bool wide)
 // read the probes' events if they are all complete (wait == false: otherwise leave them for a later call) and switch to the fastest candidate; true = thresholds changed or confirmed
 bool finishThresholdTuning(RtowContext ctx, bool wait)
 {
-    if (!ctx->tunePending || ctx->tuneEvents.empty()) return false;
-    const hipError_t q = wait ? hipEventSynchronize(ctx->tuneEvents.back()) : hipEventQuery(ctx->tuneEvents.back());
+    RtowContext_t::ThresholdTuning& tuning = ctx->tuning;
+    if (tuning.state != tuning.Pending || tuning.events.empty()) return false;
+    const hipError_t q = wait ? hipEventSynchronize(tuning.events.back()) : hipEventQuery(tuning.events.back());
     if (q == hipErrorNotReady) { (void)hipGetLastError(); return false; }
-    const int candidates = ctx->tuneCandidates, builtin = ctx->tuneBuiltin;
+    const int candidates = tuning.candidates, builtin = tuning.builtin;
     bool ok = q == hipSuccess;
     float best = 0.0f, builtinMs = 0.0f;
     int winner = -1;
@@ -122,7 +133,7 @@ bool finishThresholdTuning(RtowContext ctx, bool wait)
         float t = 0.0f;
         for (int r = 0; r < kTuneProbeRepeats; r++) {
             float ms = 0.0f;
-            if (hipEventElapsedTime(&ms, ctx->tuneEvents[(size_t)(r * candidates + c)], ctx->tuneEvents[(size_t)(r * candidates + c) + 1]) != hipSuccess) { ms = 1e30f; (void)hipGetLastError(); }
+            if (hipEventElapsedTime(&ms, tuning.events[(size_t)(r * candidates + c)], tuning.events[(size_t)(r * candidates + c) + 1]) != hipSuccess) { ms = 1e30f; (void)hipGetLastError(); }
             t = (r == 0 || ms < t) ? ms : t;
         }
         if (c == builtin) builtinMs = t;
@@ -131,17 +142,34 @@ bool finishThresholdTuning(RtowContext ctx, bool wait)
     if (ok && winner >= 0) {
         if (winner != builtin && !(best < kTuneMargin * builtinMs)) { winner = builtin; best = builtinMs; }
         candidateThresholds(winner, ctx->tune, 8);
-        ctx->tunedCandidate = winner;
-        ctx->tuneCache.push_back({ctx->sceneSignatureNow, winner});
+        tuning.cache.push_back({tuning.signature, winner});
         logf(ctx, 4, "tune", "stage thresholds measured on this scene: candidate %d of %d (%.3f ms per %d-sample probe)", winner, candidates, best, kTuneProbeSamples);
     } else {
         (void)hipGetLastError();
-        ctx->tunedCandidate = -1;
+        winner = -1;
         logf(ctx, 2, "tune", "threshold probes failed; the per-kind values stay");
     }
-    ctx->tunedScene = ctx->tunePendingScene;                    // measured (or not measurable): do not try again for this scene
-    dropThresholdTuning(ctx);
+    settleThresholdTuning(ctx, winner);                         // measured (or not measurable): do not try again for this scene
     return true;
+}
+
+// rtowUploadScene has put a new scene into ctx->scene (under both locks, the device idle): the one place where what the context knew of the old scene goes.  The camera-ray
+// lists and the chunk order carry the serial in their keys, so moving it is all they need
+void sceneReplaced(RtowContext ctx, bool wide)
+{
+    ctx->triWatchOff = false;
+    ctx->hCancel[3] = 0u;
+    ctx->sceneSerial++;
+    dropThresholdTuning(ctx);
+    ctx->tuning.sppSinceUpload = 0;
+    ctx->tuning.signature = sceneSignature(ctx->scene, wide);
+    if (ctx->userTune || (ctx->flags & RTOW_CONTEXT_NO_THRESHOLD_TUNING)) return;
+    for (const RtowContext_t::ThresholdTuning::Winner& e : ctx->tuning.cache)
+        if (e.signature == ctx->tuning.signature) {
+            // a scene like one this context has measured before (same kernel kind, entity / node / material counts): its thresholds, no new probes
+            candidateThresholds(e.winner, ctx->tune, 8);
+            settleThresholdTuning(ctx, e.winner);
+        }
 }
 
 uint64_t listCapacity(const RtowContext_t* ctx, bool volumes);    // (defined with growHitList below)
@@ -268,7 +296,7 @@ void setSchedulerValues(const RtowContext_t* ctx, const RtowSampleParams* p, Sam
     // (the adaptive {1, 50} schedule +0.5 ... 1 %) and a loss of 1 - 3 % where a pixel takes hundreds of samples (the wait costs more than the shared instructions save):
     // so by the samples a unit of work takes at most
     const unsigned unitSamples = p->rngPolicy != RTOW_RNG_REFERENCE ? kSampleGroup : (a.sampleCountMax > a.sampleCountMin ? a.sampleCountMax : a.sampleCountMin);
-    const int pixelGate = ctx->pixelGateOverride ? ctx->pixelGateOverride : (unitSamples <= 64u ? 4 : RTOW_PIXEL_GATE);
+    const int pixelGate = ctx->knob.pixelGateOverride ? ctx->knob.pixelGateOverride : (unitSamples <= 64u ? 4 : RTOW_PIXEL_GATE);
     // Lanes in a hurry (kernel: HURRY; twins of the static-sphere kind's generic reference-stream variants): a pixel that runs at more than this many rays per sample stops waiting for
     // company.  Batch groups run a pixel's batches side by side and keep every wave busy to the end: no bound, and the variants without the code.  Static spheres only: measured at
     // depth 32, same box (profiles/r06x_lanes_in_a_hurry.json) - cover scene +21 % (adaptive) / +33 % (chains), 10 000 spheres +24 %; in its first form (a bound on the batch's
@@ -354,33 +382,24 @@ int refreshCameraRays(RtowContext ctx, SampleKernelArgs& a, uint32_t ownedPixels
     const size_t pixels = (size_t)a.width * (size_t)a.height;
     const size_t listBytes = pixels * sizeof(uint4);      // 8 x 16-bit node codes per pixel; 4 x 32-bit with wide codes
     bool grew = false;
-    const int reserved = growDevice(ctx, {{&ctx->dPixCand, listBytes}}, &grew);
-    if (grew) ctx->pixCandValid = false;
+    RtowContext_t::CameraLists& lists = ctx->cameraLists;
+    const int reserved = growDevice(ctx, {{&lists.dLists, listBytes}}, &grew);
+    if (grew) lists.key.drop();
     RTOW_TRY(reserved);
     // Pruned lists (rtow_camera_lists.hip.h) leave out what no camera ray of the pixel can hit or see: the frame is the same, but BoundsHitCount / CandidateCount
     // are not - so a launch that writes the 16-byte records keeps the whole lists, and the lists are rebuilt when a context goes from one record size to the other
     const bool prune = !(ctx->flags & RTOW_CONTEXT_UNPRUNED_CAMERA_RAY_LISTS) && !(a.diagnostics && a.diagnosticsStride >= 16);
-    // a pixel's beam spans cx / Size.x .. (cx + 1) / Size.x of the view: the fraction of Size moves every beam, so the key holds the float's bits beside the integer frame
-    uint32_t sizeBits[2];
-    memcpy(&sizeBits[0], &a.sizeX, sizeof(uint32_t)); memcpy(&sizeBits[1], &a.sizeY, sizeof(uint32_t));
-    const bool same = ctx->pixCandValid && ctx->pixCandScene == ctx->sceneSerial && memcmp(&ctx->pixCandView, &a.view, sizeof(RtowView)) == 0 &&
-                      ctx->pixCandW == a.width && ctx->pixCandH == a.height && ctx->pixCandSizeBits[0] == sizeBits[0] && ctx->pixCandSizeBits[1] == sizeBits[1] &&
-                      ctx->pixCandOff == a.sliceOffset && ctx->pixCandDiv == a.sliceDivider &&
-                      ctx->pixCandJitter == (a.subPixelJitter ? 1 : 0) && ctx->pixCandPruned == prune;
-    if (!same) {
+    // everything the kernel reads that an upload does not fix (rtow_launch_cache.h) - among it the bits of the float Size: a pixel's beam spans cx / Size.x .. (cx + 1) / Size.x
+    // of the view, so the fraction of Size moves every beam
+    const CameraListKey key = cameraListKey(ctx->sceneSerial, a, prune);
+    if (!lists.key.holds(key)) {
         SampleKernelArgs perPixel = a;                       // the lists are per pixel whatever the work units are
         perPixel.totalWork = ownedPixels;
-        HIP_TRY(ctx, launchPrimaryCandidates(perPixel, ctx->dPixCand, prune, stream), RTOW_ERROR_LAUNCH_FAILURE);
-        ctx->pixCandValid = true;
-        ctx->pixCandScene = ctx->sceneSerial;
-        ctx->pixCandView = a.view;
-        ctx->pixCandW = a.width; ctx->pixCandH = a.height; ctx->pixCandOff = a.sliceOffset; ctx->pixCandDiv = a.sliceDivider;
-        ctx->pixCandSizeBits[0] = sizeBits[0]; ctx->pixCandSizeBits[1] = sizeBits[1];
-        ctx->pixCandJitter = a.subPixelJitter ? 1 : 0;
-        ctx->pixCandPruned = prune;
-        ctx->pixCandOwned = ownedPixels;
+        HIP_TRY(ctx, launchPrimaryCandidates(perPixel, lists.dLists, prune, stream), RTOW_ERROR_LAUNCH_FAILURE);
+        lists.key.set(key);
+        lists.ownedPixels = ownedPixels;
     }
-    a.pixelCandidates = ctx->dPixCand;
+    a.pixelCandidates = lists.dLists;
     return RTOW_SUCCESS;
 }
 
@@ -393,8 +412,8 @@ struct OrderPlan {
 // Ticket-map classes (regroup_tickets_kernel) for costs of at least floorCost rays per pixel
 void regroupClasses(const RtowContext_t* ctx, unsigned floorCost, unsigned out[3])
 {
-    const unsigned mode = ctx->regroupMode;
-    if (ctx->ticketMapSide == 1u) { out[0] = mode == 0u ? 0u : (2u << mode); out[1] = out[2] = 0u; return; }      // tile order: levels of the tile's cost range (mode 1 / 2 / 3: 4 / 8 / 16), 0 = by the ray count itself
+    const unsigned mode = ctx->knob.regroupMode;
+    if (ctx->knob.ticketMapSide == 1u) { out[0] = mode == 0u ? 0u : (2u << mode); out[1] = out[2] = 0u; return; }      // tile order: levels of the tile's cost range (mode 1 / 2 / 3: 4 / 8 / 16), 0 = by the ray count itself
     out[0] = mode == 0u ? 0u : floorCost; out[1] = mode >= 2u ? (floorCost * 11u) / 4u : 0xffffffffu; out[2] = mode >= 2u ? floorCost * 4u : 0xffffffffu;
 }
 
@@ -403,7 +422,7 @@ int regroupTickets(RtowContext ctx, const SampleKernelArgs& a, unsigned floorCos
     unsigned cls[3];
     regroupClasses(ctx, floorCost, cls);
     const unsigned tileRows = a.tilesPerRow ? a.tiledPixels / (64u * a.tilesPerRow) : 0u;
-    HIP_TRY(ctx, launchRegroupTickets(ctx->dPixelCost, ctx->dTicketMap, a.tilesPerRow, tileRows, ctx->ticketMapSide, cls, stream), RTOW_ERROR_LAUNCH_FAILURE);
+    HIP_TRY(ctx, launchRegroupTickets(ctx->chunkOrder.dPixelCost, ctx->chunkOrder.dTicketMap, a.tilesPerRow, tileRows, ctx->knob.ticketMapSide, cls, stream), RTOW_ERROR_LAUNCH_FAILURE);
     return RTOW_SUCCESS;
 }
 
@@ -415,8 +434,8 @@ int prepareChunkOrder(RtowContext ctx, SampleKernelArgs& a, int blocks, hipStrea
     a.chunkCount = (a.totalWork + 63u) / 64u;
     order.want = a.chunkCount >= (uint32_t)(4 * ctx->cuCount) && !(ctx->flags & RTOW_CONTEXT_NO_CHUNK_ORDER);   // tiny frames: not worth it
     // batch groups: (chunk, batch) slots a wave reserves at a time (schedulerTune[7] bits 8 .. 11 override the default for A/B runs)
-    a.slotBlock = ctx->slotBlockOverride ? ctx->slotBlockOverride : kGroupSlotBlock;
-    if (!ctx->slotBlockOverride) {
+    a.slotBlock = ctx->knob.slotBlockOverride ? ctx->knob.slotBlockOverride : kGroupSlotBlock;
+    if (!ctx->knob.slotBlockOverride) {
         // Reserving several (chunk, batch) slots per pull pays where a wave has dozens of them to work through (a whole frame's group: 79 slots per wave, +1.8 %); a launch that
         // owns a few slots per wave - the sub-batches of an 8-way row slice: 7.9 - must balance with single slots (profiles/r06j_partitions_c2.json: 10.9 ms per step against the
         // 7.9 of round 5's single slots)
@@ -424,45 +443,42 @@ int prepareChunkOrder(RtowContext ctx, SampleKernelArgs& a, int blocks, hipStrea
         if (slotsPerWave < 32u) a.slotBlock = 1u;
         else if (slotsPerWave < 64u && a.slotBlock > 2u) a.slotBlock = 2u;
     }
-    order.mapped = order.want && ctx->ticketMapSide >= 1u && a.tiledPixels != 0u && !a.unitRecords;
+    order.mapped = order.want && ctx->knob.ticketMapSide >= 1u && a.tiledPixels != 0u && !a.unitRecords;
     if (!order.want) return RTOW_SUCCESS;
+    RtowContext_t::ChunkOrder& co = ctx->chunkOrder;
     bool grew = false;
-    const int reserved = growDevice(ctx, {{&ctx->dChunkCost, (2 * (size_t)a.chunkCount + kChunkOrderScratchWords) * sizeof(unsigned)}, {&ctx->dChunkOrder, a.chunkCount * sizeof(unsigned)},
-                                          {&ctx->dPixelCost, (size_t)a.chunkCount * 64 * sizeof(unsigned short)}, {&ctx->dTicketMap, (size_t)a.chunkCount * 64 * sizeof(unsigned)}}, &grew);
-    if (grew) ctx->orderValid = false;
+    const int reserved = growDevice(ctx, {{&co.dChunkCost, (2 * (size_t)a.chunkCount + kChunkOrderScratchWords) * sizeof(unsigned)}, {&co.dChunkOrder, a.chunkCount * sizeof(unsigned)},
+                                          {&co.dPixelCost, (size_t)a.chunkCount * 64 * sizeof(unsigned short)}, {&co.dTicketMap, (size_t)a.chunkCount * 64 * sizeof(unsigned)}}, &grew);
+    if (grew) co.key.drop();
     RTOW_TRY(reserved);
-    if (ctx->orderW != a.width || ctx->orderH != a.height || ctx->orderOff != a.sliceOffset || ctx->orderDiv != a.sliceDivider || ctx->orderGroups != a.groupsPerPixel ||
-        ctx->orderMapped != order.mapped) ctx->orderValid = false;
-    a.pixelCost = ctx->dPixelCost;
-    a.ticketMap = order.mapped ? ctx->dTicketMap : nullptr;
+    const ChunkOrderKey key = chunkOrderKey(ctx->sceneSerial, a, order.mapped);      // (per-sample units are never mapped)
+    a.pixelCost = co.dPixelCost;
+    a.ticketMap = order.mapped ? co.dTicketMap : nullptr;
     order.have = true;
-    if (!ctx->orderValid && a.unitRecords) {
-        // per-sample units are small and alike: the first batch simply runs in natural order and records the map for the next
-        HIP_TRY(ctx, hipMemsetAsync(ctx->dPixelCost, 0, (size_t)a.chunkCount * 64 * sizeof(unsigned short), stream), RTOW_ERROR_LAUNCH_FAILURE);
-        order.have = false;
-        ctx->orderValid = true;
-        ctx->orderW = a.width; ctx->orderH = a.height; ctx->orderOff = a.sliceOffset; ctx->orderDiv = a.sliceDivider; ctx->orderGroups = a.groupsPerPixel;
-        ctx->orderMapped = false;
+    if (!co.key.holds(key)) {
+        co.key.drop();                                       // what follows overwrites the map on hand, however far it gets
+        if (a.unitRecords) {
+            // per-sample units are small and alike: the first batch simply runs in natural order and records the map for the next
+            HIP_TRY(ctx, hipMemsetAsync(co.dPixelCost, 0, (size_t)a.chunkCount * 64 * sizeof(unsigned short), stream), RTOW_ERROR_LAUNCH_FAILURE);
+            order.have = false;
+        } else {
+            // no cost map yet for this scene and frame configuration: a 1-sample-per-pixel probe of the same kernel (stores nothing else)
+            SampleKernelArgs probe = a;
+            probe.probeOnly = 1;
+            probe.chunkOrder = nullptr;
+            probe.ticketMap = nullptr;                           // the probe runs over the tiles themselves; the map starts from them
+            if (order.mapped) HIP_TRY(ctx, launchInitTicketMap(co.dTicketMap, a.tiledPixels, stream), RTOW_ERROR_LAUNCH_FAILURE);
+            probe.cancelFlag = nullptr;
+            probe.chainCount = 1;                                // one pass over the pixels, whatever the launch it prepares
+            HIP_TRY(ctx, hipMemsetAsync(ctx->dWorkCounter, 0, sizeof(unsigned int), stream), RTOW_ERROR_LAUNCH_FAILURE);
+            HIP_TRY(ctx, hipMemsetAsync(co.dPixelCost, 0, (size_t)a.chunkCount * 64 * sizeof(unsigned short), stream), RTOW_ERROR_LAUNCH_FAILURE);   // the last chunk's tail
+            HIP_TRY(ctx, launchSampleBatch(probe, blocks, stream), RTOW_ERROR_LAUNCH_FAILURE);
+            if (order.mapped) RTOW_TRY(regroupTickets(ctx, a, 1u, stream));
+            HIP_TRY(ctx, launchBuildChunkOrder(co.dPixelCost, co.dChunkCost, a.chunkCount, co.dChunkOrder, 0, stream), RTOW_ERROR_LAUNCH_FAILURE);
+        }
+        co.key.set(key);
     }
-    if (!ctx->orderValid) {
-        // no cost map yet for this frame configuration: a 1-sample-per-pixel probe of the same kernel (stores nothing else)
-        SampleKernelArgs probe = a;
-        probe.probeOnly = 1;
-        probe.chunkOrder = nullptr;
-        probe.ticketMap = nullptr;                           // the probe runs over the tiles themselves; the map starts from them
-        if (order.mapped) HIP_TRY(ctx, launchInitTicketMap(ctx->dTicketMap, a.tiledPixels, stream), RTOW_ERROR_LAUNCH_FAILURE);
-        probe.cancelFlag = nullptr;
-        probe.chainCount = 1;                                // one pass over the pixels, whatever the launch it prepares
-        HIP_TRY(ctx, hipMemsetAsync(ctx->dWorkCounter, 0, sizeof(unsigned int), stream), RTOW_ERROR_LAUNCH_FAILURE);
-        HIP_TRY(ctx, hipMemsetAsync(ctx->dPixelCost, 0, (size_t)a.chunkCount * 64 * sizeof(unsigned short), stream), RTOW_ERROR_LAUNCH_FAILURE);   // the last chunk's tail
-        HIP_TRY(ctx, launchSampleBatch(probe, blocks, stream), RTOW_ERROR_LAUNCH_FAILURE);
-        if (order.mapped) RTOW_TRY(regroupTickets(ctx, a, 1u, stream));
-        HIP_TRY(ctx, launchBuildChunkOrder(ctx->dPixelCost, ctx->dChunkCost, a.chunkCount, ctx->dChunkOrder, 0, stream), RTOW_ERROR_LAUNCH_FAILURE);
-        ctx->orderValid = true;
-        ctx->orderW = a.width; ctx->orderH = a.height; ctx->orderOff = a.sliceOffset; ctx->orderDiv = a.sliceDivider; ctx->orderGroups = a.groupsPerPixel;
-        ctx->orderMapped = order.mapped;
-    }
-    a.chunkOrder = order.have ? ctx->dChunkOrder : nullptr;
+    a.chunkOrder = order.have ? co.dChunkOrder : nullptr;
     return RTOW_SUCCESS;
 }
 
@@ -472,50 +488,48 @@ int prepareChunkOrder(RtowContext ctx, SampleKernelArgs& a, int blocks, hipStrea
 void measureThresholds(RtowContext ctx, SampleKernelArgs& a, int blocks, bool haveOrder, hipStream_t stream)
 {
     for (int k = 0; k < 7; k++) a.tune[k] = ctx->tune[k] < 1 ? 1 : ctx->tune[k];
-    if (ctx->tunePending && ctx->tunePendingScene == ctx->sceneSerial && finishThresholdTuning(ctx, /*wait*/ false))
+    RtowContext_t::ThresholdTuning& tuning = ctx->tuning;
+    if (finishThresholdTuning(ctx, /*wait*/ false))          // (probes in flight are this scene's: an upload drops them)
         for (int k = 0; k < 7; k++) a.tune[k] = ctx->tune[k] < 1 ? 1 : ctx->tune[k];
-    ctx->sppSinceUpload += (uint64_t)a.chainCount * (a.sampleCountMax > a.sampleCountMin ? a.sampleCountMax : a.sampleCountMin);
+    tuning.sppSinceUpload += (uint64_t)a.chainCount * (a.sampleCountMax > a.sampleCountMin ? a.sampleCountMax : a.sampleCountMin);
     hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;                   // a stream that is being captured into a graph cannot carry the event pairs: no measurement then
     if (hipStreamIsCapturing(stream, &capturing) != hipSuccess) { (void)hipGetLastError(); capturing = hipStreamCaptureStatusNone; }
     // worth it only where the scene is rendered for longer than the probes take (3 or 6 candidates x 3 repeats x 4 samples per pixel: 40 - 76 samples per
     // pixel): a one-shot render of a few samples per pixel (BASELINE.json configs[0]: 8) must not pay several times its own work first
-    const bool worthIt = ctx->sppSinceUpload >= kTuneMinSamplesPerPixel;
-    if (ctx->userTune || (ctx->flags & RTOW_CONTEXT_NO_THRESHOLD_TUNING) || ctx->tunedScene == ctx->sceneSerial || ctx->tunePending || a.unitRecords || !haveOrder ||
+    const bool worthIt = tuning.sppSinceUpload >= kTuneMinSamplesPerPixel;
+    if (ctx->userTune || (ctx->flags & RTOW_CONTEXT_NO_THRESHOLD_TUNING) || tuning.state != tuning.Unmeasured || a.unitRecords || !haveOrder ||
         !worthIt || capturing != hipStreamCaptureStatusNone)
         return;
     const bool volumes = a.layout.sceneKind == SCENE_KIND_VOLUMES || a.layout.sceneKind == SCENE_KIND_VOLUMES_TEXTURED;
     const int candidates = volumes ? 2 * kFamilies : kFamilies;                      // volume kinds: each family also with the volume stage from half of the live lanes
     const int launches = candidates * kTuneProbeRepeats;
-    ctx->tuneEvents.assign((size_t)launches + 1, nullptr);
+    tuning.events.assign((size_t)launches + 1, nullptr);
     bool ok = true;
-    for (auto& e : ctx->tuneEvents) ok = ok && hipEventCreate(&e) == hipSuccess;
-    ok = ok && ctx->dProbeSink.ensure(64) == hipSuccess;
+    for (auto& e : tuning.events) ok = ok && hipEventCreate(&e) == hipSuccess;
+    ok = ok && tuning.dProbeSink.ensure(64) == hipSuccess;
     SampleKernelArgs probe = a;
     probe.probeOnly = kTuneProbeSamples;
     probe.pixelCost = nullptr;                           // the cost map stays the cost probe's (or the previous batch's)
     probe.cancelFlag = nullptr;
-    probe.overflowFlag = ctx->dProbeSink;                // a probe's ray beyond the hit-list capacity is not the batch's (which may trace fewer samples than a probe)
+    probe.overflowFlag = tuning.dProbeSink;               // a probe's ray beyond the hit-list capacity is not the batch's (which may trace fewer samples than a probe)
     probe.chainCount = 1;
     probe.chainIndependent = 0;
     // one untimed probe first: clocks, L2 and the instruction cache are warm before the first timed one
     candidateThresholds(0, probe.tune, 7);
     if (ok) ok = hipMemsetAsync(ctx->dWorkCounter, 0, sizeof(unsigned int), stream) == hipSuccess && launchSampleBatch(probe, blocks, stream) == hipSuccess;
-    if (ok) ok = hipEventRecord(ctx->tuneEvents[0], stream) == hipSuccess;
+    if (ok) ok = hipEventRecord(tuning.events[0], stream) == hipSuccess;
     for (int l = 0; ok && l < launches; l++) {
         candidateThresholds(l % candidates, probe.tune, 7);
         ok = hipMemsetAsync(ctx->dWorkCounter, 0, sizeof(unsigned int), stream) == hipSuccess && launchSampleBatch(probe, blocks, stream) == hipSuccess &&
-             hipEventRecord(ctx->tuneEvents[(size_t)l + 1], stream) == hipSuccess;
+             hipEventRecord(tuning.events[(size_t)l + 1], stream) == hipSuccess;
     }
     if (ok) {
-        ctx->tunePending = true;
-        ctx->tunePendingScene = ctx->sceneSerial;
-        ctx->tuneCandidates = candidates;
-        ctx->tuneBuiltin = a.layout.sceneKind <= SCENE_KIND_SPHERES_MOTION ? 0 : 1;       // what rtowUploadScene set for this kernel kind
+        tuning.state = tuning.Pending;
+        tuning.candidates = candidates;
+        tuning.builtin = a.layout.sceneKind <= SCENE_KIND_SPHERES_MOTION ? 0 : 1;       // what rtowUploadScene set for this kernel kind
     } else {
         (void)hipGetLastError();
-        dropThresholdTuning(ctx);
-        ctx->tunedCandidate = -1;
-        ctx->tunedScene = ctx->sceneSerial;             // not measurable: do not try again for this scene
+        settleThresholdTuning(ctx, -1);                 // not measurable: do not try again for this scene
         logf(ctx, 2, "tune", "threshold probes failed; the per-kind values stay");
     }
 }
@@ -626,7 +640,8 @@ int enqueueLaunch(RtowContext ctx, const RtowSampleParams* p, SampleKernelArgs& 
     // refresh the order for the next batch from what this one measured (same stream, after the timed kernel)
     if (order.mapped) RTOW_TRY(regroupTickets(ctx, a, std::max(1u, a.sampleCountMin), stream));
     // (development: schedulerTune[7] + 64 orders the chunks by their TOTAL ray count instead of by their most expensive pixel)
-    if (order.want) HIP_TRY(ctx, launchBuildChunkOrder(ctx->dPixelCost, ctx->dChunkCost, a.chunkCount, ctx->dChunkOrder, ctx->orderByTotal ? 0 : 1, stream), RTOW_ERROR_LAUNCH_FAILURE);
+    if (order.want)
+        HIP_TRY(ctx, launchBuildChunkOrder(ctx->chunkOrder.dPixelCost, ctx->chunkOrder.dChunkCost, a.chunkCount, ctx->chunkOrder.dChunkOrder, ctx->knob.orderByTotal ? 0 : 1, stream), RTOW_ERROR_LAUNCH_FAILURE);
     HIP_TRY(ctx, hipEventRecord(ctx->evBatchDone, stream), RTOW_ERROR_LAUNCH_FAILURE);
     ctx->haveBatchDone = true;
     ctx->haveTiming = true;
@@ -1017,20 +1032,6 @@ RTOW_API int rtowCreateContext(const RtowContextOptions* options, RtowContext* o
         ctx->hitListCapacity = (uint32_t)options->hitListCapacity;
         bool anyTune = false;
         for (int i = 0; i < 9; i++) anyTune = anyTune || (i != 7 && options->schedulerTune[i] != 0);
-        if (options->schedulerTune[7] > 0) {                                                  // its own knob: says nothing about the thresholds
-            // packed: side (low nibble: 1 none, 3 a tile's tickets most expensive first, 2 / 4 / 8 super-tiles) + 16 x mode (0 .. 3) + 64 x chunk order by total + 256 x queue slots per pull
-            // + 4096 x lanes that wait for company at a pixel boundary.
-            // A low nibble of 0 (only the upper fields given) keeps the default side; any other value would silently switch the ticket map off
-            int v = options->schedulerTune[7];
-            if ((v & 15) == 0) v |= RTOW_DEFAULT_REGROUP_SIDE & 15;
-            const int side = v & 15;
-            if (!(side == 1 || side == 2 || side == 3 || side == 4 || side == 8) || v >= (1 << 16)) {
-                logf(ctx, 2, "rtow", "schedulerTune[7] = %d: the low four bits must be 1, 2, 3, 4 or 8 (or 0 for the default)", options->schedulerTune[7]);
-                delete ctx;
-                return RTOW_ERROR_INVALID_VALUE;
-            }
-            ctx->schedulerKnob = v;
-        }
         if (anyTune) {
             // stage thresholds below 1 mean "any lane" (1); a zero hand-over count or walk slice means "the built-in value" (3; per scene at upload), as in API v6
             for (int i = 0; i < 9; i++) ctx->tune[i] = options->schedulerTune[i] < 1 ? 1 : options->schedulerTune[i];
@@ -1039,13 +1040,11 @@ RTOW_API int rtowCreateContext(const RtowContextOptions* options, RtowContext* o
         }
         ctx->userTune = anyTune;
     }
-    {
-        const int v = ctx->schedulerKnob, side = v & 15;
-        ctx->ticketMapSide = side == 3 ? 1u : (side == 2 || side == 4 || side == 8) ? (unsigned)side : 0u;     // (1: no map)
-        ctx->regroupMode = ((unsigned)v >> 4) & 3u;
-        ctx->orderByTotal = (v & 64) != 0;
-        ctx->slotBlockOverride = ((unsigned)v >> 8) & 15u;
-        ctx->pixelGateOverride = (v >> 12) & 15;
+    // schedulerTune[7] is its own knob: it says nothing about the thresholds (0, or no options: the default word)
+    if (!decodeSchedulerKnob(options ? options->schedulerTune[7] : 0, &ctx->knob)) {
+        logf(ctx, 2, "rtow", "schedulerTune[7] = %d: the low four bits must be 1, 2, 3, 4 or 8 (or 0 for the default)", options->schedulerTune[7]);
+        delete ctx;
+        return RTOW_ERROR_INVALID_VALUE;
     }
     bool ok = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) == hipSuccess;
     ok = ok && hipEventCreate(&ctx->evStart) == hipSuccess && hipEventCreate(&ctx->evStop) == hipSuccess;
@@ -1196,21 +1195,7 @@ RTOW_API int rtowUploadScene(RtowContext ctx, const RtowSceneDesc* scene)
     ctx->ldsSceneBytes = ctx->ldsPlan.sceneBytes;
     ctx->ldsNodeCount = ctx->ldsPlan.nodeCount;
     ctx->haveScene = true;
-    ctx->triWatchOff = false;
-    ctx->hCancel[3] = 0u;
-    ctx->sceneSerial++;
-    ctx->orderValid = false;
-    dropThresholdTuning(ctx);                                   // (the device is idle: rtowUploadScene synchronised it above)
-    ctx->sppSinceUpload = 0;
-    ctx->sceneSignatureNow = sceneSignature(ctx->scene, wide);
-    if (!ctx->userTune && !(ctx->flags & RTOW_CONTEXT_NO_THRESHOLD_TUNING))
-        for (const RtowContext_t::TuneCacheEntry& e : ctx->tuneCache)
-            if (e.signature == ctx->sceneSignatureNow) {
-                // a scene like one this context has measured before (same kernel kind, entity / node / material counts): its thresholds, no new probes
-                candidateThresholds(e.winner, ctx->tune, 8);
-                ctx->tunedCandidate = e.winner;
-                ctx->tunedScene = ctx->sceneSerial;
-            }
+    sceneReplaced(ctx, wide);
     logf(ctx, 4, "scene", "%d entities, %u BVH nodes, depth %u, %u bytes (%u in LDS)%s%s", ctx->scene.entityCount, ctx->scene.layout.nodeCount,
          ctx->scene.layout.bvhDepth, ctx->scene.layout.totalBytes, ctx->ldsSceneBytes,
          ctx->scene.layout.exactTies ? ", exact-tie kernels" : "", ctx->ldsPlan.nodeImageBytes ? ", 80-byte node image" : "");
@@ -1294,7 +1279,7 @@ RTOW_API int rtowGetSceneInfo(RtowContext ctx, RtowSceneInfo* info)
     if (!ctx || !info) return RTOW_ERROR_INVALID_VALUE;
     std::lock_guard<std::mutex> lock(ctx->mu);
     if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
-    if (ctx->tunePending && hipSetDevice(ctx->device) == hipSuccess) (void)finishThresholdTuning(ctx, /*wait*/ false);     // a measurement whose probes are done by now
+    if (ctx->tuning.state == ctx->tuning.Pending && hipSetDevice(ctx->device) == hipSuccess) (void)finishThresholdTuning(ctx, /*wait*/ false);     // a measurement whose probes are done by now
     info->entityCount = ctx->scene.entityCount;
     info->materialCount = ctx->scene.materialCount;
     info->bvhNodeCount = (int32_t)ctx->scene.layout.nodeCount;
@@ -1310,9 +1295,9 @@ RTOW_API int rtowGetSceneInfo(RtowContext ctx, RtowSceneInfo* info)
     info->hitListCapacity = keepsLists ? (int32_t)(ctx->hitSpillEntries + (uint32_t)kLocalHitEntries)
                                        : tieWatch ? (int32_t)std::min<uint64_t>((uint64_t)ctx->scene.entityCount, listCapacity(ctx, false)) : 0;
     info->wideCodes = ctx->wideCodes ? 1 : 0;
-    info->thresholdSet = ctx->tunedScene == ctx->sceneSerial ? ctx->tunedCandidate : -1;
+    info->thresholdSet = ctx->tuning.winner;             // (-1 until the scene's measurement has settled)
     for (int k = 0; k < 9; k++) info->schedulerTune[k] = ctx->tune[k];
-    info->schedulerTune[7] = ctx->schedulerKnob;
+    info->schedulerTune[7] = ctx->knob.word;
     return RTOW_SUCCESS;
 }
 
@@ -1323,20 +1308,22 @@ RTOW_API int rtowGetCameraRayListStats(RtowContext ctx, RtowCameraRayListStats* 
     std::lock_guard<std::mutex> lock(ctx->mu);
     memset(stats, 0, sizeof(*stats));
     if (!ctx->haveScene) return RTOW_ERROR_NO_SCENE;
-    if (!ctx->pixCandValid || ctx->pixCandScene != ctx->sceneSerial || !ctx->dPixCand) return RTOW_SUCCESS;      // no lists: valid = 0
+    RtowContext_t::CameraLists& lists = ctx->cameraLists;
+    const CameraListKey* key = lists.key.get();
+    if (!key || key->sceneSerial != ctx->sceneSerial || !lists.dLists) return RTOW_SUCCESS;      // nothing built, built for an earlier upload, or no block: no lists, valid = 0
     hipStream_t s;
     RTOW_TRY(useDevice(ctx, nullptr, &s));
-    RTOW_TRY(growDevice(ctx, {{&ctx->dPixCandStats, 10 * sizeof(unsigned long long)}}));
+    RTOW_TRY(growDevice(ctx, {{&lists.dStats, 10 * sizeof(unsigned long long)}}));
     if (ctx->haveBatchDone) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->evBatchDone, 0), RTOW_ERROR_LAUNCH_FAILURE);
-    HIP_TRY(ctx, launchCameraListStats(ctx->dPixCand, ctx->pixCandOwned, ctx->pixCandW, ctx->pixCandOff, ctx->pixCandDiv, ctx->wideCodes, ctx->dPixCandStats, s),
+    HIP_TRY(ctx, launchCameraListStats(lists.dLists, lists.ownedPixels, key->frame.width, key->frame.sliceOffset, key->frame.sliceDivider, ctx->wideCodes, lists.dStats, s),
             RTOW_ERROR_LAUNCH_FAILURE);
     unsigned long long counts[10];
-    HIP_TRY(ctx, hipMemcpyAsync(counts, ctx->dPixCandStats, sizeof(counts), hipMemcpyDeviceToHost, s), RTOW_ERROR_LAUNCH_FAILURE);
+    HIP_TRY(ctx, hipMemcpyAsync(counts, lists.dStats, sizeof(counts), hipMemcpyDeviceToHost, s), RTOW_ERROR_LAUNCH_FAILURE);
     HIP_TRY(ctx, hipStreamSynchronize(s), RTOW_ERROR_LAUNCH_FAILURE);
     for (int k = 0; k < 9; k++) stats->pixelsWithEntries[k] = counts[k];
     stats->pixelsWithoutList = counts[9];
-    stats->ownedPixels = ctx->pixCandOwned;
-    stats->pruned = ctx->pixCandPruned ? 1 : 0;
+    stats->ownedPixels = lists.ownedPixels;
+    stats->pruned = key->pruned ? 1 : 0;
     stats->valid = 1;
     return RTOW_SUCCESS;
 }

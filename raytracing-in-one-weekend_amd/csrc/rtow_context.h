@@ -13,14 +13,10 @@
 #include "rtow_bvh.h"
 #include "rtow_device_mem.h"
 #include "rtow_kernels.h"
+#include "rtow_launch_cache.h"
 
-// The two tuning defaults the context's member initialisers need; the other tuning macros, and what the nine thresholds mean, are at the top of rtow_api.hip.
-#ifndef RTOW_DEFAULT_REGROUP_SIDE
-// RtowContextOptions.schedulerTune[7], which pixel a ticket stands for: 1 = its place in its 8 x 8 tile; 3 = the tiles as they are, each tile's tickets most expensive pixel first
-// (order_tile_tickets_kernel: +0.7 % on the headline, +0.9 % as plain launches, +1.3 % as groups, same box, three alternating runs - profiles/r05a_pixel_regrouping.json);
-// 2 / 4 / 8 (+ 16 x mode): pixels regrouped by cost or class inside super-tiles of that many tiles (0 ... -5 %: measured, not used)
-#define RTOW_DEFAULT_REGROUP_SIDE 3
-#endif
+// The tuning default the context's member initialisers need (RTOW_DEFAULT_REGROUP_SIDE is with the knob it belongs to, rtow_launch_cache.h); the other tuning macros, and
+// what the nine thresholds mean, are at the top of rtow_api.hip.
 #ifndef RTOW_DEFAULT_TUNE
 #define RTOW_DEFAULT_TUNE 24, 32, 1, 32, 28, 1, 3, 1, 16
 #endif
@@ -53,23 +49,22 @@ struct RtowContext_t {
 
     // work distribution / cancellation
     DeviceMem<unsigned int> dWorkCounter;
-    // chunk cost map -> launch order (longest chunks first); valid for one (width, height, slice, scene) configuration
     DeviceMem<unsigned int> dChunkDone;   // chained batches: pixels stored per chunk (grows with dXcdState)
     DeviceMem<uint8_t> dXcdState;         // chained batches: XcdState + kMaxXcds lists of one entry per chunk (which XCD owns which chunk)
     DeviceMem<rtow::ChainBatch> dChainBatches;   // chained batches: per-batch seed / diagnostics table of the launch being enqueued
-    DeviceMem<unsigned int> dChunkCost, dChunkOrder;   // these four grow together (prepareChunkOrder)
-    DeviceMem<unsigned short> dPixelCost;
-    DeviceMem<unsigned int> dTicketMap;   // ticket -> owned pixel (SampleKernelArgs.ticketMap), 64 entries per chunk; re-sorted from every launch's cost map
-    bool orderMapped = false;             // the cost map / order on hand were recorded under dTicketMap (else under the tiles themselves)
-    bool orderValid = false;
-    int orderW = 0, orderH = 0, orderOff = 0, orderDiv = 0;
+    // chunk cost map -> launch order (longest chunks first), and the ticket map: valid for one ChunkOrderKey (scene upload, frame and slice, groups per pixel, mapped or not)
+    struct ChunkOrder {
+        DeviceMem<unsigned int> dChunkCost, dChunkOrder;   // these four grow together (prepareChunkOrder)
+        DeviceMem<unsigned short> dPixelCost;
+        DeviceMem<unsigned int> dTicketMap;   // ticket -> owned pixel (SampleKernelArgs.ticketMap), 64 entries per chunk; re-sorted from every launch's cost map
+        rtow::Keyed<rtow::ChunkOrderKey> key; // what the cost map / order on hand were recorded under
+    } chunkOrder;
     rtow::PinnedBlock pinned;             // the 256 bytes behind the next three
     volatile uint32_t* hCancel = nullptr; // pinned, device-visible: [0] cancel, [1] hit-list overflow, [2] tie-list overflow; the metrics record of rtowReduceMetricsDevice at byte 64
     volatile RtowMetrics* hMetricsRecord = nullptr;
     RtowMetrics* dMetricsRecord = nullptr;
     // RTOW_RNG_PER_SAMPLE: one 64-byte record per (owned pixel, sample group) unit
     DeviceMem<float> dUnitRecords;
-    uint32_t orderGroups = 1;     // groups per pixel the chunk cost map was recorded with
     // RTOW_CONTEXT_REFERENCE_DIAGNOSTICS: the reference's own tree of the current scene (CompiledScene.refTree), HBM only
     DeviceMem<uint8_t> dRefTree;
     // hit lists beyond the 24 entries a lane holds itself (volume scenes, exact-tie kernels): [entry][lane] columns, grow-only
@@ -89,17 +84,14 @@ struct RtowContext_t {
     // sky cubemap (rtowUploadSkyCubemap)
     DeviceMem<uint8_t> dCubemap;
     RtowCubemapDesc cubemap{};   // .faces is not kept (host pointer): dCubemap holds the copy, null when none
-    // camera-ray candidate lists (primary_candidates_kernel): valid for one (scene upload, view, size - the integer frame and the float Size the beams divide by -,
-    // slice, jitter, pruning) configuration
-    DeviceMem<uint2> dPixCand;
-    bool pixCandValid = false;
-    uint64_t sceneSerial = 0, pixCandScene = 0;
-    RtowView pixCandView{};
-    int pixCandW = 0, pixCandH = 0, pixCandOff = 0, pixCandDiv = 0, pixCandJitter = 0;
-    uint32_t pixCandSizeBits[2] = {0u, 0u};   // the bits of SampleKernelArgs.sizeX / sizeY: compared as bits, so that a NaN Size rebuilds every time rather than never
-    bool pixCandPruned = false;           // ... built with pruning (launches that write 16-byte diagnostic records, and RTOW_CONTEXT_UNPRUNED_CAMERA_RAY_LISTS, keep whole lists)
-    uint32_t pixCandOwned = 0;            // owned pixels the lists were built for
-    DeviceMem<unsigned long long> dPixCandStats;   // rtowGetCameraRayListStats: ten counters, allocated on first use
+    uint64_t sceneSerial = 0;             // counts the uploads that succeeded: what both cache keys name the scene by
+    // camera-ray candidate lists (primary_candidates_kernel): valid for one CameraListKey (scene upload, view, frame and slice, the float Size the beams divide by, jitter, pruning)
+    struct CameraLists {
+        DeviceMem<uint2> dLists;
+        rtow::Keyed<rtow::CameraListKey> key;
+        uint32_t ownedPixels = 0;             // owned pixels the lists were built for
+        DeviceMem<unsigned long long> dStats; // rtowGetCameraRayListStats: ten counters, allocated on first use
+    } cameraLists;
 
     // grow-only staging for rtowSampleBatch (host buffers) - like CudaBuffer.EnsureCapacity (OptixApi.cs:240-251)
     DeviceMem<float> dColor, dNormal, dAlbedo, dScw;   // (grow together)
@@ -130,26 +122,23 @@ struct RtowContext_t {
     uint32_t ldsSceneBudget = 0;          // 0 = everything that fits
     int tune[9] = {RTOW_DEFAULT_TUNE};
     bool userTune = false;                // RtowContextOptions.schedulerTune was given: no per-scene adjustment
-    // RtowContextOptions.schedulerTune[7] (see RTOW_DEFAULT_REGROUP_SIDE), as given and decoded by rtowCreateContext
-    int schedulerKnob = RTOW_DEFAULT_REGROUP_SIDE;
-    unsigned ticketMapSide = 0;           // which pixel a ticket stands for: 0 = its place in its tile, 1 = a tile's tickets most expensive first, 2 / 4 / 8 = super-tiles of that many tiles
-    unsigned regroupMode = 0;             // development: what the ticket map sorts by (0 ray count, 1 sky / not sky, 2 / 3 classes of rays per sample)
-    bool orderByTotal = false;            // development: chunks ordered by their total ray count instead of by their most expensive pixel
-    unsigned slotBlockOverride = 0;       // batch groups' (chunk, batch) slots per pull (0 = by the launch: prepareChunkOrder)
-    int pixelGateOverride = 0;            // lanes that must want a pixel boundary (0 = by the samples a unit of work takes: setSchedulerValues)
+    rtow::SchedulerKnob knob{};           // RtowContextOptions.schedulerTune[7] (see RTOW_DEFAULT_REGROUP_SIDE), decoded by rtowCreateContext
     bool userSliceDefault = false;        // ... with a zero walk slice: the per-scene built-in value
     bool chainFusion = true;              // the same-XCD hand-over litmus passed on this device (rtowCreateContext): chains may run as one launch
-    uint64_t tunedScene = ~0ull;          // sceneSerial whose thresholds were measured (tuneThresholds)
-    int tunedCandidate = -1;              // which candidate won (rtowGetSceneInfo-independent; logged)
-    bool tunePending = false;             // probes of scene tunePendingScene are enqueued; their events are read by a later call, never waited for
-    uint64_t tunePendingScene = 0;
-    int tuneCandidates = 0, tuneBuiltin = 0;
-    std::vector<hipEvent_t> tuneEvents;
-    DeviceMem<uint32_t> dProbeSink;       // where probes report rays beyond the hit-list capacity (not the batch's flag)
-    uint64_t sppSinceUpload = 0;          // samples per pixel this scene has been asked for since its upload: a measurement must be worth its probes
-    uint64_t sceneSignatureNow = 0;       // of the current scene
-    struct TuneCacheEntry { uint64_t signature; int winner; };
-    std::vector<TuneCacheEntry> tuneCache;   // winners by scene signature: a re-upload of a like scene does not measure again
+    // per-scene measurement of the stage thresholds (measureThresholds): everything but the winner cache is of the current scene, and dropThresholdTuning starts it over
+    struct ThresholdTuning {
+        enum State { Unmeasured, Pending, Settled };
+        State state = Unmeasured;             // Pending: probes are enqueued, their events are read by a later call, never waited for; Settled: measured, taken from the
+                                              // winner cache, or not measurable - no further probes for this scene
+        int winner = -1;                      // Settled: which candidate's thresholds run (-1: the kernel kind's built-in ones)
+        int candidates = 0, builtin = 0;      // Pending: how many candidates the probes time, and which of them the kernel kind runs unmeasured
+        std::vector<hipEvent_t> events;
+        DeviceMem<uint32_t> dProbeSink;       // where probes report rays beyond the hit-list capacity (not the batch's flag)
+        uint64_t sppSinceUpload = 0;          // samples per pixel this scene has been asked for since its upload: a measurement must be worth its probes
+        uint64_t signature = 0;               // of the current scene (sceneSignature)
+        struct Winner { uint64_t signature; int winner; };
+        std::vector<Winner> cache;            // winners by scene signature: a re-upload of a like scene does not measure again
+    } tuning;
 
     // rtowRegisterHostBuffer: pinned + device-mapped ranges of caller memory
     struct HostRange { uint8_t* base; size_t size; uint8_t* device; };

@@ -42,7 +42,7 @@ protected:
     size_t bytes_ = 0;
 };
 
-// The block as a T*: use sites read `ctx->dScene + offset`, `if (!ctx->dTieRedo)`, `a.pixelCost = ctx->dPixelCost` as they would a raw pointer
+// The block as a T*: use sites read `ctx->dScene + offset`, `if (!ctx->dTieRedo)`, `a.pixelCost = co.dPixelCost` as they would a raw pointer
 template <typename T> class DeviceMem : public DeviceBlock {
 public:
     operator T*() const { return static_cast<T*>(p_); }
