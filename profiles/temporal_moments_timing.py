@@ -5,8 +5,8 @@ Timing: the cover scene, its camera and the camera after tests/test_gpu_temporal
 with its recommended values gives the source map (its holes are the pixels the estimate is for).  The gather over that map; the estimate in three states - no pixel
 qualifying (n = 8 everywhere), the reprojection holes qualifying (the gathered moments), every pixel qualifying (inMoments NULL) - out of place with outFilled; each
 call bracketed by HIP events on the stream it is enqueued on; after `--warmup` untimed calls, `--reps` timed calls per point, the median reported.  With
-`--ab-lib PATH` the three estimate states are timed again in a child process that loads the library at PATH (csrc/Makefile's A/B build with
-EXTRA=-DRTOW_ESTIMATE_TAPS_FROM_LDS=0: the same tap loop reading every tap from global memory).
+`--ab-lib PATH` the three estimate states are timed again in a child process that loads the library at PATH (another build of the library, csrc/Makefile's
+`OBJDIR=... LIB=...`: the parent commit's, or one with a switch under test), and recorded next to the shipped library's.
 
 Quality (`--quality`): the two frames of tests/test_gpu_temporal_moments.py (MoveFrame, SingleBatchFrame) over the grid maxBatches x minBatches x minTaps x
 normalSharpness x depthTolerance x MATCH_ENTITY; per point the squared error against 1024 spp of the frame denoised with the carried and estimated moments over that
@@ -209,8 +209,8 @@ def main():
                               capture_output=True, text=True, timeout=300)
         assert proc.returncode == 0, proc.stdout[-2000:] + proc.stderr[-2000:]
         rows = [json.loads(l) for l in proc.stdout.splitlines() if l.startswith("{") and '"pass"' in l]
-        meta["ab_rows"] = {"library": os.path.relpath(os.path.abspath(args.ab_lib), ROOT), "what": "the same source built with -DRTOW_ESTIMATE_TAPS_FROM_LDS=0: every tap "
-                           "read from global memory, no LDS staging; same box, same run", "rows": rows}
+        meta["ab_rows"] = {"library": os.path.relpath(os.path.abspath(args.ab_lib), ROOT), "what": "the three estimate states with the library given by --ab-lib, in a "
+                           "child process; same box, same run", "rows": rows}
         for r in rows:
             print(json.dumps(dict(r, library="ab")), flush=True)
     if args.out:

@@ -18,7 +18,7 @@ struct DenoiseLevel {
     float invA;                 // 1 / (albedoSigma * albedoSigma), used when useAlbedo
     int useColor, useAlbedo;    // sigma != 0
     int demodIn, remodOut;      // level 0 / last level with RTOW_DENOISE_DEMODULATE_ALBEDO
-    unsigned tilesX, tiles;     // 64 x 4 pixel tiles per row / in all
+    TileGrid grid;              // the 64 x 4 pixel tiles
 };
 
 // One lane per output pixel; a workgroup is a 64 x 4 tile, so every tap load of a wave reads one contiguous row segment (768 bytes of float3).
@@ -27,9 +27,9 @@ struct DenoiseLevel {
 __global__ void __launch_bounds__(256, 8) denoise_level_kernel(DenoiseLevel L, const float* __restrict__ inColor, const float* __restrict__ normal,
                                                                const float* __restrict__ albedo, float* __restrict__ outColor)
 {
-    for (unsigned t = blockIdx.x; t < L.tiles; t += gridDim.x) {
-        const int x = (int)(t % L.tilesX) * 64 + (int)(threadIdx.x & 63u);
-        const int y = (int)(t / L.tilesX) * 4 + (int)(threadIdx.x >> 6);
+    for (unsigned t = blockIdx.x; t < L.grid.tiles; t += gridDim.x) {
+        const int x = (int)(t % L.grid.tilesX) * kGroupW + (int)(threadIdx.x & 63u);      // a wave is the 64 pixels of one tile row
+        const int y = (int)(t / L.grid.tilesX) * kGroupH + (int)(threadIdx.x >> 6);
         if (x >= L.width || y >= L.height) continue;
         const size_t p = (size_t)y * (size_t)L.width + (size_t)x;
         const bool needAlbedo = L.demodIn || L.useAlbedo;
@@ -93,10 +93,8 @@ hipError_t launchDenoise(const RtowDenoiseParams& p, const float* inColor, const
     L.useColor = p.colorSigma != 0.0f;
     L.useAlbedo = p.albedoSigma != 0.0f;
     L.invA = L.useAlbedo ? 1.0f / (p.albedoSigma * p.albedoSigma) : 0.0f;
-    L.tilesX = ((unsigned)p.width + 63u) / 64u;
-    const uint64_t tiles = (uint64_t)L.tilesX * (((uint64_t)p.height + 3u) / 4u);   // (w / 64 + 1) (h / 4 + 1) < 2^30 for w h < 2^31
-    L.tiles = (unsigned)tiles;
-    const unsigned blocks = L.tiles < kDenoiseMaxBlocks ? L.tiles : kDenoiseMaxBlocks;
+    L.grid = tileGrid(p.width, p.height);
+    const unsigned blocks = L.grid.tiles < kDenoiseMaxBlocks ? L.grid.tiles : kDenoiseMaxBlocks;
     const bool demod = (p.flags & RTOW_DENOISE_DEMODULATE_ALBEDO) != 0;
     const float sigma2 = p.colorSigma * p.colorSigma;
     const float* src = inColor;

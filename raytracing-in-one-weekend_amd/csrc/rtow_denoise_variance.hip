@@ -13,9 +13,6 @@ namespace {
 
 using namespace taps;
 
-// float4 at a 4-byte aligned address (an accumulator colour buffer, possibly a view that starts 4 bytes into an allocation)
-struct __attribute__((packed, aligned(4))) P4 { float x, y, z, w; };
-
 constexpr unsigned kMaxBlocks = 1u << 20;       // work beyond this many blocks is walked by a grid-stride loop
 constexpr float kVarianceUnknown = -1.0f;       // a pixel without a variance estimate (fewer than 2 batches, a non-finite estimate)
 constexpr float kInvCEpsilon = 9.5367431640625e-07f;      // 2^-20
@@ -32,10 +29,8 @@ __global__ void __launch_bounds__(256) accumulate_moments_kernel(MomentsArgs A, 
     for (size_t p = (size_t)blockIdx.x * 256u + threadIdx.x; p < A.pixels; p += (size_t)gridDim.x * 256u) {
         P3 m = inMoments ? ld3(inMoments, p) : P3{0.0f, 0.0f, 0.0f};      // (s1, s2, n)
         for (int k = 0; k < A.count; ++k) {
-            const P4 c = reinterpret_cast<const P4*>(A.colors[k])[p];
-            if (!(c.w > 0.0f)) continue;                                   // no successful sample in this batch (NaN included)
-            const float l = lum(c.x / c.w, c.y / c.w, c.z / c.w);
-            if (!__builtin_isfinite(l)) continue;
+            const float l = luminance_or_nan(A.colors[k], p);
+            if (l != l) continue;                                          // no successful sample in this batch, or a luminance that is not finite
             m.x = m.x + l;
             m.y = m.y + l * l;
             m.z = m.z + 1.0f;
@@ -73,7 +68,7 @@ struct VarianceLevel {
     float invA;                 // 1 / (albedoSigma * albedoSigma), used when useAlbedo
     int useColor, useAlbedo;    // sigma != 0
     int demodIn, remodOut;      // level 0 / last level with RTOW_DENOISE_DEMODULATE_ALBEDO
-    unsigned tilesX, tiles;     // 64 x 4 pixel tiles per row / in all
+    TileGrid grid;              // the 64 x 4 pixel tiles
 };
 
 // One level: rtow_denoise.hip's kernel (same tiling, same tap loop and skip rules, from rtow_denoise_taps.hip.h) with the variance state added - per pixel the own variance,
@@ -83,9 +78,9 @@ __global__ void __launch_bounds__(256, 8) denoise_variance_level_kernel(Variance
                                                                         const float* __restrict__ albedo, const float* __restrict__ inVariance,
                                                                         float* __restrict__ outColor, float* __restrict__ outVariance)
 {
-    for (unsigned t = blockIdx.x; t < L.tiles; t += gridDim.x) {
-        const int x = (int)(t % L.tilesX) * 64 + (int)(threadIdx.x & 63u);
-        const int y = (int)(t / L.tilesX) * 4 + (int)(threadIdx.x >> 6);
+    for (unsigned t = blockIdx.x; t < L.grid.tiles; t += gridDim.x) {
+        const int x = (int)(t % L.grid.tilesX) * kGroupW + (int)(threadIdx.x & 63u);      // a wave is the 64 pixels of one tile row
+        const int y = (int)(t / L.grid.tilesX) * kGroupH + (int)(threadIdx.x >> 6);
         if (x >= L.width || y >= L.height) continue;
         const size_t p = (size_t)y * (size_t)L.width + (size_t)x;
         const bool needAlbedo = L.demodIn || L.useAlbedo;
@@ -209,10 +204,8 @@ hipError_t launchDenoiseVariance(const RtowDenoiseParams& p, const float* inColo
     L.useAlbedo = p.albedoSigma != 0.0f;
     L.sigma2 = p.colorSigma * p.colorSigma;
     L.invA = L.useAlbedo ? 1.0f / (p.albedoSigma * p.albedoSigma) : 0.0f;
-    L.tilesX = ((unsigned)p.width + 63u) / 64u;
-    const uint64_t tiles = (uint64_t)L.tilesX * (((uint64_t)p.height + 3u) / 4u);   // (w / 64 + 1) (h / 4 + 1) < 2^30 for w h < 2^31
-    L.tiles = (unsigned)tiles;
-    const unsigned blocks = L.tiles < kMaxBlocks ? L.tiles : kMaxBlocks;
+    L.grid = tileGrid(p.width, p.height);
+    const unsigned blocks = L.grid.tiles < kMaxBlocks ? L.grid.tiles : kMaxBlocks;
     const float* src = inColor;
     for (int k = 0; k < p.iterations; ++k) {
         const bool last = k == p.iterations - 1;

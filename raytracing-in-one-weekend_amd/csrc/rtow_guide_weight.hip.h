@@ -1,6 +1,6 @@
 // rtow_guide_weight.hip.h - the first-hit guide weight g(p, q) of include/rtow.h (rtowUpsampleDevice's specification), shared by the passes that weigh a neighbour by
-// whether its first hit is the surface the pixel itself sees (rtow_upsample.hip: rtowUpsampleDevice; rtow_moments_temporal.hip: rtowEstimateMomentsDevice).  The rule
-// exists once, here; every statement is one float32 operation of the specification (the units are compiled without contraction).
+// whether its first hit is the surface the pixel itself sees (rtow_upsample.hip: rtowUpsampleDevice; rtow_guided_halo.hip.h: the tap loop of rtowEstimateMomentsDevice
+// and rtowRectifyHistoryDevice).  The rule exists once, here; every statement is one float32 operation of the specification (the units are compiled without contraction).
 #pragma once
 #include <hip/hip_runtime.h>
 

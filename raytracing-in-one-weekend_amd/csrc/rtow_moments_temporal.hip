@@ -8,17 +8,10 @@
 // Launch shape.  The gather knows only pixelCount: one lane per pixel, 256-lane grid-stride; the scattered 12-byte read is what occupancy hides.  The
 // estimate uses the 64 x 4 pixel workgroup tile of the denoise levels (a wave is 64 pixels of one row).  A workgroup first asks whether any of its pixels is to be
 // estimated: after a small camera move almost none is, and the tile then copies its moments (nothing at all in place) without touching the colour or the guides.
-// Otherwise it stages its 70 x 10 halo region into LDS once - L(q) with NaN for "invalid or outside the image", entity, distance and normal, 24 bytes per pixel as six
-// planes of 700 words (16800 bytes: 9 workgroups per CU, so LDS does not cap the 8 waves per SIMD) - and the 49 taps run from there.  A wave reads 64 consecutive words of
-// a plane per tap: no bank conflict, no padding.  L(q) is computed once per pixel by the operations the specification gives, so staging changes no bit.
+// Otherwise it stages its whole 70 x 10 halo region into LDS once and the 49 taps run from there: the staging and the tap loop of rtow_guided_halo.hip.h, which
+// rtow_rectify_history.hip shares.
 #include "rtow_kernels.h"
-#include "rtow_denoise_taps.hip.h"
-#include "rtow_guide_weight.hip.h"
-
-// A/B build for same-box timing (never shipped: csrc/Makefile, EXTRA=-DRTOW_ESTIMATE_TAPS_FROM_LDS=0): the same tap loop reading every tap from global memory
-#ifndef RTOW_ESTIMATE_TAPS_FROM_LDS
-#define RTOW_ESTIMATE_TAPS_FROM_LDS 1
-#endif
+#include "rtow_guided_halo.hip.h"
 
 namespace rtow {
 
@@ -26,13 +19,7 @@ namespace {
 
 using namespace taps;
 
-// float4 at a 4-byte aligned address (an accumulator colour buffer, possibly a view that starts 4 bytes into an allocation)
-struct __attribute__((packed, aligned(4))) P4 { float x, y, z, w; };
-
 constexpr unsigned kMaxBlocks = 1u << 20;       // work beyond this many blocks is walked by a grid-stride loop
-constexpr int kEstimateTileW = 64, kEstimateTileH = 4;          // the workgroup's pixels
-constexpr int kRadius = 3;                      // 7 x 7 taps
-constexpr int kHaloW = kEstimateTileW + 2 * kRadius, kHaloH = kEstimateTileH + 2 * kRadius, kHalo = kHaloW * kHaloH;      // 70 x 10
 
 // One lane per pixel.  A source outside [0, pixels) is never used as an address.
 __global__ void __launch_bounds__(256) reproject_moments_kernel(unsigned pixels, float maxBatches, const int32_t* __restrict__ source,
@@ -57,7 +44,7 @@ __global__ void __launch_bounds__(256) reproject_moments_kernel(unsigned pixels,
 
 struct EstimateArgs {
     int width, height;
-    unsigned tilesX, tiles;             // 64 x 4 pixel tiles per row / in all
+    TileGrid grid;                      // the 64 x 4 pixel tiles
     float minBatches;                   // (float)minBatches
     int minTaps, normalSharpness, matchEntity;
     float depthTolerance;
@@ -70,41 +57,14 @@ struct EstimateArgs {
     uint8_t* outFilled;
 };
 
-// L(q) of the specification, NaN when invalid (a valid L is finite, so NaN is free to mean "no luminance")
-__device__ __forceinline__ float luminance_or_nan(const float* color, size_t q)
-{
-    const P4 c = reinterpret_cast<const P4*>(color)[q];
-    if (!(c.w > 0.0f)) return __builtin_nanf("");          // no successful sample (NaN included)
-    const float l = lum(c.x / c.w, c.y / c.w, c.z / c.w);
-    return __builtin_isfinite(l) ? l : __builtin_nanf("");
-}
-
-// the guides of a tap for guide::weight: from the staged planes, or (A/B build) from global memory
-struct TileGuides {
-    const int* E;
-    const float *T, *Nx, *Ny, *Nz;
-    int k;
-    __device__ __forceinline__ int entity() const { return E[k]; }
-    __device__ __forceinline__ float distance() const { return T[k]; }
-    __device__ __forceinline__ void normal(float& x, float& y, float& z) const { x = Nx[k]; y = Ny[k]; z = Nz[k]; }
-};
-struct GlobalGuides {
-    const EstimateArgs& A;
-    size_t q;
-    __device__ __forceinline__ int entity() const { return A.entity[q]; }
-    __device__ __forceinline__ float distance() const { return A.distance[q]; }
-    __device__ __forceinline__ void normal(float& x, float& y, float& z) const { const P3 n = ld3(A.normal, q); x = n.x; y = n.y; z = n.z; }
-};
-
 __global__ void __launch_bounds__(256, 8) estimate_moments_kernel(EstimateArgs A)
 {
-#if RTOW_ESTIMATE_TAPS_FROM_LDS
-    __shared__ float sL[kHalo], sT[kHalo], sNx[kHalo], sNy[kHalo], sNz[kHalo];
-    __shared__ int sE[kHalo];
-#endif
+    __shared__ float sL[halo::kHalo], sT[halo::kHalo], sNx[halo::kHalo], sNy[halo::kHalo], sNz[halo::kHalo];
+    __shared__ int sE[halo::kHalo];
+    const halo::Planes planes{sL, sE, sT, sNx, sNy, sNz};
     const int lx = (int)(threadIdx.x & 63u), ly = (int)(threadIdx.x >> 6);
-    for (unsigned t = blockIdx.x; t < A.tiles; t += gridDim.x) {          // the same tiles for every lane of the workgroup: the barriers below are uniform
-        const int x0 = (int)(t % A.tilesX) * kEstimateTileW, y0 = (int)(t / A.tilesX) * kEstimateTileH;
+    for (unsigned t = blockIdx.x; t < A.grid.tiles; t += gridDim.x) {          // the same tiles for every lane of the workgroup: the barriers below are uniform
+        const int x0 = (int)(t % A.grid.tilesX) * kGroupW, y0 = (int)(t / A.grid.tilesX) * kGroupH;
         const int x = x0 + lx, y = y0 + ly;
         const bool inside = x < A.width && y < A.height;
         const size_t p = (size_t)y * (size_t)A.width + (size_t)x;
@@ -119,69 +79,17 @@ __global__ void __launch_bounds__(256, 8) estimate_moments_kernel(EstimateArgs A
             }
             continue;
         }
-#if RTOW_ESTIMATE_TAPS_FROM_LDS
-        for (int k = (int)threadIdx.x; k < kHalo; k += 256) {
-            const int qx = x0 - kRadius + k % kHaloW, qy = y0 - kRadius + k / kHaloW;
-            float l = __builtin_nanf("");                                 // outside the image: skipped like an invalid L
-            if (qx >= 0 && qx < A.width && qy >= 0 && qy < A.height) {
-                const size_t q = (size_t)qy * (size_t)A.width + (size_t)qx;
-                l = luminance_or_nan(A.color, q);
-                sE[k] = A.entity[q];
-                sT[k] = A.distance[q];
-                const P3 n = ld3(A.normal, q);
-                sNx[k] = n.x; sNy[k] = n.y; sNz[k] = n.z;
-            }
-            sL[k] = l;
-        }
+        halo::stage(planes, x0, y0, A.width, A.height, halo::kMaxRadius, A.color, A.entity, A.distance, A.normal);
         __syncthreads();
-        const int centre = (ly + kRadius) * kHaloW + lx + kRadius;
-#endif
+        const int centre = halo::centre_of(lx, ly);
         bool filled = false;
-        if (wanted) {
-#if RTOW_ESTIMATE_TAPS_FROM_LDS
-            const float lp = sL[centre];
-#else
-            const float lp = luminance_or_nan(A.color, p);
-#endif
-            if (lp == lp) {
-                const int e = A.entity[p];
-                const float tp = A.distance[p];
-                const P3 np = ld3(A.normal, p);
-                float W = 0.0f, S1 = 0.0f, S2 = 0.0f;
-                int taps = 0;
-#pragma unroll 1
-                for (int j = -kRadius; j <= kRadius; ++j) {
-#pragma unroll 1
-                    for (int i = -kRadius; i <= kRadius; ++i) {
-#if RTOW_ESTIMATE_TAPS_FROM_LDS
-                        const int k = centre + j * kHaloW + i;
-                        const float l = sL[k];
-                        if (l != l) continue;                             // outside the image, or L(q) invalid
-                        const float w = (i == 0 && j == 0) ? 1.0f         // the centre consults no guide
-                                                           : guide::weight(e, tp, np.x, np.y, np.z, A.matchEntity, A.depthTolerance, A.normalSharpness,
-                                                                           TileGuides{sE, sT, sNx, sNy, sNz, k});
-#else
-                        if (j < -y || j > A.height - 1 - y || i < -x || i > A.width - 1 - x) continue;
-                        const size_t q = (size_t)(y + j) * (size_t)A.width + (size_t)(x + i);
-                        const float l = (i == 0 && j == 0) ? lp : luminance_or_nan(A.color, q);
-                        if (l != l) continue;
-                        const float w = (i == 0 && j == 0) ? 1.0f
-                                                           : guide::weight(e, tp, np.x, np.y, np.z, A.matchEntity, A.depthTolerance, A.normalSharpness,
-                                                                           GlobalGuides{A, q});
-#endif
-                        if (!(w > 0.0f)) continue;                        // NaN included
-                        W = W + w;
-                        S1 = S1 + w * l;
-                        S2 = S2 + w * (l * l);
-                        ++taps;
-                    }
-                }
-                if (taps >= A.minTaps) {
-                    const float a = S1 / W, b = S2 / W;
-                    if (__builtin_isfinite(a) && __builtin_isfinite(b)) {
-                        m = P3{a + a, b + b, 2.0f};                       // the neighbourhood's weighted moments as two batches
-                        filled = true;
-                    }
+        if (wanted && sL[centre] == sL[centre]) {                         // a pixel without a valid L of its own keeps its moments
+            const halo::Sums s = halo::neighbourhood(planes, centre, halo::kMaxRadius, A.matchEntity, A.depthTolerance, A.normalSharpness);
+            if (s.taps >= A.minTaps) {
+                const float a = s.S1 / s.W, b = s.S2 / s.W;
+                if (__builtin_isfinite(a) && __builtin_isfinite(b)) {
+                    m = P3{a + a, b + b, 2.0f};                           // the neighbourhood's weighted moments as two batches
+                    filled = true;
                 }
             }
         }
@@ -208,8 +116,7 @@ hipError_t launchEstimateMoments(const RtowEstimateMomentsParams& p, const float
     EstimateArgs A{};
     A.width = p.width;
     A.height = p.height;
-    A.tilesX = ((unsigned)p.width + kEstimateTileW - 1) / kEstimateTileW;
-    A.tiles = (unsigned)((uint64_t)A.tilesX * (((uint64_t)p.height + kEstimateTileH - 1) / kEstimateTileH));      // (w / 64 + 1) (h / 4 + 1) < 2^30 for w h < 2^31
+    A.grid = tileGrid(p.width, p.height);
     A.minBatches = (float)p.minBatches;
     A.minTaps = p.minTaps;
     A.normalSharpness = p.normalSharpness;
@@ -222,7 +129,7 @@ hipError_t launchEstimateMoments(const RtowEstimateMomentsParams& p, const float
     A.inMoments = inMoments;
     A.outMoments = outMoments;
     A.outFilled = outFilled;
-    hipLaunchKernelGGL(estimate_moments_kernel, dim3(A.tiles < kMaxBlocks ? A.tiles : kMaxBlocks), dim3(256), 0, stream, A);
+    hipLaunchKernelGGL(estimate_moments_kernel, dim3(A.grid.tiles < kMaxBlocks ? A.grid.tiles : kMaxBlocks), dim3(256), 0, stream, A);
     return hipGetLastError();
 }
 

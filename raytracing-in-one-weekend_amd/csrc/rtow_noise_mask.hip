@@ -27,9 +27,8 @@ using namespace taps;
 // on the three cache lines of the record, which the memory side serialises (measured: 0.1 ms per 1000 workgroups).  Timed on one box in one run at 256 / 512 / 1024 /
 // 2048 (dilate 0, no budget): 1920 x 1080 0.156 / 0.117 / 0.134 / 0.233 ms, 3840 x 2160 0.538 / 0.315 / 0.266 / 0.356 ms (profiles/r14_noise_mask.json).
 constexpr unsigned kMaxBlocks = 1024;
-constexpr int kNoiseTileW = 64, kNoiseTileH = 4;          // the workgroup's pixels
 constexpr int kMaxDilate = 3;
-constexpr int kQW = kNoiseTileW + 2 * kMaxDilate, kQH = kNoiseTileH + 2 * kMaxDilate;      // 70 x 10: the "qualifies" plane
+constexpr int kQW = kGroupW + 2 * kMaxDilate, kQH = kGroupH + 2 * kMaxDilate;      // 70 x 10: the "qualifies" plane
 constexpr int kEW = kQW + 2, kEH = kQH + 2;                                       // 72 x 12: the e plane
 constexpr float kUnknown = -1.0f;
 constexpr int kBins = 64;
@@ -41,7 +40,7 @@ enum : unsigned { kKnown = 0, kUnknownCount = 1, kQualifying = 2, kMasked = 3, k
 
 struct NoiseArgs {
     int width, height;
-    unsigned tilesX, tiles;             // 64 x 4 pixel tiles per row / in all
+    TileGrid grid;                      // the 64 x 4 pixel tiles
     int dilate, absolute, unknownQualifies;
     int thresholdFromRecord;            // the second pass of a budget: T is what the pick step left in the record
     float threshold;                    // errorThreshold
@@ -102,8 +101,8 @@ __global__ void __launch_bounds__(256, 8) noise_mask_kernel(NoiseArgs A)
     // (whole rows of the planes are walked, so that the row and the column of a word come from divisions by constants)
     const int e0 = kMaxDilate - D, e1 = kEW - e0, eBegin = e0 * kEW, eEnd = (kEH - e0) * kEW;
     const int q0 = kMaxDilate - D, q1 = kQW - q0, qBegin = q0 * kQW, qEnd = (kQH - q0) * kQW;
-    for (unsigned t = blockIdx.x; t < A.tiles; t += gridDim.x) {          // the same tiles for every lane of the workgroup: the barriers below are uniform
-        const int x0 = (int)(t % A.tilesX) * kNoiseTileW, y0 = (int)(t / A.tilesX) * kNoiseTileH;
+    for (unsigned t = blockIdx.x; t < A.grid.tiles; t += gridDim.x) {          // the same tiles for every lane of the workgroup: the barriers below are uniform
+        const int x0 = (int)(t % A.grid.tilesX) * kGroupW, y0 = (int)(t / A.grid.tilesX) * kGroupH;
         const int x = x0 + lx, y = y0 + ly;
         const bool inside = x < A.width && y < A.height;
         const size_t p = (size_t)y * (size_t)A.width + (size_t)x;
@@ -143,7 +142,7 @@ __global__ void __launch_bounds__(256, 8) noise_mask_kernel(NoiseArgs A)
             for (int k = qBegin + (int)threadIdx.x; k < qEnd; k += 256) {
                 const int cx = k % kQW, cy = k / kQW;                     // in the 70 x 10 plane, whose (0, 0) is the pixel (x0 - 3, y0 - 3)
                 if (cx < q0 || cx >= q1) continue;
-                if (cx >= kMaxDilate && cx < kMaxDilate + kNoiseTileW && cy >= kMaxDilate && cy < kMaxDilate + kNoiseTileH) continue;
+                if (cx >= kMaxDilate && cx < kMaxDilate + kGroupW && cy >= kMaxDilate && cy < kMaxDilate + kGroupH) continue;
                 const int qx = x0 - kMaxDilate + cx, qy = y0 - kMaxDilate + cy;
                 unsigned q = 0u;
                 if (qx >= 0 && qx < A.width && qy >= 0 && qy < A.height) {
@@ -216,8 +215,7 @@ hipError_t launchNoiseMask(const RtowNoiseMaskParams& p, const float* moments, u
     NoiseArgs A{};
     A.width = p.width;
     A.height = p.height;
-    A.tilesX = ((unsigned)p.width + kNoiseTileW - 1) / kNoiseTileW;
-    A.tiles = (unsigned)((uint64_t)A.tilesX * (((uint64_t)p.height + kNoiseTileH - 1) / kNoiseTileH));      // (w / 64 + 1) (h / 4 + 1) < 2^30 for w h < 2^31
+    A.grid = tileGrid(p.width, p.height);
     A.dilate = p.dilate;
     A.absolute = (p.flags & RTOW_NOISE_MASK_ABSOLUTE) != 0;
     A.unknownQualifies = (p.flags & RTOW_NOISE_MASK_UNKNOWN_QUALIFIES) != 0;
@@ -228,7 +226,7 @@ hipError_t launchNoiseMask(const RtowNoiseMaskParams& p, const float* moments, u
     A.outError = outError;
     A.outStats = reinterpret_cast<unsigned*>(outStats);
     A.record = static_cast<unsigned*>(scratch);
-    const dim3 blocks(A.tiles < kMaxBlocks ? A.tiles : kMaxBlocks);
+    const dim3 blocks(A.grid.tiles < kMaxBlocks ? A.grid.tiles : kMaxBlocks);
     hipError_t e = hipMemsetAsync(scratch, 0, RTOW_NOISE_MASK_SCRATCH_BYTES, stream);
     if (e != hipSuccess) return e;
     if (p.maxQualifying == 0) {

@@ -8,14 +8,12 @@
 //
 // Launch shape.  The 64 x 4 pixel workgroup tile and grid-stride tile loop of estimate_moments_kernel; a wave is 64 pixels of one row.  A workgroup
 // first asks whether any of its pixels has a valid history: a tile of holes copies through (writes nothing but outKeep in place) and reads neither the fresh colour nor
-// the guides.  Otherwise it stages the part of its 70 x 10 halo region that `radius` reaches into LDS once - L(q) of the fresh colour with NaN for "invalid or outside
-// the image", entity, distance and normal, six planes of 700 words (16800 bytes: 9 workgroups per CU, so LDS does not cap the 8 waves per SIMD) - and the (2 r + 1)^2
-// taps run from there; consecutive lanes read consecutive words of a plane.  A lane reads history and moments at its own pixel only, before it writes them: every
-// output may be the matching input.  Statistics are integers (rtow_noise_mask.hip): counts by wave ballot into LDS, and when the workgroup is through with its tiles
-// one global atomic per non-zero counter; none at all without outStats.
+// the guides.  Otherwise it stages the part of its 70 x 10 halo region that `radius` reaches into LDS once - L(q) of the fresh colour and the guides - and the
+// (2 r + 1)^2 taps run from there: the staging and the tap loop of rtow_guided_halo.hip.h, which estimate_moments_kernel shares.  A lane reads history and moments
+// at its own pixel only, before it writes them: every output may be the matching input.  Statistics are integers (rtow_noise_mask.hip): counts by wave ballot into
+// LDS, and when the workgroup is through with its tiles one global atomic per non-zero counter; none at all without outStats.
 #include "rtow_kernels.h"
-#include "rtow_denoise_taps.hip.h"
-#include "rtow_guide_weight.hip.h"
+#include "rtow_guided_halo.hip.h"
 
 namespace rtow {
 
@@ -23,16 +21,10 @@ namespace {
 
 using namespace taps;
 
-// float4 at a 4-byte aligned address (an accumulator colour buffer, possibly a view that starts 4 bytes into an allocation)
-struct __attribute__((packed, aligned(4))) P4 { float x, y, z, w; };
-
 // Tiles beyond this many workgroups are walked by the grid-stride loop, and a workgroup adds its counts to the record once, when it is through: the memory side takes
 // device-wide atomics on one cache line one after the other (rtow_noise_mask.hip measured 0.1 ms per 1000 workgroups of some 20 atomics).  2048 workgroups are the
 // 8 x 256 a device holds at once; at most four atomics each.
 constexpr unsigned kMaxBlocks = 2048;
-constexpr int kRectifyTileW = 64, kRectifyTileH = 4;          // the workgroup's pixels
-constexpr int kMaxRadius = 3;                   // 7 x 7 taps
-constexpr int kHaloW = kRectifyTileW + 2 * kMaxRadius, kHaloH = kRectifyTileH + 2 * kMaxRadius, kHalo = kHaloW * kHaloH;      // 70 x 10
 
 // the words of the record (RtowRectifyStats)
 enum : unsigned { kJudged = 0, kKept = 1, kCut = 2, kDropped = 3 };
@@ -40,7 +32,7 @@ static_assert(sizeof(RtowRectifyStats) == 16 && sizeof(RtowRectifyParams) == 40,
 
 struct RectifyArgs {
     int width, height;
-    unsigned tilesX, tiles;             // 64 x 4 pixel tiles per row / in all
+    TileGrid grid;                      // the 64 x 4 pixel tiles
     int radius, minTaps, normalSharpness, matchEntity;
     float depthTolerance;
     float K2, R2;                       // sigmaScale^2, relativeTolerance^2
@@ -54,25 +46,6 @@ struct RectifyArgs {
     float* outMoments;
     float* outKeep;
     unsigned* outStats;
-};
-
-// L(q) of the specification, NaN when invalid (a valid L is finite, so NaN is free to mean "no luminance")
-__device__ __forceinline__ float luminance_or_nan(const float* color, size_t q)
-{
-    const P4 c = reinterpret_cast<const P4*>(color)[q];
-    if (!(c.w > 0.0f)) return __builtin_nanf("");          // no successful sample (NaN included)
-    const float l = lum(c.x / c.w, c.y / c.w, c.z / c.w);
-    return __builtin_isfinite(l) ? l : __builtin_nanf("");
-}
-
-// the guides of a tap for guide::weight, from the staged planes
-struct TileGuides {
-    const int* E;
-    const float *T, *Nx, *Ny, *Nz;
-    int k;
-    __device__ __forceinline__ int entity() const { return E[k]; }
-    __device__ __forceinline__ float distance() const { return T[k]; }
-    __device__ __forceinline__ void normal(float& x, float& y, float& z) const { x = Nx[k]; y = Ny[k]; z = Nz[k]; }
 };
 
 // The kernel's one argument where it lies in the kernarg segment (a by-value struct starts at offset 0).  What a phase needs of it - the pointers of the staging, of the
@@ -106,16 +79,14 @@ __device__ __forceinline__ void write3(const float* in, float* out, size_t p, in
 
 __global__ void __launch_bounds__(256, 8) rectify_history_kernel(RectifyArgs A)
 {
-    __shared__ float sL[kHalo], sT[kHalo], sNx[kHalo], sNy[kHalo], sNz[kHalo];
-    __shared__ int sE[kHalo];
+    __shared__ float sL[halo::kHalo], sT[halo::kHalo], sNx[halo::kHalo], sNy[halo::kHalo], sNz[halo::kHalo];
+    __shared__ int sE[halo::kHalo];
     __shared__ unsigned sCount[4];
+    const halo::Planes planes{sL, sE, sT, sNx, sNy, sNz};
     const int lx = (int)(threadIdx.x & 63u), ly = (int)(threadIdx.x >> 6);
     if (threadIdx.x < 4) sCount[threadIdx.x] = 0u;          // the first barrier of the tile loop comes before any lane counts
-    // the part of the planes this radius reads: (64 + 2 r) x (4 + 2 r) from (3 - r, 3 - r); whole rows are walked, so that the row and the column of a word come from
-    // divisions by constants
-    const int R = A.radius, c0 = kMaxRadius - R, c1 = kHaloW - c0, kBegin = c0 * kHaloW, kEnd = (kHaloH - c0) * kHaloW;
-    for (unsigned t = blockIdx.x; t < A.tiles; t += gridDim.x) {          // the same tiles for every lane of the workgroup: the barriers below are uniform
-        const int x0 = (int)(t % A.tilesX) * kRectifyTileW, y0 = (int)(t / A.tilesX) * kRectifyTileH;
+    for (unsigned t = blockIdx.x; t < A.grid.tiles; t += gridDim.x) {          // the same tiles for every lane of the workgroup: the barriers below are uniform
+        const int x0 = (int)(t % A.grid.tilesX) * kGroupW, y0 = (int)(t / A.grid.tilesX) * kGroupH;
         const int x = x0 + lx, y = y0 + ly;
         const bool inside = x < A.width && y < A.height;
         const size_t p = (size_t)y * (size_t)A.width + (size_t)x;
@@ -135,51 +106,13 @@ __global__ void __launch_bounds__(256, 8) rectify_history_kernel(RectifyArgs A)
         // a barrier as well: every lane is through with the planes of the previous tile before they are staged again
         if (__syncthreads_or(valid ? 1 : 0)) {                            // else a tile of holes: no fresh colour, no guide is read
             const KernelArgs K = args_here();
-            const float *fresh = K->fresh, *distance = K->distance, *normal = K->normal;
-            const int32_t* entity = K->entity;
-#pragma unroll 1
-            for (int s = kBegin + (int)threadIdx.x; s < kEnd; s += 256) {
-                const int cx = s % kHaloW, cy = s / kHaloW;               // in the 70 x 10 plane, whose (0, 0) is the pixel (x0 - 3, y0 - 3)
-                if (cx < c0 || cx >= c1) continue;
-                const int qx = x0 - kMaxRadius + cx, qy = y0 - kMaxRadius + cy;
-                float l = __builtin_nanf("");                             // outside the image: skipped like an invalid L
-                if (qx >= 0 && qx < A.width && qy >= 0 && qy < A.height) {
-                    const size_t q = (size_t)qy * (size_t)A.width + (size_t)qx;
-                    l = luminance_or_nan(fresh, q);
-                    sE[s] = entity[q];
-                    sT[s] = distance[q];
-                    const P3 n = ld3(normal, q);
-                    sNx[s] = n.x; sNy[s] = n.y; sNz[s] = n.z;
-                }
-                sL[s] = l;
-            }
+            halo::stage(planes, x0, y0, A.width, A.height, A.radius, K->fresh, K->entity, K->distance, K->normal);
             __syncthreads();
-            const int centre = (ly + kMaxRadius) * kHaloW + lx + kMaxRadius;
-            const float lp = sL[centre];
-            if (valid && lp == lp) {
-                const int e = sE[centre];
-                const float tp = sT[centre], npx = sNx[centre], npy = sNy[centre], npz = sNz[centre];
-                float W = 0.0f, S1 = 0.0f, S2 = 0.0f;
-                int taps = 0;
-#pragma unroll 1
-                for (int j = -R; j <= R; ++j) {
-#pragma unroll 1
-                    for (int i = -R; i <= R; ++i) {
-                        const int s = centre + j * kHaloW + i;
-                        const float l = sL[s];
-                        if (l != l) continue;                             // outside the image, or L(q) invalid
-                        const float w = (i == 0 && j == 0) ? 1.0f         // the centre consults no guide
-                                                           : guide::weight(e, tp, npx, npy, npz, A.matchEntity, A.depthTolerance, A.normalSharpness,
-                                                                           TileGuides{sE, sT, sNx, sNy, sNz, s});
-                        if (!(w > 0.0f)) continue;                        // NaN included
-                        W = W + w;
-                        S1 = S1 + w * l;
-                        S2 = S2 + w * (l * l);
-                        ++taps;
-                    }
-                }
-                if (taps >= A.minTaps) {
-                    const float mu = S1 / W, b = S2 / W;
+            const int centre = halo::centre_of(lx, ly);
+            if (valid && sL[centre] == sL[centre]) {                      // a pixel without a valid fresh L of its own is not judged
+                const halo::Sums s = halo::neighbourhood(planes, centre, A.radius, A.matchEntity, A.depthTolerance, A.normalSharpness);
+                if (s.taps >= A.minTaps) {
+                    const float mu = s.S1 / s.W, b = s.S2 / s.W;
                     if (__builtin_isfinite(mu) && __builtin_isfinite(b)) {
                         const KernelArgs K = args_here();
                         float var = b - mu * mu;
@@ -244,8 +177,7 @@ hipError_t launchRectifyHistory(const RtowRectifyParams& p, const RtowAccumBuffe
     RectifyArgs A{};
     A.width = p.width;
     A.height = p.height;
-    A.tilesX = ((unsigned)p.width + kRectifyTileW - 1) / kRectifyTileW;
-    A.tiles = (unsigned)((uint64_t)A.tilesX * (((uint64_t)p.height + kRectifyTileH - 1) / kRectifyTileH));      // (w / 64 + 1) (h / 4 + 1) < 2^30 for w h < 2^31
+    A.grid = tileGrid(p.width, p.height);
     A.radius = p.radius;
     A.minTaps = p.minTaps;
     A.normalSharpness = p.normalSharpness;
@@ -267,7 +199,7 @@ hipError_t launchRectifyHistory(const RtowRectifyParams& p, const RtowAccumBuffe
         const hipError_t e = hipMemsetAsync(outStats, 0, sizeof(RtowRectifyStats), stream);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(rectify_history_kernel, dim3(A.tiles < kMaxBlocks ? A.tiles : kMaxBlocks), dim3(256), 0, stream, A);
+    hipLaunchKernelGGL(rectify_history_kernel, dim3(A.grid.tiles < kMaxBlocks ? A.grid.tiles : kMaxBlocks), dim3(256), 0, stream, A);
     return hipGetLastError();
 }
 

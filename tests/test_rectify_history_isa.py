@@ -2,9 +2,10 @@
 the method of tests/test_temporal_moments_isa.py.  Only the compiler's resource-usage remarks are read.
 
 The staging loads and the reads of a pixel's own history are hidden by occupancy, like the taps of the neighbouring post passes: the kernel must stay without scratch
-(private segment 0) and without spills - a scalar register parked in a VGPR lane counts as one; the kernel reads its write-phase pointers from the kernel arguments
-tile by tile so that none is - within 64 VGPRs, at 8 waves per SIMD as the remark reports it.  That figure counts its LDS: six planes of the 70 x 10 halo region,
-16800 bytes, next to the workgroup's four counters."""
+(private segment 0) and without spills - a scalar register parked in a VGPR lane counts as one; the kernel reads the pointers it hands to the staging
+(csrc/rtow_guided_halo.hip.h's, inlined) and its write-phase pointers from the kernel arguments tile by tile so that none is - within 64 VGPRs, at 8 waves per SIMD as
+the remark reports it.  That figure counts its LDS: six planes of the 70 x 10 halo region, 16800 bytes, declared in the kernel, next to the workgroup's four
+counters."""
 import os
 import subprocess
 

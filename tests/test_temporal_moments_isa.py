@@ -3,7 +3,8 @@ the method of tests/test_denoise_isa.py.  Only the compiler's resource-usage rem
 
 The gather's scattered 12-byte read and the estimate's staging loads are hidden by occupancy, like the taps of the neighbouring post passes: every kernel of the
 unit must stay without scratch (private segment 0, no spill) and within 64 VGPRs, at 8 waves per SIMD as the remark reports it - for the estimate that figure
-counts its LDS (six planes of the 70 x 10 halo region, 16800 bytes, next to the workgroup reduction's)."""
+counts its LDS (six planes of the 70 x 10 halo region, 16800 bytes, next to the workgroup reduction's).  The planes are declared in the kernel; their geometry, the
+staging and the tap loop are csrc/rtow_guided_halo.hip.h's, which csrc/rtow_rectify_history.hip shares (tests/test_rectify_history_isa.py)."""
 import os
 import subprocess
 
