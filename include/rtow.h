@@ -833,6 +833,62 @@ RTOW_API int rtowFinalizeToneMappedDevice(RtowContext context, const RtowToneMap
                                           const float* inColor, const float* inNormal, const float* inAlbedo,
                                           uint8_t* outColor, uint8_t* outNormal, uint8_t* outAlbedo, void* stream);
 
+/* rtowBloomDevice - HDR bloom on the scene-referred colour, in front of the meter and the tone-mapped finalize: a bright pass, a pyramid of `levels` mips, the pyramid
+ * summed upwards, and the sum added to the frame.  A host cannot do this itself: between rtowCombineDevice and the bytes the float colour never leaves the device.  The
+ * first downsample weights its taps by 1 / (1 + exposed luminance) (the "Karis average", RTOW_BLOOM_KARIS_AVERAGE), which keeps one outlier sample of a few-spp frame -
+ * a firefly - from becoming a flashing disc.  Like the tone-map pair: a pure function of its buffers, the caller's scratch, no allocation, no wait (a linear stream
+ * capture records it), stream == NULL is the context's own stream, and the exposure scale is read on the device when the kernels run, never by the host.
+ * The frame loop, on one stream: ... -> rtowUpsampleDevice -> rtowBloomDevice -> rtowMeterExposureDevice -> rtowFinalizeToneMappedDevice.  The meter runs AFTER bloom,
+ * so the threshold and the Karis weight of a frame see the exposure the PREVIOUS frame's meter left in `state` (a zero-filled state: scale 1).  The output is
+ * scene-referred: only the threshold and the Karis weight look at exposed values.
+ * Added after API version 12 without changing it: a host detects the call by its entry point (C#: EntryPointNotFoundException).
+ *
+ * Numeric specification (float32, in this order; no contraction, correctly rounded `/`; min(a, b) = a < b ? a : b and max(a, b) = a > b ? a : b):
+ *   s = params.exposure * (state && state->valid ? state->exposure : 1.0f).   lum(v) = (0.2126f * v.r + 0.7152f * v.g) + 0.0722f * v.b.
+ *   Bright pass, once for each source pixel c (not once per tap):
+ *     per channel q = c > 0 ? c : 0 (NaN and negatives give 0), then q = q < 65536 ? q : 65536.
+ *     le = lum(q) * s, d = le - threshold, k = threshold * knee.
+ *     k > 0: r = min(max(d + k, 0), 2 * k), m = max((r * r) / (4 * k), d);  otherwise m = d.     m = m > 0 ? m : 0.
+ *     g = (le > 0 && le < inf) ? m / le : 0.     b = q * g per channel.
+ *     wk = 1 / (1 + lum(b) * s) with RTOW_BLOOM_KARIS_AVERAGE, otherwise wk = 1.
+ *   Mip k is W_k x H_k texels, W_k = ceil(width / 2^k), H_k = ceil(height / 2^k), k = 1 .. levels.
+ *   Mip 1 from the frame: the taps of texel (x, y) are the pixels (2x - 1 + i, 2y - 1 + j), i, j = 0..3, each coordinate clamped into the image; j is the outer loop,
+ *     i the inner one; h = {1/8, 3/8, 3/8, 1/8}; w = (h_j * h_i) * wk; acc (per channel) and wsum start at +0 and add w * b and w in tap order; the texel is
+ *     acc / wsum per channel, and 0 when wsum is not > 0.  (Without the flag wsum is exactly 1.)
+ *   Mip k from mip k-1, k = 2 .. levels: the same sixteen taps and clamps on mip k-1, w = h_j * h_i, the texel is acc; no division.
+ *   Upwards, k = levels-1 down to 1: U_levels = mip_levels and U_k(x, y) = mip_k(x, y) + scatter * Up(U_k+1)(x, y).  Up is the 2x tent: along an axis an even x takes
+ *     the coarse texels x/2 - 1 with u = 1/4 and x/2 with u = 3/4, an odd x takes x/2 with u = 3/4 and x/2 + 1 with u = 1/4, in this order (integer division, indices
+ *     clamped into the coarse mip); the four taps have the weights u_j * u_i, j the outer loop, and acc starts at +0.  U_k reads only its own texel of mip_k and is
+ *     stored over it.
+ *   Composite: out = c + intensity * Up(U_1)(x, y) per channel with the raw input c; a pixel of c with a non-finite channel is copied through unchanged.
+ * Consequences: b <= q <= 65536 whatever s is, so the pyramid is finite for every input and every scale; a frame that stays below the threshold comes out unchanged.
+ * `scratch` holds the pyramid and nothing else: the mips one behind the other from mip 1, 16 bytes per texel (r, g, b and a word written 0), 4-byte aligned like the
+ * float3 streams.  outColor == inColor (equal bases) is the in-place form: the composite reads only its own pixel of inColor.
+ * Launches: the bright pass and first downsample (a 64 x 4 tile of mip 1 per workgroup, its 130 x 10 source pixels bright-passed once and staged in LDS), levels - 1
+ * downsamples, levels - 1 upsamples in place, the composite: 2 * levels launches in stream order, no global atomics, no clear.
+ * RTOW_ERROR_INVALID_VALUE, nothing enqueued: a NULL context, params, inColor, scratch or outColor; width or height <= 0 or width * height > INT32_MAX (in 64 bits);
+ * levels outside 1..8; a threshold or intensity that is negative or not finite; a knee or scatter that is NaN or outside [0, 1]; an exposure that is NaN or outside
+ * [0, 65536]; unknown flag bits; reserved != 0; outColor or scratch overlapping each other, the state or inColor - except outColor == inColor. */
+typedef enum RtowBloomFlags { RTOW_BLOOM_KARIS_AVERAGE = 1 } RtowBloomFlags;
+typedef struct RtowBloomParams {
+    int32_t width, height;
+    int32_t levels;      /* 1..8 mips; mip k is ceil(width / 2^k) x ceil(height / 2^k), k = 1..levels            recommended 6 */
+    float   threshold;   /* >= 0, finite, in EXPOSED units (what the tone curve sees); 0 = everything blooms       recommended 1 */
+    float   knee;        /* 0..1, share of the threshold over which the bright pass fades in; 0 = hard             recommended 0.5 */
+    float   scatter;     /* 0..1, weight of each coarser mip when the pyramid is summed upwards                    recommended 0.7 */
+    float   intensity;   /* >= 0, finite; out = in + intensity * bloom                                             recommended: the host's taste */
+    float   exposure;    /* finite, 0 <= exposure <= 65536; multiplies the state's, exactly as RtowToneMapParams.exposure does */
+    int32_t flags;       /* RtowBloomFlags                                                                         recommended KARIS_AVERAGE */
+    int32_t reserved;    /* 0 */
+} RtowBloomParams;       /* 40 bytes */
+/* the pyramid, all levels: sum over k = 1..8 of ceil(w / 2^k) * ceil(h / 2^k) texels is below w*h/3 + w + h + 8, because ceil(a) * ceil(b) < a*b + a + b + 1 and the
+ * sums of 4^-k and 2^-k stay below 1/3 and 1 */
+#define RTOW_BLOOM_SCRATCH_BYTES(w, h) ((size_t)16 * ((size_t)(w) * (size_t)(h) / 3 + (size_t)(w) + (size_t)(h) + 9))
+RTOW_API int rtowBloomDevice(RtowContext context, const RtowBloomParams* params,
+                             const RtowExposureState* state /* device or NULL */,
+                             const float* inColor /* device float3[W*H] */, void* scratch,
+                             float* outColor /* device float3[W*H]; may be inColor itself */, void* stream);
+
 /* replaces: OpenImageDenoiseJob / OptixDenoiseJob (JOBS/DenoiseJobs.cs:10-38, :44-119) in the reference's
  * ScheduleDenoise (UNITY/Raytracer.cs:874-949): float3 colour / normal / albedo from rtowCombineDevice in,
  * float3 colour out for rtowFinalizeDevice.  Not a neural denoiser: an edge-avoiding a-trous wavelet filter

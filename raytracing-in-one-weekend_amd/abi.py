@@ -520,6 +520,35 @@ class ToneMapParams(C.Structure):
     _fields_ = [("pixelCount", C.c_int32), ("curve", C.c_int32), ("exposure", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+# rtowBloomDevice (include/rtow.h): HDR bloom on the scene-referred colour, between the upsample and the meter
+RTOW_BLOOM_KARIS_AVERAGE = 1                   # RtowBloomFlags: the first downsample weights its taps by 1 / (1 + exposed luminance)
+BLOOM_KARIS_AVERAGE = RTOW_BLOOM_KARIS_AVERAGE
+BLOOM_MAX_LEVELS = 8
+BLOOM_DEFAULT_LEVELS = 6
+BLOOM_DEFAULT_THRESHOLD = 1.0                  # in exposed units: where the tone curve starts to compress
+BLOOM_DEFAULT_KNEE = 0.5
+BLOOM_DEFAULT_SCATTER = 0.7
+BLOOM_DEFAULT_INTENSITY = 0.05                 # the host's taste; a low share keeps a frame without highlights as it is
+BLOOM_DEFAULT_EXPOSURE = 1.0
+BLOOM_DEFAULT_FLAGS = RTOW_BLOOM_KARIS_AVERAGE
+
+
+def bloom_levels(w, h, levels=BLOOM_MAX_LEVELS):
+    """the sizes of mip 1 .. levels: mip k is ceil(w / 2^k) x ceil(h / 2^k)"""
+    return [(-(-int(w) // (1 << k)), -(-int(h) // (1 << k))) for k in range(1, int(levels) + 1)]
+
+
+def bloom_scratch_bytes(w, h):
+    """RTOW_BLOOM_SCRATCH_BYTES(w, h): the pyramid, 16 bytes per texel, bounded for eight levels of every size"""
+    return 16 * (int(w) * int(h) // 3 + int(w) + int(h) + 9)
+
+
+class BloomParams(C.Structure):
+    """RtowBloomParams (40 bytes)"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("levels", C.c_int32), ("threshold", C.c_float), ("knee", C.c_float), ("scatter", C.c_float),
+                ("intensity", C.c_float), ("exposure", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
 class CameraRayListStats(C.Structure):
     """RtowCameraRayListStats (96 bytes)"""
     _fields_ = [("pixelsWithEntries", C.c_uint64 * 9), ("pixelsWithoutList", C.c_uint64), ("ownedPixels", C.c_uint64), ("pruned", C.c_int32), ("valid", C.c_int32)]
@@ -540,4 +569,5 @@ EXPORTED_SYMBOLS = [
     "rtowAccumulateMomentsDevice", "rtowDenoiseVarianceDevice", "rtowReprojectMomentsDevice", "rtowEstimateMomentsDevice",
     "rtowNoiseMaskDevice", "rtowRectifyHistoryDevice", "rtowReprojectAccumBilinearDevice",
     "rtowMeterExposureDevice", "rtowFinalizeToneMappedDevice", "rtowRecordPathsDevice", "rtowGetCameraRayListStats",
+    "rtowBloomDevice",
 ]

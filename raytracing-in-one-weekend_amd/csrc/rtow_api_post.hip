@@ -1,5 +1,5 @@
 // rtow_api_post.hip - the post-pass entry points of the C ABI (include/rtow.h): metrics, combine / finalize, the denoisers, moments, reprojection, rectification,
-// noise mask, upsampling, pixel lists, exposure and tone mapping.  Each one refuses (rtow_validate.h: every check that needs no device), takes the context's lock,
+// noise mask, upsampling, pixel lists, bloom, exposure and tone mapping.  Each one refuses (rtow_validate.h: every check that needs no device), takes the context's lock,
 // and launches on the caller's stream.  The tails are written out: HIP_TRY logs the text of the expression that failed.
 #include <hip/hip_runtime.h>
 
@@ -239,6 +239,18 @@ RTOW_API int rtowFinalizeToneMappedDevice(RtowContext ctx, const RtowToneMapPara
     hipStream_t s;
     RTOW_TRY(useDevice(ctx, stream, &s));
     HIP_TRY(ctx, launchFinalizeToneMapped(*params, state, inColor, inNormal, inAlbedo, outColor, outNormal, outAlbedo, ctx->dByteThresholds, s), RTOW_ERROR_LAUNCH_FAILURE);
+    return RTOW_SUCCESS;
+}
+
+RTOW_API int rtowBloomDevice(RtowContext ctx, const RtowBloomParams* params, const RtowExposureState* state, const float* inColor, void* scratch, float* outColor,
+                             void* stream)
+{
+    if (!ctx) return RTOW_ERROR_INVALID_VALUE;
+    RTOW_TRY(validateBloom(params, state, inColor, scratch, outColor));
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    hipStream_t s;
+    RTOW_TRY(useDevice(ctx, stream, &s));
+    HIP_TRY(ctx, launchBloom(*params, state, inColor, scratch, outColor, s), RTOW_ERROR_LAUNCH_FAILURE);
     return RTOW_SUCCESS;
 }
 

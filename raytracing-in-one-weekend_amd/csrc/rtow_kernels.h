@@ -406,6 +406,9 @@ hipError_t launchMeterExposure(const RtowExposureParams& p, const float* inColor
 // pair (arguments validated by the caller)
 hipError_t launchFinalizeToneMapped(const RtowToneMapParams& p, const RtowExposureState* state, const float* inColor, const float* inNormal, const float* inAlbedo,
                                     uint8_t* outColor, uint8_t* outNormal, uint8_t* outAlbedo, const float* thresholds, hipStream_t stream);
+// rtowBloomDevice (rtow_bloom.hip): 2 * levels launches on `stream` - the bright pass with the first downsample, levels - 1 downsamples, levels - 1 upsamples in place,
+// the composite; `scratch` holds the pyramid (RTOW_BLOOM_SCRATCH_BYTES), `state` may be null, outColor may be inColor (arguments validated by the caller)
+hipError_t launchBloom(const RtowBloomParams& p, const RtowExposureState* state, const float* inColor, void* scratch, float* outColor, hipStream_t stream);
 
 // rtowDenoiseDevice (rtow_denoise.hip): one launch per a-trous level on `stream`, ping-pong between scratch and outColor (params validated by the caller)
 hipError_t launchDenoise(const RtowDenoiseParams& p, const float* inColor, const float* inNormal, const float* inAlbedo, float* scratch, float* outColor,

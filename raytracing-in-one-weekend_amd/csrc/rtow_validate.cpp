@@ -333,4 +333,22 @@ int validateFinalizeToneMapped(const RtowToneMapParams* params, const RtowExposu
     return aliasingOk(written, countOf(written), read, countOf(read)) ? RTOW_SUCCESS : kBad;
 }
 
+int validateBloom(const RtowBloomParams* params, const RtowExposureState* state, const float* inColor, const void* scratch, const float* outColor)
+{
+    if (!params || !inColor || !scratch || !outColor) return kBad;
+    const RtowBloomParams& p = *params;
+    if (!frameSizeValid(p.width, p.height)) return kBad;
+    if (p.levels < 1 || p.levels > 8) return kBad;
+    if (!finiteNonNegative(p.threshold) || !finiteNonNegative(p.intensity)) return kBad;
+    if (!(p.knee >= 0.0f && p.knee <= 1.0f) || !(p.scatter >= 0.0f && p.scatter <= 1.0f)) return kBad;      // NaN fails
+    if (!(p.exposure >= 0.0f && p.exposure <= 65536.0f)) return kBad;
+    if (!flagsValid(p.flags, RTOW_BLOOM_KARIS_AVERAGE, p.reserved)) return kBad;
+    // the composite reads only its own pixel of inColor before it writes it; the pyramid is written while inColor and the state are read
+    const size_t n = (size_t)p.width * (size_t)p.height;
+    const Range written[] = {{outColor, n * 12}, {scratch, RTOW_BLOOM_SCRATCH_BYTES(p.width, p.height)}};
+    const Range read[] = {{state, sizeof(RtowExposureState)}};
+    const Range same[] = {{inColor, n * 12}};
+    return aliasingOk(written, countOf(written), read, countOf(read), same, countOf(same)) ? RTOW_SUCCESS : kBad;
+}
+
 } // namespace rtow

@@ -89,5 +89,7 @@ int validateBuildPixelList(const RtowPixelListParams* params, const float* color
 int validateMeterExposure(const RtowExposureParams* params, const float* inColor, const void* scratch, const RtowExposureState* state);
 int validateFinalizeToneMapped(const RtowToneMapParams* params, const RtowExposureState* state, const float* inColor, const float* inNormal, const float* inAlbedo,
                                const uint8_t* outColor, const uint8_t* outNormal, const uint8_t* outAlbedo);
+// rtowBloomDevice: outColor may be inColor itself (equal bases), the one overlap the pass allows
+int validateBloom(const RtowBloomParams* params, const RtowExposureState* state, const float* inColor, const void* scratch, const float* outColor);
 
 } // namespace rtow

@@ -894,6 +894,30 @@ class ToneMapJob:
         return JobHandle(rc)
 
 
+class BloomJob:
+    """rtowBloomDevice: HDR bloom on the float3 colour between the upsample and the meter - a bright pass at Threshold (in exposed units, faded in over Knee), a
+    pyramid of Levels mips whose first downsample is luminance weighted with abi.BLOOM_KARIS_AVERAGE (fireflies), the pyramid summed upwards with Scatter, and
+    Intensity times the sum added to the frame.  Device buffers (or raw device addresses): InputColor; Scratch of abi.bloom_scratch_bytes(Width, Height) bytes;
+    OutputColor, which may be InputColor itself; State (optional), the abi.ExposureState ExposureJob keeps in device memory - bloom runs in front of the meter, so it
+    sees the previous frame's exposure."""
+
+    def __init__(self, context, Width, Height, Levels=abi.BLOOM_DEFAULT_LEVELS, Threshold=abi.BLOOM_DEFAULT_THRESHOLD, Knee=abi.BLOOM_DEFAULT_KNEE,
+                 Scatter=abi.BLOOM_DEFAULT_SCATTER, Intensity=abi.BLOOM_DEFAULT_INTENSITY, Exposure=abi.BLOOM_DEFAULT_EXPOSURE, Flags=abi.BLOOM_DEFAULT_FLAGS, Reserved=0):
+        self.context, self.Width, self.Height, self.Levels = context, Width, Height, Levels
+        self.Threshold, self.Knee, self.Scatter, self.Intensity, self.Exposure, self.Flags, self.Reserved = Threshold, Knee, Scatter, Intensity, Exposure, Flags, Reserved
+        self.State = self.InputColor = self.Scratch = self.OutputColor = None
+
+    def params(self):
+        return abi.BloomParams(int(self.Width), int(self.Height), int(self.Levels), float(self.Threshold), float(self.Knee), float(self.Scatter), float(self.Intensity),
+                               float(self.Exposure), int(self.Flags), int(self.Reserved))
+
+    def Schedule(self, stream=None):
+        p = self.params()
+        rc = load().rtowBloomDevice(self.context.handle, C.byref(p), _device_ptr(self.State), _device_ptr(self.InputColor), _device_ptr(self.Scratch),
+                                    _device_ptr(self.OutputColor), stream)
+        return JobHandle(rc)
+
+
 class PixelListJob:
     """rtowBuildPixelListDevice: the pixels of a Width x Height frame that lie in the rectangle [X0, X1) x [Y0, Y1) and in the row slice, whose Mask byte (optional) is
     not 0 and whose accumulated sample count Color[4 p + 3] (optional) is not >= MinSampleCount, as a device list in 8 x 8 tile order for rtowSamplePixelsDevice.

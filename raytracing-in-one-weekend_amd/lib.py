@@ -81,6 +81,7 @@ def load():
     lib.rtowNoiseMaskDevice.argtypes = [vp, C.POINTER(abi.NoiseMaskParams), vp, vp, vp, vp, vp, vp]
     lib.rtowMeterExposureDevice.argtypes = [vp, C.POINTER(abi.ExposureParams), vp, vp, vp, vp]
     lib.rtowFinalizeToneMappedDevice.argtypes = [vp, C.POINTER(abi.ToneMapParams), vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.rtowBloomDevice.argtypes = [vp, C.POINTER(abi.BloomParams), vp, vp, vp, vp, vp]
     lib.rtowRectifyHistoryDevice.argtypes = [vp, C.POINTER(abi.RectifyParams), AB, vp, C.POINTER(abi.HitBuffers), vp, AB, vp, vp, vp, vp]
     lib.rtowUpsampleDevice.argtypes = [vp, C.POINTER(abi.UpsampleParams), vp, C.POINTER(abi.HitBuffers), vp, C.POINTER(abi.HitBuffers), vp, vp, vp, vp]
     lib.rtowBuildPixelListDevice.argtypes = [vp, C.POINTER(abi.PixelListParams), vp, vp, vp, C.POINTER(abi.PixelList), vp]
